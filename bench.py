@@ -19,12 +19,18 @@ all-reduce) on RCCL inside the library.  Either launched by torch.distributed.ru
 or plainly as `python bench.py --gpus N`: it then starts the N ranks itself (the same torch.distributed.run command),
 forwards rank 0's line and returns non-zero if any rank failed.  Prints ONE JSON line on rank 0.
 
-The line is COMPACT (about 1.7 KB, `compact_line`): every key of the driver's contract, the dominant kernel's roofline (HIP-event
-and rocprofv3 clocks, counter traffic, SQ MFMA-busy), the whole update's MFMA / HBM fractions, the CPU baseline, one
+A plain run does only what the headline needs: set up, `--warmup` untimed updates, `--steps` timed updates, the outputs of the
+last timed update when `--dump-outputs DIR` is given (`dump_outputs`), and the line.  `--full` adds everything that is reported
+beside the headline, each measured after it: the per-kernel HIP-event pass and the roofline, the brief runs of the other
+BASELINE.json configurations, the drop-in legs, the CPU baseline and, for N > 1, the other discriminator mode and the other
+all-reduce form.
+
+The line is COMPACT (about 1.7 KB with --full, `compact_line`): every key of the driver's contract, the dominant kernel's roofline
+(HIP-event and rocprofv3 clocks, counter traffic, SQ MFMA-busy), the whole update's MFMA / HBM fractions, the CPU baseline, one
 [ms, env-steps/s, frac, MFMA-busy] quadruple per other BASELINE.json configuration, the drop-in legs, and for N > 1 the comm block
-(which discriminator mode ran, the other mode's value, both all-reduce forms).  The FULL record -- per-kernel tables, spreads,
-sample descriptions, per-rank lists -- is written to gpurun_out/bench_full_<workload>_n<N>.json (named in the line as
-`full_record`) and to stderr; `--full-line` prints it on stdout instead.
+(which discriminator mode ran, the other mode's value, both all-reduce forms).  With --full the FULL record -- per-kernel tables,
+spreads, sample descriptions, per-rank lists -- is also written to a JSON file (`write_full`, named in the line as `full_record`)
+and to stderr; `--full-line` prints it on stdout instead.
 
 `--loopback` (self-test of the N > 1 path on a box with fewer than N GPUs): the ranks share the visible device(s) and use
 the library's shared-memory loopback communicator instead of RCCL; the line says so and is not a scaling measurement.
@@ -355,6 +361,30 @@ def run_updates(ctx, learner, steps):
     per = [ctx.mark_elapsed(marks[i], marks[i + 1]) for i in range(steps)]
     ctx.marks_reset()
     return wall, per, last
+
+
+def dump_outputs(out_dir, ctx, pol, disc, ro, last):
+    """--dump-outputs: what the timed path handed its caller in the last timed update, one .npy file per array -- the losses the
+    update returned (float64), the policy's and the discriminator's weights after it, the rollout's returns and advantages and,
+    with a discriminator, the relabelled rewards (float32, downloaded from the device-resident rollout).  Under 1 MB for every
+    workload; the inputs are seeded, so the same arguments give the same inputs from run to run."""
+    from simgan_amd import _lib
+    ctx.synchronize()
+    arrays = {f"loss_{k}": np.array([float(v)], np.float64) for k, v in dict(last).items()}
+    arrays["policy_params"] = pol.get_flat_params()
+    T, N = ro.num_steps, ro.num_processes
+    fields = {"returns": (_lib.F_RETURNS, (T + 1, N, 1)), "advantages": (_lib.F_ADVANTAGES, (T, N, 1))}
+    if disc is not None:
+        arrays["disc_params"] = disc.get_flat_params()
+        fields["rewards"] = (_lib.F_REWARDS, (T, N, 1))
+    for name, (field, shape) in fields.items():
+        a = np.empty(shape, np.float32)
+        _lib.check(ro.lib.sg_rollout_download(ro.h, field, _lib.fptr(a), a.size))
+        arrays[name] = a
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def profile_pass(ctx, learner):
@@ -772,13 +802,19 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="northstar", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what is reported beside it: per-kernel pass and roofline, the other "
+                         "configurations, the drop-in legs, the CPU baseline, for N > 1 the other discriminator mode and all-reduce "
+                         "form; writes the full record (the --no-* options below select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed update computed (losses, weights, returns, advantages, rewards) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the brief runs of BASELINE.json's other configurations")
     ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in legs (the unchanged main's call sequence on host tensors)")
     ap.add_argument("--no-line-keeper", action="store_true", help="print the line from this process only (no helper process holding it after the headline)")
-    ap.add_argument("--full-line", action="store_true", help="print the FULL record on stdout instead of the compact line (the default writes it to gpurun_out/bench_full_<workload>_n<N>.json and stderr)")
-    ap.add_argument("--headline-only", action="store_true", help="only the headline measurement (+ cpu baseline unless --no-cpu-baseline)")
+    ap.add_argument("--full-line", action="store_true", help="print the FULL record on stdout instead of the compact line (with --full the record otherwise goes to a JSON file named in the line, and to stderr)")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: only the headline measurement and its per-kernel pass (+ cpu baseline unless --no-cpu-baseline)")
     ap.add_argument("--no-other-disc-mode", action="store_true", help="N > 1: skip timing the non-default discriminator mode")
     ap.add_argument("--no-other-allreduce", action="store_true", help="N > 1: skip timing the other form of the per-step all-reduce (peer mesh / base communicator)")
     ap.add_argument("--init-timeout", type=float, default=480.0, help="watchdog budget (s) for start-up: imports, context, communicator, problem build")
@@ -803,13 +839,13 @@ def main():
         """stdout gets the compact line (--full-line: the whole record); the whole record goes to a file and to stderr."""
         if args.full_line:
             return obj
-        path = write_full(obj, args.workload, int(os.environ.get("WORLD_SIZE", "1")))
+        path = write_full(obj, args.workload, int(os.environ.get("WORLD_SIZE", "1"))) if args.full else None
         return compact_line(obj, path)
 
     def emit(obj):
         k, keeper["k"] = keeper["k"], None
         line = shape(obj)
-        if not args.full_line:
+        if args.full and not args.full_line:
             sys.stderr.write("[bench] full record: " + json.dumps(obj) + "\n")
         if k is not None and k.finish(line):
             return
@@ -895,11 +931,16 @@ def main():
 
     spreads = []
     elapsed, per_rank, last = timed(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dog.stage("writing the outputs of the last timed update", args.stage_timeout)
+        dump_outputs(args.dump_outputs, ctx, pol, disc, ro, last)
     # self-test of the N > 1 reporting path on one GPU (with SG_COMM_ALWAYS=1 the collectives stay in the launch sequence)
-    force_alt = world == 1 and os.environ.get("SG_BENCH_FORCE_ALT") == "1" and ctx.comm_info()[1] == 1 and os.environ.get("SG_COMM_ALWAYS") == "1"
-    # per-kernel durations with HIP events on the library's stream (separate, untimed pass)
-    dog.stage("per-kernel HIP-event pass", args.stage_timeout)
-    prof = profile_pass(ctx, learner)
+    force_alt = args.full and world == 1 and os.environ.get("SG_BENCH_FORCE_ALT") == "1" and ctx.comm_info()[1] == 1 and os.environ.get("SG_COMM_ALWAYS") == "1"
+    prof = None
+    if args.full:
+        # per-kernel durations with HIP events on the library's stream (separate, untimed pass)
+        dog.stage("per-kernel HIP-event pass", args.stage_timeout)
+        prof = profile_pass(ctx, learner)
 
     if rank == 0:
         work = algorithmic_work(w, world, ctx.disc_sharded)
@@ -907,26 +948,6 @@ def main():
         ms_per_step = 1e3 * elapsed / args.steps
         value = env_steps * args.steps / elapsed
         name, num_cu, hbm = ctx.device_info()
-        # PMC passes and rocprofv3's kernel trace cannot run inside the timed process: counter traffic and the profiler's
-        # own per-kernel durations come from the committed summary of the last profile run of THIS workload
-        # (tools/profile_workload.sh -> tools/make_traffic.py -> profiles/traffic.json), which records the sha256 of the
-        # library it profiled; a summary taken with another build is flagged, not silently reused.
-        import hashlib
-        with open(_lib.LIB_PATH, "rb") as f:
-            lib_sha = hashlib.sha256(f.read()).hexdigest()
-        tdoc = load_tdoc(args.workload)
-        traffic_sha = tdoc.get("lib_sha256")
-        traffic_stale = bool(tdoc) and traffic_sha != lib_sha
-        cdoc = load_cdoc(args.workload)
-        kmap, dom = kernel_report(w, work, prof, tdoc, cdoc)
-        dom_kernel, dom_flops, dg_avg_s, dg_n, achieved, traffic = dom["kernel"], dom["flops"], dom["avg_s"], dom["launches"], dom["achieved"], dom["traffic"]
-
-        def profiled_us(kname):
-            try:
-                return tdoc["kernels"][kname]["rocprof_avg_us"]
-            except KeyError:
-                return None
-
         out = {
             "metric": "env-steps/sec of GAIL-dyn PPO update" if w["E_d"] else ("env-steps/sec of PPO update (policy refinement, a2c/main.py)" if args.workload == "refine" else "env-steps/sec of PPO update (a2c/main.py)"), "value": round(value, 1), "unit": "env-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
@@ -940,42 +961,65 @@ def main():
                                     f"entropy_coef={w.get('ecoef', 0.0)} lr={w['lr']}{' linear decay' if w.get('lr_decay', True) else ''}"),
                        "optimizer_steps_per_update": work["d_steps"] + work["ppo_steps"],
                        "parallelism": f"dp{world} (env columns sharded, RCCL grad all-reduce)" if world > 1 else "single GPU"},
-            "roofline": {"bound": "mfma", "kernel": dom_kernel, "achieved": round(achieved, 3),
-                         "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_F32_MFMA_TFLOPS, 5),
-                         # two clocks for the same launches: HIP events around every launch in THIS process (graphs bypassed while
-                         # they are recorded) and rocprofv3's kernel trace of the committed profile run, whose interception sits on
-                         # every dispatch and reads 10-20 % longer on 4-7 us kernels.  `frac` is the HIP-event one (measured live, as
-                         # the contract asks); `frac_profiled` is what a reader recomputes from profiles/.
-                         "frac_basis": "hip_events", "frac_events": round(achieved / PEAK_F32_MFMA_TFLOPS, 5),
-                         "frac_profiled": (round(dom_flops / (profiled_us(dom_kernel) * 1e-6) / 1e12 / PEAK_F32_MFMA_TFLOPS, 5)
-                                           if profiled_us(dom_kernel) else None),
-                         "rocprof_avg_launch_us": profiled_us(dom_kernel),
-                         "rocprof_source": tdoc.get("kernel_trace", "no kernel trace of this workload committed"),
-                         "lib_sha256": lib_sha, "traffic_lib_sha256": traffic_sha, "traffic_stale": traffic_stale,
-                         # SQ counters of the committed counter passes (tools/profile_counters.sh -> profiles/counters.json): the matrix
-                         # pipes' busy cycles over (the cycles the kernel keeps a shader engine busy x the chip's 1024 SIMDs), and the
-                         # same over the CU-cycles in which a CU holds a wave of the kernel
-                         "mfma_busy": dom["counters"]["mfma_busy"], "mfma_busy_resident_cus": dom["counters"]["mfma_busy_resident"],
-                         "counters": dom["counters"], "counters_lib_sha256": cdoc.get("lib_sha256"),
-                         "counters_stale": bool(cdoc) and cdoc.get("lib_sha256") != lib_sha,
-                         "counters_source": f"profiles/counters.json (tag {load_ctag()}, passes {cdoc.get('passes')})" if cdoc else "no counter passes of this workload committed",
-                         "traffic": traffic, "traffic_unit": "HBM-side bytes per launch: rocprofv3 PMC FETCH_SIZE and WRITE_SIZE (separate passes) with the per-access-width calibration named in profiles/traffic.json; " + str(tdoc.get("source", "no profile of this workload committed")),
-                         "avg_launch_us": round(dg_avg_s * 1e6, 2), "launches": dg_n,
-                         "kernels": kmap,
-                         "algorithmic_flops_per_launch": dom_flops,
-                         "note": ("serial chain of 7 dependent GEMM phases on 96 four-row workgroups per 128-row step: latency-bound, see DESIGN.md section 4"
-                                  if w["E_d"] else "fused forward + loss + backward + weight gradients of one minibatch, one row group per workgroup"),
-                         "whole_update": {"TFLOP/s": round(work["flops"] * args.steps / elapsed / 1e12, 3),
-                                          "GB/s": round(work["bytes"] * args.steps / elapsed / 1e9, 2),
-                                          "frac_mfma": round(work["flops"] * args.steps / elapsed / 1e12 / PEAK_F32_MFMA_TFLOPS, 5),
-                                          "frac_hbm": round(work["bytes"] * args.steps / elapsed / 1e9 / PEAK_HBM_GBS, 6)}},
-            "kernel_us": {k: round(1e3 * v[0] / max(v[1], 1), 2) for k, v in prof.items()},
-            "kernel_launches": {k: v[1] for k, v in prof.items()},
             "us_per_optimizer_step": round(1e3 * ms_per_step / (work["d_steps"] + work["ppo_steps"]), 2),
             "last_losses": dict(last),
             "device": name, "num_cu": num_cu,
             "per_rank_ms_per_step": [round(1e3 * x / args.steps, 3) for x in per_rank],
         }
+        if prof is not None:
+            # PMC passes and rocprofv3's kernel trace cannot run inside the timed process: counter traffic and the profiler's
+            # own per-kernel durations come from the committed summary of the last profile run of THIS workload
+            # (tools/profile_workload.sh -> tools/make_traffic.py -> profiles/traffic.json), which records the sha256 of the
+            # library it profiled; a summary taken with another build is flagged, not silently reused.
+            import hashlib
+            with open(_lib.LIB_PATH, "rb") as f:
+                lib_sha = hashlib.sha256(f.read()).hexdigest()
+            tdoc = load_tdoc(args.workload)
+            traffic_sha = tdoc.get("lib_sha256")
+            traffic_stale = bool(tdoc) and traffic_sha != lib_sha
+            cdoc = load_cdoc(args.workload)
+            kmap, dom = kernel_report(w, work, prof, tdoc, cdoc)
+            dom_kernel, dom_flops, dg_avg_s, dg_n, achieved, traffic = dom["kernel"], dom["flops"], dom["avg_s"], dom["launches"], dom["achieved"], dom["traffic"]
+
+            def profiled_us(kname):
+                try:
+                    return tdoc["kernels"][kname]["rocprof_avg_us"]
+                except KeyError:
+                    return None
+
+            out.update({
+                "roofline": {"bound": "mfma", "kernel": dom_kernel, "achieved": round(achieved, 3),
+                             "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_F32_MFMA_TFLOPS, 5),
+                             # two clocks for the same launches: HIP events around every launch in THIS process (graphs bypassed while
+                             # they are recorded) and rocprofv3's kernel trace of the committed profile run, whose interception sits on
+                             # every dispatch and reads 10-20 % longer on 4-7 us kernels.  `frac` is the HIP-event one (measured live, as
+                             # the contract asks); `frac_profiled` is what a reader recomputes from profiles/.
+                             "frac_basis": "hip_events", "frac_events": round(achieved / PEAK_F32_MFMA_TFLOPS, 5),
+                             "frac_profiled": (round(dom_flops / (profiled_us(dom_kernel) * 1e-6) / 1e12 / PEAK_F32_MFMA_TFLOPS, 5)
+                                               if profiled_us(dom_kernel) else None),
+                             "rocprof_avg_launch_us": profiled_us(dom_kernel),
+                             "rocprof_source": tdoc.get("kernel_trace", "no kernel trace of this workload committed"),
+                             "lib_sha256": lib_sha, "traffic_lib_sha256": traffic_sha, "traffic_stale": traffic_stale,
+                             # SQ counters of the committed counter passes (tools/profile_counters.sh -> profiles/counters.json): the matrix
+                             # pipes' busy cycles over (the cycles the kernel keeps a shader engine busy x the chip's 1024 SIMDs), and the
+                             # same over the CU-cycles in which a CU holds a wave of the kernel
+                             "mfma_busy": dom["counters"]["mfma_busy"], "mfma_busy_resident_cus": dom["counters"]["mfma_busy_resident"],
+                             "counters": dom["counters"], "counters_lib_sha256": cdoc.get("lib_sha256"),
+                             "counters_stale": bool(cdoc) and cdoc.get("lib_sha256") != lib_sha,
+                             "counters_source": f"profiles/counters.json (tag {load_ctag()}, passes {cdoc.get('passes')})" if cdoc else "no counter passes of this workload committed",
+                             "traffic": traffic, "traffic_unit": "HBM-side bytes per launch: rocprofv3 PMC FETCH_SIZE and WRITE_SIZE (separate passes) with the per-access-width calibration named in profiles/traffic.json; " + str(tdoc.get("source", "no profile of this workload committed")),
+                             "avg_launch_us": round(dg_avg_s * 1e6, 2), "launches": dg_n,
+                             "kernels": kmap,
+                             "algorithmic_flops_per_launch": dom_flops,
+                             "note": ("serial chain of 7 dependent GEMM phases on 96 four-row workgroups per 128-row step: latency-bound, see DESIGN.md section 4"
+                                      if w["E_d"] else "fused forward + loss + backward + weight gradients of one minibatch, one row group per workgroup"),
+                             "whole_update": {"TFLOP/s": round(work["flops"] * args.steps / elapsed / 1e12, 3),
+                                              "GB/s": round(work["bytes"] * args.steps / elapsed / 1e9, 2),
+                                              "frac_mfma": round(work["flops"] * args.steps / elapsed / 1e12 / PEAK_F32_MFMA_TFLOPS, 5),
+                                              "frac_hbm": round(work["bytes"] * args.steps / elapsed / 1e9 / PEAK_HBM_GBS, 6)}},
+                "kernel_us": {k: round(1e3 * v[0] / max(v[1], 1), 2) for k, v in prof.items()},
+                "kernel_launches": {k: v[1] for k, v in prof.items()},
+            })
         if world > 1 or force_alt:
             kind = ctx.comm_kind()
             out["comm"] = {"backend": ("RCCL (dlopen) on the library stream, captured into the update's hipGraphs" if kind == "rccl" else
@@ -984,11 +1028,12 @@ def main():
                            "kind": kind, "nranks_reported_by_rccl": ctx.comm_info()[1], "rank0_reported_by_rccl": ctx.comm_info()[0],
                            "disc_mode": "sharded" if ctx.disc_sharded else "replicated",
                            "peer_allreduce": ctx.comm_peer(),   # SG_COMM_PEER=1: the per-step gradient all-reduce as one peer-write kernel
-                           # the per-step float32 gradient all-reduce of the headline run, bracketed by HIP events in the separate
-                           # profile pass (device time from reaching the collective to leaving it: the wait for the slowest rank included)
-                           "allreduce_us": round(1e3 * prof["comm_f32"][0] / max(prof["comm_f32"][1], 1), 2),
-                           "allreduce_count_per_update": prof["comm_f32"][1],
                            "allreduce_form": "peer mesh" if ctx.comm_peer() else kind}
+            if prof is not None:
+                # the per-step float32 gradient all-reduce of the headline run, bracketed by HIP events in the separate
+                # profile pass (device time from reaching the collective to leaving it: the wait for the slowest rank included)
+                out["comm"].update(allreduce_us=round(1e3 * prof["comm_f32"][0] / max(prof["comm_f32"][1], 1), 2),
+                                   allreduce_count_per_update=prof["comm_f32"][1])
     else:
         out = None
     # N > 1: the discriminator has two data-parallel modes.  `value` is the default (replicated:
@@ -1017,7 +1062,7 @@ def main():
         time.sleep(0.5)
         os.kill(os.getpid(), signal.SIGKILL)
     dog.stage("other discriminator mode / cpu baseline / output", 1e9)   # the other-mode timing has its own watchdog below
-    if (world > 1 or force_alt) and w["E_d"] and not args.no_other_disc_mode:
+    if args.full and (world > 1 or force_alt) and w["E_d"] and not args.no_other_disc_mode:
         import threading
         k2 = max(2, args.steps // 2)
         other = "replicated" if ctx.disc_sharded else "sharded"
@@ -1048,7 +1093,7 @@ def main():
     # N > 1: the OTHER form of the per-step all-reduce -- the peer mesh when the headline ran on the base communicator (RCCL),
     # the base communicator when SG_COMM_PEER=1 -- on the same communicator, toggled collectively (sg_ctx_comm_set_peer), so
     # that the first multi-GPU run comes back with both timed.  Own watchdog; a failure leaves an `error` entry.
-    if (world > 1 or force_alt) and not args.no_other_allreduce:
+    if args.full and (world > 1 or force_alt) and not args.no_other_allreduce:
         import threading
         k2 = max(2, args.steps // 2)
         was_peer = ctx.comm_peer()
@@ -1086,7 +1131,7 @@ def main():
         if rank == 0:
             out["comm"][field] = leg
             keep()
-    if world == 1 and not force_alt and not args.headline_only:
+    if args.full and world == 1 and not force_alt and not args.headline_only:
         # Everything below is reported BESIDE `value`, never as it; the headline is complete.  A leg that fails or runs out
         # of its budget leaves an `error` entry: the line is not lost (the stage watchdog prints what it has and ends the run).
         import gc
@@ -1110,7 +1155,7 @@ def main():
             keep()
         dog.stage("cpu baseline / output", 1e9)
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(w, expert, args.cpu_seconds)
             out["cpu_baseline"]["host_cores_available"] = os.cpu_count()
         emit(out)

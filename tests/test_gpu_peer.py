@@ -4,9 +4,12 @@ over peer-mapped device memory -- on one device: ranks as threads of one process
 everything downstream must be BIT-identical to the same run without it, and equal to the world-1 oracle as before.
 Across GPUs (xGMI) it has never run: a gpurun box has one GPU.
 
-The thread-rank cases run in a FRESH interpreter with GPU_MAX_HW_QUEUES=8: a collective kernel waits for the other ranks'
-kernels, and streams of one process that share a hardware queue (4 by default, assigned by the runtime as it sees fit -- the
-pytest process holds streams of earlier tests) cannot wait for each other.  `python tests/test_gpu_peer.py` runs them directly."""
+The thread-rank cases run in FRESH interpreters with GPU_MAX_HW_QUEUES=8, one per case: a collective kernel waits for the other
+ranks' kernels, and streams of one process that share a hardware queue (4 by default, assigned by the runtime as it sees fit -- the
+pytest process holds streams of earlier tests) cannot wait for each other.  A context's stream lives as long as its process, so
+the cases of one interpreter would pile their streams onto the same 8 queues, and an earlier case's objects freed by the garbage
+collector in the middle of a later case's collectives (hipFree waits for the whole device, the rank that frees included) stall
+the mesh until its time-out.  `python tests/test_gpu_peer.py [case index ...]` runs them directly."""
 import json
 import os
 import subprocess
@@ -158,18 +161,21 @@ THREAD_CASES = [("setup_failure",), ("ppo", 2, "mlp_small"), ("ppo", 3, "mlp_sma
                 ("disc_sharded", 2, "northstar"), ("disc_sharded", 4, "split"), ("refused",)]
 
 
-def main():
+def main(indices):
     import test_gpu_world as tw
-    for case in THREAD_CASES:
+    for case in [THREAD_CASES[i] for i in indices]:
         {"ppo": case_ppo, "disc_sharded": case_disc_sharded, "refused": case_refused, "setup_failure": case_setup_failure_is_collective}[case[0]](tw, *case[1:])
         print("OK", *case, flush=True)
 
 
 def test_thread_ranks_over_the_peer_mesh_equal_the_loopback_sums_and_the_oracle():
     env = dict(os.environ, GPU_MAX_HW_QUEUES="8", HSA_ENABLE_IPC_MODE_LEGACY="0", SG_LOOPBACK_TIMEOUT_S="120")
-    r = subprocess.run([sys.executable, os.path.abspath(__file__)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
-    done = [ln for ln in r.stdout.splitlines() if ln.startswith("OK ")]
-    assert r.returncode == 0 and len(done) == len(THREAD_CASES), (done, r.stdout[-1500:], r.stderr[-4000:])
+    done = []
+    for i, case in enumerate(THREAD_CASES):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), str(i)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        done += [ln for ln in r.stdout.splitlines() if ln.startswith("OK ")]
+        assert r.returncode == 0 and done[-1:] == ["OK " + " ".join(map(str, case))], (case, done, r.stdout[-1500:], r.stderr[-4000:])
+    assert len(done) == len(THREAD_CASES), done
 
 
 def _bench(extra_env, gpus=2):
@@ -177,7 +183,7 @@ def _bench(extra_env, gpus=2):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", str(gpus), "--loopback", "--steps", "2", "--warmup", "1", "--workload", "refine",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-6000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -197,4 +203,4 @@ def test_ranks_in_separate_processes_map_each_other_through_hipipc(gpus):
 
 
 if __name__ == "__main__":
-    main()
+    main([int(a) for a in sys.argv[1:]] or range(len(THREAD_CASES)))

@@ -531,7 +531,7 @@ def test_bench_launches_its_own_ranks_and_reports_the_n_gpu_line(workload, gpus)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", str(gpus), "--loopback", "--steps", "2", "--warmup", "1",
-                        "--workload", workload, "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--workload", workload, "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-6000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -626,6 +626,36 @@ def test_bench_line_survives_the_death_of_the_bench_process_after_the_headline()
     assert r.returncode == 0 and len(lines) == 1 and "error_after_headline" not in json.loads(lines[0]), (r.returncode, lines, r.stderr[-2000:])
 
 
+def test_bench_dumps_the_last_timed_update_and_a_plain_run_carries_the_headline_only(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed update handed its caller as float32 / float64 .npy files; the same
+    arguments give the same inputs, so two runs give the same arrays.  Without --full the line holds the headline and nothing
+    measured beside it."""
+    import json
+    import subprocess
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--workload", "refine", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / tag)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f32", out
+        assert not {"roofline", "cpu_baseline", "other_workloads_ms_envsteps_frac_busy", "full_record"} & set(out), out
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"policy_params.npy", "returns.npy", "advantages.npy", "loss_value_loss.npy", "loss_action_loss.npy"} <= set(names), names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+
+
 def test_bench_line_survives_a_peer_rank_dying_after_the_headline():
     """N > 1: rank 1 is killed after the headline (in what would be the other-mode / peer-mesh legs); the launcher ends rank 0,
     whose watchdog prints the line it had -- the measured value with `error_after_headline`, not an empty line."""
@@ -635,7 +665,7 @@ def test_bench_line_survives_a_peer_rank_dying_after_the_headline():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--loopback", "--workload", "refine", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, (lines, r.stderr[-3000:])
     out = json.loads(lines[0])

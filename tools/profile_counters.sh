@@ -25,7 +25,7 @@ for p in $passes; do
     d=/tmp/prof_${wl}_$p
     rm -rf $d
     timeout ${PASS_TIMEOUT:-420} rocprofv3 --pmc ${PASS[$p]} --kernel-trace -d $d -o $p --output-format rocpd -- \
-        python $root/bench.py --workload $wl --steps ${PROF_STEPS:-2} --warmup ${PROF_WARMUP:-1} --no-cpu-baseline --headline-only > $d.out 2> $d.err
+        python $root/bench.py --workload $wl --steps ${PROF_STEPS:-2} --warmup ${PROF_WARMUP:-1} --no-cpu-baseline --headline-only --full > $d.out 2> $d.err
     rc=$?
     db=$(find $d -name "*.db" 2>/dev/null | head -1)
     if [ -n "$db" ]; then
