@@ -192,6 +192,18 @@ SG_API int sg_results_fetch(sg_ctx *ctx, int slot, double out13[13]);
 SG_API int sg_ppo_last_perms(sg_ppo *a, int64_t *perms, int64_t count);
 SG_API int sg_ppo_get_adam(sg_ppo *a, float *m, float *v, int64_t n, int64_t *step);
 SG_API int sg_ppo_set_adam(sg_ppo *a, const float *m, const float *v, int64_t n, int64_t step);
+/* Mirror-symmetry loss of PPO.update, a2c/algo/ppo.py:110-143 (a2c/main.py:133-146, --loss-sym): every optimizer step adds
+ * coef * mean((M_a mu(s) - mu(mirror_obs(s)))^2) over the minibatch's B x A elements, mu = the DiagGaussian mean (fc_mean);
+ * M_a mu(s) is a constant of the loss (the reference mirrors it through numpy), so its gradient reaches the actor trunk and
+ * fc_mean through the mirrored pass mu(mirror_obs(s)) only, never the critic or the log-std.  Policy (MLP)
+ * only.  coef == 0 turns it off (plain PPO, today's kernels).  m_act [A*A] (required when coef > 0) and m_obs [O*O] are
+ * row-major linear maps: mirrored = M x.  m_obs NULL: the caller mirrors the rollout's observations itself and hands them
+ * over with sg_ppo_set_mirrored_obs before every update (the reference's per-row callable, my_pybullet_envs/utils.py:334-357). */
+SG_API int sg_ppo_set_symmetry(sg_ppo *a, float coef, const float *m_obs, const float *m_act);
+/* host[T*N*O] = mirror_obs(obs[t, n]) for the first T rollout steps, row t*N + n; consumed by the next sg_ppo_update */
+SG_API int sg_ppo_set_mirrored_obs(sg_ppo *a, const float *host, int64_t count);
+/* the last update's symmetry_loss.item() averaged over its ppo_epoch * num_mini_batch steps (0 when the loss is off) */
+SG_API int sg_ppo_last_symmetry_loss(sg_ppo *a, float *out);
 
 /* ------------------------------------------------------------ discriminator */
 /* Discriminator(input_dim, hidden_dim, device) a2c/algo/gail.py:35-51; Adam(lr 1e-3, eps 1e-8). */

@@ -77,6 +77,9 @@ PROTOTYPES = {
     "sg_ppo_last_perms": (C.c_int, [H, c_i64_p, C.c_int64]),
     "sg_ppo_get_adam": (C.c_int, [H, c_float_p, c_float_p, C.c_int64, c_i64_p]),
     "sg_ppo_set_adam": (C.c_int, [H, c_float_p, c_float_p, C.c_int64, C.c_int64]),
+    "sg_ppo_set_symmetry": (C.c_int, [H, C.c_float, c_float_p, c_float_p]),
+    "sg_ppo_set_mirrored_obs": (C.c_int, [H, c_float_p, C.c_int64]),
+    "sg_ppo_last_symmetry_loss": (C.c_int, [H, c_float_p]),
     "sg_disc_create": (C.c_int, [H, C.c_int, C.c_int, C.POINTER(H)]),
     "sg_disc_destroy": (C.c_int, [H]),
     "sg_disc_num_params": (C.c_int, [H, c_i64_p]),

@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
+from .. import symmetry as _sym
 from ..utils import derive_seed
 
 
@@ -51,9 +52,6 @@ class PPO():
                  mirror_obs=None,
                  mirror_act=None,
                  seed=0):
-        if mirror_obs and symmetry_coef > 0:
-            # a2c/algo/ppo.py:110-136: never enabled by any shipped script
-            raise NotImplementedError("mirror-symmetry loss is out of scope")
         self.actor_critic = actor_critic
         self.clip_param = clip_param
         self.ppo_epoch = ppo_epoch
@@ -80,6 +78,47 @@ class PPO():
         self.optimizer = _Optimizer(self, lr, eps)
         self._calls = 0
         self.seed = derive_seed(seed, 0xBADC0FFEE)   # minibatch-permutation stream (a2c/storage.py:159-162)
+        self._mirror_obs_fn = None
+        # a2c/algo/ppo.py:110: the symmetry loss runs when mirror_obs is given and symmetry_coef > 0, plain PPO otherwise
+        if mirror_obs is not None and symmetry_coef > 0:
+            self._set_symmetry(float(symmetry_coef), mirror_obs, mirror_act)
+
+    def _set_symmetry(self, coef, mirror_obs, mirror_act):
+        """mirror_obs: per-row callable (applied on the host each update, any map) or [O, O] matrix (all on the device);
+        mirror_act: per-row callable (must be linear: probed into its matrix) or [A, A] matrix.  Matrices act on rows:
+        mirrored = M @ x."""
+        ac = self.actor_critic
+        if type(ac).__name__ == "SplitPolicy":
+            raise NotImplementedError("mirror-symmetry loss: implemented for Policy (MLP) only, not for SplitPolicy")
+        if mirror_act is None:
+            raise ValueError("mirror-symmetry loss: mirror_obs was given without mirror_act")
+        O, A = ac.obs_dim, ac.act_dim
+        m_act = _sym.probe_linear(mirror_act, A, "mirror_act") if callable(mirror_act) else _sym.as_matrix(mirror_act, A, "mirror_act")
+        if callable(mirror_obs):
+            self._mirror_obs_fn, m_obs = mirror_obs, None
+        else:
+            m_obs = _sym.as_matrix(mirror_obs, O, "mirror_obs")
+        self._m_act, self._m_obs = m_act, m_obs
+        _lib.check(self.lib.sg_ppo_set_symmetry(self.h, coef, None if m_obs is None else _lib.fptr(m_obs), _lib.fptr(m_act)))
+
+    @property
+    def last_symmetry_loss(self):
+        """The last update's symmetry_loss.item(), averaged over its ppo_epoch * num_mini_batch steps like the returned losses
+        (0.0 with the loss off).  Not part of update()'s return value, which stays the reference's triple."""
+        out = C.c_float(0.0)
+        _lib.check(self.lib.sg_ppo_last_symmetry_loss(self.h, C.byref(out)))
+        return float(out.value)
+
+    def _upload_mirrored_obs(self, rollouts):
+        """Callable mirror_obs: the rollout's first T steps mirrored row by row on the host and handed to the next update."""
+        T, N = rollouts.num_steps, rollouts.num_processes
+        if rollouts.device_resident:
+            obs = np.empty(((T + 1) * N, self.actor_critic.obs_dim), np.float32)
+            _lib.check(rollouts.lib.sg_rollout_download(rollouts.h, _lib.F_OBS, _lib.fptr(obs), obs.size))
+        else:
+            obs = rollouts._host_np(_lib.F_OBS)
+        rows = _sym.mirror_rows(self._mirror_obs_fn, obs.reshape(-1, self.actor_critic.obs_dim)[:T * N])
+        _lib.check(self.lib.sg_ppo_set_mirrored_obs(self.h, _lib.fptr(rows), rows.size))
 
     def __del__(self):
         try:
@@ -97,6 +136,8 @@ class PPO():
         (include/simgan_hip.h: sg_ppo_update).  fetch_losses=False: queue the update and return None without waiting for
         it (the losses are read later through the results ring, simgan_amd/driver.py)."""
         rollouts._push([_lib.F_OBS, _lib.F_ACTIONS, _lib.F_VALUE_PREDS, _lib.F_RETURNS, _lib.F_LOGP])
+        if self._mirror_obs_fn is not None:
+            self._upload_mirrored_obs(rollouts)
         out = (C.c_float * 3)()
         self._calls += 1
         if perms is not None:

@@ -234,7 +234,7 @@ struct sg_ppo {
     uint64_t scratch_key = 0;    // layout the scratch buffers were last cleared for
     hipGraphExec_t steps_graph = nullptr;   // the update's optimizer steps, captured once and replayed
     bool graph_refused = false;             // a capture with collectives failed once: stay on direct launches
-    uint64_t steps_graph_key[16] = {0};
+    uint64_t steps_graph_key[18] = {0};
     sg_ctx* ctx;
     sg_policy* policy;
     sg_ppo_config cfg;
@@ -253,6 +253,13 @@ struct sg_ppo {
     unsigned* d_pair = nullptr;    // k_ppo_pair: error word
     bool self_wait_failed = false; // a k_ppo_pair hand-off timed out on this object: its later updates run the two-launch step
     bool pair_primed = false;      // the row stacks were cleared for k_ppo_pair's tagged words and no other mode has run since
+    // mirror-symmetry loss (sg_ppo_set_symmetry): off while sym_coef == 0
+    float sym_coef = 0.f;
+    float* d_mobs_mat = nullptr;   // [O][O] linear obs mirror, or NULL: the rows come from the host (sg_ppo_set_mirrored_obs)
+    float* d_mact = nullptr;       // [A][A] action mirror
+    float* d_mrows = nullptr;      // [T*N][O] the mirrored rollout observations the next / last update reads
+    int64_t mrows_cap = 0;         // floats
+    int64_t mrows_host = 0;        // floats sg_ppo_set_mirrored_obs uploaded for the next update (0: none pending)
 };
 
 struct sg_disc {

@@ -10,6 +10,9 @@
 //   per epoch:   k_ppo_epoch_gather                  permuted copy of the rollout
 //   per step:    k_ppo_fwd -> k_ppo_bwd -> k_ppo_reduce [-> all-reduce -> k_sumsq] -> k_ppo_adam
 //   then         k_opt_commit                        Adam's step base += E*M
+// With the mirror-symmetry loss (sg_ppo_set_symmetry) the rollout's mirrored observations are formed first (k_mirror_rows, or
+// uploaded by the host), the epoch gather permutes them too and every step runs k_ppo_fwd_sym -> k_ppo_bwd_sym ->
+// k_ppo_reduce_sym -> k_ppo_adam_sym: the two-launch form with a third grid column, the actor trunk on the mirrored rows.
 // Everything from the first epoch gather on is captured into a hipGraph once and replayed per update (single GPU;
 // with a communicator the RCCL calls are issued directly between the kernels).
 #include <math.h>
@@ -65,6 +68,12 @@ static size_t ppo_bwd_lds(const SgPolicyDesc& d, int MT, bool gw) {
     const int R = 16 * MT;
     return sizeof(float) * ((gw ? 0 : (size_t)(ppo_fused(d, MT) ? max_trunk_floats(d) : max_bwd_floats(d))) + R * d.ldO + 2 * R * d.ldH + 2 * R * stack_ldP(d) +
                             ((R * d.A + 3) & ~3) + 7 * R);
+}
+// k_ppo_bwd_sym: the unfused backward's tiles + the other actor column's head tile + M_a
+static size_t ppo_bwd_sym_lds(const SgPolicyDesc& d, int MT, bool gw) {
+    const int R = 16 * MT;
+    return sizeof(float) * ((gw ? 0 : (size_t)max_bwd_floats(d)) + R * d.ldO + 2 * R * d.ldH + 3 * R * stack_ldP(d) +
+                            ((R * d.A + 3) & ~3) + 7 * R + ((d.A * d.A + 3) & ~3));
 }
 
 // shape-specialised instances for the shipped configurations at the row-group
@@ -140,6 +149,36 @@ static void launch_ppo_bwd(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 grid
     else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<1, 0, 0>), grid, block, lds, pa);
 }
 
+// Policy with the mirror-symmetry loss: grid (row groups, 3), the Laikago refinement shape specialised
+static void launch_ppo_fwd_sym(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 grid, size_t lds, const PpoArgs& pa, bool gw) {
+    const int ko = d.Op / 16, kh = d.Hc == d.H ? d.Hp / 16 : 0;
+    const dim3 block(ppo_block_threads(MT));
+    if (gw) {
+        if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_sym<2, 0, 0, true>), grid, block, lds, pa);
+        else SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_sym<1, 0, 0, true>), grid, block, lds, pa);
+    } else if (MT == 2 && ko == 7 && kh == 4) {
+        SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_sym<2, 7, 4>), grid, block, lds, pa);
+    } else if (MT == 2) {
+        SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_sym<2, 0, 0>), grid, block, lds, pa);
+    } else {
+        SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_sym<1, 0, 0>), grid, block, lds, pa);
+    }
+}
+static void launch_ppo_bwd_sym(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 grid, size_t lds, const PpoArgs& pa, bool gw) {
+    const int ko = d.Op / 16, kh = d.Hc == d.H ? d.Hp / 16 : 0;
+    const dim3 block(ppo_block_threads(MT));
+    if (gw) {
+        if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd_sym<2, 0, 0, true>), grid, block, lds, pa);
+        else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd_sym<1, 0, 0, true>), grid, block, lds, pa);
+    } else if (MT == 2 && ko == 7 && kh == 4) {
+        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd_sym<2, 7, 4>), grid, block, lds, pa);
+    } else if (MT == 2) {
+        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd_sym<2, 0, 0>), grid, block, lds, pa);
+    } else {
+        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd_sym<1, 0, 0>), grid, block, lds, pa);
+    }
+}
+
 // ---------------------------------------------------------------------------------- PPO API
 extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg, sg_ppo** out) {
     SG_DEVICE_WIDE();
@@ -180,7 +219,7 @@ extern "C" int sg_ppo_destroy(sg_ppo* a) {
     (void)hipStreamSynchronize(a->ctx->stream);
     sg_ctx_learner_gone(a->ctx);
     for (auto& q : a->ctx->res_a) if (q == a) q = nullptr;
-    float* ptrs[] = {a->d_m, a->d_v, a->d_grad, a->d_slabs, a->d_state, a->d_part, a->d_stacks};
+    float* ptrs[] = {a->d_m, a->d_v, a->d_grad, a->d_slabs, a->d_state, a->d_part, a->d_stacks, a->d_mobs_mat, a->d_mact, a->d_mrows};
     for (float* q : ptrs) if (q) (void)sg_dev_free(q);
     if (a->d_perms) (void)sg_dev_free(a->d_perms);
     if (a->d_loss_acc) (void)sg_dev_free(a->d_loss_acc);
@@ -200,6 +239,65 @@ extern "C" int sg_ppo_set_lr(sg_ppo* a, float lr) {
     // by kernel argument, in stream order: no host synchronisation (the schedule writes it before every update)
     hipLaunchKernelGGL(k_set_lr, dim3(1), dim3(1), 0, a->ctx->stream, reinterpret_cast<SgOptState*>(a->d_state), lr);
     SG_CHECK(hipGetLastError());
+    return 0;
+}
+
+// a2c/algo/ppo.py:110-136 (enabled by a2c/main.py:133-146, --loss-sym): symmetry_coef > 0 adds coef * mean((M_a mu(s) -
+// mu(mirror_obs(s)))^2) to every optimizer step's loss.  m_obs NULL: the caller mirrors the rows itself and hands them over
+// before every update (sg_ppo_set_mirrored_obs).
+extern "C" int sg_ppo_set_symmetry(sg_ppo* a, float coef, const float* m_obs, const float* m_act) {
+    SG_REQUIRE(a, "sg_ppo_set_symmetry: NULL argument");
+    SG_REQUIRE(coef >= 0.f && coef < INFINITY, "sg_ppo_set_symmetry: symmetry_coef must be finite and >= 0 (got %g)", (double)coef);
+    sg_ctx* ctx = a->ctx;
+    const SgPolicyDesc& d = a->policy->desc;
+    SG_CHECK(hipSetDevice(ctx->device));
+    SG_CHECK(hipStreamSynchronize(ctx->stream));   // a queued update may still read the mirrors
+    if (coef == 0.f) { a->sym_coef = 0.f; return 0; }   // a2c/algo/ppo.py:111: plain PPO
+    SG_REQUIRE(m_act, "sg_ppo_set_symmetry: symmetry_coef > 0 needs the action mirror m_act");
+    SG_REQUIRE(d.kind == SG_POLICY_MLP, "sg_ppo_set_symmetry: the mirror-symmetry loss is implemented for Policy (MLP) only, "
+               "not for SplitPolicy");
+    SG_REQUIRE(ppo_bwd_sym_lds(d, 1, true) <= (size_t)ctx->lds_bytes,
+               "sg_ppo_set_symmetry: the 16-row tiles of the symmetric step do not fit LDS (%zu > %d bytes)", ppo_bwd_sym_lds(d, 1, true),
+               ctx->lds_bytes);
+    if (!a->d_mact) SG_CHECK(sg_dev_malloc((void**)&a->d_mact, sizeof(float) * d.A * d.A));
+    SG_COPY_SYNC(ctx, a->d_mact, m_act, sizeof(float) * d.A * d.A, hipMemcpyHostToDevice);
+    if (m_obs) {
+        if (!a->d_mobs_mat) SG_CHECK(sg_dev_malloc((void**)&a->d_mobs_mat, sizeof(float) * d.O * d.O));
+        SG_COPY_SYNC(ctx, a->d_mobs_mat, m_obs, sizeof(float) * d.O * d.O, hipMemcpyHostToDevice);
+    } else if (a->d_mobs_mat) {
+        SG_CHECK(sg_dev_free(a->d_mobs_mat));
+        a->d_mobs_mat = nullptr;
+    }
+    a->sym_coef = coef;
+    return 0;
+}
+
+// mirror_obsact_batch(obs, ..., mirror_obs, augment=False) of every rollout row (my_pybullet_envs/utils.py:334-357), done by
+// the caller: host[T*N][O] float32, consumed by the next sg_ppo_update (which requires count == T*N*O)
+extern "C" int sg_ppo_set_mirrored_obs(sg_ppo* a, const float* host, int64_t count) {
+    SG_REQUIRE(a && host, "sg_ppo_set_mirrored_obs: NULL argument");
+    SG_REQUIRE(count > 0 && count % a->policy->desc.O == 0, "sg_ppo_set_mirrored_obs: %lld floats is not a whole number of %d-float rows",
+               (long long)count, a->policy->desc.O);
+    sg_ctx* ctx = a->ctx;
+    SG_CHECK(hipSetDevice(ctx->device));
+    SG_CHECK(hipStreamSynchronize(ctx->stream));   // a queued update may still read the previous rows
+    if (a->mrows_cap < count) {
+        if (a->d_mrows) SG_CHECK(sg_dev_free(a->d_mrows));
+        SG_CHECK(sg_dev_malloc((void**)&a->d_mrows, sizeof(float) * count));
+        a->mrows_cap = count;
+    }
+    SG_COPY_SYNC(ctx, a->d_mrows, host, sizeof(float) * count, hipMemcpyHostToDevice);
+    a->mrows_host = count;
+    return 0;
+}
+
+// the last update's symmetry_loss.item(), averaged over its ppo_epoch * num_mini_batch steps like out3 (0 with the loss off)
+extern "C" int sg_ppo_last_symmetry_loss(sg_ppo* a, float* out) {
+    SG_REQUIRE(a && out, "sg_ppo_last_symmetry_loss: NULL argument");
+    SG_CHECK(hipSetDevice(a->ctx->device));
+    double acc = 0.0;
+    SG_TRY(sg_ctx_fetch_f64(a->ctx, a->d_loss_acc + 3, &acc, 1));
+    *out = (float)(acc / ((double)a->cfg.ppo_epoch * a->cfg.num_mini_batch));
     return 0;
 }
 
@@ -318,6 +416,27 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
             for (int k = 0; k < M; ++k) { step_cnt[(size_t)e * M + k] = mb; step_off[(size_t)e * M + k] = k * mb; }
     }
 
+    // mirrored observations of the rollout's T*N rows (the same for every epoch: the reference mirrors each minibatch anew)
+    const bool sym = a->sym_coef > 0.f;
+    if (sym) {
+        if (a->d_mobs_mat) {
+            if (a->mrows_cap < TN * d.O) {
+                SG_CHECK(hipStreamSynchronize(ctx->stream));
+                if (a->d_mrows) SG_CHECK(sg_dev_free(a->d_mrows));
+                SG_CHECK(sg_dev_malloc((void**)&a->d_mrows, sizeof(float) * TN * d.O));
+                a->mrows_cap = TN * d.O;
+            }
+            hipLaunchKernelGGL(k_mirror_rows, dim3((unsigned)((TN * d.O + 255) / 256)), dim3(256), 0, ctx->stream,
+                               r->d_field[SG_F_OBS], a->d_mobs_mat, a->d_mrows, TN, d.O);
+            SG_CHECK(hipGetLastError());
+        } else {
+            SG_REQUIRE(a->mrows_host == TN * d.O, "sg_ppo_update: the symmetry loss takes its mirrored observations from the host: "
+                       "sg_ppo_set_mirrored_obs must hand over %lld floats (T*N rows of %d) before every update (pending: %lld)",
+                       (long long)(TN * d.O), d.O, (long long)a->mrows_host);
+            a->mrows_host = 0;
+        }
+    }
+
     // advantages (global mean / unbiased std)
     float* adv = r->d_field[SG_F_ADVANTAGES];
     double* stats = a->d_loss_acc + 4;
@@ -354,17 +473,19 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     // launch geometry: 32-row groups as long as they still give every CU a workgroup (half the gradient slabs for
     // k_ppo_reduce to stream: -1.8 us per step at the north-star shape against +0.6 us in k_ppo_bwd), or when the
     // 16-row slabs would exceed 24 MB; otherwise 16-row groups (more workgroups in flight hide the phases' latencies)
+    const int ncols = d.n_trunks + (sym ? 1 : 0);   // grid columns: the trunks, + the mirrored actor
     int MT = ((size_t)((mb + 15) / 16) * (size_t)(d.total + 8) * sizeof(float) > ((size_t)24 << 20) ||
-              ((mb + 31) / 32) * d.n_trunks >= ctx->num_cu) ? 2 : 1;
+              ((mb + 31) / 32) * ncols >= ctx->num_cu) ? 2 : 1;
     if (const char* e = getenv("SG_PPO_ROWS")) {   // tuning knob
         const int v = atoi(e);
         if (v == 16 || v == 32 || v == 64) MT = v / 16;
     }
     // global-weight instances when a trunk (+ one 16-row tile) does not fit LDS: in the forward, or in the backward launch
     const bool gw = sg_policy_needs_gw(ctx, d) || ppo_fwd_lds(d, 1, false) > (size_t)ctx->lds_bytes ||
-                    ppo_bwd_lds(d, 1, false) > (size_t)ctx->lds_bytes;
-    if (gw && MT > 2) MT = 2;
-    while (MT > 1 && (ppo_fwd_lds(d, MT, gw) > (size_t)ctx->lds_bytes || ppo_bwd_lds(d, MT, gw) > (size_t)ctx->lds_bytes)) MT /= 2;
+                    ppo_bwd_lds(d, 1, false) > (size_t)ctx->lds_bytes || (sym && ppo_bwd_sym_lds(d, 1, false) > (size_t)ctx->lds_bytes);
+    if ((gw || sym) && MT > 2) MT = 2;
+    while (MT > 1 && (ppo_fwd_lds(d, MT, gw) > (size_t)ctx->lds_bytes || ppo_bwd_lds(d, MT, gw) > (size_t)ctx->lds_bytes ||
+                      (sym && ppo_bwd_sym_lds(d, MT, gw) > (size_t)ctx->lds_bytes))) MT /= 2;
     const int R = 16 * MT;
     const int G = (mb + R - 1) / R;
     const int mbp = G * R;
@@ -376,10 +497,12 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     // slack rows: the last row tile may read past the last minibatch (owned mode: a short step still reads mbp rows)
     const int TNp = (int)TN + 64 + (owned ? mbp : 0);
 
-    // scratch: slabs | epoch copy (X, ACT, SC) | per-trunk row stacks (H1, H2, OUT)
-    const size_t slab_f = (size_t)G * slab_stride;
-    const size_t epoch_f = (size_t)TNp * (d.ldO + d.A + 4);
-    const size_t stack_f = (size_t)d.n_trunks * mbp * (2 * (size_t)d.ldH + ldP);
+    // scratch: slabs | epoch copy (X, ACT, SC[, Xm]) | per-column row stacks (H1, H2, OUT)
+    // (symmetry: G more slabs for the mirrored column, the mirrored epoch copy at a 16-byte boundary, a third stack set)
+    const size_t slab_f = (size_t)(sym ? 2 : 1) * G * slab_stride;
+    const size_t xm_off = ((size_t)TNp * (d.ldO + d.A + 4) + 3) & ~(size_t)3;
+    const size_t epoch_f = sym ? xm_off + (size_t)TNp * d.ldO : (size_t)TNp * (d.ldO + d.A + 4);
+    const size_t stack_f = (size_t)ncols * mbp * (2 * (size_t)d.ldH + ldP);
     if (a->slabs_cap < slab_f || a->stacks_cap < epoch_f + stack_f) {
         SG_CHECK(hipStreamSynchronize(ctx->stream));
         if (a->d_slabs) SG_CHECK(sg_dev_free(a->d_slabs));
@@ -393,24 +516,27 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     // ld-padding columns of the slabs are never written by the kernels and must read as zero; the epoch copy's
     // slack rows must be finite.  Both hold for as long as the scratch layout is unchanged, so the 35 MB are
     // cleared when the layout changes, not on every update.
-    const uint64_t key = ((uint64_t)G << 40) ^ ((uint64_t)slab_stride << 20) ^ ((uint64_t)mbp << 8) ^ (uint64_t)TNp ^ ((uint64_t)MT << 60);
+    const uint64_t key = ((uint64_t)G << 40) ^ ((uint64_t)slab_stride << 20) ^ ((uint64_t)mbp << 8) ^ (uint64_t)TNp ^ ((uint64_t)MT << 60) ^
+                         ((uint64_t)sym << 63);
     if (a->scratch_key != key) {
         SG_CHECK(hipMemsetAsync(a->d_slabs, 0, sizeof(float) * slab_f, ctx->stream));
         SG_CHECK(hipMemsetAsync(a->d_stacks, 0, sizeof(float) * (epoch_f + stack_f), ctx->stream));
         a->scratch_key = key;
     }
-    hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 3);
+    hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 4);
 
     float* epX = a->d_stacks;
     float* epACT = epX + (size_t)TNp * d.ldO;
     float* epSC = epACT + (size_t)TNp * d.A;
-    float* stk = epSC + (size_t)TNp * 4;
+    float* epXm = sym ? a->d_stacks + xm_off : nullptr;
+    float* stk = a->d_stacks + epoch_f;
 
     EpochGatherArgs ga;
     ga.obs = r->d_field[SG_F_OBS]; ga.actions = r->d_field[SG_F_ACTIONS]; ga.old_logp = r->d_field[SG_F_LOGP];
     ga.adv = adv; ga.vpred = r->d_field[SG_F_VALUE_PREDS]; ga.ret = r->d_field[SG_F_RETURNS];
     ga.TN = TN; ga.O = d.O; ga.Op = d.Op; ga.ldO = d.ldO; ga.A = d.A; ga.sc_stride = TNp;
     ga.X = epX; ga.ACT = epACT; ga.SC = epSC;
+    ga.mobs = sym ? a->d_mrows : nullptr; ga.Xm = epXm;
 
     PpoArgs pa;
     pa.d = d; pa.params = a->policy->d_params;
@@ -420,14 +546,16 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     pa.slabs = a->d_slabs; pa.slab_stride = slab_stride; pa.ldP = ldP; pa.dbg = a->d_dbg;
     pa.st = reinterpret_cast<SgOptState*>(a->d_state); pa.G = G; pa.k1 = 0;
     pa.pair = a->d_pair;
+    pa.Xm = nullptr; pa.MA = a->d_mact;
+    pa.sym_c = sym ? (float)(2.0 * a->sym_coef / ((double)mb_global * d.A)) : 0.f;
     for (int t = 0; t < 3; ++t) {
-        const bool on = t < d.n_trunks;
+        const bool on = t < ncols;
         pa.H1[t] = on ? stk : nullptr; if (on) stk += (size_t)mbp * d.ldH;
         pa.H2[t] = on ? stk : nullptr; if (on) stk += (size_t)mbp * d.ldH;
         pa.OUT[t] = on ? stk : nullptr; if (on) stk += (size_t)mbp * ldP;
     }
     const int wb_f = gw ? 0 : max_trunk_floats(d), wb_b = gw ? 0 : max_bwd_floats(d);
-    const bool fused = ppo_fused(d, MT);
+    const bool fused = !sym && ppo_fused(d, MT);
     // SplitPolicy with more (row group, trunk) workgroups than CUs: the critic's whole fused forward + backward rides in the
     // forward launch (k_ppo_fwd_critic), the backward launch covers the two actor trunks.  SG_PPO_CRITIC_FIRST=0/1 forces it.
     const size_t lds_fc = sizeof(float) * ((size_t)wb_f + R * d.ldO + 2 * R * d.ldH + 2 * R * ldP + ((R * d.A + 3) & ~3) + 7 * R);
@@ -446,7 +574,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     // and a bit pattern must never be mistaken for a tagged word -- clear them whenever the mode is (re-)entered
     if (pair && !a->pair_primed) SG_CHECK(hipMemsetAsync(a->d_stacks, 0, sizeof(float) * (epoch_f + stack_f), ctx->stream));
     a->pair_primed = pair;
-    const size_t lds_f = ppo_fwd_lds(d, MT, gw), lds_b = ppo_bwd_lds(d, MT, gw);
+    const size_t lds_f = ppo_fwd_lds(d, MT, gw), lds_b = sym ? ppo_bwd_sym_lds(d, MT, gw) : ppo_bwd_lds(d, MT, gw);
     const int nblk = (d.total + 8 + 255) / 256;
     const int nblk_r = (d.total + 8 + SG_PPO_REDUCE_PARAMS - 1) / SG_PPO_REDUCE_PARAMS;
     SgOptState* st = reinterpret_cast<SgOptState*>(a->d_state);
@@ -459,13 +587,20 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
         for (int e = 0; e < E; ++e) {
             ga.perm = a->d_perms + (size_t)e * TN;
             ga.TN = epoch_rows[e];
-            if (ga.TN) hipLaunchKernelGGL(k_ppo_epoch_gather, dim3((unsigned)((ga.TN + 63) / 64)), dim3(256), 0, ctx->stream, ga);
+            if (ga.TN) hipLaunchKernelGGL(sym ? k_ppo_epoch_gather_sym : k_ppo_epoch_gather, dim3((unsigned)((ga.TN + 63) / 64)), dim3(256), 0,
+                                          ctx->stream, ga);
             for (int k = 0; k < M; ++k) {
                 const size_t rb = (size_t)step_off[(size_t)e * M + k];
                 pa.mb = step_cnt[(size_t)e * M + k];
                 pa.X = epX + rb * d.ldO; pa.ACT = epACT + rb * d.A; pa.SC = epSC + rb;
+                if (sym) pa.Xm = epXm + rb * d.ldO;
                 pa.k1 = e * M + k + 1;
-                if (pair) {
+                if (sym) {
+                    pa.wbuf_floats = wb_f;
+                    launch_ppo_fwd_sym(ctx, MT, d, dim3(G, 3), lds_f, pa, gw);
+                    pa.wbuf_floats = wb_b;
+                    launch_ppo_bwd_sym(ctx, MT, d, dim3(G, 3), lds_b, pa, gw);
+                } else if (pair) {
                     pa.wbuf_floats = wb_f;
                     launch_ppo_pair(ctx, MT, d, G, lds_fc, pa);
                 } else if (crit_first) {
@@ -481,15 +616,17 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
                     pa.wbuf_floats = fused ? wb_f : wb_b;
                     launch_ppo_bwd(ctx, MT, d, dim3(G, d.n_trunks), lds_b, pa, fused, gw);
                 }
-                SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_ppo_reduce, dim3(nblk_r), dim3(256), 0, a->d_slabs, G, slab_stride,
-                          d.total, a->d_grad, a->d_part);
+                if (sym) SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_ppo_reduce_sym, dim3(nblk_r), dim3(256), 0, a->d_slabs, G, slab_stride,
+                                   d.total, a->d_grad, a->d_part, d.trunk[0].off, d.trunk[0].off + d.trunk[0].ex);
+                else SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_ppo_reduce, dim3(nblk_r), dim3(256), 0, a->d_slabs, G, slab_stride,
+                               d.total, a->d_grad, a->d_part);
                 if (ctx->use_comm) {
                     SG_TRY(sg_comm_allreduce_f32(ctx, a->d_grad, d.total + 8));
                     hipLaunchKernelGGL(k_sumsq, dim3(nblk), dim3(256), 0, ctx->stream, a->d_grad, d.total, a->d_part);
                 }
-                SG_LAUNCH(ctx, SG_PROF_PPO_ADAM, k_ppo_adam, dim3(nblk), dim3(256), 0, a->policy->d_params, a->d_m, a->d_v,
-                          a->d_grad, a->d_part, ctx->use_comm ? nblk : nblk_r, d.total, st, e * M + k + 1, a->cfg.eps, a->cfg.max_grad_norm,
-                          pa.inv_B, a->d_loss_acc);
+                SG_LAUNCH(ctx, SG_PROF_PPO_ADAM, sym ? k_ppo_adam_sym : k_ppo_adam, dim3(nblk), dim3(256), 0, a->policy->d_params, a->d_m,
+                          a->d_v, a->d_grad, a->d_part, ctx->use_comm ? nblk : nblk_r, d.total, st, e * M + k + 1, a->cfg.eps,
+                          a->cfg.max_grad_norm, pa.inv_B, a->d_loss_acc);
             }
         }
         hipLaunchKernelGGL(k_opt_commit, dim3(1), dim3(1), 0, ctx->stream, st, E * M);
@@ -506,13 +643,16 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
         uint32_t fbits[6];
         const float fv[6] = {a->cfg.clip_param, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B};
         memcpy(fbits, fv, sizeof fbits);
-        const uint64_t key[16] = {(uint64_t)(uintptr_t)a->d_slabs, (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_perms,
+        uint32_t cbits;
+        memcpy(&cbits, &a->sym_coef, sizeof cbits);
+        const uint64_t key[18] = {(uint64_t)(uintptr_t)a->d_slabs, (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_perms,
                                   (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
                                   (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)a->policy->d_params,
                                   (uint64_t)TN, ((uint64_t)E << 32) | (uint64_t)M, ((uint64_t)MT << 32) | (uint64_t)G,
                                   ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
                                   ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)a->cfg.use_clipped_value_loss,
-                                  (uint64_t)(uintptr_t)r->d_field[SG_F_LOGP], 0x50504full + (fused ? 1 : 0) + (ctx->use_comm ? 2 : 0) + (crit_first ? 4 : 0) + (gw ? 8 : 0) + (pair ? 16 : 0) + (sg_comm_peer_on(ctx) ? 32 : 0) + ((uint64_t)sg_comm_peer_generation(ctx) << 32)};
+                                  (uint64_t)(uintptr_t)r->d_field[SG_F_LOGP], 0x50504full + (fused ? 1 : 0) + (ctx->use_comm ? 2 : 0) + (crit_first ? 4 : 0) + (gw ? 8 : 0) + (pair ? 16 : 0) + (sg_comm_peer_on(ctx) ? 32 : 0) + (sym ? 64 : 0) + ((uint64_t)sg_comm_peer_generation(ctx) << 32),
+                                  sym ? (uint64_t)(uintptr_t)a->d_mrows : 0, sym ? (uint64_t)cbits : 0};   // (M_a lives at one address for the object's life: read at run time)
         if (!a->steps_graph || memcmp(key, a->steps_graph_key, sizeof key) != 0) {
             if (a->steps_graph) { SG_CHECK(hipGraphExecDestroy(a->steps_graph)); a->steps_graph = nullptr; }
             if (sg_try_capture(ctx, &a->steps_graph, enqueue_steps) != 0) {

@@ -46,6 +46,11 @@ struct PpoArgs {
     SgOptState* st;       // optimizer scalars (read by k_ppo_adam; prepared one step ahead by the previous k_ppo_adam)
     int k1, G;            // 1-based step index within the update; row groups
     unsigned* pair;       // k_ppo_pair: the error word an actor workgroup raises when its partner never shows up
+    // mirror-symmetry loss (SYM instances only, a2c/algo/ppo.py:110-136): column 2 of the grid runs the actor trunk on the
+    // mirrored rows
+    const float* Xm;      // [mb..][ldO] mirrored rows, permuted like X
+    const float* MA;      // [A][A] action mirror M_a (row-major: (M_a mu)_k = sum_j MA[k A + j] mu_j)
+    float sym_c;          // symmetry_coef * 2 / (B A): d(coef * mean(e^2)) / d e, e = M_a mu(s) - mu(s_m)
 };
 
 // k_ppo_pair (SplitPolicy, one launch per step): the two actor workgroups of a row group exchange their head outputs
@@ -68,9 +73,12 @@ struct EpochGatherArgs {
     int64_t TN;
     int O, Op, ldO, A, sc_stride;
     float *X, *ACT, *SC;
+    const float* mobs;    // SYM: [T*N][O] mirrored observations, gathered into Xm like obs into X
+    float* Xm;
 };
 
-__global__ __launch_bounds__(256) void k_ppo_epoch_gather(EpochGatherArgs a) {
+template <bool SYM = false>
+__device__ __forceinline__ void sg_ppo_epoch_gather_body(const EpochGatherArgs& a) {
     __shared__ int IDX[64];
     const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * 64;
@@ -99,6 +107,19 @@ __global__ __launch_bounds__(256) void k_ppo_epoch_gather(EpochGatherArgs a) {
             const int i = base + u * blockDim.x;
             if (i < 64 * a.Op && IDX[i / a.Op] >= 0) a.X[(size_t)(row0 + i / a.Op) * a.ldO + (i % a.Op)] = v[u];
         }
+        if (SYM) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = base + u * blockDim.x;
+                const int r = i / a.Op, c = i - r * a.Op;
+                v[u] = (i < 64 * a.Op && IDX[r] >= 0 && c < a.O) ? a.mobs[(size_t)IDX[r] * a.O + c] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = base + u * blockDim.x;
+                if (i < 64 * a.Op && IDX[i / a.Op] >= 0) a.Xm[(size_t)(row0 + i / a.Op) * a.ldO + (i % a.Op)] = v[u];
+            }
+        }
     }
     for (int i = tid; i < 64 * a.A; i += blockDim.x) {
         const int r = i / a.A, c = i - r * a.A;
@@ -106,10 +127,32 @@ __global__ __launch_bounds__(256) void k_ppo_epoch_gather(EpochGatherArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void k_ppo_epoch_gather(EpochGatherArgs a) { sg_ppo_epoch_gather_body<false>(a); }
+__global__ __launch_bounds__(256) void k_ppo_epoch_gather_sym(EpochGatherArgs a) { sg_ppo_epoch_gather_body<true>(a); }
+
+// mirrored observations of the rollout from a linear obs mirror: out[r] = M_obs obs[r] for rows r < rows (T*N), in double
+// (the reference mirrors float32 rows in numpy float64 and casts the result back: my_pybullet_envs/utils.py:334-357);
+// zero entries of M_obs are skipped
+__global__ __launch_bounds__(256) void k_mirror_rows(const float* obs, const float* m, float* out, int64_t rows, int O) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rows * O) return;
+    const int64_t r = idx / O;
+    const int i = (int)(idx - r * O);
+    const float* x = obs + r * O;
+    const float* mi = m + (size_t)i * O;
+    double s = 0.0;
+    for (int j = 0; j < O; ++j) {
+        const float w = mi[j];
+        if (w != 0.f) s += (double)w * (double)x[j];
+    }
+    out[idx] = (float)s;
+}
+
 // --------------------------------------------------------------------------------- forward
 // GW (sg_gemm.hpp): the trunk's parameter block is read from global memory by the layer GEMMs instead of being staged
 // into LDS -- the general-shape instances for trunks larger than a CU's LDS (run-time extents only: KO = KH = 0).
-template <int MT, int KO, int KH, bool GW = false>
+// SYM: t = 2 is the mirrored column -- the actor trunk's parameters on the mirrored rows Xm, outputs to stacks 2.
+template <int MT, int KO, int KH, bool GW = false, bool SYM = false>
 __device__ __forceinline__ void sg_ppo_fwd_body(const PpoArgs& a, const int t, const int bx) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int R = 16 * MT;
@@ -117,7 +160,8 @@ __device__ __forceinline__ void sg_ppo_fwd_body(const PpoArgs& a, const int t, c
     // with compile-time KO/KH the four extents below fold to constants
     const SgPolicyDesc& d = a.d;
     const int tid = threadIdx.x;
-    const SgTrunk tr = d.trunk[t];
+    const bool mirror = SYM && t == 2;
+    const SgTrunk tr = d.trunk[mirror ? 0 : t];
     // (run-time instances: the trunk's OWN hidden width -- a critic rebuilt by Policy.reset_critic differs from the actors)
     const int Op = (KO > 0 && KH > 0) ? 16 * KO : d.Op, Hp = (KO > 0 && KH > 0) ? 16 * KH : tr.Hp;
     const int ldO = Op + 4, ldH = Hp + 4, ldP = a.ldP;
@@ -131,7 +175,7 @@ __device__ __forceinline__ void sg_ppo_fwd_body(const PpoArgs& a, const int t, c
     float4 wv[12];
     if (!GW) sg_stage_issue<12>(wv, a.params + tr.off, tr.size / 4);
     {   // the row tile: contiguous in the epoch's permuted copy
-        const float4* gx = reinterpret_cast<const float4*>(a.X + (size_t)row0 * ldO);
+        const float4* gx = reinterpret_cast<const float4*>((mirror ? a.Xm : a.X) + (size_t)row0 * ldO);
         float4* lx = reinterpret_cast<float4*>(X);
         for (int i = tid; i < R * ldO / 4; i += blockDim.x) lx[i] = gx[i];
     }
@@ -168,6 +212,11 @@ template <int MT, int KO, int KH, bool GW = false>
 __global__ __launch_bounds__(512) void k_ppo_fwd(PpoArgs a) {
     sg_ppo_fwd_body<MT, KO, KH, GW>(a, blockIdx.y, blockIdx.x);
 }
+// Policy with the mirror-symmetry loss: grid (row groups, 3) -- actor, critic, actor on the mirrored rows
+template <int MT, int KO, int KH, bool GW = false>
+__global__ __launch_bounds__(512) void k_ppo_fwd_sym(PpoArgs a) {
+    sg_ppo_fwd_body<MT, KO, KH, GW, true>(a, blockIdx.y, blockIdx.x);
+}
 
 // -------------------------------------------------------------------------------- backward
 // FUSED (Policy: the actor and critic trunks do not depend on each other's outputs): the workgroup stages the
@@ -184,8 +233,17 @@ __global__ __launch_bounds__(512) void k_ppo_fwd(PpoArgs a) {
 // stacks and the loss code below is unchanged: results are bit-identical to the two-launch step.  Both workgroups wait for each
 // other, so they must be resident together: they are neighbours in dispatch order (trunk index fastest) and the launch is only
 // used when all its workgroups fit the chip at once; the spin is bounded by the wall clock all the same.
-template <int MT, int KO, int KH, bool FUSED, bool GW = false, bool PAIR = false>
+// SYM (Policy, two-launch form, grid (row groups, 3)): the mirror-symmetry loss coef * mean((M_a mu(s) - mu(s_m))^2)
+// (a2c/algo/ppo.py:110-143).  Column 2 is the actor trunk on the mirrored rows (its forward came from k_ppo_fwd_sym).
+// Both actor columns read both head stacks and form e = M_a mu(s) - mu(s_m) per row.  The reference mirrors mu(s) through
+// numpy (mirror_obsact_batch, my_pybullet_envs/utils.py:334-357: .detach().numpy() -> torch.Tensor), so M_a mu(s) is a
+// constant of the loss and the gradient flows through mu(s_m) alone: the mirrored column back-propagates -sym_c e through
+// the actor weights on Xm and writes its partial gradient to slab G + row group (k_ppo_reduce_sym adds those slabs over the
+// actor's range only).  The critic and the log-std get nothing from it; the actor column records sum(e^2) / A as the 4th loss
+// sum and is otherwise unchanged.
+template <int MT, int KO, int KH, bool FUSED, bool GW = false, bool PAIR = false, bool SYM = false>
 __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, const int bx) {
+    static_assert(!(SYM && (FUSED || PAIR)), "the symmetric step runs the two-launch form");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // (No spare workgroup for Adam's bias corrections any more: with G x trunks = 256 row-group blocks, two extra blocks
     // made 258 for 256 CUs, and whenever the dispatcher doubled two row groups up on one CU before the spare blocks had
@@ -195,7 +253,8 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
     // with compile-time KO/KH the four extents below fold to constants
     const SgPolicyDesc& d = a.d;
     const int tid = threadIdx.x;
-    const SgTrunk tr = d.trunk[t];
+    const bool mirror = SYM && t == 2;             // the actor trunk on the mirrored rows
+    const SgTrunk tr = d.trunk[mirror ? 0 : t];
     const int Op = (KO > 0 && KH > 0) ? 16 * KO : d.Op, Hp = (KO > 0 && KH > 0) ? 16 * KH : tr.Hp;   // the trunk's own width
     const bool critic = t == d.n_trunks - 1;
     const bool mlp = d.kind == SG_POLICY_MLP;
@@ -214,8 +273,10 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
     float* SC = ACT + ((R * A + 3) & ~3);          // [4][R]
     float* ROWL = SC + 4 * R;                      // [2][R]
     int* VALID = reinterpret_cast<int*>(ROWL + 2 * R);
+    float* OM = reinterpret_cast<float*>(VALID + R);   // SYM: the other actor column's head outputs, then e
+    float* MA = OM + R * ldP;                          // SYM: M_a [A][A]
     const int row0 = bx * R;
-    float* slab = a.slabs + (size_t)bx * a.slab_stride;
+    float* slab = a.slabs + (size_t)(mirror ? a.G + bx : bx) * a.slab_stride;
 
     SG_PPO_STAMP(8);
     SG_PPO_WALL(6);
@@ -227,23 +288,25 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
     if (!GW) sg_stage_issue<12>(wv, a.params + tr.off + w_first, wfl / 4);
     constexpr int UX = MT <= 2 ? 4 : 8;          // float4 per thread for an [R][ld <= 116] tile at 256 threads
     constexpr int UO = MT <= 2 ? 2 : 4;          // ... for an [R][ldP <= 64] tile
-    const int ta = critic ? t : 0;
+    const int ta = critic ? t : (mirror ? 2 : 0);
     const bool two_heads = !critic && !mlp;
-    const float* gX = a.X + (size_t)row0 * ldO;
+    const float* gX = (mirror ? a.Xm : a.X) + (size_t)row0 * ldO;
     const float* gH1 = a.H1[t] + (size_t)row0 * ldH;
     const float* gH2 = a.H2[t] + (size_t)row0 * ldH;
     const float* gO0 = a.OUT[ta] + (size_t)row0 * ldP;
     const float* gO1 = a.OUT[two_heads ? 1 : ta] + (size_t)row0 * ldP;
-    float4 xv[UX], h1v[UX], h2v[UX], o0v[UO], o1v[UO];
+    const float* gOM = SYM ? a.OUT[mirror ? 0 : 2] + (size_t)row0 * ldP : nullptr;
+    float4 xv[UX], h1v[UX], h2v[UX], o0v[UO], o1v[UO], omv[UO];
     sg_stage_issue<UX>(xv, gX, R * ldO / 4);
     if (!FUSED) {
         sg_stage_issue<UX>(h1v, gH1, R * ldH / 4);
         sg_stage_issue<UX>(h2v, gH2, R * ldH / 4);
         sg_stage_issue<UO>(o0v, gO0, R * ldP / 4);
         if (two_heads) sg_stage_issue<UO>(o1v, gO1, R * ldP / 4);
+        if (SYM && !critic) sg_stage_issue<UO>(omv, gOM, R * ldP / 4);
     }
     float actv[2] = {0.f, 0.f}, scv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!critic) {
+    if (!critic && !mirror) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) { const int i = tid + u * 256; actv[u] = a.ACT[(size_t)row0 * A + (i < R * A ? i : 0)]; }
     }
@@ -258,8 +321,12 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
         sg_stage_commit<UX>(H2, h2v, gH2, R * ldH / 4);
         sg_stage_commit<UO>(O0, o0v, gO0, R * ldP / 4);
         if (two_heads) sg_stage_commit<UO>(O1, o1v, gO1, R * ldP / 4);
+        if (SYM && !critic) {
+            sg_stage_commit<UO>(OM, omv, gOM, R * ldP / 4);
+            for (int i = tid; i < A * A; i += blockDim.x) MA[i] = a.MA[i];
+        }
     }
-    if (!critic) {
+    if (!critic && !mirror) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) { const int i = tid + u * 256; if (i < R * A) ACT[i] = actv[u]; }
         for (int i = tid + 512; i < R * A; i += blockDim.x) ACT[i] = a.ACT[(size_t)row0 * A + i];
@@ -323,8 +390,29 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
     }
     SG_PPO_STAMP(9);
 
+    if (SYM && !critic) {
+        // e = M_a mu(s) - mu(s_m), zero on rows past the minibatch.  The actor column keeps e in OM; the mirrored column turns
+        // its own head tile into d loss / d mu(s_m) = -sym_c e (zero padding columns: the head GEMMs read them).  Every
+        // element is read and rewritten by the thread that owns it; the other operand tile is only read.
+        float* own = mirror ? O0 : OM;
+        const float* mu = mirror ? OM : O0;
+        for (int i = tid; i < R * tr.Pp; i += blockDim.x) {
+            const int r = i / tr.Pp, k = i - r * tr.Pp;
+            float e = 0.f;
+            if (k < A && VALID[r]) {
+                float s = 0.f;
+                for (int j = 0; j < A; ++j) s += MA[k * A + j] * mu[r * ldP + j];
+                e = s - (mirror ? O0 : OM)[r * ldP + k];
+            }
+            own[r * ldP + k] = mirror ? -a.sym_c * e : e;
+        }
+        __syncthreads();
+    }
+
     // ---- loss and d(loss)/d(head outputs)  (a2c/algo/ppo.py:92-106)
-    if (critic) {
+    if (mirror) {
+        // (no PPO loss on the mirrored rows: d/d mu(s_m) is already in O0)
+    } else if (critic) {
         if (tid < R) {
             const int r = tid;
             const float v = O0[r * ldP];
@@ -474,22 +562,28 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
     }
     __syncthreads();
     SG_PPO_STAMP(10);
-    float* dout = (critic || t == 0) ? O0 : O1;     // this trunk's d loss / d head outputs
+    float* dout = (critic || t == 0 || mirror) ? O0 : O1;     // this trunk's d loss / d head outputs
     // loss sums of this row group (recorded once: by the critic and by actor trunk 0)
     if (tid < 64 && (critic || t == 0)) {   // first wave: R <= 64 row losses, one per lane
         float s0 = tid < R ? ROWL[tid] : 0.f, s1 = (tid < R && !critic) ? ROWL[R + tid] : 0.f;
         s0 = sg_wave_sum(s0); s1 = sg_wave_sum(s1);
+        float s3 = 0.f;
+        if (SYM) {   // sum of e^2 / A over the row group: the symmetry loss is this over B
+            if (tid < R && !critic)
+                for (int k = 0; k < A; ++k) s3 += OM[tid * ldP + k] * OM[tid * ldP + k];
+            s3 = sg_wave_sum(s3) / (float)A;
+        }
         if (tid == 0) {
             float* ls = slab + d.total;
             if (critic) ls[0] = s0;
-            else { ls[1] = s0; ls[2] = s1; }
+            else { ls[1] = s0; ls[2] = s1; if (SYM) ls[3] = s3; }
         }
     }
     float* g = slab + tr.off;
     // head weight / bias gradients (needs h2 before it is overwritten)
     sg_grad_tn<MT, (MT >= 2 ? 8 : 0), true>(dout, ldP, H2, ldH, tr.Pp, Hp, g + tr.wh, ldH, false);
     sg_colsum(dout, ldP, R, tr.Pp, g + tr.bh, false);
-    if (tr.EX) sg_colsum(O1, ldP, R, SG_PAD16(tr.EX), g + tr.ex, false);
+    if (tr.EX && !mirror) sg_colsum(O1, ldP, R, SG_PAD16(tr.EX), g + tr.ex, false);
     SG_LDS_SYNC();
     SG_PPO_STAMP(11);
     {
@@ -522,6 +616,11 @@ template <int MT, int KO, int KH, bool FUSED = false, bool GW = false>
 __global__ __launch_bounds__(512) void k_ppo_bwd(PpoArgs a) {
     sg_ppo_bwd_body<MT, KO, KH, FUSED, GW>(a, blockIdx.y, blockIdx.x);
 }
+// Policy with the mirror-symmetry loss: grid (row groups, 3), after k_ppo_fwd_sym
+template <int MT, int KO, int KH, bool GW = false>
+__global__ __launch_bounds__(512) void k_ppo_bwd_sym(PpoArgs a) {
+    sg_ppo_bwd_body<MT, KO, KH, false, GW, false, true>(a, blockIdx.y, blockIdx.x);
+}
 
 // SplitPolicy, ONE launch per step when its 3 G workgroups fit the chip together: every trunk's fused forward + loss + backward,
 // the two actors of a row group joined by the hand-off described at sg_ppo_bwd_body.  Workgroup 3 g + y is trunk y of row group
@@ -547,12 +646,16 @@ __global__ __launch_bounds__(512) void k_ppo_fwd_critic(PpoArgs a) {
 // grad[i] = sum over slabs; part[block] = sum of squares of this block's grads.  A block owns 64 consecutive
 // parameters; its 4 waves each sum a quarter of the slabs (16 independent loads in flight per lane, i.e. two
 // round trips for 128 slabs instead of sixteen) and combine through LDS in a fixed order.
+// SYM: parameters [lo2, hi2) (the actor trunk up to its log-std) also sum the n_slabs slabs behind the first n_slabs (the
+// mirrored column's); everything else reads the first n_slabs only.
 #define SG_PPO_REDUCE_PARAMS 64
-__global__ __launch_bounds__(256) void k_ppo_reduce(const float* slabs, int n_slabs, int slab_stride, int total,
-                                                    float* grad, float* part) {
+template <bool SYM>
+__device__ __forceinline__ void sg_ppo_reduce_body(const float* slabs, int n_slabs_, int slab_stride, int total,
+                                                   float* grad, float* part, int lo2, int hi2) {
     __shared__ float red[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blockIdx.x * SG_PPO_REDUCE_PARAMS + lane;
+    const int n_slabs = (SYM && i >= lo2 && i < hi2) ? 2 * n_slabs_ : n_slabs_;
     float g = 0.f;
     if (i < total + 8) {
         for (int s0 = wave; s0 < n_slabs; s0 += 64) {
@@ -576,6 +679,14 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(const float* slabs, int n_sl
         if (lane == 0) part[blockIdx.x] = sq;
     }
 }
+__global__ __launch_bounds__(256) void k_ppo_reduce(const float* slabs, int n_slabs, int slab_stride, int total,
+                                                    float* grad, float* part) {
+    sg_ppo_reduce_body<false>(slabs, n_slabs, slab_stride, total, grad, part, 0, 0);
+}
+__global__ __launch_bounds__(256) void k_ppo_reduce_sym(const float* slabs, int n_slabs, int slab_stride, int total,
+                                                        float* grad, float* part, int lo2, int hi2) {
+    sg_ppo_reduce_body<true>(slabs, n_slabs, slab_stride, total, grad, part, lo2, hi2);
+}
 
 // Adam scalars of the update's first step (every later step's are prepared by the preceding k_ppo_adam)
 __global__ void k_opt_prepare_first(SgOptState* st) { sg_opt_prepare(st, st->t0 + 1); }
@@ -593,10 +704,12 @@ __global__ __launch_bounds__(256) void k_sumsq(const float* grad, int total, flo
 
 // clip_grad_norm_ + Adam (a2c/algo/ppo.py:143-145; torch.optim.Adam single-tensor math).
 // (argument order: everything the first instructions need sits in the 16 dwords the command processor preloads)
-__global__ __launch_bounds__(256) void k_ppo_adam(float* params, float* m, float* v, const float* grad,
-                                                  const float* part, int n_part, int total,
-                                                  const SgOptState* st, int k1, float eps, float max_norm,
-                                                  float inv_mb, double* loss_acc) {
+// NL: loss sums carried in the gradient's tail (3; 4 with the symmetry loss)
+template <int NL>
+__device__ __forceinline__ void sg_ppo_adam_body(float* params, float* m, float* v, const float* grad,
+                                                 const float* part, int n_part, int total,
+                                                 const SgOptState* st, int k1, float eps, float max_norm,
+                                                 float inv_mb, double* loss_acc) {
     __shared__ float s_coef;
     // Adam step t = st->t0 + k1; its bias-correction scalars were prepared in slot t & 1 by this step's k_ppo_bwd
     const int t = st->t0 + k1;
@@ -626,10 +739,22 @@ __global__ __launch_bounds__(256) void k_ppo_adam(float* params, float* m, float
         m[i] = mi;
         v[i] = vi;
     }
-    if (blockIdx.x == 0 && threadIdx.x < 3)  // value_loss.item() etc. are float32, summed in Python doubles
+    if (blockIdx.x == 0 && threadIdx.x < NL)  // value_loss.item() etc. are float32, summed in Python doubles
         loss_acc[threadIdx.x] += (double)(grad[total + threadIdx.x] * inv_mb);
     // the next step's bias corrections (double pow) into the other slot: nobody reads that slot before the next k_ppo_adam
     if (blockIdx.x == 0 && threadIdx.x == 64) sg_opt_prepare(const_cast<SgOptState*>(st), t + 1);
+}
+__global__ __launch_bounds__(256) void k_ppo_adam(float* params, float* m, float* v, const float* grad,
+                                                  const float* part, int n_part, int total,
+                                                  const SgOptState* st, int k1, float eps, float max_norm,
+                                                  float inv_mb, double* loss_acc) {
+    sg_ppo_adam_body<3>(params, m, v, grad, part, n_part, total, st, k1, eps, max_norm, inv_mb, loss_acc);
+}
+__global__ __launch_bounds__(256) void k_ppo_adam_sym(float* params, float* m, float* v, const float* grad,
+                                                      const float* part, int n_part, int total,
+                                                      const SgOptState* st, int k1, float eps, float max_norm,
+                                                      float inv_mb, double* loss_acc) {
+    sg_ppo_adam_body<4>(params, m, v, grad, part, n_part, total, st, k1, eps, max_norm, inv_mb, loss_acc);
 }
 
 // adv = returns[:-1] - value_preds[:-1]; sums for mean / unbiased std (a2c/algo/ppo.py:66-68)
