@@ -205,6 +205,28 @@ SG_API int sg_ppo_set_mirrored_obs(sg_ppo *a, const float *host, int64_t count);
 /* the last update's symmetry_loss.item() averaged over its ppo_epoch * num_mini_batch steps (0 when the loss is off) */
 SG_API int sg_ppo_last_symmetry_loss(sg_ppo *a, float *out);
 
+/* ---------------------------------------------------------------------- A2C */
+typedef struct {
+    float value_loss_coef;
+    float entropy_coef;
+    float lr;
+    float eps;
+    float alpha;
+    float max_grad_norm;
+} sg_a2c_config;
+/* A2C_ACKTR(actor_critic, value_loss_coef, entropy_coef, lr, eps, alpha, max_grad_norm, acktr=False)  a2c/algo/a2c_acktr.py:30-51,
+ * built by a2c/main.py:123-131 (--algo a2c): RMSprop(lr, eps, alpha; centered False, momentum 0), square_avg starting at zero.
+ * The handle is an sg_ppo in A2C mode: sg_ppo_update (perms == NULL only; out3 == NULL queues it), sg_ppo_set_lr, sg_ppo_destroy
+ * and sg_results_publish (step count 1) take it; sg_ppo_get_adam / sg_ppo_set_adam / sg_ppo_set_symmetry /
+ * sg_ppo_set_mirrored_obs refuse it.  Refused here: SplitPolicy, and a context with a communicator of world > 1.
+ * One update (a2c/algo/a2c_acktr.py:52-102): evaluate_actions on all T*N rollout rows with the current parameters,
+ * adv = returns[:-1] - values, out3 = {mean(adv^2), -mean(adv.detach() * logp), mean(entropy)}, loss = out3[0] * vcoef +
+ * out3[1] - out3[2] * ecoef, clip_grad_norm_(max_grad_norm), one RMSprop step. */
+SG_API int sg_a2c_create(sg_ctx *ctx, sg_policy *p, const sg_a2c_config *cfg, sg_ppo **out);
+/* RMSprop state for checkpoint/parity: square_avg flat [n] in state_dict order; *step = optimizer steps taken. */
+SG_API int sg_a2c_get_rmsprop(sg_ppo *a, float *square_avg, int64_t n, int64_t *step);
+SG_API int sg_a2c_set_rmsprop(sg_ppo *a, const float *square_avg, int64_t n, int64_t step);
+
 /* ------------------------------------------------------------ discriminator */
 /* Discriminator(input_dim, hidden_dim, device) a2c/algo/gail.py:35-51; Adam(lr 1e-3, eps 1e-8). */
 SG_API int sg_disc_create(sg_ctx *ctx, int input_dim, int hidden_dim, sg_disc **out);

@@ -33,6 +33,11 @@ class PPOConfig(C.Structure):
                 ("use_clipped_value_loss", C.c_int)]
 
 
+class A2CConfig(C.Structure):
+    _fields_ = [("value_loss_coef", C.c_float), ("entropy_coef", C.c_float), ("lr", C.c_float), ("eps", C.c_float),
+                ("alpha", C.c_float), ("max_grad_norm", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol of include/simgan_hip.h
 PROTOTYPES = {
     "sg_last_error": (C.c_char_p, []),
@@ -80,6 +85,9 @@ PROTOTYPES = {
     "sg_ppo_set_symmetry": (C.c_int, [H, C.c_float, c_float_p, c_float_p]),
     "sg_ppo_set_mirrored_obs": (C.c_int, [H, c_float_p, C.c_int64]),
     "sg_ppo_last_symmetry_loss": (C.c_int, [H, c_float_p]),
+    "sg_a2c_create": (C.c_int, [H, H, C.POINTER(A2CConfig), C.POINTER(H)]),
+    "sg_a2c_get_rmsprop": (C.c_int, [H, c_float_p, C.c_int64, c_i64_p]),
+    "sg_a2c_set_rmsprop": (C.c_int, [H, c_float_p, C.c_int64, C.c_int64]),
     "sg_disc_create": (C.c_int, [H, C.c_int, C.c_int, C.POINTER(H)]),
     "sg_disc_destroy": (C.c_int, [H]),
     "sg_disc_num_params": (C.c_int, [H, c_i64_p]),

@@ -260,6 +260,9 @@ struct sg_ppo {
     float* d_mrows = nullptr;      // [T*N][O] the mirrored rollout observations the next / last update reads
     int64_t mrows_cap = 0;         // floats
     int64_t mrows_host = 0;        // floats sg_ppo_set_mirrored_obs uploaded for the next update (0: none pending)
+    // A2C (sg_a2c_create): one RMSprop step over the whole rollout per update; d_v holds square_avg, opt_t counts the steps
+    bool a2c = false;
+    float alpha = 0.f;
 };
 
 struct sg_disc {

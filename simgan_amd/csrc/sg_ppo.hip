@@ -15,6 +15,11 @@
 // k_ppo_reduce_sym -> k_ppo_adam_sym: the two-launch form with a third grid column, the actor trunk on the mirrored rows.
 // Everything from the first epoch gather on is captured into a hipGraph once and replayed per update (single GPU;
 // with a communicator the RCCL calls are issued directly between the kernels).
+//
+// A2C (sg_a2c_create: a mode of the same object, a2c/algo/a2c_acktr.py:30-102 with acktr=False), one update:
+//   k_a2c_gather                                    the rollout's T*N rows in their own order (no permutation, no advantages)
+//   per chunk of <= SG_A2C_CHUNK_ROWS rows:  k_ppo_fwd -> k_a2c_bwd -> k_a2c_reduce (adds to the gradient)
+//   then         k_a2c_rmsprop                      clip + RMSprop, the update's one optimizer step
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -75,6 +80,16 @@ static size_t ppo_bwd_sym_lds(const SgPolicyDesc& d, int MT, bool gw) {
     return sizeof(float) * ((gw ? 0 : (size_t)max_bwd_floats(d)) + R * d.ldO + 2 * R * d.ldH + 3 * R * stack_ldP(d) +
                             ((R * d.A + 3) & ~3) + 7 * R + ((d.A * d.A + 3) & ~3));
 }
+
+// k_a2c_bwd: the unfused backward's tiles (w2 on in LDS), whatever ppo_fused says
+static size_t a2c_bwd_lds(const SgPolicyDesc& d, int MT, bool gw) {
+    const int R = 16 * MT;
+    return sizeof(float) * ((gw ? 0 : (size_t)max_bwd_floats(d)) + R * d.ldO + 2 * R * d.ldH + 2 * R * stack_ldP(d) +
+                            ((R * d.A + 3) & ~3) + 7 * R);
+}
+// rows of the rollout one A2C forward / backward / reduce pass covers: the slabs and row stacks are sized for this many rows
+// whatever T*N is (the north-star PPO minibatch: 65,536 rows / 16)
+#define SG_A2C_CHUNK_ROWS 4096
 
 // shape-specialised instances for the shipped configurations at the row-group
 // size the launch heuristic picks for them, plus run-time-shape fallbacks
@@ -179,6 +194,24 @@ static void launch_ppo_bwd_sym(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 
     }
 }
 
+// A2C's backward: the north-star shape (obs 47, h64) specialised, run-time shapes and the global-weight instances otherwise
+static void launch_a2c_bwd(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 grid, size_t lds, const PpoArgs& pa, bool gw) {
+    const int ko = d.Op / 16, kh = d.Hc == d.H ? d.Hp / 16 : 0;
+    const dim3 block(ppo_block_threads(MT));
+    if (gw) {
+        if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<2, 0, 0, true>), grid, block, lds, pa);
+        else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<1, 0, 0, true>), grid, block, lds, pa);
+    } else if (MT == 2 && ko == 3 && kh == 4) {
+        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<2, 3, 4>), grid, block, lds, pa);
+    } else if (MT == 1 && ko == 3 && kh == 4) {
+        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<1, 3, 4>), grid, block, lds, pa);
+    } else if (MT == 2) {
+        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<2, 0, 0>), grid, block, lds, pa);
+    } else {
+        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<1, 0, 0>), grid, block, lds, pa);
+    }
+}
+
 // ---------------------------------------------------------------------------------- PPO API
 extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg, sg_ppo** out) {
     SG_DEVICE_WIDE();
@@ -209,6 +242,29 @@ extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg
     SG_CHECK(hipMemcpyAsync(a->d_state, &st, sizeof st, hipMemcpyHostToDevice, ctx->stream));
     SG_CHECK(hipStreamSynchronize(ctx->stream));
     sg_ctx_learner_born(ctx);
+    *out = a;
+    return 0;
+}
+
+// a2c/main.py:123-131 -> A2C_ACKTR(actor_critic, value_loss_coef, entropy_coef, lr, eps, alpha, max_grad_norm), acktr=False
+// (a2c/algo/a2c_acktr.py:30-51: RMSprop, square_avg starting at zero).  Policy (MLP) on one rank only.
+extern "C" int sg_a2c_create(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg, sg_ppo** out) {
+    SG_REQUIRE(ctx && p && cfg && out, "sg_a2c_create: NULL argument");
+    SG_REQUIRE(p->desc.kind == SG_POLICY_MLP, "sg_a2c_create: A2C is implemented for Policy (MLP) only, not for SplitPolicy");
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_a2c_create: A2C runs on one rank: this context has a communicator of "
+               "world %d (data-parallel A2C is not implemented)", ctx->world);
+    SG_REQUIRE(cfg->alpha >= 0.f && cfg->alpha <= 1.f && cfg->eps >= 0.f && cfg->max_grad_norm > 0.f,
+               "sg_a2c_create: alpha must lie in [0, 1], eps >= 0 and max_grad_norm > 0 (got %g, %g, %g)", (double)cfg->alpha,
+               (double)cfg->eps, (double)cfg->max_grad_norm);
+    sg_ppo_config pc;
+    memset(&pc, 0, sizeof pc);
+    pc.ppo_epoch = 1; pc.num_mini_batch = 1;   // one optimizer step per update: the results ring's step count
+    pc.value_loss_coef = cfg->value_loss_coef; pc.entropy_coef = cfg->entropy_coef;
+    pc.lr = cfg->lr; pc.eps = cfg->eps; pc.max_grad_norm = cfg->max_grad_norm;
+    sg_ppo* a = nullptr;
+    SG_TRY(sg_ppo_create(ctx, p, &pc, &a));
+    a->a2c = true;
+    a->alpha = cfg->alpha;
     *out = a;
     return 0;
 }
@@ -247,6 +303,7 @@ extern "C" int sg_ppo_set_lr(sg_ppo* a, float lr) {
 // before every update (sg_ppo_set_mirrored_obs).
 extern "C" int sg_ppo_set_symmetry(sg_ppo* a, float coef, const float* m_obs, const float* m_act) {
     SG_REQUIRE(a, "sg_ppo_set_symmetry: NULL argument");
+    SG_REQUIRE(!a->a2c, "sg_ppo_set_symmetry: the mirror-symmetry loss is a PPO option; this is an A2C handle");
     SG_REQUIRE(coef >= 0.f && coef < INFINITY, "sg_ppo_set_symmetry: symmetry_coef must be finite and >= 0 (got %g)", (double)coef);
     sg_ctx* ctx = a->ctx;
     const SgPolicyDesc& d = a->policy->desc;
@@ -276,6 +333,7 @@ extern "C" int sg_ppo_set_symmetry(sg_ppo* a, float coef, const float* m_obs, co
 // the caller: host[T*N][O] float32, consumed by the next sg_ppo_update (which requires count == T*N*O)
 extern "C" int sg_ppo_set_mirrored_obs(sg_ppo* a, const float* host, int64_t count) {
     SG_REQUIRE(a && host, "sg_ppo_set_mirrored_obs: NULL argument");
+    SG_REQUIRE(!a->a2c, "sg_ppo_set_mirrored_obs: the mirror-symmetry loss is a PPO option; this is an A2C handle");
     SG_REQUIRE(count > 0 && count % a->policy->desc.O == 0, "sg_ppo_set_mirrored_obs: %lld floats is not a whole number of %d-float rows",
                (long long)count, a->policy->desc.O);
     sg_ctx* ctx = a->ctx;
@@ -314,6 +372,7 @@ extern "C" int sg_ppo_last_perms(sg_ppo* a, int64_t* perms, int64_t count) {
 
 extern "C" int sg_ppo_get_adam(sg_ppo* a, float* m, float* v, int64_t n, int64_t* step) {
     SG_REQUIRE(a && m && v && step, "sg_ppo_get_adam: NULL argument");
+    SG_REQUIRE(!a->a2c, "sg_ppo_get_adam: an A2C handle has RMSprop state, not Adam's (sg_a2c_get_rmsprop)");
     const SgPolicyDesc& d = a->policy->desc;
     SG_REQUIRE(n == sg_policy_flat_count(d), "sg_ppo_get_adam: bad length");
     std::vector<float> pm(d.total), pv(d.total);
@@ -328,6 +387,7 @@ extern "C" int sg_ppo_get_adam(sg_ppo* a, float* m, float* v, int64_t n, int64_t
 
 extern "C" int sg_ppo_set_adam(sg_ppo* a, const float* m, const float* v, int64_t n, int64_t step) {
     SG_REQUIRE(a && m && v, "sg_ppo_set_adam: NULL argument");
+    SG_REQUIRE(!a->a2c, "sg_ppo_set_adam: an A2C handle has RMSprop state, not Adam's (sg_a2c_set_rmsprop)");
     const SgPolicyDesc& d = a->policy->desc;
     SG_REQUIRE(n == sg_policy_flat_count(d), "sg_ppo_set_adam: bad length");
     std::vector<float> pm(d.total, 0.f), pv(d.total, 0.f);
@@ -347,8 +407,180 @@ extern "C" int sg_ppo_set_adam(sg_ppo* a, const float* m, const float* v, int64_
     return 0;
 }
 
+// square_avg [n] flat in state_dict order, *step = completed RMSprop steps
+extern "C" int sg_a2c_get_rmsprop(sg_ppo* a, float* square_avg, int64_t n, int64_t* step) {
+    SG_REQUIRE(a && square_avg && step, "sg_a2c_get_rmsprop: NULL argument");
+    SG_REQUIRE(a->a2c, "sg_a2c_get_rmsprop: not an A2C handle (sg_ppo_get_adam)");
+    const SgPolicyDesc& d = a->policy->desc;
+    SG_REQUIRE(n == sg_policy_flat_count(d), "sg_a2c_get_rmsprop: bad length");
+    std::vector<float> pv(d.total);
+    SG_CHECK(hipSetDevice(a->ctx->device));
+    SG_CHECK(hipStreamSynchronize(a->ctx->stream));
+    SG_COPY_SYNC(a->ctx, pv.data(), a->d_v, sizeof(float) * d.total, hipMemcpyDeviceToHost);
+    sg_policy_unpad(d, pv.data(), square_avg);
+    *step = a->opt_t;
+    return 0;
+}
+
+extern "C" int sg_a2c_set_rmsprop(sg_ppo* a, const float* square_avg, int64_t n, int64_t step) {
+    SG_REQUIRE(a && square_avg, "sg_a2c_set_rmsprop: NULL argument");
+    SG_REQUIRE(a->a2c, "sg_a2c_set_rmsprop: not an A2C handle (sg_ppo_set_adam)");
+    const SgPolicyDesc& d = a->policy->desc;
+    SG_REQUIRE(n == sg_policy_flat_count(d), "sg_a2c_set_rmsprop: bad length");
+    SG_REQUIRE(step >= 0, "sg_a2c_set_rmsprop: step out of range");
+    std::vector<float> pv(d.total, 0.f);
+    sg_policy_pad(d, square_avg, pv.data());
+    SG_CHECK(hipSetDevice(a->ctx->device));
+    SG_CHECK(hipStreamSynchronize(a->ctx->stream));
+    SG_COPY_SYNC(a->ctx, a->d_v, pv.data(), sizeof(float) * d.total, hipMemcpyHostToDevice);
+    a->opt_t = step;
+    return 0;
+}
+
+// A2C_ACKTR.update(rollouts), acktr=False (a2c/algo/a2c_acktr.py:52-102): evaluate_actions on all T*N rows with the current
+// parameters, adv = returns[:-1] - values, loss = vcoef mean(adv^2) + (-mean(adv.detach() logp)) - ecoef mean(ent), one
+// clip_grad_norm_ + RMSprop step.  The rows are taken in chunks of SG_A2C_CHUNK_ROWS; each chunk's slabs are added to the
+// gradient, so the scratch does not grow with T*N.
+static int a2c_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
+    sg_ctx* ctx = a->ctx;
+    const SgPolicyDesc& d = a->policy->desc;
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_ppo_update: A2C runs on one rank (this context's world is %d)", ctx->world);
+    const int64_t TN = (int64_t)r->T * r->N;
+    SG_REQUIRE(TN > 0 && TN < (1ll << 30), "sg_ppo_update: %lld rollout rows", (long long)TN);
+    SG_CHECK(hipSetDevice(ctx->device));
+    const int chunk = (int)std::min<int64_t>(TN, SG_A2C_CHUNK_ROWS);
+    const int n_chunks = (int)((TN + chunk - 1) / chunk);
+    // row-group size: PPO's heuristic at a minibatch of `chunk` rows (two grid columns: actor, critic)
+    int MT = ((size_t)((chunk + 15) / 16) * (size_t)(d.total + 8) * sizeof(float) > ((size_t)24 << 20) ||
+              ((chunk + 31) / 32) * d.n_trunks >= ctx->num_cu) ? 2 : 1;
+    if (const char* e = getenv("SG_PPO_ROWS")) {   // tuning knob
+        const int v = atoi(e);
+        if (v == 16 || v == 32) MT = v / 16;
+    }
+    const bool gw = sg_policy_needs_gw(ctx, d) || ppo_fwd_lds(d, 1, false) > (size_t)ctx->lds_bytes ||
+                    a2c_bwd_lds(d, 1, false) > (size_t)ctx->lds_bytes;
+    SG_REQUIRE(ppo_fwd_lds(d, 1, gw) <= (size_t)ctx->lds_bytes && a2c_bwd_lds(d, 1, gw) <= (size_t)ctx->lds_bytes,
+               "sg_ppo_update: the 16-row tiles of the A2C step do not fit LDS");
+    while (MT > 1 && (ppo_fwd_lds(d, MT, gw) > (size_t)ctx->lds_bytes || a2c_bwd_lds(d, MT, gw) > (size_t)ctx->lds_bytes)) MT /= 2;
+    const int R = 16 * MT;
+    const int G = (chunk + R - 1) / R;   // row groups of a full chunk: the slab count
+    const int mbp = G * R;
+    const int ldP = stack_ldP(d);
+    const int slab_stride = (d.total + 8 + 63) & ~63;
+    const int TNp = (int)TN + 64;        // slack rows: the last row tile reads up to R - 1 <= 63 rows past the rollout
+    const size_t slab_f = (size_t)G * slab_stride;
+    const size_t epoch_f = (size_t)TNp * (d.ldO + d.A + 4);
+    const size_t stack_f = (size_t)d.n_trunks * mbp * (2 * (size_t)d.ldH + ldP);
+    if (a->slabs_cap < slab_f || a->stacks_cap < epoch_f + stack_f) {
+        SG_CHECK(hipStreamSynchronize(ctx->stream));
+        if (a->d_slabs) SG_CHECK(sg_dev_free(a->d_slabs));
+        if (a->d_stacks) SG_CHECK(sg_dev_free(a->d_stacks));
+        SG_CHECK(sg_dev_malloc((void**)&a->d_slabs, sizeof(float) * slab_f));
+        SG_CHECK(sg_dev_malloc((void**)&a->d_stacks, sizeof(float) * (epoch_f + stack_f)));
+        a->slabs_cap = slab_f;
+        a->stacks_cap = epoch_f + stack_f;
+        a->scratch_key = 0;
+    }
+    // as for PPO: slab padding columns must read as zero, the copy's slack rows must be finite
+    const uint64_t key = ((uint64_t)G << 40) ^ ((uint64_t)slab_stride << 20) ^ ((uint64_t)mbp << 8) ^ (uint64_t)TNp ^ ((uint64_t)MT << 60) ^
+                         (1ull << 62);
+    if (a->scratch_key != key) {
+        SG_CHECK(hipMemsetAsync(a->d_slabs, 0, sizeof(float) * slab_f, ctx->stream));
+        SG_CHECK(hipMemsetAsync(a->d_stacks, 0, sizeof(float) * (epoch_f + stack_f), ctx->stream));
+        a->scratch_key = key;
+    }
+    hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 4);
+
+    float* epX = a->d_stacks;
+    float* epACT = epX + (size_t)TNp * d.ldO;
+    float* epSC = epACT + (size_t)TNp * d.A;
+    float* stk = a->d_stacks + epoch_f;
+
+    EpochGatherArgs ga;
+    memset(&ga, 0, sizeof ga);
+    ga.obs = r->d_field[SG_F_OBS]; ga.actions = r->d_field[SG_F_ACTIONS]; ga.ret = r->d_field[SG_F_RETURNS];
+    ga.TN = TN; ga.O = d.O; ga.Op = d.Op; ga.ldO = d.ldO; ga.A = d.A; ga.sc_stride = TNp;
+    ga.X = epX; ga.ACT = epACT; ga.SC = epSC;
+
+    PpoArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.d = d; pa.params = a->policy->d_params;
+    pa.sc_stride = TNp; pa.mbp = mbp; pa.inv_B = 1.0f / (float)TN;
+    pa.vcoef = a->cfg.value_loss_coef; pa.ecoef = a->cfg.entropy_coef;
+    pa.slabs = a->d_slabs; pa.slab_stride = slab_stride; pa.ldP = ldP;
+    pa.st = reinterpret_cast<SgOptState*>(a->d_state); pa.G = G; pa.k1 = 1;
+    for (int t = 0; t < d.n_trunks; ++t) {
+        pa.H1[t] = stk; stk += (size_t)mbp * d.ldH;
+        pa.H2[t] = stk; stk += (size_t)mbp * d.ldH;
+        pa.OUT[t] = stk; stk += (size_t)mbp * ldP;
+    }
+    const int wb_f = gw ? 0 : max_trunk_floats(d), wb_b = gw ? 0 : max_bwd_floats(d);
+    const size_t lds_f = ppo_fwd_lds(d, MT, gw), lds_b = a2c_bwd_lds(d, MT, gw);
+    const int nblk = (d.total + 8 + 255) / 256;
+    const int nblk_r = (d.total + 8 + SG_PPO_REDUCE_PARAMS - 1) / SG_PPO_REDUCE_PARAMS;
+    const double oma = 1.0 - (double)a->alpha;   // torch: value = 1 - alpha in Python doubles
+
+    auto enqueue_step = [&]() -> int {
+        hipLaunchKernelGGL(k_a2c_gather, dim3((unsigned)((TN + 63) / 64)), dim3(256), 0, ctx->stream, ga);
+        for (int c = 0; c < n_chunks; ++c) {
+            const int64_t rb = (int64_t)c * chunk;
+            const int cnt = (int)std::min<int64_t>(chunk, TN - rb);
+            const int Gc = (cnt + R - 1) / R;
+            pa.mb = cnt;
+            pa.X = epX + rb * d.ldO; pa.ACT = epACT + rb * d.A; pa.SC = epSC + rb;
+            pa.wbuf_floats = wb_f;
+            launch_ppo_fwd(ctx, MT, d, dim3(Gc, d.n_trunks), lds_f, pa, gw);
+            pa.wbuf_floats = wb_b;
+            launch_a2c_bwd(ctx, MT, d, dim3(Gc, d.n_trunks), lds_b, pa, gw);
+            SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_a2c_reduce, dim3(nblk_r), dim3(256), 0, a->d_slabs, Gc, slab_stride, d.total, a->d_grad,
+                      a->d_part, c > 0 ? 1 : 0);
+        }
+        SG_LAUNCH(ctx, SG_PROF_PPO_ADAM, k_a2c_rmsprop, dim3(nblk), dim3(256), 0, a->policy->d_params, a->d_v, a->d_grad, a->d_part,
+                  nblk_r, d.total, pa.st, a->alpha, (float)oma, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B, a->d_loss_acc);
+        return 0;
+    };
+    const char* genv = getenv("SG_PPO_GRAPH");
+    bool use_graph = !a->graph_refused && !ctx->use_comm && !ctx->profile && !(genv && !strcmp(genv, "0"));
+    if (use_graph) {
+        uint32_t fbits[6];
+        const float fv[6] = {a->alpha, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B};
+        memcpy(fbits, fv, sizeof fbits);
+        const uint64_t key[18] = {(uint64_t)(uintptr_t)a->d_slabs, (uint64_t)(uintptr_t)a->d_stacks, 0,
+                                  (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
+                                  (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)a->policy->d_params,
+                                  (uint64_t)TN, ((uint64_t)n_chunks << 32) | (uint64_t)chunk, ((uint64_t)MT << 32) | (uint64_t)G,
+                                  ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
+                                  ((uint64_t)fbits[4] << 32) | fbits[5], 0, 0, 0x413243ull + (gw ? 8 : 0) + (1ull << 7), 0, 0};
+        if (!a->steps_graph || memcmp(key, a->steps_graph_key, sizeof key) != 0) {
+            if (a->steps_graph) { SG_CHECK(hipGraphExecDestroy(a->steps_graph)); a->steps_graph = nullptr; }
+            if (sg_try_capture(ctx, &a->steps_graph, enqueue_step) != 0) {
+                a->graph_refused = true;
+                use_graph = false;
+            } else {
+                memcpy(a->steps_graph_key, key, sizeof key);
+            }
+        }
+        if (use_graph) SG_CHECK(hipGraphLaunch(a->steps_graph, ctx->stream));
+    }
+    if (!use_graph) SG_TRY(enqueue_step());
+    SG_CHECK(hipGetLastError());
+    a->opt_t += 1;
+    if (!out3) return 0;   // queued: the losses come through the results ring (step count 1)
+    double acc[3];
+    SG_TRY(sg_ctx_fetch_f64(ctx, a->d_loss_acc, acc, 3));
+    for (int i = 0; i < 3; ++i) out3[i] = (float)acc[i];
+    return 0;
+}
+
 extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_t n_perms, uint64_t seed, float out3[3]) {
     SG_REQUIRE(a && r, "sg_ppo_update: NULL argument");
+    if (a->a2c) {
+        SG_REQUIRE(!perms, "sg_ppo_update: an A2C update takes the rollout in its own order: perms must be NULL");
+        SG_REQUIRE(r->O == a->policy->desc.O && r->A == a->policy->desc.A,
+                   "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)", r->O, r->A,
+                   a->policy->desc.O, a->policy->desc.A);
+        return a2c_update(a, r, out3);
+    }
     sg_ctx* ctx = a->ctx;
     const SgPolicyDesc& d = a->policy->desc;
     SG_REQUIRE(r->O == d.O && r->A == d.A, "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)",

@@ -14,6 +14,9 @@
 //   k_ppo_reduce          slab sum per parameter (64 parameters per block, waves split the slabs), per-block
 //                         sum of squares.
 //   k_ppo_adam            clip coefficient max_norm/(||g||+1e-6) (<= 1), then Adam.
+// A2C (a2c/algo/a2c_acktr.py:52-102, acktr=False) reuses them: k_a2c_gather (the rollout in its own order), k_ppo_fwd,
+// k_a2c_bwd (the A2C loss variant of the backward body), k_a2c_reduce (adds each chunk's slabs to the gradient) and
+// k_a2c_rmsprop (clip + RMSprop).
 // Splitting forward / backward per trunk keeps every workgroup's LDS to one trunk's parameters
 // (the split policy's trunks are 69-98 KB each) and lets all trunks of all row groups run
 // concurrently: 2 x 128 workgroups for Policy, 3 x 128 for SplitPolicy at 4096-row minibatches.
@@ -77,16 +80,19 @@ struct EpochGatherArgs {
     float* Xm;
 };
 
-template <bool SYM = false>
+// ROLLOUT_ORDER (A2C): row i is rollout row i (no permutation) and only the return is copied into the per-row scalars
+template <bool SYM = false, bool ROLLOUT_ORDER = false>
 __device__ __forceinline__ void sg_ppo_epoch_gather_body(const EpochGatherArgs& a) {
     __shared__ int IDX[64];
     const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * 64;
     if (tid < 64) {
         const int64_t rr = row0 + tid;
-        const int idx = rr < a.TN ? (int)a.perm[rr] : -1;
+        const int idx = rr < a.TN ? (ROLLOUT_ORDER ? (int)rr : (int)a.perm[rr]) : -1;
         IDX[tid] = idx;
-        if (idx >= 0) {
+        if (ROLLOUT_ORDER) {
+            if (idx >= 0) a.SC[3 * (size_t)a.sc_stride + rr] = a.ret[idx];
+        } else if (idx >= 0) {
             a.SC[0 * (size_t)a.sc_stride + rr] = a.old_logp[idx];
             a.SC[1 * (size_t)a.sc_stride + rr] = a.adv[idx];
             a.SC[2 * (size_t)a.sc_stride + rr] = a.vpred[idx];
@@ -129,6 +135,7 @@ __device__ __forceinline__ void sg_ppo_epoch_gather_body(const EpochGatherArgs& 
 
 __global__ __launch_bounds__(256) void k_ppo_epoch_gather(EpochGatherArgs a) { sg_ppo_epoch_gather_body<false>(a); }
 __global__ __launch_bounds__(256) void k_ppo_epoch_gather_sym(EpochGatherArgs a) { sg_ppo_epoch_gather_body<true>(a); }
+__global__ __launch_bounds__(256) void k_a2c_gather(EpochGatherArgs a) { sg_ppo_epoch_gather_body<false, true>(a); }
 
 // mirrored observations of the rollout from a linear obs mirror: out[r] = M_obs obs[r] for rows r < rows (T*N), in double
 // (the reference mirrors float32 rows in numpy float64 and casts the result back: my_pybullet_envs/utils.py:334-357);
@@ -241,9 +248,13 @@ __global__ __launch_bounds__(512) void k_ppo_fwd_sym(PpoArgs a) {
 // the actor weights on Xm and writes its partial gradient to slab G + row group (k_ppo_reduce_sym adds those slabs over the
 // actor's range only).  The critic and the log-std get nothing from it; the actor column records sum(e^2) / A as the 4th loss
 // sum and is otherwise unchanged.
-template <int MT, int KO, int KH, bool FUSED, bool GW = false, bool PAIR = false, bool SYM = false>
+// A2C (Policy, two-launch form, a2c/algo/a2c_acktr.py:56-91): loss = vcoef mean(adv^2) - mean(adv.detach() logp) - ecoef
+// mean(ent), adv = R - v with v the critic's head output of the SAME forward (k_ppo_fwd's critic OUT stack; the actor columns
+// read it in place of old_logp).  No ratio, no clip, no clipped value loss; the entropy term is PPO's.
+template <int MT, int KO, int KH, bool FUSED, bool GW = false, bool PAIR = false, bool SYM = false, bool A2C = false>
 __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, const int bx) {
     static_assert(!(SYM && (FUSED || PAIR)), "the symmetric step runs the two-launch form");
+    static_assert(!(A2C && (FUSED || PAIR || SYM)), "the A2C step runs the two-launch form");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // (No spare workgroup for Adam's bias corrections any more: with G x trunks = 256 row-group blocks, two extra blocks
     // made 258 for 256 CUs, and whenever the dispatcher doubled two row groups up on one CU before the spare blocks had
@@ -312,8 +323,13 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
     }
     {
         const int r = tid < R ? tid : 0;
+        if (A2C) {   // SC[0] <- v of the row (actor columns), SC[3] <- its return
+            scv[3] = a.SC[(size_t)3 * a.sc_stride + row0 + r];
+            if (!critic) scv[0] = a.OUT[d.n_trunks - 1][(size_t)(row0 + r) * ldP];
+        } else {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) scv[q] = a.SC[(size_t)q * a.sc_stride + row0 + r];
+            for (int q = 0; q < 4; ++q) scv[q] = a.SC[(size_t)q * a.sc_stride + row0 + r];
+        }
     }
     sg_stage_commit<UX>(X, xv, gX, R * ldO / 4);
     if (!FUSED) {
@@ -419,7 +435,10 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
             float dv = 0.f, lv = 0.f;
             if (VALID[r]) {
                 const float Rt = SC[3 * R + r], vo = SC[2 * R + r];
-                if (a.use_clipped) {
+                if (A2C) {   // d(mean((R - v)^2)) / dv
+                    dv = 2.f * a.inv_B * (v - Rt);
+                    lv = (Rt - v) * (Rt - v);
+                } else if (a.use_clipped) {
                     const float dvv = v - vo;
                     const float vc = vo + fminf(fmaxf(dvv, -a.clip), a.clip);
                     const float u = (v - Rt) * (v - Rt), w = (vc - Rt) * (vc - Rt);
@@ -483,7 +502,11 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
             const float logp = lp, ent = en;
             const bool valid = VALID[r];
             float dlogp = 0.f, la = 0.f;
-            if (valid) {
+            if (valid && A2C) {
+                const float adv = SC[3 * R + r] - SC[0 * R + r];   // R - v
+                dlogp = -a.inv_B * adv;
+                la = -adv * logp;
+            } else if (valid) {
                 const float adv = SC[1 * R + r];
                 const float ratio = __expf(logp - SC[0 * R + r]);
                 const float surr1 = ratio * adv;
@@ -531,7 +554,11 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
             }
             const bool valid = VALID[r];
             float dlogp = 0.f, la = 0.f;
-            if (valid) {
+            if (valid && A2C) {
+                const float adv = SC[3 * R + r] - SC[0 * R + r];
+                dlogp = -a.inv_B * adv;
+                la = -adv * logp;
+            } else if (valid) {
                 const float adv = SC[1 * R + r];
                 const float ratio = expf(logp - SC[0 * R + r]);
                 const float surr1 = ratio * adv;
@@ -622,6 +649,12 @@ __global__ __launch_bounds__(512) void k_ppo_bwd_sym(PpoArgs a) {
     sg_ppo_bwd_body<MT, KO, KH, false, GW, false, true>(a, blockIdx.y, blockIdx.x);
 }
 
+// A2C over one chunk of the rollout: grid (row groups, 2), after k_ppo_fwd
+template <int MT, int KO, int KH, bool GW = false>
+__global__ __launch_bounds__(512) void k_a2c_bwd(PpoArgs a) {
+    sg_ppo_bwd_body<MT, KO, KH, false, GW, false, false, true>(a, blockIdx.y, blockIdx.x);
+}
+
 // SplitPolicy, ONE launch per step when its 3 G workgroups fit the chip together: every trunk's fused forward + loss + backward,
 // the two actors of a row group joined by the hand-off described at sg_ppo_bwd_body.  Workgroup 3 g + y is trunk y of row group
 // g (y = 2: the critic), so partners are dispatched back to back.
@@ -648,10 +681,12 @@ __global__ __launch_bounds__(512) void k_ppo_fwd_critic(PpoArgs a) {
 // round trips for 128 slabs instead of sixteen) and combine through LDS in a fixed order.
 // SYM: parameters [lo2, hi2) (the actor trunk up to its log-std) also sum the n_slabs slabs behind the first n_slabs (the
 // mirrored column's); everything else reads the first n_slabs only.
+// ACC (A2C's rollout chunks): acc != 0 adds the slab sums to grad instead of replacing it; part is the sum of squares of the
+// accumulated gradient, so after the last chunk it is the whole update's.
 #define SG_PPO_REDUCE_PARAMS 64
-template <bool SYM>
+template <bool SYM, bool ACC = false>
 __device__ __forceinline__ void sg_ppo_reduce_body(const float* slabs, int n_slabs_, int slab_stride, int total,
-                                                   float* grad, float* part, int lo2, int hi2) {
+                                                   float* grad, float* part, int lo2, int hi2, int acc = 0) {
     __shared__ float red[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blockIdx.x * SG_PPO_REDUCE_PARAMS + lane;
@@ -673,6 +708,7 @@ __device__ __forceinline__ void sg_ppo_reduce_body(const float* slabs, int n_sla
     __syncthreads();
     if (wave == 0) {
         g = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+        if (ACC && acc && i < total + 8) g += grad[i];
         if (i < total + 8) grad[i] = g;
         float sq = (i < total) ? g * g : 0.f;
         sq = sg_wave_sum(sq);
@@ -686,6 +722,10 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(const float* slabs, int n_sl
 __global__ __launch_bounds__(256) void k_ppo_reduce_sym(const float* slabs, int n_slabs, int slab_stride, int total,
                                                         float* grad, float* part, int lo2, int hi2) {
     sg_ppo_reduce_body<true>(slabs, n_slabs, slab_stride, total, grad, part, lo2, hi2);
+}
+__global__ __launch_bounds__(256) void k_a2c_reduce(const float* slabs, int n_slabs, int slab_stride, int total,
+                                                    float* grad, float* part, int acc) {
+    sg_ppo_reduce_body<false, true>(slabs, n_slabs, slab_stride, total, grad, part, 0, 0, acc);
 }
 
 // Adam scalars of the update's first step (every later step's are prepared by the preceding k_ppo_adam)
@@ -755,6 +795,38 @@ __global__ __launch_bounds__(256) void k_ppo_adam_sym(float* params, float* m, f
                                                       const SgOptState* st, int k1, float eps, float max_norm,
                                                       float inv_mb, double* loss_acc) {
     sg_ppo_adam_body<4>(params, m, v, grad, part, n_part, total, st, k1, eps, max_norm, inv_mb, loss_acc);
+}
+
+// clip_grad_norm_ + RMSprop (a2c/algo/a2c_acktr.py:94-98; torch.optim.RMSprop single-tensor math, alpha, eps, centered=False,
+// momentum 0, weight decay 0, float32 state):  sq = alpha sq + (1 - alpha) g^2;  p -= lr g / (sqrt(sq) + eps), with 1 - alpha
+// formed in double on the host as Python forms it.
+// The learning rate is read from the device scalars (sg_ppo_set_lr).  Loss sums: the gradient's tail, over inv_b = 1 / (T N).
+__global__ __launch_bounds__(256) void k_a2c_rmsprop(float* params, float* sq, const float* grad, const float* part, int n_part,
+                                                     int total, const SgOptState* st, float alpha, float one_m_alpha, float eps,
+                                                     float max_norm, float inv_b, double* loss_acc) {
+    __shared__ float s_coef;
+    __shared__ float s_ws[4];
+    {
+        float s = 0.f;
+        for (int j = threadIdx.x; j < n_part; j += 256) s += part[j];
+        s = sg_wave_sum(s);
+        if ((threadIdx.x & 63) == 0) s_ws[threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float norm = sqrtf((s_ws[0] + s_ws[1]) + (s_ws[2] + s_ws[3]));
+        const float coef = max_norm / (norm + 1e-6f);
+        s_coef = coef > 1.f ? 1.f : coef;
+    }
+    __syncthreads();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total) {
+        const float g = grad[i] * s_coef;
+        const float s = sq[i] * alpha + one_m_alpha * g * g;   // mul_(alpha).addcmul_(g, g, value=1 - alpha)
+        params[i] = params[i] + (-st->lr) * (g / (sqrtf(s) + eps));
+        sq[i] = s;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 3) loss_acc[threadIdx.x] += (double)(grad[total + threadIdx.x] * inv_b);
 }
 
 // adv = returns[:-1] - value_preds[:-1]; sums for mean / unbiased std (a2c/algo/ppo.py:66-68)
