@@ -227,6 +227,42 @@ SG_API int sg_a2c_create(sg_ctx *ctx, sg_policy *p, const sg_a2c_config *cfg, sg
 SG_API int sg_a2c_get_rmsprop(sg_ppo *a, float *square_avg, int64_t n, int64_t *step);
 SG_API int sg_a2c_set_rmsprop(sg_ppo *a, const float *square_avg, int64_t n, int64_t step);
 
+/* -------------------------------------------------------------------- ACKTR */
+typedef struct {
+    float value_loss_coef;
+    float entropy_coef;
+    float lr;            /* KFACOptimizer(lr=0.25): the SGD step is lr * (1 - momentum), kl_clip bounds it through lr^2 */
+    float momentum;      /* 0.9 */
+    float stat_decay;    /* 0.99 */
+    float kl_clip;       /* 0.001 */
+    float damping;       /* 1e-2 */
+    int Tf;              /* 10: eigendecompositions every Tf updates */
+} sg_acktr_config;
+/* A2C_ACKTR(actor_critic, value_loss_coef, entropy_coef, acktr=True)  a2c/algo/a2c_acktr.py:30-51, built by a2c/main.py:159-161
+ * (--algo acktr) with KFACOptimizer(actor_critic) a2c/algo/kfac.py:97-150 (weight_decay 0, Ts 1; the constructor values
+ * above).  The handle is an sg_ppo in ACKTR mode: sg_ppo_update (perms == NULL only; out3 == NULL queues it; seed keys the
+ * library's own value noise), sg_ppo_destroy and sg_results_publish (step count 1) take it; sg_ppo_get_adam / sg_ppo_set_adam /
+ * sg_a2c_get_rmsprop / sg_a2c_set_rmsprop / sg_ppo_set_symmetry / sg_ppo_set_mirrored_obs refuse it; sg_ppo_set_lr is accepted
+ * and read by nothing (KFACOptimizer.step never reads its param_groups).  Refused here: SplitPolicy, and a context with a
+ * communicator of world > 1.
+ * One update (a2c/algo/a2c_acktr.py:52-102, kfac.py:152-255): A2C's loss and gradient over all T*N rows (no clip); the sampled
+ * Fisher loss -mean(logp) - mean((v - (v + eps).detach())^2) back-propagated for the Kronecker factors A = a^T a / B and
+ * G = B g^T g of the 13 K-FAC modules (split_bias: every Linear weight and bias, dist.logstd), folded into running averages;
+ * symeig of the factors when steps % Tf == 0; v = Q_g ((Q_g^T grad Q_a) / (d_g d_a^T + damping)) Q_a^T;
+ * nu = min(1, sqrt(kl_clip / sum(v grad lr^2))); SGD(lr (1 - momentum), momentum) on nu v; steps += 1.
+ * If the eigensolver hits its sweep cap, a fetching call fails (the losses come back with the error); a queued update
+ * (out3 == NULL) reports it through sg_results_fetch of the slot sg_results_publish filled for it, and so does every later
+ * one, since the word stays raised. */
+SG_API int sg_acktr_create(sg_ctx *ctx, sg_policy *p, const sg_acktr_config *cfg, sg_ppo **out);
+/* eps [n] float32, n = T*N in rollout order: torch.randn(values.size()) of a2c/algo/a2c_acktr.py:82 for the NEXT update only;
+ * NULL: the library draws its own (keyed on sg_ppo_update's seed, the update index and the row). */
+SG_API int sg_acktr_set_value_noise(sg_ppo *a, const float *eps, int64_t n);
+/* K-FAC state (kfac.py:131-133, 148): m_aa / m_gg of the 13 modules in module (= state_dict) order, each [in][in] / [out][out]
+ * row-major and packed back to back (a bias module's m_aa is [[1]]; n_aa / n_gg must be the packed sizes); SGD's momentum
+ * buffer flat [n] in state_dict order (zero before the first update); *steps = KFACOptimizer.steps. */
+SG_API int sg_acktr_get_state(sg_ppo *a, float *m_aa, int64_t n_aa, float *m_gg, int64_t n_gg, float *momentum_buf, int64_t n,
+                              int64_t *steps);
+
 /* ------------------------------------------------------------ discriminator */
 /* Discriminator(input_dim, hidden_dim, device) a2c/algo/gail.py:35-51; Adam(lr 1e-3, eps 1e-8). */
 SG_API int sg_disc_create(sg_ctx *ctx, int input_dim, int hidden_dim, sg_disc **out);

@@ -38,6 +38,11 @@ class A2CConfig(C.Structure):
                 ("alpha", C.c_float), ("max_grad_norm", C.c_float)]
 
 
+class ACKTRConfig(C.Structure):
+    _fields_ = [("value_loss_coef", C.c_float), ("entropy_coef", C.c_float), ("lr", C.c_float), ("momentum", C.c_float),
+                ("stat_decay", C.c_float), ("kl_clip", C.c_float), ("damping", C.c_float), ("Tf", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol of include/simgan_hip.h
 PROTOTYPES = {
     "sg_last_error": (C.c_char_p, []),
@@ -88,6 +93,9 @@ PROTOTYPES = {
     "sg_a2c_create": (C.c_int, [H, H, C.POINTER(A2CConfig), C.POINTER(H)]),
     "sg_a2c_get_rmsprop": (C.c_int, [H, c_float_p, C.c_int64, c_i64_p]),
     "sg_a2c_set_rmsprop": (C.c_int, [H, c_float_p, C.c_int64, C.c_int64]),
+    "sg_acktr_create": (C.c_int, [H, H, C.POINTER(ACKTRConfig), C.POINTER(H)]),
+    "sg_acktr_set_value_noise": (C.c_int, [H, c_float_p, C.c_int64]),
+    "sg_acktr_get_state": (C.c_int, [H, c_float_p, C.c_int64, c_float_p, C.c_int64, c_float_p, C.c_int64, c_i64_p]),
     "sg_disc_create": (C.c_int, [H, C.c_int, C.c_int, C.POINTER(H)]),
     "sg_disc_destroy": (C.c_int, [H]),
     "sg_disc_num_params": (C.c_int, [H, c_i64_p]),
@@ -141,6 +149,9 @@ TEST_PROTOTYPES = {
     "sg_test_disc_gathers": (C.c_int, [H, c_ll_p]),
     "sg_test_ppo_phase_times": (C.c_int, [H, C.c_int, c_ll_p, C.c_int]),
     "sg_test_rng": (C.c_int, [H, C.c_int, C.c_int64, C.c_uint64, C.c_void_p]),
+    "sg_test_kfac_eig": (C.c_int, [H, C.c_int, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_int)]),
+    "sg_test_acktr_noise": (C.c_int, [H, C.c_int64, C.c_uint64, C.c_int64, c_float_p]),
+    "sg_test_raise_kfac_error": (C.c_int, [H]),
     "sg_test_tear_probe": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_ll_p]),
     "sg_test_raise_handoff_error": (C.c_int, [H, H]),
 }

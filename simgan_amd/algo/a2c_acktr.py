@@ -1,12 +1,18 @@
-"""A2C_ACKTR -- host mirror of a2c/algo/a2c_acktr.py:30-102 with acktr=False (the --algo a2c branch of a2c/main.py:123-131).
-update() runs entirely on the GPU: evaluate_actions over the whole rollout, the A2C loss, its gradient, global-norm clipping
-and one RMSprop step.  The device object is an sg_ppo in A2C mode (include/simgan_hip.h: sg_a2c_create)."""
+"""A2C_ACKTR -- host mirror of a2c/algo/a2c_acktr.py:30-102: acktr=False (the --algo a2c branch of a2c/main.py:123-131) and
+acktr=True (--algo acktr, a2c/main.py:159-161, with KFACOptimizer of a2c/algo/kfac.py).
+update() runs entirely on the GPU: evaluate_actions over the whole rollout, the A2C loss and its gradient, then either
+global-norm clipping and one RMSprop step, or the K-FAC statistics, preconditioning and KL-bounded momentum-SGD step.  The
+device object is an sg_ppo in A2C or ACKTR mode (include/simgan_hip.h: sg_a2c_create, sg_acktr_create)."""
 import ctypes as C
 
 import numpy as np
 
 from .. import _lib
+from ..utils import derive_seed
 from .ppo import _Group, _ParamGroups
+
+# KFACOptimizer's constructor defaults (a2c/algo/kfac.py:97-107), which a2c/main.py:159-161 keeps
+KFAC_DEFAULTS = dict(lr=0.25, momentum=0.9, stat_decay=0.99, kl_clip=0.001, damping=1e-2, weight_decay=0, Ts=1, Tf=10)
 
 
 class _RMSprop(object):
@@ -23,6 +29,30 @@ class _RMSprop(object):
         return self._agent.get_rmsprop()
 
 
+class _KFAC(object):
+    """agent.optimizer of an ACKTR agent: KFACOptimizer's constants, steps, and param_groups.  KFACOptimizer.step never reads its
+    param_groups, so lr writes (update_linear_schedule under --use-linear-lr-decay, a2c/main.py:203-205) are recorded in
+    lr_writes and change nothing on the device."""
+
+    def __init__(self, agent):
+        self._agent = agent
+        for k, v in KFAC_DEFAULTS.items():
+            setattr(self, k, v)
+        self.lr_writes = []
+        self.param_groups = _ParamGroups([_Group(self)])
+
+    def _set_lr(self, lr):
+        self.lr_writes.append(lr)
+
+    @property
+    def steps(self):
+        """KFACOptimizer.steps: the updates this agent has issued (counted on the host; no device round trip)."""
+        return self._agent._steps
+
+    def state(self):
+        return self._agent.get_kfac()
+
+
 class A2C_ACKTR():
     def __init__(self,
                  actor_critic,
@@ -32,12 +62,20 @@ class A2C_ACKTR():
                  eps=None,
                  alpha=None,
                  max_grad_norm=None,
-                 acktr=False):
+                 acktr=False,
+                 seed=0):
         if acktr:
-            raise NotImplementedError("A2C_ACKTR(acktr=True): ACKTR (the K-FAC optimizer of a2c/algo/kfac.py) is not implemented; "
-                                      "acktr=False (A2C with RMSprop) is")
+            given = [k for k, v in (("lr", lr), ("eps", eps), ("alpha", alpha), ("max_grad_norm", max_grad_norm)) if v is not None]
+            if given:
+                raise NotImplementedError(f"A2C_ACKTR(acktr=True) with {', '.join(given)}: ACKTR's K-FAC optimizer "
+                                          "(a2c/algo/kfac.py) ignores the RMSprop arguments -- it steps with its own lr 0.25 and "
+                                          "bounds the step by KL, not by a gradient-norm clip; call it as a2c/main.py:159-161 "
+                                          "does, without lr, eps, alpha and max_grad_norm")
         if type(actor_critic).__name__ == "SplitPolicy":
             raise NotImplementedError("A2C_ACKTR: implemented for Policy (MLP) only, not for SplitPolicy")
+        if acktr:
+            self._init_acktr(actor_critic, value_loss_coef, entropy_coef, seed)
+            return
         missing = [k for k, v in (("lr", lr), ("eps", eps), ("alpha", alpha), ("max_grad_norm", max_grad_norm)) if v is None]
         if missing:
             raise ValueError(f"A2C_ACKTR(acktr=False) needs {', '.join(missing)} (RMSprop and clip_grad_norm_ take them; "
@@ -59,6 +97,57 @@ class A2C_ACKTR():
             actor_critic._register_handle_user(self)
         self.optimizer = _RMSprop(self, lr, eps, alpha)
 
+    def _init_acktr(self, actor_critic, value_loss_coef, entropy_coef, seed):
+        self.actor_critic = actor_critic
+        self.acktr = True
+        self.value_loss_coef = value_loss_coef
+        self.entropy_coef = entropy_coef
+        self.max_grad_norm = None
+        self.is_cuda = True
+        self.seed = derive_seed(seed, 0xACC7)   # the library's own value noise (a2c/algo/a2c_acktr.py:82)
+        self._steps = 0
+        self.ctx = actor_critic.ctx
+        self.lib = self.ctx.lib
+        d = KFAC_DEFAULTS
+        cfg = _lib.ACKTRConfig(float(value_loss_coef), float(entropy_coef), d["lr"], d["momentum"], d["stat_decay"], d["kl_clip"],
+                               d["damping"], d["Tf"])
+        h = _lib.H()
+        _lib.check(self.lib.sg_acktr_create(self.ctx.h, actor_critic.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        if hasattr(actor_critic, "_register_handle_user"):
+            actor_critic._register_handle_user(self)
+        self.optimizer = _KFAC(self)
+
+    def kfac_modules(self):
+        """[(name, (out, in))] of KFACOptimizer.modules in order (split_bias: a bias is an [out, 1] AddBias module)."""
+        p = self.actor_critic
+        O, A, H, Hc = p.obs_dim, p.act_dim, p.hidden_size, p.critic_hidden
+        mods = []
+        for name, (o, i) in (("actor.0", (H, O)), ("actor.2", (H, H)), ("critic.0", (Hc, O)), ("critic.2", (Hc, Hc)),
+                             ("critic_linear", (1, Hc)), ("dist.fc_mean", (A, H))):
+            mods += [(name + ".weight", (o, i)), (name + ".bias", (o, 1))]
+        mods.append(("dist.logstd", (A, 1)))
+        return mods
+
+    def get_kfac(self):
+        """-> {"m_aa": [13 arrays [in, in]], "m_gg": [13 arrays [out, out]], "momentum_buffer": flat, "steps": int}, the K-FAC
+        state of a2c/algo/kfac.py in module (state_dict) order."""
+        mods = self.kfac_modules()
+        n_aa = sum(i * i for _, (o, i) in mods)
+        n_gg = sum(o * o for _, (o, i) in mods)
+        aa, gg = np.empty(n_aa, np.float32), np.empty(n_gg, np.float32)
+        buf = np.empty(self.actor_critic.num_params, np.float32)
+        steps = C.c_int64(0)
+        _lib.check(self.lib.sg_acktr_get_state(self.h, _lib.fptr(aa), n_aa, _lib.fptr(gg), n_gg, _lib.fptr(buf), buf.size,
+                                               C.byref(steps)))
+        out_aa, out_gg, ia, ig = [], [], 0, 0
+        for _, (o, i) in mods:
+            out_aa.append(aa[ia:ia + i * i].reshape(i, i))
+            out_gg.append(gg[ig:ig + o * o].reshape(o, o))
+            ia += i * i
+            ig += o * o
+        return {"m_aa": out_aa, "m_gg": out_gg, "momentum_buffer": buf, "steps": steps.value}
+
     def __del__(self):
         try:
             if getattr(self, "h", None):
@@ -67,12 +156,23 @@ class A2C_ACKTR():
         except Exception:
             pass
 
-    def update(self, rollouts, fetch_losses=True):
+    def update(self, rollouts, fetch_losses=True, value_noise=None):
         """a2c/algo/a2c_acktr.py:52-102 -> (value_loss, action_loss, dist_entropy).  fetch_losses=False: queue the update and
-        return None without waiting for it (the losses are read later through the results ring, simgan_amd/driver.py)."""
+        return None without waiting for it (the losses are read later through the results ring, simgan_amd/driver.py).
+        value_noise (ACKTR only): the update's torch.randn(values.size()) [T, N, 1] instead of the library's own draws."""
         rollouts._push([_lib.F_OBS, _lib.F_ACTIONS, _lib.F_RETURNS])
+        seed = 0
+        if self.acktr:
+            if value_noise is not None:
+                eps = np.ascontiguousarray(np.asarray(value_noise, np.float32).reshape(-1))
+                _lib.check(self.lib.sg_acktr_set_value_noise(self.h, _lib.fptr(eps), eps.size))
+            seed = self.seed
+        elif value_noise is not None:
+            raise ValueError("value_noise is ACKTR's (acktr=True); A2C draws no noise")
         out = (C.c_float * 3)()
-        _lib.check(self.lib.sg_ppo_update(self.h, rollouts.h, None, 0, 0, out if fetch_losses else None))
+        _lib.check(self.lib.sg_ppo_update(self.h, rollouts.h, None, 0, seed, out if fetch_losses else None))
+        if self.acktr:
+            self._steps += 1
         return (float(out[0]), float(out[1]), float(out[2])) if fetch_losses else None
 
     def get_rmsprop(self):

@@ -9,8 +9,10 @@ under `third_party.a2c_ppo_acktr.*`.  This module
     unpickler resolves ONLY an explicit allowlist of (module, name) pairs -- the tensor / storage / parameter
     rebuilders, the three torch.nn layer classes and the Adam optimizer the reference's modules contain, the numpy
     array rebuilders and the plain containers; classes under `third_party.` (the reference's own) become inert
-    stand-ins that only receive their `__dict__`; every other global (builtins.eval, os.system, torch.hub, ...) raises
-    `pickle.UnpicklingError`.  Parameters are collected by walking `_parameters` / `_modules` (== `state_dict()` order);
+    stand-ins that only receive their `__dict__`; `getattr` resolves to a guard that accepts only the two K-FAC hooks of
+    a reference KFACOptimizer (a policy saved after ACKTR) and returns an inert callable for them; every other global
+    (builtins.eval, os.system, torch.hub, ...) raises `pickle.UnpicklingError`.  Parameters are collected by walking
+    `_parameters` / `_modules` (== `state_dict()` order; SplitBias keys are folded back to the plain layout);
   * writes files the reference's `torch.load` accepts: real torch.nn layers inside objects whose classes carry the
     reference's module paths and attribute names (`base.actor`, `dist.fc_mean`, `dist.logstd._bias`, ...), in the
     legacy (non-zip) container the shipped `trained_models_*/ppo/*.pt` use.
@@ -71,10 +73,36 @@ def _stub_class(module, name):
     return _STUBS[key]
 
 
+# A policy saved after ACKTR (a2c/main.py:261-269 with --algo acktr) carries the hooks KFACOptimizer._prepare_model registered on
+# its Linear / AddBias modules (a2c/algo/kfac.py:144-150): pickle stores each bound method as getattr(<KFACOptimizer>, name).
+_KFAC_HOOKS = ("_save_input", "_save_grad_output")
+
+
+class _InertHook(object):
+    """What a pickled K-FAC hook becomes: a callable that does nothing (the hooks only feed the optimizer's statistics)."""
+
+    def __init__(self, owner, name):
+        self._ref_path = f"{getattr(owner, '_ref_path', type(owner).__name__)}.{name}"
+
+    def __call__(self, *a, **k):
+        return None
+
+
+def _guarded_getattr(obj, name, *default):
+    """The only `getattr` a reference checkpoint may apply: to a reference stand-in (the pickled KFACOptimizer) for one of the
+    two K-FAC hook names.  Any other target or name -- a real class, a module, a builtin -- is refused."""
+    if isinstance(obj, _RefStub) and not isinstance(obj, type) and name in _KFAC_HOOKS and not default:
+        return _InertHook(obj, name)
+    raise pickle.UnpicklingError(f"checkpoint applies getattr to {type(obj).__name__}.{name!s:.64}: refusing to resolve it "
+                                 "(only the K-FAC hooks of a reference KFACOptimizer are accepted)")
+
+
 class _StubUnpickler(pickle.Unpickler):
     def find_class(self, module, name):
         if (module, name) in _ALLOWED or (module == "torch" and (name in _TORCH_STORAGES or name in _TORCH_DTYPES)):
             return super().find_class(module, name)
+        if (module, name) in (("builtins", "getattr"), ("__builtin__", "getattr")):
+            return _guarded_getattr
         if module.split(".")[0] in _STUB_ROOTS:
             return _stub_class(module, name)
         raise pickle.UnpicklingError(f"checkpoint names the global {module}.{name}, which a SimGAN checkpoint has no use "
@@ -112,6 +140,21 @@ def _walk(obj, prefix, out):
     return out
 
 
+def _normalise_split_bias(sd):
+    """KFACOptimizer's split_bias (a2c/algo/kfac.py:96-105, 115-121) replaced every biased Linear `x` by SplitBias(x): its
+    parameters are `x.module.weight` and `x.add_bias._bias` [out, 1].  -> the plain layout `x.weight`, `x.bias` [out], in
+    the same order (the flat parameter order does not change)."""
+    out = collections.OrderedDict()
+    for k, v in sd.items():
+        if k.endswith(".module.weight"):
+            out[k[:-len(".module.weight")] + ".weight"] = v
+        elif k.endswith(".add_bias._bias"):
+            out[k[:-len(".add_bias._bias")] + ".bias"] = v.reshape(-1)
+        else:
+            out[k] = v
+    return out
+
+
 def _rms_state(rms):
     if rms is None:
         return None
@@ -139,7 +182,7 @@ def policy_from_module_state(class_name, state):
     `third_party.a2c_ppo_acktr` alias modules) -> (dims dict, state_dict)."""
     holder = _RefStub()
     holder.__setstate__(state)
-    sd = _walk(holder, "", collections.OrderedDict())
+    sd = _normalise_split_bias(_walk(holder, "", collections.OrderedDict()))
     return _policy_dims(class_name, sd), sd
 
 
@@ -148,7 +191,7 @@ def read_reference_checkpoint(path):
     state_dict is an OrderedDict name -> float32 array in the reference's `state_dict()` order."""
     obj = _torch_load(path)
     actor_critic, ob_rms = (obj[0], obj[1]) if isinstance(obj, (list, tuple)) else (obj, None)
-    sd = _walk(actor_critic, "", collections.OrderedDict())
+    sd = _normalise_split_bias(_walk(actor_critic, "", collections.OrderedDict()))
     name = type(actor_critic).__name__
     out = _policy_dims(name, sd)
     out.update(class_name=name, state_dict=sd, ob_rms=_rms_state(ob_rms))

@@ -263,6 +263,8 @@ struct sg_ppo {
     // A2C (sg_a2c_create): one RMSprop step over the whole rollout per update; d_v holds square_avg, opt_t counts the steps
     bool a2c = false;
     float alpha = 0.f;
+    // ACKTR (sg_acktr_create): A2C's gradient (a2c is set too), then the K-FAC step (sg_ppo.hip); d_m holds SGD's momentum buffer
+    struct SgKfac* kfac = nullptr;
 };
 
 struct sg_disc {

@@ -20,6 +20,11 @@
 //   k_a2c_gather                                    the rollout's T*N rows in their own order (no permutation, no advantages)
 //   per chunk of <= SG_A2C_CHUNK_ROWS rows:  k_ppo_fwd -> k_a2c_bwd -> k_a2c_reduce (adds to the gradient)
 //   then         k_a2c_rmsprop                      clip + RMSprop, the update's one optimizer step
+//
+// ACKTR (sg_acktr_create: A2C's gradient with the K-FAC step of a2c/algo/kfac.py, sg_kfac.hpp), one update:
+//   k_a2c_gather
+//   per chunk:  k_ppo_fwd -> k_a2c_bwd -> k_a2c_reduce -> k_acktr_fisher -> k_kfac_stats (adds to the factor sums)
+//   then        k_kfac_fold -> k_kfac_eig (exits unless steps % Tf == 0) -> k_kfac_gemm x4 -> k_kfac_step -> k_kfac_tick
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -30,6 +35,7 @@
 #include "sg_common.h"
 #include "sg_rng.hpp"
 #include "sg_ppo_kernels.hpp"
+#include "sg_kfac.hpp"
 
 __global__ void k_fill_perm(int64_t* perm, int64_t n, int half_bits, uint64_t key) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -212,6 +218,124 @@ static void launch_a2c_bwd(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 grid
     }
 }
 
+// ---------------------------------------------------------------------------------- ACKTR (K-FAC) state
+static void kfac_free(sg_ppo* a) {
+    SgKfac* k = a->kfac;
+    if (!k) return;
+    void* ptrs[] = {k->d_acc, k->d_m, k->d_Q, k->d_d, k->d_work, k->d_ks, k->d_vec, k->d_t0, k->d_t1, k->d_one, k->d_vpart,
+                    k->d_jobs, k->d_tiles, k->d_eps, k->d_fish};
+    for (void* q : ptrs) if (q) (void)sg_dev_free(q);
+    delete k;
+    a->kfac = nullptr;
+}
+
+static int kfac_setup(sg_ctx* ctx, SgKfac* k, const SgPolicyDesc& d, float* d_grad) {
+    const SgTrunk& ac = d.trunk[0];
+    const SgTrunk& cr = d.trunk[1];
+    const int O = d.O, A = d.A, H = ac.H, Hc = cr.H;
+    const int nf[SG_KFAC_NF] = {O, H, H, Hc, Hc, H, H, Hc, Hc, 1, A, A};
+    int fo = 0, vo = 0;
+    int64_t wo = 0;
+    k->lds_n = 0;
+    while (16 * (k->lds_n + 1) * (k->lds_n + 1) + 8192 <= ctx->lds_bytes) ++k->lds_n;
+    for (int f = 0; f < SG_KFAC_NF; ++f) {
+        if (f == SG_KFAC_NA) k->g_start = fo;
+        k->n[f] = nf[f]; k->off[f] = fo; k->voff[f] = vo; k->woff[f] = wo;
+        fo += nf[f] * nf[f]; vo += nf[f];
+        if (nf[f] > k->lds_n) wo += 2 * (int64_t)nf[f] * nf[f];
+        SG_REQUIRE(nf[f] <= 512, "sg_acktr_create: a %d-wide Kronecker factor is larger than the eigensolver's 512", nf[f]);
+    }
+    k->fac_total = fo; k->vec_total = vo; k->work_doubles = wo;
+    const KfacModule mods[SG_KFAC_MODULES] = {
+        {0, 5, ac.off + ac.w1, d.ldO, H, O, 0},     {-1, 5, ac.off + ac.b1, 1, H, 1, 0},
+        {1, 6, ac.off + ac.w2, ac.ldH, H, H, 0},    {-1, 6, ac.off + ac.b2, 1, H, 1, 0},
+        {0, 7, cr.off + cr.w1, d.ldO, Hc, O, 0},    {-1, 7, cr.off + cr.b1, 1, Hc, 1, 0},
+        {3, 8, cr.off + cr.w2, cr.ldH, Hc, Hc, 0},  {-1, 8, cr.off + cr.b2, 1, Hc, 1, 0},
+        {4, 9, cr.off + cr.wh, cr.ldH, 1, Hc, 0},   {-1, 9, cr.off + cr.bh, 1, 1, 1, 0},
+        {2, 10, ac.off + ac.wh, ac.ldH, A, H, 0},   {-1, 10, ac.off + ac.bh, 1, A, 1, 0},
+        {-1, 11, ac.off + ac.ex, 1, A, 1, 0}};
+    int to = 0;
+    k->max_tiles = 0;
+    for (int m = 0; m < SG_KFAC_MODULES; ++m) {
+        k->mod[m] = mods[m];
+        k->mod[m].toff = to;
+        to += mods[m].out * mods[m].in;
+        k->max_tiles = std::max(k->max_tiles, ((mods[m].out + 31) / 32) * ((mods[m].in + 31) / 32));
+    }
+    k->tmp_total = to;
+    SG_CHECK(sg_dev_malloc((void**)&k->d_acc, sizeof(float) * fo));
+    SG_CHECK(sg_dev_malloc((void**)&k->d_m, sizeof(float) * fo));
+    SG_CHECK(sg_dev_malloc((void**)&k->d_Q, sizeof(float) * fo));
+    SG_CHECK(sg_dev_malloc((void**)&k->d_d, sizeof(float) * vo));
+    if (wo) SG_CHECK(sg_dev_malloc((void**)&k->d_work, sizeof(double) * wo));
+    SG_CHECK(sg_dev_malloc((void**)&k->d_ks, sizeof(KfacDevState)));
+    SG_CHECK(sg_dev_malloc((void**)&k->d_vec, sizeof(float) * (d.total + 8)));
+    SG_CHECK(sg_dev_malloc((void**)&k->d_t0, sizeof(float) * to));
+    SG_CHECK(sg_dev_malloc((void**)&k->d_t1, sizeof(float) * to));
+    SG_CHECK(sg_dev_malloc((void**)&k->d_one, sizeof(float) * 4));
+    SG_CHECK(sg_dev_malloc((void**)&k->d_vpart, sizeof(float) * SG_KFAC_MODULES * k->max_tiles));
+    SG_CHECK(hipMemsetAsync(k->d_m, 0, sizeof(float) * fo, ctx->stream));
+    SG_CHECK(hipMemsetAsync(k->d_Q, 0, sizeof(float) * fo, ctx->stream));
+    SG_CHECK(hipMemsetAsync(k->d_d, 0, sizeof(float) * vo, ctx->stream));
+    SG_CHECK(hipMemsetAsync(k->d_ks, 0, sizeof(KfacDevState), ctx->stream));
+    SG_CHECK(hipMemsetAsync(k->d_vec, 0, sizeof(float) * (d.total + 8), ctx->stream));
+    const float one[4] = {1.f, 1.f, 1.f, 1.f};
+    SG_COPY_SYNC(ctx, k->d_one, one, sizeof one, hipMemcpyHostToDevice);
+    // the four preconditioning stages of every module (see k_kfac_gemm): t0 = Q_g^T grad; t1 = (t0 Q_a) / (d_g d_a^T + la);
+    // t0 = Q_g t1; v = t0 Q_a^T (with the tile sums of v * grad)
+    std::vector<KfacJob> jobs(4 * SG_KFAC_MODULES);
+    for (int m = 0; m < SG_KFAC_MODULES; ++m) {
+        const KfacModule& md = k->mod[m];
+        const float* Qa = md.a_f >= 0 ? k->d_Q + k->off[md.a_f] : k->d_one;
+        const float* da = md.a_f >= 0 ? k->d_d + k->voff[md.a_f] : k->d_one;
+        const float* Qg = k->d_Q + k->off[md.g_f];
+        const float* dg = k->d_d + k->voff[md.g_f];
+        float* t0 = k->d_t0 + md.toff;
+        float* t1 = k->d_t1 + md.toff;
+        const int M = md.out, N = md.in;
+        KfacJob j;
+        memset(&j, 0, sizeof j);
+        j.M = M; j.N = N;
+        KfacJob s1 = j, s2 = j, s3 = j, s4 = j;
+        s1.K = M; s1.A = Qg; s1.lda = M; s1.ta = 1; s1.B = d_grad + md.goff; s1.ldb = md.gld; s1.C = t0; s1.ldc = N;
+        s2.K = N; s2.A = t0; s2.lda = N; s2.B = Qa; s2.ldb = N; s2.C = t1; s2.ldc = N; s2.epi = 1; s2.dg = dg; s2.da = da;
+        s3.K = M; s3.A = Qg; s3.lda = M; s3.B = t1; s3.ldb = N; s3.C = t0; s3.ldc = N;
+        s4.K = N; s4.A = t0; s4.lda = N; s4.B = Qa; s4.ldb = N; s4.tb = 1; s4.C = k->d_vec + md.goff; s4.ldc = md.gld; s4.epi = 2;
+        s4.G = d_grad + md.goff; s4.ldg = md.gld;
+        jobs[0 * SG_KFAC_MODULES + m] = s1;
+        jobs[1 * SG_KFAC_MODULES + m] = s2;
+        jobs[2 * SG_KFAC_MODULES + m] = s3;
+        jobs[3 * SG_KFAC_MODULES + m] = s4;
+    }
+    SG_CHECK(sg_dev_malloc((void**)&k->d_jobs, sizeof(KfacJob) * jobs.size()));
+    SG_COPY_SYNC(ctx, k->d_jobs, jobs.data(), sizeof(KfacJob) * jobs.size(), hipMemcpyHostToDevice);
+    std::vector<int4> tiles;
+    for (int f = 0; f < SG_KFAC_NF; ++f) {
+        const int T = (k->n[f] + 15) / 16;
+        for (int ti = 0; ti < T; ++ti)
+            for (int tj = ti; tj < T; ++tj) tiles.push_back(make_int4(f, ti, tj, 0));
+    }
+    k->n_tiles = (int)tiles.size();
+    SG_CHECK(sg_dev_malloc((void**)&k->d_tiles, sizeof(int4) * tiles.size()));
+    SG_COPY_SYNC(ctx, k->d_tiles, tiles.data(), sizeof(int4) * tiles.size(), hipMemcpyHostToDevice);
+    return 0;
+}
+
+static KfacEigArgs kfac_eig_args(const SgKfac* k) {
+    KfacEigArgs e;
+    memset(&e, 0, sizeof e);
+    e.m = k->d_m; e.Q = k->d_Q; e.dv = k->d_d; e.work = k->d_work;
+    for (int f = 0; f < SG_KFAC_NF; ++f) { e.n[f] = k->n[f]; e.off[f] = k->off[f]; e.voff[f] = k->voff[f]; e.woff[f] = k->woff[f]; }
+    e.lds_n = k->lds_n; e.tf = k->cfg.Tf; e.ks = k->d_ks;
+    return e;
+}
+
+static size_t kfac_eig_lds(const SgKfac* k) {
+    int nl = 0;
+    for (int f = 0; f < SG_KFAC_NF; ++f) if (k->n[f] <= k->lds_n) nl = std::max(nl, k->n[f]);
+    return sizeof(double) * 2 * (size_t)nl * nl;
+}
+
 // ---------------------------------------------------------------------------------- PPO API
 extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg, sg_ppo** out) {
     SG_DEVICE_WIDE();
@@ -269,6 +393,90 @@ extern "C" int sg_a2c_create(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg
     return 0;
 }
 
+// a2c/main.py:159-161 -> A2C_ACKTR(actor_critic, value_loss_coef, entropy_coef, acktr=True): KFACOptimizer(actor_critic) with
+// the constructor values in cfg (a2c/algo/kfac.py:97-150).  Policy (MLP) on one rank only.
+extern "C" int sg_acktr_create(sg_ctx* ctx, sg_policy* p, const sg_acktr_config* cfg, sg_ppo** out) {
+    SG_DEVICE_WIDE();   // kfac_setup's clears and copies on ctx->stream, never beside a capture in flight (recursive with sg_ppo_create's)
+    SG_REQUIRE(ctx && p && cfg && out, "sg_acktr_create: NULL argument");
+    SG_REQUIRE(p->desc.kind == SG_POLICY_MLP, "sg_acktr_create: ACKTR is implemented for Policy (MLP) only, not for SplitPolicy");
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_acktr_create: ACKTR runs on one rank: this context has a communicator of "
+               "world %d (data-parallel ACKTR is not implemented)", ctx->world);
+    SG_REQUIRE(cfg->lr > 0.f && cfg->momentum >= 0.f && cfg->momentum < 1.f && cfg->stat_decay > 0.f && cfg->stat_decay < 1.f &&
+               cfg->kl_clip > 0.f && cfg->damping >= 0.f && cfg->Tf >= 1,
+               "sg_acktr_create: need lr > 0, momentum in [0, 1), stat_decay in (0, 1), kl_clip > 0, damping >= 0 and Tf >= 1");
+    sg_a2c_config ac;
+    memset(&ac, 0, sizeof ac);
+    ac.value_loss_coef = cfg->value_loss_coef; ac.entropy_coef = cfg->entropy_coef;
+    ac.lr = cfg->lr; ac.eps = 1.f; ac.alpha = 0.f; ac.max_grad_norm = 1.f;   // unused: no RMSprop, no clip
+    sg_ppo* a = nullptr;
+    SG_TRY(sg_a2c_create(ctx, p, &ac, &a));
+    a->kfac = new SgKfac();
+    a->kfac->cfg = *cfg;
+    const int rc = kfac_setup(ctx, a->kfac, p->desc, a->d_grad);
+    if (rc != 0) {
+        const std::string err = sg_last_error();
+        sg_ppo_destroy(a);
+        sg_set_error("%s", err.c_str());
+        return rc;
+    }
+    *out = a;
+    return 0;
+}
+
+extern "C" int sg_acktr_set_value_noise(sg_ppo* a, const float* eps, int64_t n) {
+    SG_REQUIRE(a, "sg_acktr_set_value_noise: NULL argument");
+    SG_REQUIRE(a->kfac, "sg_acktr_set_value_noise: not an ACKTR handle");
+    SgKfac* k = a->kfac;
+    if (!eps) {
+        k->eps_pending = false;
+        k->eps_host.clear();
+        return 0;
+    }
+    SG_REQUIRE(n > 0 && n < (1ll << 30), "sg_acktr_set_value_noise: %lld values", (long long)n);
+    k->eps_host.assign(eps, eps + n);
+    k->eps_pending = true;
+    return 0;
+}
+
+extern "C" int sg_acktr_get_state(sg_ppo* a, float* m_aa, int64_t n_aa, float* m_gg, int64_t n_gg, float* momentum_buf,
+                                  int64_t n, int64_t* steps) {
+    SG_REQUIRE(a && m_aa && m_gg && momentum_buf && steps, "sg_acktr_get_state: NULL argument");
+    SG_REQUIRE(a->kfac, "sg_acktr_get_state: not an ACKTR handle");
+    const SgKfac* k = a->kfac;
+    const SgPolicyDesc& d = a->policy->desc;
+    SG_REQUIRE(n == sg_policy_flat_count(d), "sg_acktr_get_state: bad momentum length");
+    int64_t want_aa = 0, want_gg = 0;
+    for (int m = 0; m < SG_KFAC_MODULES; ++m) {
+        want_aa += (int64_t)k->mod[m].in * k->mod[m].in;
+        want_gg += (int64_t)k->mod[m].out * k->mod[m].out;
+    }
+    SG_REQUIRE(n_aa == want_aa && n_gg == want_gg, "sg_acktr_get_state: m_aa / m_gg take %lld / %lld floats", (long long)want_aa,
+               (long long)want_gg);
+    std::vector<float> fac(k->fac_total), buf(d.total);
+    KfacDevState ks;
+    SG_CHECK(hipSetDevice(a->ctx->device));
+    SG_CHECK(hipStreamSynchronize(a->ctx->stream));
+    SG_COPY_SYNC(a->ctx, fac.data(), k->d_m, sizeof(float) * k->fac_total, hipMemcpyDeviceToHost);
+    SG_COPY_SYNC(a->ctx, buf.data(), a->d_m, sizeof(float) * d.total, hipMemcpyDeviceToHost);
+    SG_COPY_SYNC(a->ctx, &ks, k->d_ks, sizeof ks, hipMemcpyDeviceToHost);
+    SG_REQUIRE(!ks.err, "sg_acktr_get_state: k_kfac_eig hit its sweep cap (%d) on an earlier update", SG_KFAC_SWEEPS);
+    float *pa = m_aa, *pg = m_gg;
+    for (int m = 0; m < SG_KFAC_MODULES; ++m) {
+        const KfacModule& md = k->mod[m];
+        if (md.a_f >= 0) {
+            memcpy(pa, fac.data() + k->off[md.a_f], sizeof(float) * md.in * md.in);
+        } else {
+            pa[0] = ks.steps > 0 ? 1.f : 0.f;   // ones^T ones / B
+        }
+        pa += (int64_t)md.in * md.in;
+        memcpy(pg, fac.data() + k->off[md.g_f], sizeof(float) * md.out * md.out);
+        pg += (int64_t)md.out * md.out;
+    }
+    sg_policy_unpad(d, buf.data(), momentum_buf);
+    *steps = ks.steps;
+    return 0;
+}
+
 extern "C" int sg_ppo_destroy(sg_ppo* a) {
     SG_DEVICE_WIDE();
     if (!a) return 0;
@@ -282,6 +490,7 @@ extern "C" int sg_ppo_destroy(sg_ppo* a) {
     if (a->d_dbg) (void)sg_dev_free(a->d_dbg);
     if (a->d_pair) (void)sg_dev_free(a->d_pair);
     if (a->steps_graph) (void)hipGraphExecDestroy(a->steps_graph);
+    kfac_free(a);
     delete a;
     return 0;
 }
@@ -303,7 +512,7 @@ extern "C" int sg_ppo_set_lr(sg_ppo* a, float lr) {
 // before every update (sg_ppo_set_mirrored_obs).
 extern "C" int sg_ppo_set_symmetry(sg_ppo* a, float coef, const float* m_obs, const float* m_act) {
     SG_REQUIRE(a, "sg_ppo_set_symmetry: NULL argument");
-    SG_REQUIRE(!a->a2c, "sg_ppo_set_symmetry: the mirror-symmetry loss is a PPO option; this is an A2C handle");
+    SG_REQUIRE(!a->a2c, "sg_ppo_set_symmetry: the mirror-symmetry loss is a PPO option; this is an A2C / ACKTR handle");
     SG_REQUIRE(coef >= 0.f && coef < INFINITY, "sg_ppo_set_symmetry: symmetry_coef must be finite and >= 0 (got %g)", (double)coef);
     sg_ctx* ctx = a->ctx;
     const SgPolicyDesc& d = a->policy->desc;
@@ -333,7 +542,7 @@ extern "C" int sg_ppo_set_symmetry(sg_ppo* a, float coef, const float* m_obs, co
 // the caller: host[T*N][O] float32, consumed by the next sg_ppo_update (which requires count == T*N*O)
 extern "C" int sg_ppo_set_mirrored_obs(sg_ppo* a, const float* host, int64_t count) {
     SG_REQUIRE(a && host, "sg_ppo_set_mirrored_obs: NULL argument");
-    SG_REQUIRE(!a->a2c, "sg_ppo_set_mirrored_obs: the mirror-symmetry loss is a PPO option; this is an A2C handle");
+    SG_REQUIRE(!a->a2c, "sg_ppo_set_mirrored_obs: the mirror-symmetry loss is a PPO option; this is an A2C / ACKTR handle");
     SG_REQUIRE(count > 0 && count % a->policy->desc.O == 0, "sg_ppo_set_mirrored_obs: %lld floats is not a whole number of %d-float rows",
                (long long)count, a->policy->desc.O);
     sg_ctx* ctx = a->ctx;
@@ -372,6 +581,7 @@ extern "C" int sg_ppo_last_perms(sg_ppo* a, int64_t* perms, int64_t count) {
 
 extern "C" int sg_ppo_get_adam(sg_ppo* a, float* m, float* v, int64_t n, int64_t* step) {
     SG_REQUIRE(a && m && v && step, "sg_ppo_get_adam: NULL argument");
+    SG_REQUIRE(!a->kfac, "sg_ppo_get_adam: an ACKTR handle has K-FAC state, not Adam's (sg_acktr_get_state)");
     SG_REQUIRE(!a->a2c, "sg_ppo_get_adam: an A2C handle has RMSprop state, not Adam's (sg_a2c_get_rmsprop)");
     const SgPolicyDesc& d = a->policy->desc;
     SG_REQUIRE(n == sg_policy_flat_count(d), "sg_ppo_get_adam: bad length");
@@ -387,6 +597,7 @@ extern "C" int sg_ppo_get_adam(sg_ppo* a, float* m, float* v, int64_t n, int64_t
 
 extern "C" int sg_ppo_set_adam(sg_ppo* a, const float* m, const float* v, int64_t n, int64_t step) {
     SG_REQUIRE(a && m && v, "sg_ppo_set_adam: NULL argument");
+    SG_REQUIRE(!a->kfac, "sg_ppo_set_adam: an ACKTR handle has K-FAC state, not Adam's (sg_acktr_get_state)");
     SG_REQUIRE(!a->a2c, "sg_ppo_set_adam: an A2C handle has RMSprop state, not Adam's (sg_a2c_set_rmsprop)");
     const SgPolicyDesc& d = a->policy->desc;
     SG_REQUIRE(n == sg_policy_flat_count(d), "sg_ppo_set_adam: bad length");
@@ -410,6 +621,7 @@ extern "C" int sg_ppo_set_adam(sg_ppo* a, const float* m, const float* v, int64_
 // square_avg [n] flat in state_dict order, *step = completed RMSprop steps
 extern "C" int sg_a2c_get_rmsprop(sg_ppo* a, float* square_avg, int64_t n, int64_t* step) {
     SG_REQUIRE(a && square_avg && step, "sg_a2c_get_rmsprop: NULL argument");
+    SG_REQUIRE(!a->kfac, "sg_a2c_get_rmsprop: an ACKTR handle has K-FAC state, not RMSprop's (sg_acktr_get_state)");
     SG_REQUIRE(a->a2c, "sg_a2c_get_rmsprop: not an A2C handle (sg_ppo_get_adam)");
     const SgPolicyDesc& d = a->policy->desc;
     SG_REQUIRE(n == sg_policy_flat_count(d), "sg_a2c_get_rmsprop: bad length");
@@ -424,6 +636,7 @@ extern "C" int sg_a2c_get_rmsprop(sg_ppo* a, float* square_avg, int64_t n, int64
 
 extern "C" int sg_a2c_set_rmsprop(sg_ppo* a, const float* square_avg, int64_t n, int64_t step) {
     SG_REQUIRE(a && square_avg, "sg_a2c_set_rmsprop: NULL argument");
+    SG_REQUIRE(!a->kfac, "sg_a2c_set_rmsprop: an ACKTR handle has K-FAC state, not RMSprop's (sg_acktr_get_state)");
     SG_REQUIRE(a->a2c, "sg_a2c_set_rmsprop: not an A2C handle (sg_ppo_set_adam)");
     const SgPolicyDesc& d = a->policy->desc;
     SG_REQUIRE(n == sg_policy_flat_count(d), "sg_a2c_set_rmsprop: bad length");
@@ -441,7 +654,7 @@ extern "C" int sg_a2c_set_rmsprop(sg_ppo* a, const float* square_avg, int64_t n,
 // parameters, adv = returns[:-1] - values, loss = vcoef mean(adv^2) + (-mean(adv.detach() logp)) - ecoef mean(ent), one
 // clip_grad_norm_ + RMSprop step.  The rows are taken in chunks of SG_A2C_CHUNK_ROWS; each chunk's slabs are added to the
 // gradient, so the scratch does not grow with T*N.
-static int a2c_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
+static int a2c_update(sg_ppo* a, sg_rollout* r, uint64_t seed, float out3[3]) {
     sg_ctx* ctx = a->ctx;
     const SgPolicyDesc& d = a->policy->desc;
     SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_ppo_update: A2C runs on one rank (this context's world is %d)", ctx->world);
@@ -520,6 +733,67 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
     const int nblk_r = (d.total + 8 + SG_PPO_REDUCE_PARAMS - 1) / SG_PPO_REDUCE_PARAMS;
     const double oma = 1.0 - (double)a->alpha;   // torch: value = 1 - alpha in Python doubles
 
+    // ACKTR: the value noise of this update (injected, or drawn outside the graph), the chunk's Fisher stacks
+    SgKfac* kf = a->kfac;
+    AcktrFisherArgs fa;
+    KfacStatsArgs sa;
+    KfacEigArgs ea;
+    memset(&fa, 0, sizeof fa);
+    memset(&sa, 0, sizeof sa);
+    memset(&ea, 0, sizeof ea);
+    size_t lds_fish = 0, lds_eig = 0;
+    if (kf) {
+        SG_REQUIRE(!kf->eps_pending || (int64_t)kf->eps_host.size() == TN,
+                   "sg_ppo_update: the injected value noise has %lld values, the rollout %lld rows", (long long)kf->eps_host.size(),
+                   (long long)TN);
+        const int frows = (chunk + 63) & ~63;
+        const int ldZ = d.ldH;
+        const size_t fish_f = (size_t)frows * (4 * (size_t)ldZ + 2 * (size_t)d.A + 1);
+        if (kf->eps_cap < TN || kf->fish_cap < fish_f) {
+            SG_CHECK(hipStreamSynchronize(ctx->stream));
+            if (kf->eps_cap < TN) {
+                if (kf->d_eps) SG_CHECK(sg_dev_free(kf->d_eps));
+                SG_CHECK(sg_dev_malloc((void**)&kf->d_eps, sizeof(float) * TN));
+                kf->eps_cap = TN;
+            }
+            if (kf->fish_cap < fish_f) {
+                if (kf->d_fish) SG_CHECK(sg_dev_free(kf->d_fish));
+                SG_CHECK(sg_dev_malloc((void**)&kf->d_fish, sizeof(float) * fish_f));
+                kf->fish_cap = fish_f;
+            }
+        }
+        if (kf->eps_pending) {
+            SG_COPY_SYNC(ctx, kf->d_eps, kf->eps_host.data(), sizeof(float) * TN, hipMemcpyHostToDevice);
+            kf->eps_pending = false;
+            kf->eps_host.clear();
+        } else {
+            hipLaunchKernelGGL(k_acktr_noise, dim3((unsigned)((TN + 255) / 256)), dim3(256), 0, ctx->stream, kf->d_eps, TN, seed,
+                               (int64_t)a->opt_t);
+        }
+        fa.d = d; fa.params = a->policy->d_params; fa.ldP = ldP; fa.ldZ = ldZ; fa.inv_B = pa.inv_B;
+        float* fz = kf->d_fish;
+        for (int t = 0; t < 2; ++t) {
+            fa.H1[t] = pa.H1[t]; fa.H2[t] = pa.H2[t]; fa.OUT[t] = pa.OUT[t];
+            fa.Z1[t] = fz; fz += (size_t)frows * ldZ;
+            fa.Z2[t] = fz; fz += (size_t)frows * ldZ;
+        }
+        fa.GMU = fz; fz += (size_t)frows * d.A;
+        fa.GLS = fz; fz += (size_t)frows * d.A;
+        fa.GV = fz;
+        lds_fish = sizeof(float) * SG_ACKTR_FROWS * (size_t)(d.A + d.Hp);
+        const SgTrunk& ac = d.trunk[0];
+        const SgTrunk& cr = d.trunk[1];
+        const float* src[SG_KFAC_NF] = {nullptr, pa.H1[0], pa.H2[0], pa.H1[1], pa.H2[1], fa.Z1[0], fa.Z2[0], fa.Z1[1], fa.Z2[1],
+                                        fa.GV, fa.GMU, fa.GLS};
+        const int lds_[SG_KFAC_NF] = {d.ldO, ac.ldH, ac.ldH, cr.ldH, cr.ldH, ldZ, ldZ, ldZ, ldZ, 1, d.A, d.A};
+        for (int f = 0; f < SG_KFAC_NF; ++f) {
+            sa.U[f] = src[f]; sa.ld[f] = lds_[f]; sa.n[f] = kf->n[f]; sa.off[f] = kf->off[f];
+        }
+        sa.tiles = kf->d_tiles; sa.acc = kf->d_acc;
+        ea = kfac_eig_args(kf);
+        lds_eig = kfac_eig_lds(kf);
+    }
+
     auto enqueue_step = [&]() -> int {
         hipLaunchKernelGGL(k_a2c_gather, dim3((unsigned)((TN + 63) / 64)), dim3(256), 0, ctx->stream, ga);
         for (int c = 0; c < n_chunks; ++c) {
@@ -534,6 +808,31 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
             launch_a2c_bwd(ctx, MT, d, dim3(Gc, d.n_trunks), lds_b, pa, gw);
             SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_a2c_reduce, dim3(nblk_r), dim3(256), 0, a->d_slabs, Gc, slab_stride, d.total, a->d_grad,
                       a->d_part, c > 0 ? 1 : 0);
+            if (kf) {
+                fa.ACT = epACT + rb * d.A; fa.eps = kf->d_eps + rb; fa.cnt = cnt;
+                hipLaunchKernelGGL(k_acktr_fisher, dim3((unsigned)((cnt + SG_ACKTR_FROWS - 1) / SG_ACKTR_FROWS), 2), dim3(256),
+                                   lds_fish, ctx->stream, fa);
+                sa.U[0] = epX + rb * d.ldO; sa.cnt = cnt; sa.accumulate = c > 0 ? 1 : 0;
+                hipLaunchKernelGGL(k_kfac_stats, dim3((unsigned)kf->n_tiles), dim3(64 * SG_KFAC_STATS_WAVES), 0, ctx->stream, sa);
+            }
+        }
+        if (kf) {
+            const sg_acktr_config& kc = kf->cfg;
+            const double sd = (double)kc.stat_decay;
+            hipLaunchKernelGGL(k_kfac_fold, dim3((unsigned)((kf->fac_total + 255) / 256)), dim3(256), 0, ctx->stream, kf->d_m,
+                               kf->d_acc, kf->fac_total, kf->g_start, pa.inv_B, (float)TN, kf->d_ks, (float)(sd / (1.0 - sd)),
+                               (float)(1.0 - sd));
+            hipLaunchKernelGGL(k_kfac_eig, dim3(SG_KFAC_NF), dim3(512), lds_eig, ctx->stream, ea);
+            for (int st = 0; st < 4; ++st)
+                hipLaunchKernelGGL(k_kfac_gemm, dim3((unsigned)kf->max_tiles, SG_KFAC_MODULES), dim3(256), 0, ctx->stream,
+                                   kf->d_jobs + st * SG_KFAC_MODULES, kf->max_tiles, kc.damping, kf->d_vpart);
+            const double mom = (double)kc.momentum;
+            hipLaunchKernelGGL(k_kfac_step, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, a->policy->d_params, a->d_m,
+                               kf->d_vec, kf->d_vpart, SG_KFAC_MODULES * kf->max_tiles, d.total, kf->d_ks, kc.lr, kc.kl_clip,
+                               kc.momentum, (float)((double)kc.lr * (1.0 - mom)));
+            hipLaunchKernelGGL(k_kfac_tick, dim3(1), dim3(64), 0, ctx->stream, kf->d_ks, a->d_grad, d.total, pa.inv_B,
+                               a->d_loss_acc);
+            return 0;
         }
         SG_LAUNCH(ctx, SG_PROF_PPO_ADAM, k_a2c_rmsprop, dim3(nblk), dim3(256), 0, a->policy->d_params, a->d_v, a->d_grad, a->d_part,
                   nblk_r, d.total, pa.st, a->alpha, (float)oma, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B, a->d_loss_acc);
@@ -550,7 +849,9 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
                                   (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)a->policy->d_params,
                                   (uint64_t)TN, ((uint64_t)n_chunks << 32) | (uint64_t)chunk, ((uint64_t)MT << 32) | (uint64_t)G,
                                   ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
-                                  ((uint64_t)fbits[4] << 32) | fbits[5], 0, 0, 0x413243ull + (gw ? 8 : 0) + (1ull << 7), 0, 0};
+                                  ((uint64_t)fbits[4] << 32) | fbits[5], kf ? (uint64_t)(uintptr_t)kf->d_eps : 0,
+                                  kf ? (uint64_t)(uintptr_t)kf->d_fish : 0, 0x413243ull + (gw ? 8 : 0) + (1ull << 7) + (kf ? (1ull << 9) : 0),
+                                  0, 0};
         if (!a->steps_graph || memcmp(key, a->steps_graph_key, sizeof key) != 0) {
             if (a->steps_graph) { SG_CHECK(hipGraphExecDestroy(a->steps_graph)); a->steps_graph = nullptr; }
             if (sg_try_capture(ctx, &a->steps_graph, enqueue_step) != 0) {
@@ -566,9 +867,11 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
     SG_CHECK(hipGetLastError());
     a->opt_t += 1;
     if (!out3) return 0;   // queued: the losses come through the results ring (step count 1)
-    double acc[3];
-    SG_TRY(sg_ctx_fetch_f64(ctx, a->d_loss_acc, acc, 3));
+    double acc[4];
+    SG_TRY(sg_ctx_fetch_f64(ctx, a->d_loss_acc, acc, kf ? 4 : 3));
     for (int i = 0; i < 3; ++i) out3[i] = (float)acc[i];
+    SG_REQUIRE(!kf || acc[3] == 0.0, "sg_ppo_update: k_kfac_eig hit its sweep cap (%d): the K-FAC eigenbases are not valid",
+               SG_KFAC_SWEEPS);
     return 0;
 }
 
@@ -579,7 +882,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
         SG_REQUIRE(r->O == a->policy->desc.O && r->A == a->policy->desc.A,
                    "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)", r->O, r->A,
                    a->policy->desc.O, a->policy->desc.A);
-        return a2c_update(a, r, out3);
+        return a2c_update(a, r, seed, out3);
     }
     sg_ctx* ctx = a->ctx;
     const SgPolicyDesc& d = a->policy->desc;
@@ -944,7 +1247,9 @@ extern "C" int sg_results_publish(sg_ctx* ctx, sg_disc* d, sg_ppo* a, int slot) 
                        d ? d->d_scal : nullptr, a ? a->d_loss_acc : nullptr, d ? (double)d->last_n_d : 1.0,
                        a ? (double)a->cfg.ppo_epoch * a->cfg.num_mini_batch : 1.0,
                        d ? sg_disc_err_word(d) : nullptr,
-                       (a && a->d_pair) ? a->d_pair + SG_PAIR_ERR_WORD : nullptr, sg_comm_peer_err_word(ctx));
+                       (a && a->kfac) ? reinterpret_cast<const unsigned*>(&a->kfac->d_ks->err)   // ACKTR: the eigensolver's word
+                                      : (a && a->d_pair) ? a->d_pair + SG_PAIR_ERR_WORD : nullptr,
+                       sg_comm_peer_err_word(ctx));
     SG_CHECK(hipGetLastError());
     SG_CHECK(hipEventRecord(ctx->res_ev[slot], ctx->stream));
     ctx->res_d[slot] = d;
@@ -959,7 +1264,10 @@ extern "C" int sg_results_fetch(sg_ctx* ctx, int slot, double out13[13]) {
     SG_CHECK(hipEventSynchronize(ctx->res_ev[slot]));
     const double* src = ctx->results + 16 * slot;
     memcpy(out13, src, sizeof(double) * 13);
-    const bool d_err = src[13] != 0.0, a_err = src[14] != 0.0;
+    const bool d_err = src[13] != 0.0;
+    // slot 14 is the policy object's word: k_ppo_pair's hand-off time-out, or for an ACKTR object k_kfac_eig's sweep cap
+    const bool k_err = src[14] != 0.0 && ctx->res_a[slot] && ctx->res_a[slot]->kfac;
+    const bool a_err = src[14] != 0.0 && !k_err;
     if (src[15] != 0.0) {
         SG_CHECK(hipSetDevice(ctx->device));
         if (unsigned* w = sg_comm_peer_err_word(ctx)) SG_CHECK(hipMemsetAsync(w, 0, sizeof(unsigned), ctx->stream));
@@ -983,5 +1291,7 @@ extern "C" int sg_results_fetch(sg_ctx* ctx, int slot, double out13[13]) {
                    "multi-launch form", d_err ? "k_disc_step4" : "", d_err && a_err ? " and " : "", a_err ? "k_ppo_pair" : "",
                    d_err && a_err ? "discriminator's and the policy's state are" : d_err ? "discriminator's state is" : "policy's state is");
     }
+    SG_REQUIRE(!k_err, "sg_results_fetch: k_kfac_eig hit its sweep cap (%d) during or before the ACKTR update this slot reports: "
+               "the K-FAC eigenbases are not valid and the update stepped with them", SG_KFAC_SWEEPS);
     return 0;
 }

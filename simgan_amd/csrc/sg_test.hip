@@ -13,6 +13,7 @@
 #include "sg_rng.hpp"
 #include "sg_test_api.h"
 #include "sg_thin.hpp"
+#include "sg_kfac.hpp"
 
 // this library's own error slot (the product's sg_set_error is not exported)
 static thread_local char g_test_err[1024] = "";
@@ -705,5 +706,61 @@ extern "C" int sg_test_tear_probe(sg_ctx* ctx, int mode, int pairs4, int iters, 
     SG_CHECK(hipStreamSynchronize(ctx->stream));
     SG_CHECK(hipMemcpy(out4, d_out, 32, hipMemcpyDeviceToHost));
     (void)hipFree(d_words); (void)hipFree(d_done); (void)hipFree(d_out);
+    return 0;
+}
+
+// k_kfac_eig on one symmetric matrix (its upper triangle): A [n][n] -> Q [n][n] (eigenvector columns), d [n] (<= 1e-6 set to 0),
+// *sweeps = Jacobi sweeps taken (-1: the sweep cap was hit).  The LDS path for n <= the object's limit, global memory above.
+extern "C" int sg_test_kfac_eig(sg_ctx* ctx, int n, const float* A, float* Q, float* d, int* sweeps) {
+    SG_REQUIRE(ctx && A && Q && d && sweeps && n >= 1 && n <= 512, "sg_test_kfac_eig: bad arguments");
+    int lds_n = 0;
+    while (16 * (lds_n + 1) * (lds_n + 1) + 8192 <= ctx->lds_bytes) ++lds_n;
+    const size_t nn = (size_t)n * n;
+    float *dm = nullptr, *dq = nullptr, *dd = nullptr;
+    double* dw = nullptr;
+    int* dsw = nullptr;
+    SG_CHECK(hipSetDevice(ctx->device));
+    SG_CHECK(hipMalloc((void**)&dm, sizeof(float) * nn));
+    SG_CHECK(hipMalloc((void**)&dq, sizeof(float) * nn));
+    SG_CHECK(hipMalloc((void**)&dd, sizeof(float) * n));
+    SG_CHECK(hipMalloc((void**)&dw, sizeof(double) * 2 * nn));
+    SG_CHECK(hipMalloc((void**)&dsw, sizeof(int) * SG_KFAC_NF));
+    SG_CHECK(hipMemcpy(dm, A, sizeof(float) * nn, hipMemcpyHostToDevice));
+    KfacEigArgs e;
+    memset(&e, 0, sizeof e);
+    e.m = dm; e.Q = dq; e.dv = dd; e.work = dw; e.n[0] = n; e.lds_n = lds_n; e.tf = 1; e.ks = nullptr; e.sweeps = dsw;
+    const size_t lds = n <= lds_n ? sizeof(double) * 2 * nn : 0;
+    hipLaunchKernelGGL(k_kfac_eig, dim3(1), dim3(512), lds, ctx->stream, e);
+    SG_CHECK(hipGetLastError());
+    SG_CHECK(hipStreamSynchronize(ctx->stream));
+    SG_CHECK(hipMemcpy(Q, dq, sizeof(float) * nn, hipMemcpyDeviceToHost));
+    SG_CHECK(hipMemcpy(d, dd, sizeof(float) * n, hipMemcpyDeviceToHost));
+    SG_CHECK(hipMemcpy(sweeps, dsw, sizeof(int), hipMemcpyDeviceToHost));
+    (void)hipFree(dm); (void)hipFree(dq); (void)hipFree(dd); (void)hipFree(dw); (void)hipFree(dsw);
+    return 0;
+}
+
+// k_acktr_noise: the value noise ACKTR draws for `update` of a handle whose sg_ppo_update got `seed`
+extern "C" int sg_test_acktr_noise(sg_ctx* ctx, int64_t n, uint64_t seed, int64_t update, float* out) {
+    SG_REQUIRE(ctx && out && n > 0, "sg_test_acktr_noise: bad arguments");
+    float* dv = nullptr;
+    SG_CHECK(hipSetDevice(ctx->device));
+    SG_CHECK(hipMalloc((void**)&dv, sizeof(float) * n));
+    hipLaunchKernelGGL(k_acktr_noise, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, dv, n, seed, update);
+    SG_CHECK(hipGetLastError());
+    SG_CHECK(hipStreamSynchronize(ctx->stream));
+    SG_CHECK(hipMemcpy(out, dv, sizeof(float) * n, hipMemcpyDeviceToHost));
+    (void)hipFree(dv);
+    return 0;
+}
+
+// raises an ACKTR object's sticky eigensolver word on the device, as k_kfac_eig does when it hits its sweep cap (tests: how a
+// fetching and a queued update report it)
+extern "C" int sg_test_raise_kfac_error(sg_ppo* a) {
+    SG_REQUIRE(a && a->kfac, "sg_test_raise_kfac_error: not an ACKTR handle");
+    const int one = 1;
+    SG_CHECK(hipSetDevice(a->ctx->device));
+    SG_CHECK(hipMemcpyAsync(&a->kfac->d_ks->err, &one, sizeof one, hipMemcpyHostToDevice, a->ctx->stream));
+    SG_CHECK(hipStreamSynchronize(a->ctx->stream));
     return 0;
 }

@@ -32,6 +32,12 @@ SG_API int sg_test_rng(sg_ctx *ctx, int kind, int64_t n, uint64_t seed, void *ou
 /* raises the sticky time-out word of k_disc_step4 (d) and / or k_ppo_pair (a) on the device, as a workgroup that gave up
  * waiting would: the next one-launch steps end at once with NaN losses (tests: how a queued update reports it) */
 SG_API int sg_test_raise_handoff_error(sg_disc *d, sg_ppo *a);
+/* ACKTR: k_kfac_eig on one matrix (Q columns = eigenvectors, d <= 1e-6 set to 0, *sweeps -1 at the sweep cap) and the value
+ * noise k_acktr_noise draws for one update */
+SG_API int sg_test_kfac_eig(sg_ctx *ctx, int n, const float *A, float *Q, float *d, int *sweeps);
+SG_API int sg_test_acktr_noise(sg_ctx *ctx, int64_t n, uint64_t seed, int64_t update, float *out);
+/* raises an ACKTR object's sticky eigensolver error word, as k_kfac_eig does at its sweep cap */
+SG_API int sg_test_raise_kfac_error(sg_ppo *a);
 #ifdef __cplusplus
 }
 #endif
