@@ -78,7 +78,14 @@ SG_API int sg_ctx_comm_info(sg_ctx *ctx, int *rank, int *world);
 SG_API int sg_ctx_set_disc_dp(sg_ctx *ctx, int sharded);
 
 /* ------------------------------------------------------------------- policy */
-enum { SG_POLICY_MLP = 0, SG_POLICY_SPLIT = 1 };
+enum { SG_POLICY_MLP = 0, SG_POLICY_SPLIT = 1, SG_POLICY_GRU = 2 };
+/* kind SG_POLICY_GRU (sg_policy_create / sg_policy_create2; num_feet ignored): Policy(..., base_kwargs={'recurrent': True,
+ * 'hidden_size': H}), a2c/model.py:117-131,233-253 -- nn.GRU(obs_dim, H) (one layer, gates r, z, n), then the actor and critic
+ * trunks on the H-wide GRU state, critic_linear and DiagGaussian.  Flat parameter order: base.gru.weight_ih_l0 [3H, O],
+ * weight_hh_l0 [3H, H], bias_ih_l0 [3H], bias_hh_l0 [3H], then the MLP kind's order with obs_dim replaced by H.  Such a policy
+ * is served by the sg_policy_*_rnn entry points below; sg_policy_act / _get_value / _evaluate / _act_ensemble refuse it (and
+ * the _rnn calls refuse a feed-forward policy), as do sg_a2c_create, sg_acktr_create, sg_rollout_compute_returns_policy and
+ * sg_rollout_fill_synthetic.  sg_ppo_create takes it: sg_ppo_update then runs PPO through time (sg_ppo_set_hidden_states). */
 /* Policy(obs_shape, action_space, base_kwargs)            a2c/model.py:38-67   (kind MLP)
  * SplitPolicy(obs_shape, action_space, base_kwargs)       a2c/model_split.py:40-52 (kind SPLIT;
  * requires act_dim == 7*num_feet, a2c/model_split.py:205). Parameters start at zero. */
@@ -104,6 +111,20 @@ SG_API int sg_policy_get_value(sg_policy *p, const float *obs, int n, float *val
 /* Policy.evaluate_actions a2c/model.py:107-114: value[n], logp[n], *entropy = dist.entropy().mean() */
 SG_API int sg_policy_evaluate(sg_policy *p, const float *obs, const float *action, int n, float *value,
                        float *logp, float *entropy);
+/* Recurrent forms (kind SG_POLICY_GRU).  One step, MLPBase.forward -> NNBase._forward_gru with x.size(0) == hxs.size(0),
+ * a2c/model.py:137-141,255-264: h' = GRU(obs, hxs * masks); the heads run on h'.  obs[n,O], hxs[n,H], masks[n] ->
+ * hxs_out[n,H] = h'; the other arguments as in sg_policy_act (Policy.act, a2c/model.py:89-101). */
+SG_API int sg_policy_act_rnn(sg_policy *p, const float *obs, const float *hxs, const float *masks, int n, const float *noise,
+                      uint64_t seed, int deterministic, float *value, float *action, float *logp, float *hxs_out);
+/* Policy.get_value a2c/model.py:103-105 on a recurrent policy (the new state is dropped, as the reference drops it). */
+SG_API int sg_policy_get_value_rnn(sg_policy *p, const float *obs, const float *hxs, const float *masks, int n, float *value);
+/* Policy.evaluate_actions a2c/model.py:107-114 over a sequence, NNBase._forward_gru's second branch a2c/model.py:142-199:
+ * obs[T*n,O], masks[T*n] and action[T*n,A] are time-major (row t*n + j), hxs[n,H] is the state before step 0.  The reference
+ * cuts the sequence where a mask is 0 and multiplies h by masks[t] at the head of each piece; for 0/1 masks that is
+ * h_{t-1} * masks[t] at every step, which is what runs here.  value[T*n], logp[T*n], *entropy = dist.entropy().mean(),
+ * hxs_out[n,H] = the state after step T-1.  T == 1 is the one-step form. */
+SG_API int sg_policy_evaluate_rnn(sg_policy *p, const float *obs, const float *hxs, const float *masks, const float *action,
+                           int T, int n, float *value, float *logp, float *entropy, float *hxs_out);
 /* The policies that live INSIDE the reference's hybrid-sim environments, batched over the N environments of a
  * pool: every worker calls a batch-1 actor_critic.act per step, in refinement mode on one of five saved dynamics
  * policies drawn per step (my_pybullet_envs/hopper_env_combined_policy.py:113-140,211-216,
@@ -186,12 +207,23 @@ SG_API int sg_ppo_update(sg_ppo *a, sg_rollout *r, const int64_t *perms, int64_t
  * n_d, ppo_epoch * num_mini_batch}; losses = sums / their step count (float32, as the synchronous calls return them). */
 SG_API int sg_results_publish(sg_ctx *ctx, sg_disc *d, sg_ppo *a, int slot);
 SG_API int sg_results_fetch(sg_ctx *ctx, int slot, double out13[13]);
-/* Adam state access for checkpoint/parity: m, v flat [n] in state_dict order; *step = t. */
-/* The permutations the last sg_ppo_update consumed ([ppo_epoch][T*N], injected or library-drawn), so a run made
+/* The permutations the last sg_ppo_update consumed ([ppo_epoch][T*N]; [ppo_epoch][N] for a recurrent policy: the environments of
+ * every epoch; injected or library-drawn), so a run made
  * with the library's generator can be replayed elsewhere (the role torch.manual_seed plays for the reference). */
 SG_API int sg_ppo_last_perms(sg_ppo *a, int64_t *perms, int64_t count);
+/* Adam state access for checkpoint/parity: m, v flat [n] in state_dict order (a recurrent policy: the GRU's tensors first); *step = t. */
 SG_API int sg_ppo_get_adam(sg_ppo *a, float *m, float *v, int64_t n, int64_t *step);
 SG_API int sg_ppo_set_adam(sg_ppo *a, const float *m, const float *v, int64_t n, int64_t step);
+/* PPO.update with a recurrent policy (kind SG_POLICY_GRU), a2c/algo/ppo.py:74-90 over RolloutStorage.recurrent_generator
+ * a2c/storage.py:194-251: sg_ppo_update then takes whole environments per minibatch -- per = N // num_mini_batch of them, all T
+ * steps each, N // per optimizer steps per epoch (more than num_mini_batch when per does not divide N into that many; the
+ * returned losses are still divided by ppo_epoch * num_mini_batch, as the reference divides them; N % per != 0, where the
+ * reference runs past its permutation, is an error) -- and back-propagates through the GRU scan.  perms is [ppo_epoch][N], the
+ * torch.randperm(num_processes) of every epoch (sg_ppo_last_perms returns the same shape), or NULL.  The sequences start from
+ * rollouts.recurrent_hidden_states[0] (a2c/storage.py:216-217) and use masks[:-1]: the rollout's MASKS field must be current,
+ * and the states of slot 0, hxs0[N*H], are handed over with this call before EVERY update (the device rollout has no
+ * hidden-state field).  One rank only; sg_ppo_set_symmetry refuses a recurrent policy. */
+SG_API int sg_ppo_set_hidden_states(sg_ppo *a, const float *hxs0, int64_t count);
 /* Mirror-symmetry loss of PPO.update, a2c/algo/ppo.py:110-143 (a2c/main.py:133-146, --loss-sym): every optimizer step adds
  * coef * mean((M_a mu(s) - mu(mirror_obs(s)))^2) over the minibatch's B x A elements, mu = the DiagGaussian mean (fc_mean);
  * M_a mu(s) is a constant of the loss (the reference mirrors it through numpy), so its gradient reaches the actor trunk and

@@ -22,7 +22,7 @@ H = C.c_void_p  # opaque handle
 # field ids (include/simgan_hip.h)
 F_OBS, F_OBS_FEAT, F_ACTIONS, F_REWARDS, F_VALUE_PREDS, F_RETURNS, F_LOGP, F_MASKS, F_BAD_MASKS, \
     F_ADVANTAGES = range(10)
-POLICY_MLP, POLICY_SPLIT = 0, 1
+POLICY_MLP, POLICY_SPLIT, POLICY_GRU = 0, 1, 2
 PROF_DISC_CHAIN, PROF_DISC_WGRAD, PROF_PPO_FWD, PROF_PPO_BWD, PROF_PPO_REDUCE, PROF_RELABEL, PROF_PPO_ADAM = range(7)
 
 
@@ -67,6 +67,11 @@ PROTOTYPES = {
     "sg_policy_act": (C.c_int, [H, c_float_p, C.c_int, c_float_p, C.c_uint64, C.c_int, c_float_p, c_float_p, c_float_p]),
     "sg_policy_get_value": (C.c_int, [H, c_float_p, C.c_int, c_float_p]),
     "sg_policy_evaluate": (C.c_int, [H, c_float_p, c_float_p, C.c_int, c_float_p, c_float_p, c_float_p]),
+    "sg_policy_act_rnn": (C.c_int, [H, c_float_p, c_float_p, c_float_p, C.c_int, c_float_p, C.c_uint64, C.c_int, c_float_p, c_float_p,
+                                    c_float_p, c_float_p]),
+    "sg_policy_get_value_rnn": (C.c_int, [H, c_float_p, c_float_p, c_float_p, C.c_int, c_float_p]),
+    "sg_policy_evaluate_rnn": (C.c_int, [H, c_float_p, c_float_p, c_float_p, c_float_p, C.c_int, C.c_int, c_float_p, c_float_p,
+                                         c_float_p, c_float_p]),
     "sg_policy_act_ensemble": (C.c_int, [C.POINTER(H), C.c_int, C.POINTER(C.c_int32), c_float_p, C.c_int, c_float_p, C.c_uint64,
                                          C.c_int, c_float_p, c_float_p, c_float_p]),
     "sg_rollout_create": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(H)]),
@@ -85,6 +90,7 @@ PROTOTYPES = {
     "sg_ppo_set_lr": (C.c_int, [H, C.c_float]),
     "sg_ppo_update": (C.c_int, [H, H, c_i64_p, C.c_int64, C.c_uint64, c_float_p]),
     "sg_ppo_last_perms": (C.c_int, [H, c_i64_p, C.c_int64]),
+    "sg_ppo_set_hidden_states": (C.c_int, [H, c_float_p, C.c_int64]),
     "sg_ppo_get_adam": (C.c_int, [H, c_float_p, c_float_p, C.c_int64, c_i64_p]),
     "sg_ppo_set_adam": (C.c_int, [H, c_float_p, c_float_p, C.c_int64, C.c_int64]),
     "sg_ppo_set_symmetry": (C.c_int, [H, C.c_float, c_float_p, c_float_p]),

@@ -65,6 +65,12 @@ class PPO():
         self.mirror_act = mirror_act
         self.is_cuda = True   # the rollout the update reads lives in HBM whatever the host tensors are
 
+        self.recurrent = bool(getattr(actor_critic, "is_recurrent", False))   # a2c/algo/ppo.py:74-76: recurrent_generator
+        if self.recurrent and mirror_obs is not None and symmetry_coef > 0:
+            raise NotImplementedError("mirror-symmetry loss: implemented for feed-forward policies only, not for a recurrent Policy")
+        if self.recurrent and getattr(actor_critic.ctx, "world", 1) > 1:
+            raise NotImplementedError("PPO with a recurrent Policy runs on one rank: data-parallel PPO through time is not implemented "
+                                      f"(this context's communicator has world {actor_critic.ctx.world})")
         self.ctx = actor_critic.ctx
         self.lib = self.ctx.lib
         cfg = _lib.PPOConfig(float(clip_param), int(ppo_epoch), int(num_mini_batch), float(value_loss_coef),
@@ -136,6 +142,16 @@ class PPO():
         (include/simgan_hip.h: sg_ppo_update).  fetch_losses=False: queue the update and return None without waiting for
         it (the losses are read later through the results ring, simgan_amd/driver.py)."""
         rollouts._push([_lib.F_OBS, _lib.F_ACTIONS, _lib.F_VALUE_PREDS, _lib.F_RETURNS, _lib.F_LOGP])
+        if self.recurrent:
+            # whole environments per minibatch, from the state of slot 0 (a2c/storage.py:194-251): `perms` is [ppo_epoch, N]
+            rollouts._push([_lib.F_MASKS])
+            hxs0 = rollouts.recurrent_hidden_states[0]
+            hxs0 = np.ascontiguousarray(hxs0.numpy() if hasattr(hxs0, "numpy") else hxs0, np.float32)
+            if hxs0.shape != (rollouts.num_processes, self.actor_critic.recurrent_hidden_state_size):
+                raise ValueError(f"rollouts.recurrent_hidden_states[0] is {hxs0.shape}; the policy's state is "
+                                 f"[{rollouts.num_processes}, {self.actor_critic.recurrent_hidden_state_size}] (build RolloutStorage with "
+                                 "actor_critic.recurrent_hidden_state_size)")
+            _lib.check(self.lib.sg_ppo_set_hidden_states(self.h, _lib.fptr(hxs0), hxs0.size))
         if self._mirror_obs_fn is not None:
             self._upload_mirrored_obs(rollouts)
         out = (C.c_float * 3)()
@@ -145,11 +161,12 @@ class PPO():
         _lib.check(self.lib.sg_ppo_update(self.h, rollouts.h, None if perms is None else _lib.i64ptr(perms),
                                           0 if perms is None else perms.size, (self.seed + self._calls) & (2 ** 64 - 1),
                                           out if fetch_losses else None))
-        self._last_perm_shape = (self.ppo_epoch, rollouts.num_steps * rollouts.num_processes)
+        self._last_perm_shape = (self.ppo_epoch, rollouts.num_processes if self.recurrent else rollouts.num_steps * rollouts.num_processes)
         return (float(out[0]), float(out[1]), float(out[2])) if fetch_losses else None
 
     def last_perms(self):
-        """[ppo_epoch, T*N] permutations the last update() consumed (injected or library-drawn)."""
+        """[ppo_epoch, T*N] permutations the last update() consumed (injected or library-drawn); [ppo_epoch, N] for a recurrent
+        policy (the environments of every epoch's minibatches)."""
         perms = np.empty(self._last_perm_shape, np.int64)
         _lib.check(self.lib.sg_ppo_last_perms(self.h, _lib.i64ptr(perms), perms.size))
         return perms

@@ -47,6 +47,8 @@ _ALLOWED = {
     ("numpy", "ndarray"), ("numpy", "dtype"), ("numpy", "float64"), ("numpy", "float32"), ("numpy", "int64"),
     ("types", "SimpleNamespace"),
 }
+# a recurrent policy's base.gru: read as a stand-in (its four tensors sit in `_parameters`); nn.GRU's own __setstate__ is not run
+_GRU = ("torch.nn.modules.rnn", "GRU")
 _STUB_ROOTS = ("third_party", "a2c_ppo_acktr")   # the reference's own classes (also when imported via sys.path.append("third_party"))
 _TORCH_STORAGES = ("FloatStorage", "DoubleStorage", "HalfStorage", "BFloat16Storage", "LongStorage", "IntStorage",
                    "ShortStorage", "CharStorage", "ByteStorage", "BoolStorage")
@@ -103,7 +105,7 @@ class _StubUnpickler(pickle.Unpickler):
             return super().find_class(module, name)
         if (module, name) in (("builtins", "getattr"), ("__builtin__", "getattr")):
             return _guarded_getattr
-        if module.split(".")[0] in _STUB_ROOTS:
+        if module.split(".")[0] in _STUB_ROOTS or (module, name) == _GRU:
             return _stub_class(module, name)
         raise pickle.UnpicklingError(f"checkpoint names the global {module}.{name}, which a SimGAN checkpoint has no use "
                                      "for: refusing to resolve it")
@@ -166,6 +168,11 @@ def _policy_dims(class_name, sd):
         H, O = sd["base.actor.0.weight"].shape
         A = sd["dist.fc_mean.weight"].shape[0]
         Hc = sd["base.critic.0.weight"].shape[0]     # 64 beside any actor width once reset_critic has run (a2c/model.py:80-87)
+        if "base.gru.weight_ih_l0" in sd:            # recurrent=True (a2c/model.py:124-131): the trunks read the H-wide GRU state
+            G3, O_in = sd["base.gru.weight_ih_l0"].shape
+            assert G3 == 3 * H and O == H and sd["base.gru.weight_hh_l0"].shape == (3 * H, H) and \
+                sd["base.critic.0.weight"].shape == (Hc, H), "inconsistent GRU / trunk shapes in the checkpoint"
+            return dict(kind="mlp", obs_dim=int(O_in), act_dim=int(A), hidden=int(H), num_feet=1, critic_hidden=int(Hc), recurrent=True)
         assert sd["base.critic.0.weight"].shape == (Hc, O) and sd["base.critic.2.weight"].shape == (Hc, Hc) and \
             sd["base.critic_linear.weight"].shape == (1, Hc), "inconsistent critic shapes in the checkpoint"
         return dict(kind="mlp", obs_dim=int(O), act_dim=int(A), hidden=int(H), num_feet=1, critic_hidden=int(Hc))
@@ -404,6 +411,11 @@ def reference_module_state(kind, sd):
 
 
 # ---------------------------------------------------------------------------------- device wrappers
+# nn.GRU pickles private attributes (_flat_weights_names, _all_weights, proj_size, ...) whose set changes between torch releases;
+# a stand-in written here would load only on the torch it was modelled on, so the reference's layout is not written at all
+RECURRENT_SAVE_MSG = ("a recurrent Policy cannot be written in the reference's object layout (nn.GRU's pickled attributes are private to "
+                      "the torch release that wrote them); pickle the policy natively (pickle / torch.save of the object) or save "
+                      "policy.state_dict()")
 class _Box(object):
     def __init__(self, n):
         self.shape = (int(n),)
@@ -418,7 +430,7 @@ def load_policy(path, ctx=None):
     from .model_split import SplitPolicy
     ck = read_reference_checkpoint(path)
     if ck["kind"] == "mlp":
-        pol = Policy((ck["obs_dim"],), _Box(ck["act_dim"]), base_kwargs={"recurrent": False, "hidden_size": ck["hidden"]}, ctx=ctx,
+        pol = Policy((ck["obs_dim"],), _Box(ck["act_dim"]), base_kwargs={"recurrent": bool(ck.get("recurrent")), "hidden_size": ck["hidden"]}, ctx=ctx,
                      critic_hidden=ck.get("critic_hidden"))
     else:
         pol = SplitPolicy((ck["obs_dim"],), _Box(ck["act_dim"]),
@@ -429,6 +441,8 @@ def load_policy(path, ctx=None):
 
 def save_policy(path, policy, ob_rms=None):
     """a2c/main.py:260-269: a file the reference's `torch.load(path)` turns back into `[actor_critic, ob_rms]`."""
+    if policy.is_recurrent:
+        raise NotImplementedError(RECURRENT_SAVE_MSG)
     save_reference_checkpoint(path, "mlp" if policy.KIND == 0 else "split", policy.state_dict(), ob_rms)
 
 

@@ -190,13 +190,32 @@ SgEv sg_prof_events(sg_ctx* ctx, int which);
     } while (0)
 #endif
 
+// GRU base of a recurrent Policy (a2c/model.py:117-201: nn.GRU(obs_dim, H), gate order r, z, n).  Padded image behind the
+// heads' block in sg_policy::d_params: every gate's [H, K] weight is its own [Hp][ld(K)] tile block (gate g at g * Hp * ld),
+// every bias [3][Hp], so the three gates of one hidden unit are the same (row, column) of three MFMA tiles.
+struct SgGruDesc {
+    int O, H, Op, ldO, Hp, ldH;
+    int off;                   // start of the block in d_params (== the heads' desc.total)
+    int wih, whh, bih, bhh;    // offsets relative to `off`
+    int total;                 // block length (floats, multiple of 4)
+};
+SgGruDesc sg_make_gru_desc(int O, int H, int off);
+int64_t sg_gru_flat_count(const SgGruDesc& g);
+void sg_gru_pad(const SgGruDesc& g, const float* flat, float* padded);     // padded -> the block's first float, zeroed
+void sg_gru_unpad(const SgGruDesc& g, const float* padded, float* flat);
+
 struct sg_policy {
     sg_ctx* ctx;
-    SgPolicyDesc desc;
+    SgPolicyDesc desc;           // recurrent: the heads on h_t, i.e. an MLP policy whose observation is the GRU state (O == H)
+    bool recurrent = false;      // kind SG_POLICY_GRU: d_params = heads block | GRU block, flat order = GRU tensors first
+    SgGruDesc gru;
     float* d_params = nullptr;   // padded
     float* d_io = nullptr;       // staging for the host-pointer entry points
     size_t io_bytes = 0;
 };
+
+size_t sg_policy_padded_count(const sg_policy* p);          // floats of d_params (heads + GRU block)
+bool sg_gru_fits(const sg_ctx* ctx, const SgGruDesc& g);   // sg_gru.hip: the GRU kernels' 16-row tiles fit a CU's LDS
 
 // Layout of sg_disc::d_state behind the SgOptState at its head, in unsigned words: k_disc_step4's hand-off flags (one
 // 128-byte line per chain workgroup) and its sticky time-out word; sg_ppo::d_pair: k_ppo_pair's time-out word.
@@ -229,6 +248,7 @@ struct sg_rollout {
     uint64_t feat_version = sg_next_feat_version();
 };
 
+#define SG_H0_SLOTS 8
 struct sg_ppo {
     int64_t opt_t = 0;           // completed Adam steps (mirrors SgOptState::t0 on the device)
     uint64_t scratch_key = 0;    // layout the scratch buffers were last cleared for
@@ -260,6 +280,15 @@ struct sg_ppo {
     float* d_mrows = nullptr;      // [T*N][O] the mirrored rollout observations the next / last update reads
     int64_t mrows_cap = 0;         // floats
     int64_t mrows_host = 0;        // floats sg_ppo_set_mirrored_obs uploaded for the next update (0: none pending)
+    // recurrent policy (PPO through time): the hidden states of rollout slot 0 (sg_ppo_set_hidden_states) and the GRU's scratch
+    float* d_h0 = nullptr;         // [N][H]
+    int64_t h0_cap = 0, h0_count = 0;   // floats allocated / handed over for the next update (0: none pending)
+    float* h_h0 = nullptr;         // [SG_H0_SLOTS][h0_cap] page-locked staging: the hand-over never makes the host wait for queued updates
+    hipEvent_t h0_ev[8] = {nullptr};
+    uint64_t h0_calls = 0;
+    float* d_gru = nullptr;        // epoch copy of obs / masks / h0, GI, saved gates, gate gradients, dX, weight-gradient partials
+    size_t gru_cap = 0;
+    int64_t gru_layout[8] = {0};   // the scratch layout the buffers were last cleared for
     // A2C (sg_a2c_create): one RMSprop step over the whole rollout per update; d_v holds square_avg, opt_t counts the steps
     bool a2c = false;
     float alpha = 0.f;

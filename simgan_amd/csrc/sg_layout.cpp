@@ -108,6 +108,47 @@ void sg_policy_unpad(const SgPolicyDesc& d, const float* padded, float* flat) {
     });
 }
 
+// GRU block (a2c/model.py:124-131): state_dict order weight_ih_l0 [3H, O], weight_hh_l0 [3H, H], bias_ih_l0 [3H], bias_hh_l0 [3H]
+SgGruDesc sg_make_gru_desc(int O, int H, int off) {
+    SgGruDesc g;
+    memset(&g, 0, sizeof g);
+    g.O = O; g.H = H; g.Op = SG_PAD16(O); g.ldO = SG_LD(O); g.Hp = SG_PAD16(H); g.ldH = SG_LD(H);
+    g.off = off;
+    int o = 0;
+    g.wih = o; o += 3 * g.Hp * g.ldO;
+    g.whh = o; o += 3 * g.Hp * g.ldH;
+    g.bih = o; o += 3 * g.Hp;
+    g.bhh = o; o += 3 * g.Hp;
+    g.total = o;
+    return g;
+}
+
+static int64_t gru_segments(const SgGruDesc& g, const SegFn& f) {
+    int64_t fo = 0;
+    auto mat = [&](int64_t po, int rows, int cols, int ld) { f(fo, po, rows, cols, ld); fo += (int64_t)rows * cols; };
+    for (int k = 0; k < 3; ++k) mat(g.wih + (int64_t)k * g.Hp * g.ldO, g.H, g.O, g.ldO);
+    for (int k = 0; k < 3; ++k) mat(g.whh + (int64_t)k * g.Hp * g.ldH, g.H, g.H, g.ldH);
+    for (int k = 0; k < 3; ++k) mat(g.bih + k * g.Hp, 1, g.H, g.H);
+    for (int k = 0; k < 3; ++k) mat(g.bhh + k * g.Hp, 1, g.H, g.H);
+    return fo;
+}
+
+int64_t sg_gru_flat_count(const SgGruDesc& g) {
+    return gru_segments(g, [](int64_t, int64_t, int, int, int) {});
+}
+
+void sg_gru_pad(const SgGruDesc& g, const float* flat, float* padded) {
+    gru_segments(g, [&](int64_t fo, int64_t po, int rows, int cols, int ld) {
+        for (int r = 0; r < rows; ++r) memcpy(padded + po + (int64_t)r * ld, flat + fo + (int64_t)r * cols, sizeof(float) * cols);
+    });
+}
+
+void sg_gru_unpad(const SgGruDesc& g, const float* padded, float* flat) {
+    gru_segments(g, [&](int64_t fo, int64_t po, int rows, int cols, int ld) {
+        for (int r = 0; r < rows; ++r) memcpy(flat + fo + (int64_t)r * cols, padded + po + (int64_t)r * ld, sizeof(float) * cols);
+    });
+}
+
 SgDiscDesc sg_make_disc_desc(int F, int Hd) {
     SgDiscDesc d;
     d.F = F; d.Hd = Hd;

@@ -229,7 +229,7 @@ extern "C" int sg_policy_create2(sg_ctx* ctx, int kind, int obs_dim, int act_dim
     SG_DEVICE_WIDE();
     SG_REQUIRE(ctx && out, "sg_policy_create: NULL argument");
     SG_REQUIRE(critic_hidden >= 0, "sg_policy_create2: bad critic_hidden");
-    SG_REQUIRE(kind == SG_POLICY_MLP || kind == SG_POLICY_SPLIT, "sg_policy_create: unknown kind %d", kind);
+    SG_REQUIRE(kind == SG_POLICY_MLP || kind == SG_POLICY_SPLIT || kind == SG_POLICY_GRU, "sg_policy_create: unknown kind %d", kind);
     SG_REQUIRE(obs_dim > 0 && act_dim > 0 && hidden > 0, "sg_policy_create: bad dims");
     if (kind == SG_POLICY_SPLIT)
         SG_REQUIRE(num_feet > 0 && act_dim == 7 * num_feet,
@@ -237,15 +237,27 @@ extern "C" int sg_policy_create2(sg_ctx* ctx, int kind, int obs_dim, int act_dim
     SG_CHECK(hipSetDevice(ctx->device));
     sg_policy* p = new sg_policy();
     p->ctx = ctx;
-    p->desc = sg_make_policy_desc(kind, obs_dim, act_dim, hidden, num_feet, critic_hidden);
+    if (kind == SG_POLICY_GRU) {
+        // a2c/model.py:233-253 with recurrent=True: the trunks' first layers take the GRU state (H inputs), not the observation
+        p->recurrent = true;
+        p->desc = sg_make_policy_desc(SG_POLICY_MLP, hidden, act_dim, hidden, 1, critic_hidden);
+        p->gru = sg_make_gru_desc(obs_dim, hidden, p->desc.total);
+        if (!sg_gru_fits(ctx, p->gru)) {
+            delete p;
+            sg_set_error("sg_policy_create: one 16-row tile of this GRU (obs %d, hidden %d) does not fit the %d-byte LDS", obs_dim, hidden,
+                         ctx->lds_bytes);
+            return -2;
+        }
+    } else
+        p->desc = sg_make_policy_desc(kind, obs_dim, act_dim, hidden, num_feet, critic_hidden);
     // any width the reference's constructor accepts (a2c/arguments.py:107-109, a2c/model.py:233-253): a trunk that fits a
     // CU's LDS runs on the LDS-resident kernels, a larger one on the global-weight instances; only one 16-row activation
     // tile has to fit
     SG_REQUIRE(fwd_lds_bytes(p->desc, 1, true) <= (size_t)ctx->lds_bytes - 1024,
                "sg_policy_create: one 16-row activation tile of this policy (obs %d, hidden %d: %zu bytes) does not fit the %d-byte LDS",
                obs_dim, hidden, fwd_lds_bytes(p->desc, 1, true), ctx->lds_bytes);
-    SG_CHECK(sg_dev_malloc((void**)&p->d_params, sizeof(float) * p->desc.total));
-    SG_CHECK(hipMemsetAsync(p->d_params, 0, sizeof(float) * p->desc.total, ctx->stream));
+    SG_CHECK(sg_dev_malloc((void**)&p->d_params, sizeof(float) * sg_policy_padded_count(p)));
+    SG_CHECK(hipMemsetAsync(p->d_params, 0, sizeof(float) * sg_policy_padded_count(p), ctx->stream));
     *out = p;
     return 0;
 }
@@ -260,18 +272,29 @@ extern "C" int sg_policy_destroy(sg_policy* p) {
     return 0;
 }
 
+// flat (state_dict) and padded (device) sizes of the whole policy: a recurrent one carries its GRU's four tensors FIRST in the
+// flat order (base.gru.* precede base.actor.*, a2c/model.py:124-131,240-251) and BEHIND the heads' block on the device
+static int64_t policy_flat_total(const sg_policy* p) {
+    return sg_policy_flat_count(p->desc) + (p->recurrent ? sg_gru_flat_count(p->gru) : 0);
+}
+size_t sg_policy_padded_count(const sg_policy* p) {
+    return (size_t)p->desc.total + (p->recurrent ? (size_t)p->gru.total : 0);
+}
+
 extern "C" int sg_policy_num_params(const sg_policy* p, int64_t* n) {
     SG_REQUIRE(p && n, "sg_policy_num_params: NULL argument");
-    *n = sg_policy_flat_count(p->desc);
+    *n = policy_flat_total(p);
     return 0;
 }
 
 extern "C" int sg_policy_set_params(sg_policy* p, const float* flat, int64_t n) {
     SG_REQUIRE(p && flat, "sg_policy_set_params: NULL argument");
-    SG_REQUIRE(n == sg_policy_flat_count(p->desc), "sg_policy_set_params: expected %lld floats, got %lld",
-               (long long)sg_policy_flat_count(p->desc), (long long)n);
-    std::vector<float> padded(p->desc.total, 0.f);
-    sg_policy_pad(p->desc, flat, padded.data());
+    SG_REQUIRE(n == policy_flat_total(p), "sg_policy_set_params: expected %lld floats, got %lld",
+               (long long)policy_flat_total(p), (long long)n);
+    std::vector<float> padded(sg_policy_padded_count(p), 0.f);
+    const int64_t n_gru = p->recurrent ? sg_gru_flat_count(p->gru) : 0;
+    if (p->recurrent) sg_gru_pad(p->gru, flat, padded.data() + p->gru.off);
+    sg_policy_pad(p->desc, flat + n_gru, padded.data());
     SG_CHECK(hipStreamSynchronize(p->ctx->stream));
     SG_COPY_SYNC(p->ctx, p->d_params, padded.data(), sizeof(float) * padded.size(), hipMemcpyHostToDevice);
     return 0;
@@ -279,12 +302,14 @@ extern "C" int sg_policy_set_params(sg_policy* p, const float* flat, int64_t n) 
 
 extern "C" int sg_policy_get_params(sg_policy* p, float* flat, int64_t n) {
     SG_REQUIRE(p && flat, "sg_policy_get_params: NULL argument");
-    SG_REQUIRE(n == sg_policy_flat_count(p->desc), "sg_policy_get_params: expected %lld floats, got %lld",
-               (long long)sg_policy_flat_count(p->desc), (long long)n);
-    std::vector<float> padded(p->desc.total);
+    SG_REQUIRE(n == policy_flat_total(p), "sg_policy_get_params: expected %lld floats, got %lld",
+               (long long)policy_flat_total(p), (long long)n);
+    std::vector<float> padded(sg_policy_padded_count(p));
     SG_CHECK(hipStreamSynchronize(p->ctx->stream));
     SG_COPY_SYNC(p->ctx, padded.data(), p->d_params, sizeof(float) * padded.size(), hipMemcpyDeviceToHost);
-    sg_policy_unpad(p->desc, padded.data(), flat);
+    const int64_t n_gru = p->recurrent ? sg_gru_flat_count(p->gru) : 0;
+    if (p->recurrent) sg_gru_unpad(p->gru, padded.data() + p->gru.off, flat);
+    sg_policy_unpad(p->desc, padded.data(), flat + n_gru);
     return 0;
 }
 
@@ -332,11 +357,13 @@ static int policy_host_call(sg_policy* p, const float* obs, int n, int mode, con
 extern "C" int sg_policy_act(sg_policy* p, const float* obs, int n, const float* noise, uint64_t seed,
                              int deterministic, float* value, float* action, float* logp) {
     SG_REQUIRE(p && obs && value && action && logp, "sg_policy_act: NULL argument");
+    SG_REQUIRE(!p->recurrent, "%s: this policy is recurrent (kind SG_POLICY_GRU); call %s_rnn with its hidden state and masks", "sg_policy_act", "sg_policy_act");
     return policy_host_call(p, obs, n, deterministic ? 1 : 0, noise, seed, nullptr, value, action, logp, nullptr);
 }
 
 extern "C" int sg_policy_get_value(sg_policy* p, const float* obs, int n, float* value) {
     SG_REQUIRE(p && obs && value, "sg_policy_get_value: NULL argument");
+    SG_REQUIRE(!p->recurrent, "%s: this policy is recurrent (kind SG_POLICY_GRU); call %s_rnn with its hidden state and masks", "sg_policy_get_value", "sg_policy_get_value");
     return policy_host_call(p, obs, n, 1, nullptr, 0, nullptr, value, nullptr, nullptr, nullptr);
 }
 
@@ -463,6 +490,8 @@ extern "C" int sg_policy_act_ensemble(sg_policy* const* policies, int n_policies
     EnsArgs a;
     for (int k = 0; k < n_policies; ++k) {
         SG_REQUIRE(policies[k] && policies[k]->ctx == ctx, "sg_policy_act_ensemble: member %d is NULL or lives on another context", k);
+        SG_REQUIRE(!policies[k]->recurrent, "sg_policy_act_ensemble: member %d is a recurrent policy; the ensemble launch carries no hidden "
+                   "state (feed-forward policies only)", k);
         const SgPolicyDesc& e = policies[k]->desc;
         SG_REQUIRE(e.kind == d.kind && e.O == d.O && e.A == d.A && e.H == d.H && e.Hc == d.Hc && e.num_feet == d.num_feet,
                    "sg_policy_act_ensemble: member %d has a different shape", k);
@@ -517,6 +546,7 @@ extern "C" int sg_policy_act_ensemble(sg_policy* const* policies, int n_policies
 extern "C" int sg_policy_evaluate(sg_policy* p, const float* obs, const float* action, int n, float* value,
                                   float* logp, float* entropy) {
     SG_REQUIRE(p && obs && action && value && logp && entropy, "sg_policy_evaluate: NULL argument");
+    SG_REQUIRE(!p->recurrent, "%s: this policy is recurrent (kind SG_POLICY_GRU); call %s_rnn with its hidden state and masks", "sg_policy_evaluate", "sg_policy_evaluate");
     std::vector<float> ent(n);
     SG_TRY(policy_host_call(p, obs, n, 2, nullptr, 0, action, value, nullptr, logp, ent.data()));
     double s = 0.0;

@@ -36,6 +36,7 @@
 #include "sg_rng.hpp"
 #include "sg_ppo_kernels.hpp"
 #include "sg_kfac.hpp"
+#include "sg_gru_kernels.hpp"
 
 __global__ void k_fill_perm(int64_t* perm, int64_t n, int half_bits, uint64_t key) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -340,6 +341,8 @@ static size_t kfac_eig_lds(const SgKfac* k) {
 extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg, sg_ppo** out) {
     SG_DEVICE_WIDE();
     SG_REQUIRE(ctx && p && cfg && out, "sg_ppo_create: NULL argument");
+    SG_REQUIRE(!(p->recurrent && ctx->use_comm && ctx->world > 1), "sg_ppo_create: PPO with a recurrent policy runs on one rank: this "
+               "context has a communicator of world %d (data-parallel PPO through time is not implemented)", ctx->world);
     SG_REQUIRE(cfg->ppo_epoch > 0 && cfg->num_mini_batch > 0, "sg_ppo_create: ppo_epoch and num_mini_batch must be positive");
     // a policy whose trunk does not fit a CU's LDS runs on the global-weight instances; only the 16-row tiles must fit
     SG_REQUIRE(ppo_fwd_lds(p->desc, 1, true) <= (size_t)ctx->lds_bytes && ppo_bwd_lds(p->desc, 1, true) <= (size_t)ctx->lds_bytes,
@@ -348,13 +351,14 @@ extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg
     SG_CHECK(hipSetDevice(ctx->device));
     sg_ppo* a = new sg_ppo();
     a->ctx = ctx; a->policy = p; a->cfg = *cfg;
-    const size_t tot = (size_t)p->desc.total + 8;
+    const size_t tot = sg_policy_padded_count(p) + 8;   // (recurrent: heads block | GRU block, one Adam over both)
     SG_CHECK(sg_dev_malloc((void**)&a->d_m, sizeof(float) * tot));
     SG_CHECK(sg_dev_malloc((void**)&a->d_v, sizeof(float) * tot));
     SG_CHECK(sg_dev_malloc((void**)&a->d_grad, sizeof(float) * tot));
     SG_CHECK(sg_dev_malloc((void**)&a->d_state, sizeof(SgOptState)));
     SG_CHECK(sg_dev_malloc((void**)&a->d_loss_acc, sizeof(double) * 8));
-    SG_CHECK(sg_dev_malloc((void**)&a->d_part, sizeof(float) * ((tot + 8 + SG_PPO_REDUCE_PARAMS - 1) / SG_PPO_REDUCE_PARAMS + 8)));
+    SG_CHECK(sg_dev_malloc((void**)&a->d_part, sizeof(float) * ((tot + 8 + SG_PPO_REDUCE_PARAMS - 1) / SG_PPO_REDUCE_PARAMS + 8 +
+                                                                 (p->recurrent ? (p->gru.total + 255) / 256 : 0))));
     SG_CHECK(hipMemsetAsync(a->d_m, 0, sizeof(float) * tot, ctx->stream));
     SG_CHECK(hipMemsetAsync(a->d_v, 0, sizeof(float) * tot, ctx->stream));
     SG_CHECK(hipMemsetAsync(a->d_loss_acc, 0, sizeof(double) * 8, ctx->stream));
@@ -374,6 +378,7 @@ extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg
 // (a2c/algo/a2c_acktr.py:30-51: RMSprop, square_avg starting at zero).  Policy (MLP) on one rank only.
 extern "C" int sg_a2c_create(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg, sg_ppo** out) {
     SG_REQUIRE(ctx && p && cfg && out, "sg_a2c_create: NULL argument");
+    SG_REQUIRE(!p->recurrent, "sg_a2c_create: A2C is implemented for feed-forward policies only, not for a recurrent Policy");
     SG_REQUIRE(p->desc.kind == SG_POLICY_MLP, "sg_a2c_create: A2C is implemented for Policy (MLP) only, not for SplitPolicy");
     SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_a2c_create: A2C runs on one rank: this context has a communicator of "
                "world %d (data-parallel A2C is not implemented)", ctx->world);
@@ -398,6 +403,8 @@ extern "C" int sg_a2c_create(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg
 extern "C" int sg_acktr_create(sg_ctx* ctx, sg_policy* p, const sg_acktr_config* cfg, sg_ppo** out) {
     SG_DEVICE_WIDE();   // kfac_setup's clears and copies on ctx->stream, never beside a capture in flight (recursive with sg_ppo_create's)
     SG_REQUIRE(ctx && p && cfg && out, "sg_acktr_create: NULL argument");
+    SG_REQUIRE(!p->recurrent, "sg_acktr_create: ACKTR is not defined for a recurrent Policy (the reference refuses it too: "
+               "a2c/arguments.py:253-255)");
     SG_REQUIRE(p->desc.kind == SG_POLICY_MLP, "sg_acktr_create: ACKTR is implemented for Policy (MLP) only, not for SplitPolicy");
     SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_acktr_create: ACKTR runs on one rank: this context has a communicator of "
                "world %d (data-parallel ACKTR is not implemented)", ctx->world);
@@ -483,12 +490,15 @@ extern "C" int sg_ppo_destroy(sg_ppo* a) {
     (void)hipStreamSynchronize(a->ctx->stream);
     sg_ctx_learner_gone(a->ctx);
     for (auto& q : a->ctx->res_a) if (q == a) q = nullptr;
-    float* ptrs[] = {a->d_m, a->d_v, a->d_grad, a->d_slabs, a->d_state, a->d_part, a->d_stacks, a->d_mobs_mat, a->d_mact, a->d_mrows};
+    float* ptrs[] = {a->d_m, a->d_v, a->d_grad, a->d_slabs, a->d_state, a->d_part, a->d_stacks, a->d_mobs_mat, a->d_mact, a->d_mrows,
+                     a->d_h0, a->d_gru};
     for (float* q : ptrs) if (q) (void)sg_dev_free(q);
     if (a->d_perms) (void)sg_dev_free(a->d_perms);
     if (a->d_loss_acc) (void)sg_dev_free(a->d_loss_acc);
     if (a->d_dbg) (void)sg_dev_free(a->d_dbg);
     if (a->d_pair) (void)sg_dev_free(a->d_pair);
+    if (a->h_h0) (void)sg_host_release(a->h_h0);
+    for (hipEvent_t ev : a->h0_ev) if (ev) (void)hipEventDestroy(ev);
     if (a->steps_graph) (void)hipGraphExecDestroy(a->steps_graph);
     kfac_free(a);
     delete a;
@@ -522,6 +532,8 @@ extern "C" int sg_ppo_set_symmetry(sg_ppo* a, float coef, const float* m_obs, co
     SG_REQUIRE(m_act, "sg_ppo_set_symmetry: symmetry_coef > 0 needs the action mirror m_act");
     SG_REQUIRE(d.kind == SG_POLICY_MLP, "sg_ppo_set_symmetry: the mirror-symmetry loss is implemented for Policy (MLP) only, "
                "not for SplitPolicy");
+    SG_REQUIRE(!a->policy->recurrent, "sg_ppo_set_symmetry: the mirror-symmetry loss is implemented for feed-forward policies only, "
+               "not for a recurrent Policy");
     SG_REQUIRE(ppo_bwd_sym_lds(d, 1, true) <= (size_t)ctx->lds_bytes,
                "sg_ppo_set_symmetry: the 16-row tiles of the symmetric step do not fit LDS (%zu > %d bytes)", ppo_bwd_sym_lds(d, 1, true),
                ctx->lds_bytes);
@@ -584,13 +596,20 @@ extern "C" int sg_ppo_get_adam(sg_ppo* a, float* m, float* v, int64_t n, int64_t
     SG_REQUIRE(!a->kfac, "sg_ppo_get_adam: an ACKTR handle has K-FAC state, not Adam's (sg_acktr_get_state)");
     SG_REQUIRE(!a->a2c, "sg_ppo_get_adam: an A2C handle has RMSprop state, not Adam's (sg_a2c_get_rmsprop)");
     const SgPolicyDesc& d = a->policy->desc;
-    SG_REQUIRE(n == sg_policy_flat_count(d), "sg_ppo_get_adam: bad length");
-    std::vector<float> pm(d.total), pv(d.total);
+    const sg_policy* pol = a->policy;
+    const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;   // the GRU's tensors come first in the flat order
+    SG_REQUIRE(n == sg_policy_flat_count(d) + n_gru, "sg_ppo_get_adam: bad length");
+    const size_t ptot = sg_policy_padded_count(pol);
+    std::vector<float> pm(ptot), pv(ptot);
     SG_CHECK(hipStreamSynchronize(a->ctx->stream));
-    SG_COPY_SYNC(a->ctx, pm.data(), a->d_m, sizeof(float) * d.total, hipMemcpyDeviceToHost);
-    SG_COPY_SYNC(a->ctx, pv.data(), a->d_v, sizeof(float) * d.total, hipMemcpyDeviceToHost);
-    sg_policy_unpad(d, pm.data(), m);
-    sg_policy_unpad(d, pv.data(), v);
+    SG_COPY_SYNC(a->ctx, pm.data(), a->d_m, sizeof(float) * ptot, hipMemcpyDeviceToHost);
+    SG_COPY_SYNC(a->ctx, pv.data(), a->d_v, sizeof(float) * ptot, hipMemcpyDeviceToHost);
+    if (pol->recurrent) {
+        sg_gru_unpad(pol->gru, pm.data() + pol->gru.off, m);
+        sg_gru_unpad(pol->gru, pv.data() + pol->gru.off, v);
+    }
+    sg_policy_unpad(d, pm.data(), m + n_gru);
+    sg_policy_unpad(d, pv.data(), v + n_gru);
     *step = a->opt_t;
     return 0;
 }
@@ -600,15 +619,22 @@ extern "C" int sg_ppo_set_adam(sg_ppo* a, const float* m, const float* v, int64_
     SG_REQUIRE(!a->kfac, "sg_ppo_set_adam: an ACKTR handle has K-FAC state, not Adam's (sg_acktr_get_state)");
     SG_REQUIRE(!a->a2c, "sg_ppo_set_adam: an A2C handle has RMSprop state, not Adam's (sg_a2c_set_rmsprop)");
     const SgPolicyDesc& d = a->policy->desc;
-    SG_REQUIRE(n == sg_policy_flat_count(d), "sg_ppo_set_adam: bad length");
-    std::vector<float> pm(d.total, 0.f), pv(d.total, 0.f);
-    sg_policy_pad(d, m, pm.data());
-    sg_policy_pad(d, v, pv.data());
+    const sg_policy* pol = a->policy;
+    const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;
+    SG_REQUIRE(n == sg_policy_flat_count(d) + n_gru, "sg_ppo_set_adam: bad length");
+    const size_t ptot = sg_policy_padded_count(pol);
+    std::vector<float> pm(ptot, 0.f), pv(ptot, 0.f);
+    if (pol->recurrent) {
+        sg_gru_pad(pol->gru, m, pm.data() + pol->gru.off);
+        sg_gru_pad(pol->gru, v, pv.data() + pol->gru.off);
+    }
+    sg_policy_pad(d, m + n_gru, pm.data());
+    sg_policy_pad(d, v + n_gru, pv.data());
     SG_REQUIRE(step >= 0 && step < (1ll << 30), "sg_ppo_set_adam: step out of range");
     const int t0 = (int)step;
     SG_CHECK(hipStreamSynchronize(a->ctx->stream));
-    SG_COPY_SYNC(a->ctx, a->d_m, pm.data(), sizeof(float) * d.total, hipMemcpyHostToDevice);
-    SG_COPY_SYNC(a->ctx, a->d_v, pv.data(), sizeof(float) * d.total, hipMemcpyHostToDevice);
+    SG_COPY_SYNC(a->ctx, a->d_m, pm.data(), sizeof(float) * ptot, hipMemcpyHostToDevice);
+    SG_COPY_SYNC(a->ctx, a->d_v, pv.data(), sizeof(float) * ptot, hipMemcpyHostToDevice);
     SG_COPY_SYNC(a->ctx, &reinterpret_cast<SgOptState*>(a->d_state)->t0, &t0, sizeof t0, hipMemcpyHostToDevice);
     // the words k_ppo_pair's actor workgroups swap carry Adam step numbers: a step count set from outside may repeat old ones,
     // so the row stacks they live in are cleared before the next update
@@ -875,6 +901,279 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, uint64_t seed, float out3[3]) {
     return 0;
 }
 
+// ------------------------------------------------------------------- PPO through time (recurrent policy)
+// rollouts.recurrent_hidden_states[0] ([N][H], a2c/storage.py:216-217: the minibatches start from the state of slot 0) for the
+// NEXT sg_ppo_update of a recurrent policy; the rollout's device twin has no hidden-state field, so the caller hands it over
+extern "C" int sg_ppo_set_hidden_states(sg_ppo* a, const float* hxs0, int64_t count) {
+    SG_REQUIRE(a && hxs0, "sg_ppo_set_hidden_states: NULL argument");
+    SG_REQUIRE(a->policy->recurrent, "sg_ppo_set_hidden_states: the policy is feed-forward: it has no hidden state");
+    const int H = a->policy->gru.H;
+    SG_REQUIRE(count > 0 && count % H == 0, "sg_ppo_set_hidden_states: %lld floats is not a whole number of %d-float states",
+               (long long)count, H);
+    sg_ctx* ctx = a->ctx;
+    SG_CHECK(hipSetDevice(ctx->device));
+    if (a->h0_cap < count) {
+        SG_DEVICE_WIDE();
+        SG_CHECK(hipStreamSynchronize(ctx->stream));
+        if (a->d_h0) SG_CHECK(sg_dev_free(a->d_h0));
+        if (a->h_h0) SG_CHECK(sg_host_release(a->h_h0));
+        a->d_h0 = nullptr; a->h_h0 = nullptr; a->h0_cap = 0;
+        SG_CHECK(sg_dev_malloc((void**)&a->d_h0, sizeof(float) * count));
+        SG_CHECK(sg_host_malloc((void**)&a->h_h0, sizeof(float) * count * SG_H0_SLOTS));
+        a->h0_cap = count;
+    }
+    // No host wait for the queued updates: the states go through one of SG_H0_SLOTS page-locked staging slots and an asynchronous
+    // copy in stream order (behind the previous update's reads); a slot is reused only once its own copy has run.
+    const int slot = (int)(a->h0_calls++ % SG_H0_SLOTS);
+    if (!a->h0_ev[slot]) SG_CHECK(hipEventCreateWithFlags(&a->h0_ev[slot], hipEventDisableTiming));
+    else SG_CHECK(hipEventSynchronize(a->h0_ev[slot]));
+    float* stage = a->h_h0 + (size_t)slot * a->h0_cap;
+    memcpy(stage, hxs0, sizeof(float) * count);
+    SG_CHECK(hipMemcpyAsync(a->d_h0, stage, sizeof(float) * count, hipMemcpyHostToDevice, ctx->stream));
+    SG_CHECK(hipEventRecord(a->h0_ev[slot], ctx->stream));
+    a->h0_count = count;
+    return 0;
+}
+
+// PPO.update with actor_critic.is_recurrent (a2c/algo/ppo.py:74-90) over RolloutStorage.recurrent_generator's minibatches
+// (a2c/storage.py:194-251): per = N // num_mini_batch whole environments per optimizer step, N // per steps per epoch.
+//   k_adv_stats x3
+//   per epoch:  k_gru_epoch_gather            environment-permuted, time-major copy of the rollout
+//   per step:   k_gru_inproj -> k_gru_scan_fwd<TRAIN> (h_t = the heads' input rows) -> k_ppo_bwd<fused, DX> -> k_ppo_reduce
+//               -> k_gru_scan_bwd -> k_gru_wgrad -> k_gru_reduce -> k_ppo_adam over heads + GRU (one norm, one clip)
+//   then        k_opt_commit
+// All of it from the first gather on is one captured graph, replayed per update; no host wait inside.
+static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_t n_perms, uint64_t seed, float out3[3]) {
+    sg_ctx* ctx = a->ctx;
+    sg_policy* pol = a->policy;
+    const SgPolicyDesc& d = pol->desc;
+    const SgGruDesc& g = pol->gru;
+    SG_REQUIRE(r->O == g.O && r->A == d.A, "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)", r->O, r->A,
+               g.O, d.A);
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_ppo_update: PPO with a recurrent policy runs on one rank (world %d)", ctx->world);
+    const int T = r->T, N = r->N, M = a->cfg.num_mini_batch, E = a->cfg.ppo_epoch;
+    // a2c/storage.py:196-199
+    SG_REQUIRE(N >= M, "PPO requires the number of processes (%d) to be greater than or equal to the number of PPO mini batches (%d).", N, M);
+    const int per = N / M;
+    SG_REQUIRE(N % per == 0, "sg_ppo_update: %d processes do not split into minibatches of %d = %d // %d environments (the reference "
+               "indexes past its permutation here)", N, per, N, M);
+    const int S = N / per;                        // optimizer steps per epoch (a2c/storage.py:202: range(0, N, per))
+    SG_REQUIRE((int64_t)a->h0_count == (int64_t)N * g.H, "sg_ppo_update: a recurrent policy takes the hidden states of rollout slot 0 "
+               "from the host: sg_ppo_set_hidden_states must hand over %lld floats before every update (pending: %lld)",
+               (long long)N * g.H, (long long)a->h0_count);
+    a->h0_count = 0;
+    const int64_t TN = (int64_t)T * N;
+    SG_REQUIRE(TN < (1ll << 30), "sg_ppo_update: rollout too large");
+    if (perms) {
+        SG_REQUIRE(n_perms == (int64_t)E * N, "sg_ppo_update: perms holds %lld indices, %d epochs x %d environments need %lld",
+                   (long long)n_perms, E, N, (long long)E * N);
+        std::vector<uint8_t> seen((size_t)N);
+        for (int e = 0; e < E; ++e) {
+            std::fill(seen.begin(), seen.end(), (uint8_t)0);
+            for (int i = 0; i < N; ++i) {
+                const int64_t v = perms[(size_t)e * N + i];
+                SG_REQUIRE(v >= 0 && v < N && !seen[(size_t)v], "sg_ppo_update: perms of epoch %d are not a permutation of the %d environments", e, N);
+                seen[(size_t)v] = 1;
+            }
+        }
+    }
+    SG_CHECK(hipSetDevice(ctx->device));
+
+    // advantages (global mean / unbiased std over all T*N, as for the feed-forward update)
+    float* adv = r->d_field[SG_F_ADVANTAGES];
+    double* stats = a->d_loss_acc + 4;
+    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(1024), 0, ctx->stream, r->d_field[SG_F_RETURNS], r->d_field[SG_F_VALUE_PREDS], TN, adv, stats, 0);
+    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(1024), 0, ctx->stream, r->d_field[SG_F_RETURNS], r->d_field[SG_F_VALUE_PREDS], TN, adv, stats, 1);
+    hipLaunchKernelGGL(k_adv_stats, dim3(64), dim3(1024), 0, ctx->stream, r->d_field[SG_F_RETURNS], r->d_field[SG_F_VALUE_PREDS], TN, adv, stats, 2);
+    SG_CHECK(hipGetLastError());
+
+    // permutations of the environments: [E][N]
+    if (a->perms_cap < (int64_t)E * N) {
+        SG_CHECK(hipStreamSynchronize(ctx->stream));
+        if (a->d_perms) SG_CHECK(sg_dev_free(a->d_perms));
+        a->d_perms = nullptr; a->perms_cap = 0;
+        SG_CHECK(sg_dev_malloc((void**)&a->d_perms, sizeof(int64_t) * (size_t)E * N));
+        a->perms_cap = (int64_t)E * N;
+    }
+    a->last_perm_count = (int64_t)E * N;
+    if (perms) {
+        SG_CHECK(hipMemcpyAsync(a->d_perms, perms, sizeof(int64_t) * (size_t)E * N, hipMemcpyHostToDevice, ctx->stream));
+        if (!out3) SG_CHECK(hipStreamSynchronize(ctx->stream));
+    } else {
+        for (int e = 0; e < E; ++e) SG_TRY(sg_fill_perm(ctx, a->d_perms + (size_t)e * N, N, seed, (uint64_t)e * 2654435761ull));
+    }
+
+    // geometry.  Heads: the fused forward + backward on 16- or 32-row groups of the step's T*per rows.  Scans: one workgroup per
+    // 16 environments of the minibatch.
+    const int mb = T * per;
+    const bool gw = sg_policy_needs_gw(ctx, d) || ppo_fwd_lds(d, 1, false) > (size_t)ctx->lds_bytes;
+    const int ldP = stack_ldP(d);
+    auto bwd_lds = [&](int mt) {
+        const int R = 16 * mt;
+        return sizeof(float) * ((gw ? 0 : (size_t)max_trunk_floats(d)) + R * d.ldO + 2 * R * d.ldH + 2 * R * ldP + ((R * d.A + 3) & ~3) + 7 * R);
+    };
+    int MT = ((mb + 31) / 32) * d.n_trunks >= ctx->num_cu ? 2 : 1;
+    if (MT == 2 && bwd_lds(2) > (size_t)ctx->lds_bytes) MT = 1;
+    SG_REQUIRE(bwd_lds(MT) <= (size_t)ctx->lds_bytes, "sg_ppo_update: the heads' 16-row tiles do not fit LDS (%zu bytes)", bwd_lds(MT));
+    const int R = 16 * MT, G = (mb + R - 1) / R, mbp = G * R;
+    const int slab_stride = (d.total + 8 + 63) & ~63;
+    const int TNp = (int)TN + 64;
+    const int rows_p = (mb + 15) & ~15;
+    const int Hp = g.Hp, G3 = 3 * Hp;
+    const int chunks = rows_p / 16;
+    const int KS = std::max(1, std::min(16, chunks / 8));
+    const int gblocks = (g.total + 255) / 256;
+    const int nblk_r = (d.total + 8 + SG_PPO_REDUCE_PARAMS - 1) / SG_PPO_REDUCE_PARAMS;
+    const int tot_all = d.total + g.total;
+    const int nblk = (tot_all + 8 + 255) / 256;
+
+    // scratch: slabs; d_stacks = heads' input rows | ACT | SC; d_gru = everything of the GRU
+    const size_t slab_f = (size_t)G * slab_stride;
+    const size_t hx_f = (size_t)(mbp + 64) * d.ldO;
+    const size_t stack_f = hx_f + (size_t)TNp * d.A + 4 * (size_t)TNp;
+    auto r4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    const size_t o_x = 0, o_mk = o_x + r4((size_t)TNp * g.ldO), o_h0 = o_mk + r4((size_t)TNp), o_gi = o_h0 + r4((size_t)N * g.H);
+    const size_t o_sr = o_gi + (size_t)rows_p * G3, o_sz = o_sr + (size_t)rows_p * Hp, o_sn = o_sz + (size_t)rows_p * Hp;
+    const size_t o_shn = o_sn + (size_t)rows_p * Hp, o_hm = o_shn + (size_t)rows_p * Hp, o_dgi = o_hm + (size_t)rows_p * g.ldH;
+    const size_t o_dgh = o_dgi + (size_t)rows_p * G3, o_dxa = o_dgh + (size_t)rows_p * G3, o_dxc = o_dxa + (size_t)mbp * d.ldO;
+    const size_t o_part = o_dxc + (size_t)mbp * d.ldO, gru_f = o_part + (size_t)KS * g.total;
+    if (a->slabs_cap < slab_f || a->stacks_cap < stack_f || a->gru_cap < gru_f) {
+        SG_CHECK(hipStreamSynchronize(ctx->stream));
+        if (a->d_slabs) SG_CHECK(sg_dev_free(a->d_slabs));
+        if (a->d_stacks) SG_CHECK(sg_dev_free(a->d_stacks));
+        if (a->d_gru) SG_CHECK(sg_dev_free(a->d_gru));
+        a->d_slabs = a->d_stacks = a->d_gru = nullptr;
+        a->slabs_cap = a->stacks_cap = a->gru_cap = 0;
+        SG_CHECK(sg_dev_malloc((void**)&a->d_slabs, sizeof(float) * slab_f));
+        SG_CHECK(sg_dev_malloc((void**)&a->d_stacks, sizeof(float) * stack_f));
+        SG_CHECK(sg_dev_malloc((void**)&a->d_gru, sizeof(float) * gru_f));
+        a->slabs_cap = slab_f; a->stacks_cap = stack_f; a->gru_cap = gru_f;
+        a->scratch_key = 0;
+    }
+    // padding columns / rows past the minibatch are never written and must read as zero: cleared when the layout changes (the
+    // whole tuple is compared, not a hash of it)
+    const int64_t layout[8] = {G, slab_stride, mbp, TNp, MT, KS, per, ((int64_t)g.total << 32) | (int64_t)rows_p};
+    if (a->scratch_key != 0x475255ull || memcmp(layout, a->gru_layout, sizeof layout) != 0) {
+        SG_CHECK(hipMemsetAsync(a->d_slabs, 0, sizeof(float) * slab_f, ctx->stream));
+        SG_CHECK(hipMemsetAsync(a->d_stacks, 0, sizeof(float) * stack_f, ctx->stream));
+        SG_CHECK(hipMemsetAsync(a->d_gru, 0, sizeof(float) * gru_f, ctx->stream));
+        memcpy(a->gru_layout, layout, sizeof layout);
+        a->scratch_key = 0x475255ull;   // (0 after a reallocation or sg_ppo_set_adam: clear again)
+    }
+    hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 4);
+
+    float* hX = a->d_stacks;
+    float* epACT = hX + hx_f;
+    float* epSC = epACT + (size_t)TNp * d.A;
+    float* gb = a->d_gru;
+
+    GruGatherArgs ga;
+    ga.obs = r->d_field[SG_F_OBS]; ga.actions = r->d_field[SG_F_ACTIONS]; ga.old_logp = r->d_field[SG_F_LOGP]; ga.adv = adv;
+    ga.vpred = r->d_field[SG_F_VALUE_PREDS]; ga.ret = r->d_field[SG_F_RETURNS]; ga.masks = r->d_field[SG_F_MASKS]; ga.h0 = a->d_h0;
+    ga.T = T; ga.N = N; ga.per = per; ga.O = g.O; ga.ldO = g.ldO; ga.A = d.A; ga.H = g.H; ga.sc_stride = TNp;
+    ga.X = gb + o_x; ga.ACT = epACT; ga.SC = epSC; ga.MK = gb + o_mk; ga.H0 = gb + o_h0;
+
+    PpoArgs pa;
+    pa.d = d; pa.params = pol->d_params;
+    pa.sc_stride = TNp; pa.mb = mb; pa.mbp = mbp; pa.inv_B = 1.0f / (float)mb;
+    pa.clip = a->cfg.clip_param; pa.vcoef = a->cfg.value_loss_coef; pa.ecoef = a->cfg.entropy_coef;
+    pa.use_clipped = a->cfg.use_clipped_value_loss;
+    pa.slabs = a->d_slabs; pa.slab_stride = slab_stride; pa.ldP = ldP; pa.dbg = nullptr;
+    pa.st = reinterpret_cast<SgOptState*>(a->d_state); pa.G = G; pa.k1 = 0;
+    pa.pair = a->d_pair; pa.Xm = nullptr; pa.MA = nullptr; pa.sym_c = 0.f;
+    for (int t = 0; t < 3; ++t) { pa.H1[t] = hX; pa.H2[t] = hX; pa.OUT[t] = hX; }   // the fused form keeps its activations in LDS
+    pa.X = hX;
+    pa.DX[0] = gb + o_dxa; pa.DX[1] = gb + o_dxc;
+    pa.wbuf_floats = gw ? 0 : max_trunk_floats(d);
+
+    GruScanArgs tr;
+    tr.sr = gb + o_sr; tr.sz = gb + o_sz; tr.sn = gb + o_sn; tr.shn = gb + o_shn; tr.hm = gb + o_hm;
+    GruBwdArgs ba;
+    ba.g = g; ba.W = pol->d_params + g.off; ba.dxa = gb + o_dxa; ba.dxc = gb + o_dxc; ba.dx_ld = d.ldO;
+    ba.sr = tr.sr; ba.sz = tr.sz; ba.sn = tr.sn; ba.shn = tr.shn; ba.hm = tr.hm; ba.T = T; ba.n = per;
+    ba.dgi = gb + o_dgi; ba.dgh = gb + o_dgh;
+    GruWgradArgs wa;
+    wa.g = g; wa.dgi = ba.dgi; wa.dgh = ba.dgh; wa.hm = tr.hm; wa.rows_p = rows_p; wa.KS = KS; wa.partial = gb + o_part;
+    const bool gw_scan = sg_gru_force_gw() || sg_gru_scan_lds(g, false) > (size_t)ctx->lds_bytes - 1024 ||
+                         sg_gru_bwd_lds(g, false) > (size_t)ctx->lds_bytes - 1024;
+    const int n_tiles = (G3 / 16) * (g.Op / 16 + Hp / 16) + 2 * (G3 / 16);
+    const size_t lds_b = bwd_lds(MT);
+    const dim3 hblock(ppo_block_threads(MT));
+    SgOptState* st = reinterpret_cast<SgOptState*>(a->d_state);
+
+    auto enqueue_steps = [&]() -> int {
+        hipLaunchKernelGGL(k_opt_prepare_first, dim3(1), dim3(1), 0, ctx->stream, st);
+        for (int e = 0; e < E; ++e) {
+            ga.perm = a->d_perms + (size_t)e * N;
+            hipLaunchKernelGGL(k_gru_epoch_gather<0>, dim3((unsigned)TN), dim3(64), 0, ctx->stream, ga);
+            for (int k = 0; k < S; ++k) {
+                const size_t rb = (size_t)k * mb;
+                const float* xk = gb + o_x + rb * g.ldO;
+                const float* mk = gb + o_mk + rb;
+                SG_TRY(sg_gru_forward_launch(ctx, g, pol->d_params + g.off, xk, g.ldO, gb + o_h0 + (size_t)k * per * g.H, mk, T, per,
+                                             gb + o_gi, hX, d.ldO, nullptr, &tr));
+                pa.ACT = epACT + rb * d.A; pa.SC = epSC + rb;
+                pa.k1 = e * S + k + 1;
+                const dim3 grid(G, 2);
+                if (gw) {
+                    if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<2, 0, 0, true, true, true>), grid, hblock, lds_b, pa);
+                    else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<1, 0, 0, true, true, true>), grid, hblock, lds_b, pa);
+                } else if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<2, 0, 0, true, false, true>), grid, hblock, lds_b, pa);
+                else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<1, 0, 0, true, false, true>), grid, hblock, lds_b, pa);
+                SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_ppo_reduce, dim3(nblk_r), dim3(256), 0, a->d_slabs, G, slab_stride, d.total, a->d_grad,
+                          a->d_part);
+                ba.masks = mk;
+                if (gw_scan) hipLaunchKernelGGL(k_gru_scan_bwd<true>, dim3((per + 15) / 16), dim3(256), sg_gru_bwd_lds(g, true), ctx->stream, ba);
+                else hipLaunchKernelGGL(k_gru_scan_bwd<false>, dim3((per + 15) / 16), dim3(256), sg_gru_bwd_lds(g, false), ctx->stream, ba);
+                wa.x = xk;
+                hipLaunchKernelGGL(k_gru_wgrad<0>, dim3(n_tiles, KS), dim3(64), 0, ctx->stream, wa);
+                hipLaunchKernelGGL(k_gru_reduce<0>, dim3(gblocks), dim3(256), 0, ctx->stream, wa.partial, KS, g.total, a->d_grad, d.total,
+                                   a->d_part, nblk_r);
+                SG_LAUNCH(ctx, SG_PROF_PPO_ADAM, k_ppo_adam, dim3(nblk), dim3(256), 0, pol->d_params, a->d_m, a->d_v, a->d_grad, a->d_part,
+                          nblk_r + gblocks, tot_all, st, e * S + k + 1, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B, a->d_loss_acc);
+            }
+        }
+        hipLaunchKernelGGL(k_opt_commit, dim3(1), dim3(1), 0, ctx->stream, st, E * S);
+        SG_CHECK(hipGetLastError());
+        return 0;
+    };
+    const char* genv = getenv("SG_PPO_GRAPH");
+    bool use_graph = !a->graph_refused && !ctx->profile && !(genv && !strcmp(genv, "0"));
+    if (use_graph) {
+        uint32_t fbits[6];
+        const float fv[6] = {a->cfg.clip_param, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B};
+        memcpy(fbits, fv, sizeof fbits);
+        const uint64_t gkey[18] = {(uint64_t)(uintptr_t)a->d_slabs, (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_perms,
+                                   (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
+                                   (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)pol->d_params,
+                                   (uint64_t)TN, ((uint64_t)E << 32) | (uint64_t)M, ((uint64_t)MT << 32) | (uint64_t)G,
+                                   ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
+                                   ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)a->cfg.use_clipped_value_loss,
+                                   (uint64_t)(uintptr_t)r->d_field[SG_F_LOGP],
+                                   0x475255ull + (gw ? 8 : 0) + (gw_scan ? 16 : 0) + ((uint64_t)N << 32),   // 'GRU': the recurrent step sequence
+                                   (uint64_t)(uintptr_t)a->d_gru, (uint64_t)(uintptr_t)a->d_h0 ^ ((uint64_t)(uintptr_t)r->d_field[SG_F_MASKS] << 1)};
+        if (!a->steps_graph || memcmp(gkey, a->steps_graph_key, sizeof gkey) != 0) {
+            if (a->steps_graph) { SG_CHECK(hipGraphExecDestroy(a->steps_graph)); a->steps_graph = nullptr; }
+            if (sg_try_capture(ctx, &a->steps_graph, enqueue_steps) != 0) {
+                a->graph_refused = true;
+                use_graph = false;
+            } else {
+                memcpy(a->steps_graph_key, gkey, sizeof gkey);
+            }
+        }
+        if (use_graph) SG_CHECK(hipGraphLaunch(a->steps_graph, ctx->stream));
+    }
+    if (!use_graph) SG_TRY(enqueue_steps());
+    SG_CHECK(hipGetLastError());
+    a->opt_t += (int64_t)E * S;
+    if (!out3) return 0;
+    double acc[3];
+    SG_TRY(sg_ctx_fetch_f64(ctx, a->d_loss_acc, acc, 3));
+    const double nu = (double)E * M;   // a2c/algo/ppo.py:151-155 divides by ppo_epoch * num_mini_batch whatever N // per is
+    for (int i = 0; i < 3; ++i) out3[i] = (float)(acc[i] / nu);
+    return 0;
+}
+
 extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_t n_perms, uint64_t seed, float out3[3]) {
     SG_REQUIRE(a && r, "sg_ppo_update: NULL argument");
     if (a->a2c) {
@@ -884,6 +1183,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
                    a->policy->desc.O, a->policy->desc.A);
         return a2c_update(a, r, seed, out3);
     }
+    if (a->policy->recurrent) return gru_ppo_update(a, r, perms, n_perms, seed, out3);
     sg_ctx* ctx = a->ctx;
     const SgPolicyDesc& d = a->policy->desc;
     SG_REQUIRE(r->O == d.O && r->A == d.A, "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)",

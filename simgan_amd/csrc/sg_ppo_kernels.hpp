@@ -54,6 +54,8 @@ struct PpoArgs {
     const float* Xm;      // [mb..][ldO] mirrored rows, permuted like X
     const float* MA;      // [A][A] action mirror M_a (row-major: (M_a mu)_k = sum_j MA[k A + j] mu_j)
     float sym_c;          // symmetry_coef * 2 / (B A): d(coef * mean(e^2)) / d e, e = M_a mu(s) - mu(s_m)
+    // DX instances only (recurrent policy: the rows are GRU states): d loss / d X of trunk t, [mbp][ldO]
+    float* DX[2] = {nullptr, nullptr};
 };
 
 // k_ppo_pair (SplitPolicy, one launch per step): the two actor workgroups of a row group exchange their head outputs
@@ -251,9 +253,10 @@ __global__ __launch_bounds__(512) void k_ppo_fwd_sym(PpoArgs a) {
 // A2C (Policy, two-launch form, a2c/algo/a2c_acktr.py:56-91): loss = vcoef mean(adv^2) - mean(adv.detach() logp) - ecoef
 // mean(ent), adv = R - v with v the critic's head output of the SAME forward (k_ppo_fwd's critic OUT stack; the actor columns
 // read it in place of old_logp).  No ratio, no clip, no clipped value loss; the entropy term is PPO's.
-template <int MT, int KO, int KH, bool FUSED, bool GW = false, bool PAIR = false, bool SYM = false, bool A2C = false>
+template <int MT, int KO, int KH, bool FUSED, bool GW = false, bool PAIR = false, bool SYM = false, bool A2C = false, bool DX = false>
 __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, const int bx) {
     static_assert(!(SYM && (FUSED || PAIR)), "the symmetric step runs the two-launch form");
+    static_assert(!DX || ((FUSED || GW) && !PAIR && !SYM && !A2C), "d loss / d X needs w1 at hand: the fused or the global-weight form");
     static_assert(!(A2C && (FUSED || PAIR || SYM)), "the A2C step runs the two-launch form");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // (No spare workgroup for Adam's bias corrections any more: with G x trunks = 256 row-group blocks, two extra blocks
@@ -631,6 +634,10 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
         sg_colsum(H1, ldH, R, Hp, g + tr.b1, false);
         SG_LDS_SYNC();
     }
+    if (DX) {   // H1 holds d loss / d (layer-1 pre-activation): dX = that times W1, this trunk's share of d loss / d h_t
+        float* gdx = a.DX[t] + (size_t)row0 * ldO;
+        sg_layer_nn_u<MT>(H1, ldH, W + tr.w1, ldO, Hp, Op, [&](int r, int c, float v) { gdx[r * ldO + c] = v; });
+    }
     SG_PPO_STAMP(15);
     SG_PPO_WALL(7);
     if (PAIR && pair_failed && tid == 0) {   // the partner never published: the host sees NaN losses, then the error word
@@ -639,9 +646,9 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
     }
 }
 
-template <int MT, int KO, int KH, bool FUSED = false, bool GW = false>
+template <int MT, int KO, int KH, bool FUSED = false, bool GW = false, bool DX = false>
 __global__ __launch_bounds__(512) void k_ppo_bwd(PpoArgs a) {
-    sg_ppo_bwd_body<MT, KO, KH, FUSED, GW>(a, blockIdx.y, blockIdx.x);
+    sg_ppo_bwd_body<MT, KO, KH, FUSED, GW, false, false, false, DX>(a, blockIdx.y, blockIdx.x);
 }
 // Policy with the mirror-symmetry loss: grid (row groups, 3), after k_ppo_fwd_sym
 template <int MT, int KO, int KH, bool GW = false>

@@ -201,6 +201,8 @@ extern "C" int sg_rollout_compute_returns(sg_rollout* r, const float* next_value
 extern "C" int sg_rollout_compute_returns_policy(sg_rollout* r, sg_policy* p, int use_gae, float gamma,
                                                  float gae_lambda, int use_proper_time_limits) {
     SG_REQUIRE(r && p, "sg_rollout_compute_returns_policy: NULL argument");
+    SG_REQUIRE(!p->recurrent, "sg_rollout_compute_returns_policy: the policy is recurrent and the device rollout holds no hidden state; "
+               "pass get_value's result to sg_rollout_compute_returns");
     SG_REQUIRE(p->desc.O == r->O, "sg_rollout_compute_returns_policy: obs dim mismatch");
     // next_value = get_value(obs[T]) lands in returns[T] (a slot the GAE branch never reads or writes)
     float* d_nv = r->d_field[SG_F_RETURNS] + (size_t)r->T * r->N;
@@ -261,6 +263,7 @@ __global__ void k_fill_const(float* x, int64_t n, float v) {
 
 extern "C" int sg_rollout_fill_synthetic(sg_rollout* r, sg_policy* p, uint64_t seed, float p_done) {
     SG_REQUIRE(r && p, "sg_rollout_fill_synthetic: NULL argument");
+    SG_REQUIRE(!p->recurrent, "sg_rollout_fill_synthetic: feed-forward policies only (the device rollout holds no hidden state)");
     SG_REQUIRE(p->desc.O == r->O && p->desc.A == r->A, "sg_rollout_fill_synthetic: policy/rollout dims differ");
     sg_ctx* ctx = r->ctx;
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };

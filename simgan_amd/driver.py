@@ -199,6 +199,21 @@ class GailDynLearner(object):
                 "action_loss": ppo[1], "dist_entropy": ppo[2], "r_sa": r_sa}
 
 
+def _returns_resident(self):
+    """GAE on a device-resident rollout.  Feed-forward policy: get_value(obs[T]) and the reverse scan both on the device, nothing
+    waits.  Recurrent policy: the device rollout has no hidden-state field, so the value of slot T comes from get_value on the
+    HOST mirrors (obs[-1], recurrent_hidden_states[-1], masks[-1], which the host-side collector filled through insert()) -- one
+    host wait per update, the only one -- and the scan runs on the device's rewards / values / masks."""
+    ro, lib = self.rollouts, self.rollouts.lib
+    if self.actor_critic.is_recurrent:
+        nv = _lib.as_f32(self.actor_critic.get_value(ro.obs[-1], ro.recurrent_hidden_states[-1], ro.masks[-1])).reshape(-1)
+        _lib.check(lib.sg_rollout_compute_returns(ro.h, _lib.fptr(nv), 1 if self.use_gae else 0, float(self.gamma), float(self.gae_lambda),
+                                                  1 if self.use_proper_time_limits else 0))
+        return
+    _lib.check(lib.sg_rollout_compute_returns_policy(ro.h, self.actor_critic.h, 1 if self.use_gae else 0, float(self.gamma),
+                                                     float(self.gae_lambda), 1 if self.use_proper_time_limits else 0))
+
+
 def _gail_update_resident(self):
     """GailDynLearner.update() on a device-resident rollout: the same call sequence, every call only QUEUES work on the
     library's stream -- discriminator epochs without their loss read-back, the alive-bonus offset from the device's done
@@ -211,8 +226,7 @@ def _gail_update_resident(self):
     for _ in range(self.gail_epoch):            # :255-256
         self.discr.update_gail_dyn(self.loader, ro, fetch_losses=False)
     self.discr.relabel_rewards_auto(ro, self.gamma, self.gail_tar_length, self.no_alive_bonus)     # :258-297
-    _lib.check(lib.sg_rollout_compute_returns_policy(ro.h, self.actor_critic.h, 1 if self.use_gae else 0, float(self.gamma),
-                                                     float(self.gae_lambda), 1 if self.use_proper_time_limits else 0))
+    _returns_resident(self)
     self.agent.update(ro, fetch_losses=False)   # :302
     ro.after_update()                           # :304
     self.j += 1
@@ -274,9 +288,7 @@ class PpoLearner(object):
         if self.use_linear_lr_decay:
             update_linear_schedule(self.agent.optimizer, self.j, self.num_updates, self.lr)
         if ro.device_resident:   # nothing below waits for the device: the losses are read from the results ring on demand
-            _lib.check(lib.sg_rollout_compute_returns_policy(ro.h, self.actor_critic.h, 1 if self.use_gae else 0,
-                                                             float(self.gamma), float(self.gae_lambda),
-                                                             1 if self.use_proper_time_limits else 0))
+            _returns_resident(self)
             self.agent.update(ro, fetch_losses=False)
             ro.after_update()
             self.j += 1

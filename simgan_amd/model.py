@@ -1,5 +1,5 @@
-"""Policy -- host mirror of a2c/model.py:37-114 (MLPBase + DiagGaussian, Box actions,
-non-recurrent).  Parameters live in HBM inside libsimgan_hip.so; this class keeps the
+"""Policy -- host mirror of a2c/model.py:37-114 (MLPBase + DiagGaussian, Box actions; feed-forward, or
+recurrent with the GRU base of a2c/model.py:117-201).  Parameters live in HBM inside libsimgan_hip.so; this class keeps the
 reference's constructor and method signatures and hands host tensors across the C ABI."""
 import ctypes as C
 
@@ -19,7 +19,8 @@ MATERIALISE_CTX = None
 class _PolicyBase(object):
     KIND = None
 
-    def _create(self, obs_dim, act_dim, hidden, num_feet, ctx, critic_hidden=None):
+    def _create(self, obs_dim, act_dim, hidden, num_feet, ctx, critic_hidden=None, recurrent=False):
+        self.__dict__["recurrent"] = bool(recurrent)   # GRU base (a2c/model.py:117-131): the device kind is POLICY_GRU, the class stays Policy
         self.ctx = ctx or _lib.Context.default()
         self.lib = self.ctx.lib
         self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
@@ -27,7 +28,7 @@ class _PolicyBase(object):
         # width of the critic trunk: the actors' unless reset_critic rebuilt it (a2c/model.py:80-87: always 64 units)
         self.critic_hidden = int(critic_hidden) if critic_hidden else self.hidden_size
         h = _lib.H()
-        _lib.check(self.lib.sg_policy_create2(self.ctx.h, self.KIND, self.obs_dim, self.act_dim, self.hidden_size, self.num_feet,
+        _lib.check(self.lib.sg_policy_create2(self.ctx.h, _lib.POLICY_GRU if self._rec() else self.KIND, self.obs_dim, self.act_dim, self.hidden_size, self.num_feet,
                                               0 if self.critic_hidden == self.hidden_size else self.critic_hidden, C.byref(h)))
         self.h = h
         n = C.c_int64(0)
@@ -35,6 +36,13 @@ class _PolicyBase(object):
         self.num_params = n.value
         self.seed = derive_seed(0, 0x5EED, per_instance=True)   # action-noise stream; re-derived from the constructor seed below
         self._act_calls = 0
+
+    def _rec(self):
+        """True for the GRU base.  Objects assembled without the constructor (a torch.load still pending, a bare instance that
+        only lends its class's layout) count as feed-forward until their device twin says otherwise."""
+        if "recurrent" not in self.__dict__ and self.__dict__.get("_pending") is not None:
+            self._materialise()
+        return self.__dict__.get("recurrent", False)
 
     def _register_handle_user(self, obj):
         """Objects that keep this policy's device handle (PPO, PolicyEnsemble) announce themselves: reset_critic refuses to
@@ -67,7 +75,7 @@ class _PolicyBase(object):
             # the context an unpickled policy lands on: `simgan_amd.model.MATERIALISE_CTX` when the caller set one,
             # the process default otherwise (see the module-level comment)
             self._create(dims["obs_dim"], dims["act_dim"], dims["hidden"], dims["num_feet"], MATERIALISE_CTX,
-                         critic_hidden=dims.get("critic_hidden"))
+                         critic_hidden=dims.get("critic_hidden"), recurrent=dims.get("recurrent", False))
             self.seed = derive_seed(0, 0x5EED, per_instance=True)
             self.load_state_dict(sd)
         except BaseException:
@@ -81,12 +89,12 @@ class _PolicyBase(object):
     # ---- nn.Module-ish surface the reference mains touch
     @property
     def is_recurrent(self):
-        return False
+        return self._rec()
 
     @property
     def recurrent_hidden_state_size(self):
         """Size of rnn_hx."""
-        return 1
+        return self.hidden_size if self._rec() else 1
 
     def to(self, device):
         return self
@@ -132,7 +140,8 @@ class _PolicyBase(object):
 
     def __getstate__(self):
         return {"obs_dim": self.obs_dim, "act_dim": self.act_dim, "hidden": self.hidden_size,
-                "num_feet": self.num_feet, "critic_hidden": self.critic_hidden, "flat": self.get_flat_params()}
+                "num_feet": self.num_feet, "critic_hidden": self.critic_hidden, "recurrent": self._rec(),
+                "flat": self.get_flat_params()}
 
     def __reduce_ex__(self, protocol):
         """A policy built through the reference's import path (`third_party.a2c_ppo_acktr.model[_split]`, i.e. by the
@@ -141,6 +150,9 @@ class _PolicyBase(object):
         workers do, my_pybullet_envs/utils.py:24-57).  Loading it here goes through `__setstate__`'s "_modules" branch like
         any reference checkpoint.  The package's own classes keep their compact native pickle."""
         if type(self).__module__.startswith("third_party."):
+            if self._rec():
+                from .checkpoint import RECURRENT_SAVE_MSG
+                raise NotImplementedError(RECURRENT_SAVE_MSG)
             import copyreg
             from .checkpoint import reference_module_state
             return (copyreg.__newobj__, (type(self),), reference_module_state("mlp" if self.KIND == _lib.POLICY_MLP else "split", self.state_dict()))
@@ -152,9 +164,19 @@ class _PolicyBase(object):
             # weights are read when the policy is first used, not here.
             self.__dict__["_pending"] = st
             return
-        self._create(st["obs_dim"], st["act_dim"], st["hidden"], st["num_feet"], None, critic_hidden=st.get("critic_hidden"))
+        self._create(st["obs_dim"], st["act_dim"], st["hidden"], st["num_feet"], None, critic_hidden=st.get("critic_hidden"),
+                     recurrent=st.get("recurrent", False))
         self.seed = derive_seed(0, 0x5EED, per_instance=True)
         self.set_flat_params(st["flat"])
+
+    def _rnn_inputs(self, rnn_hxs, masks, n_env, n_rows):
+        if rnn_hxs is None or masks is None:
+            raise ValueError("a recurrent policy needs rnn_hxs [n, hidden_size] and masks [rows, 1]")
+        hxs = _lib.as_f32(rnn_hxs).reshape(-1, self.hidden_size)
+        m = _lib.as_f32(masks).reshape(-1)
+        if hxs.shape[0] != n_env or m.size != n_rows:
+            raise ValueError(f"recurrent policy: rnn_hxs {tuple(hxs.shape)} / masks [{m.size}] do not match {n_env} states and {n_rows} rows")
+        return hxs, m
 
     # ---- the three calls on the hot path
     def act(self, inputs, rnn_hxs, masks, deterministic=False, noise=None):
@@ -167,6 +189,14 @@ class _PolicyBase(object):
         logp = np.empty((n, 1), np.float32)
         nz = None if noise is None else _lib.as_f32(noise).reshape(n, self.act_dim)
         self._act_calls += 1
+        if self._rec():
+            hxs, m = self._rnn_inputs(rnn_hxs, masks, n, n)
+            hxs_out = np.empty_like(hxs)
+            _lib.check(self.lib.sg_policy_act_rnn(self.h, _lib.fptr(obs), _lib.fptr(hxs), _lib.fptr(m), n,
+                                                  None if nz is None else _lib.fptr(nz), (self.seed + self._act_calls) & (2 ** 64 - 1),
+                                                  1 if deterministic else 0, _lib.fptr(value), _lib.fptr(action), _lib.fptr(logp),
+                                                  _lib.fptr(hxs_out)))
+            return to_host_tensor(value), to_host_tensor(action), to_host_tensor(logp), to_host_tensor(hxs_out)
         _lib.check(self.lib.sg_policy_act(self.h, _lib.fptr(obs), n,
                                           None if nz is None else _lib.fptr(nz), (self.seed + self._act_calls) & (2 ** 64 - 1),
                                           1 if deterministic else 0, _lib.fptr(value),
@@ -177,6 +207,10 @@ class _PolicyBase(object):
         """a2c/model.py:103-105"""
         obs = _lib.as_f32(inputs).reshape(-1, self.obs_dim)
         value = np.empty((obs.shape[0], 1), np.float32)
+        if self._rec():
+            hxs, m = self._rnn_inputs(rnn_hxs, masks, obs.shape[0], obs.shape[0])
+            _lib.check(self.lib.sg_policy_get_value_rnn(self.h, _lib.fptr(obs), _lib.fptr(hxs), _lib.fptr(m), obs.shape[0], _lib.fptr(value)))
+            return to_host_tensor(value)
         _lib.check(self.lib.sg_policy_get_value(self.h, _lib.fptr(obs), obs.shape[0], _lib.fptr(value)))
         return to_host_tensor(value)
 
@@ -188,6 +222,16 @@ class _PolicyBase(object):
         value = np.empty((n, 1), np.float32)
         logp = np.empty((n, 1), np.float32)
         ent = C.c_float(0)
+        if self._rec():
+            # a2c/model.py:137-199: rnn_hxs [n_env, H] with inputs [T * n_env, O] flattened time-major (T == 1: one step)
+            n_env = _lib.as_f32(rnn_hxs).reshape(-1, self.hidden_size).shape[0]
+            if n_env == 0 or n % n_env:
+                raise ValueError(f"evaluate_actions: {n} input rows are not a whole number of steps of the {n_env} hidden states")
+            hxs, m = self._rnn_inputs(rnn_hxs, masks, n_env, n)
+            hxs_out = np.empty_like(hxs)
+            _lib.check(self.lib.sg_policy_evaluate_rnn(self.h, _lib.fptr(obs), _lib.fptr(hxs), _lib.fptr(m), _lib.fptr(act), n // n_env, n_env,
+                                                       _lib.fptr(value), _lib.fptr(logp), C.byref(ent), _lib.fptr(hxs_out)))
+            return to_host_tensor(value), to_host_tensor(logp), to_host_tensor(np.array(ent.value, np.float32)), to_host_tensor(hxs_out)
         _lib.check(self.lib.sg_policy_evaluate(self.h, _lib.fptr(obs), _lib.fptr(act), n,
                                                _lib.fptr(value), _lib.fptr(logp), C.byref(ent)))
         ent_t = to_host_tensor(np.array(ent.value, np.float32))
@@ -202,34 +246,41 @@ class Policy(_PolicyBase):
             base_kwargs = {}
         if base is not None or len(obs_shape) != 1:
             raise NotImplementedError("only the MLP base on 1-D observations is built (SURVEY.md section 2, row 3)")
-        if base_kwargs.get("recurrent", False):
-            raise NotImplementedError("recurrent policies are not used by any shipped SimGAN config")
         if action_space.__class__.__name__ != "Box":
             raise NotImplementedError("only Box action spaces (a2c/model.py:55-57)")
         hidden = base_kwargs.get("hidden_size", 64)
-        self._create(obs_shape[0], action_space.shape[0], hidden, 1, ctx, critic_hidden=critic_hidden)
+        self._create(obs_shape[0], action_space.shape[0], hidden, 1, ctx, critic_hidden=critic_hidden,
+                     recurrent=base_kwargs.get("recurrent", False))
         self.seed = derive_seed(seed, 0x5EED, per_instance=True)
         self._init_params(np.random.default_rng(seed))
 
     def param_shapes(self):
         O, A, Hh, Hc = self.obs_dim, self.act_dim, self.hidden_size, self.critic_hidden
-        return [("base.actor.0.weight", (Hh, O)), ("base.actor.0.bias", (Hh,)),
-                ("base.actor.2.weight", (Hh, Hh)), ("base.actor.2.bias", (Hh,)),
-                ("base.critic.0.weight", (Hc, O)), ("base.critic.0.bias", (Hc,)),
-                ("base.critic.2.weight", (Hc, Hc)), ("base.critic.2.bias", (Hc,)),
-                ("base.critic_linear.weight", (1, Hc)), ("base.critic_linear.bias", (1,)),
-                ("dist.fc_mean.weight", (A, Hh)), ("dist.fc_mean.bias", (A,)),
-                ("dist.logstd._bias", (A, 1))]
+        gru = []
+        if self._rec():   # a2c/model.py:124-131: nn.GRU's four tensors come first and the trunks read its H-wide state
+            gru = [("base.gru.weight_ih_l0", (3 * Hh, O)), ("base.gru.weight_hh_l0", (3 * Hh, Hh)),
+                   ("base.gru.bias_ih_l0", (3 * Hh,)), ("base.gru.bias_hh_l0", (3 * Hh,))]
+            O = Hh
+        return gru + [("base.actor.0.weight", (Hh, O)), ("base.actor.0.bias", (Hh,)),
+                      ("base.actor.2.weight", (Hh, Hh)), ("base.actor.2.bias", (Hh,)),
+                      ("base.critic.0.weight", (Hc, O)), ("base.critic.0.bias", (Hc,)),
+                      ("base.critic.2.weight", (Hc, Hc)), ("base.critic.2.bias", (Hc,)),
+                      ("base.critic_linear.weight", (1, Hc)), ("base.critic_linear.bias", (1,)),
+                      ("dist.fc_mean.weight", (A, Hh)), ("dist.fc_mean.bias", (A,)),
+                      ("dist.logstd._bias", (A, 1))]
 
     def _init_params(self, rng):
         """a2c/model.py:240-251 (orthogonal, gain sqrt2, zero bias), a2c/distributions.py:95-104
-        (fc_mean gain 1 then /50, logstd -0.5)."""
+        (fc_mean gain 1 then /50, logstd -0.5); the GRU, a2c/model.py:126-130: orthogonal (gain 1) on each whole [3H, .]
+        weight, zero biases."""
         sd = {}
         for name, shape in self.param_shapes():
             if name.endswith("logstd._bias"):
                 sd[name] = np.full(shape, -0.5, np.float32)
-            elif name.endswith("bias"):
+            elif name.endswith("bias") or name.startswith("base.gru.bias"):
                 sd[name] = np.zeros(shape, np.float32)
+            elif name.startswith("base.gru.weight"):
+                sd[name] = orthogonal(rng, *shape, gain=1.0)
             elif name.startswith("dist.fc_mean"):
                 sd[name] = orthogonal(rng, *shape, gain=1.0) / 50.0
             else:
@@ -250,6 +301,10 @@ class Policy(_PolicyBase):
         policy, as the reference's main does (:85 then :149): an agent built earlier holds the old device handle."""
         if int(obs_shape[0]) != self.obs_dim:
             raise ValueError(f"reset_critic: obs_shape {tuple(obs_shape)} != the policy's observation size {self.obs_dim}")
+        if self._rec() and self.obs_dim != self.hidden_size:
+            # the reference builds Linear(obs_shape[0], 64) against the H-wide GRU state: its next forward fails unless O == H
+            raise ValueError(f"reset_critic on a recurrent policy needs obs size == hidden size (the reference's new critic reads "
+                             f"{self.obs_dim} inputs from a {self.hidden_size}-wide GRU state)")
         rng = np.random.default_rng(seed)
         sd = self.state_dict()
         if self.critic_hidden != 64:
@@ -259,7 +314,8 @@ class Policy(_PolicyBase):
                                    "hold its device handle, which a critic of another width replaces; call reset_critic first "
                                    "(a2c/main.py:85 precedes :149) or rebuild them afterwards")
             old, seed_, calls_ = self.h, self.seed, self._act_calls
-            self._create(self.obs_dim, self.act_dim, self.hidden_size, self.num_feet, self.ctx, critic_hidden=64)
+            self._create(self.obs_dim, self.act_dim, self.hidden_size, self.num_feet, self.ctx, critic_hidden=64,
+                         recurrent=self._rec())
             self.seed, self._act_calls = seed_, calls_     # the action-noise stream goes on where it was
             self.lib.sg_policy_destroy(old)
         for name, shape in self.param_shapes():

@@ -248,6 +248,52 @@ class RolloutStorage(object):
         global generator."""
         return feed_forward_batches(self, advantages, num_mini_batch, mini_batch_size, perm)
 
+    def recurrent_generator(self, advantages, num_mini_batch, perm=None):
+        """a2c/storage.py:194-251 -- host-side generator: whole environments per minibatch, rows time-major, the hidden
+        state of slot 0.  `perm` injects the reference's torch.randperm(num_processes) draw; default: numpy's generator."""
+        return recurrent_batches(self, advantages, num_mini_batch, perm)
+
+
+def recurrent_batches(ro, advantages, num_mini_batch, perm=None):
+    """a2c/storage.py:194-251 on any object carrying the rollout's host buffers (needs no device): minibatch k holds the
+    environments perm[k*per : (k+1)*per], per = N // num_mini_batch, all T steps each, stacked time-major (row t*per + j);
+    the hidden state is the one of slot 0 only ([per, H]).  The reference's loop is range(0, N, per): N // per minibatches
+    (more than num_mini_batch when per does not divide N into exactly that many), and it dies with an IndexError when
+    N % per != 0 -- a ValueError here."""
+    num_steps, num_processes = ro.rewards.shape[0:2]
+    assert num_processes >= num_mini_batch, (
+        "PPO requires the number of processes ({}) "
+        "to be greater than or equal to the number of "
+        "PPO mini batches ({}).".format(num_processes, num_mini_batch))
+    per = num_processes // num_mini_batch
+    if num_processes % per:
+        raise ValueError(f"recurrent_generator: {num_processes} processes do not split into minibatches of "
+                         f"{per} = {num_processes} // {num_mini_batch} environments (the reference indexes past its permutation here)")
+    if perm is None:
+        perm = np.random.permutation(num_processes)
+    else:
+        perm = _lib.as_i64(perm).reshape(-1)
+        assert perm.size == num_processes and np.array_equal(np.sort(perm), np.arange(num_processes)), \
+            "perm must be a permutation of the N environment ids"
+
+    def arr(t):
+        return t.numpy() if hasattr(t, "numpy") else t
+
+    for start in range(0, num_processes, per):
+        envs = perm[start:start + per]
+
+        def g(t, sl):   # [T(+1), N, w] -> the minibatch's [T * per, w], time-major
+            a = arr(t)[sl][:, envs]
+            return to_host_tensor(np.ascontiguousarray(a.reshape(-1, a.shape[-1])))
+
+        cur, al = slice(None, -1), slice(None)
+        adv = None if advantages is None else to_host_tensor(np.ascontiguousarray(
+            _lib.as_f32(advantages).reshape(num_steps, num_processes, 1)[:, envs].reshape(-1, 1)))
+        hxs = to_host_tensor(np.ascontiguousarray(arr(ro.recurrent_hidden_states)[0, envs]))
+        # (the reference's recurrent generator yields 8 fields: no obs_feat pair, a2c/storage.py:249-251)
+        yield (g(ro.obs, cur), hxs, g(ro.actions, al), g(ro.value_preds, cur), g(ro.returns, cur), g(ro.masks, cur),
+               g(ro.action_log_probs, al), adv)
+
 
 def feed_forward_batches(ro, advantages, num_mini_batch=None, mini_batch_size=None, perm=None):
     """The generator body on any object carrying the rollout's host buffers (needs no device): yields the reference's
