@@ -22,9 +22,9 @@ def param_shapes(O, A, H, Hc=None):
             ("dist.logstd._bias", (A, 1))]
 
 
-def unflatten(flat, O, A, H, Hc=None):
+def unflatten(flat, O, A, H, Hc=None, dtype=np.float64):
     out, off = {}, 0
-    flat = np.asarray(flat, np.float64).reshape(-1)
+    flat = np.asarray(flat, dtype).reshape(-1)
     for name, shape in param_shapes(O, A, H, Hc):
         n = int(np.prod(shape))
         out[name] = flat[off:off + n].reshape(shape)
@@ -116,10 +116,15 @@ def _trunk_bwd(sd, pre, x, h1, h2, dh2, g):
     return d1 @ sd[pre + ".0.weight"]
 
 
-def minibatch_grad(sd, obs, hxs, masks, action, old_logp, adv, vpred, ret, clip, vcoef, ecoef, use_clipped=True):
-    """obs [T*n, O] time-major ... -> (gradient dict, (value_loss, action_loss, entropy))"""
-    obs, h = np.asarray(obs, np.float64), np.asarray(hxs, np.float64)
-    masks = np.asarray(masks, np.float64).reshape(-1)
+def minibatch_grad(sd, obs, hxs, masks, action, old_logp, adv, vpred, ret, clip, vcoef, ecoef, use_clipped=True, dtype=np.float64):
+    """obs [T*n, O] time-major ... -> (gradient dict, (value_loss, action_loss, entropy)).  dtype=np.float32 (with sd
+    unflattened at float32) carries every array in float32: the same algorithm at the library's precision, for tests that
+    measure the library's distance from float64 against a float32 evaluation's own."""
+    f = dtype
+    HALF_LOG_2PI = f(0.5 * np.log(2.0 * np.pi))  # noqa: N806  (a float32 scalar must not promote the arrays)
+    clip, vcoef, ecoef = f(clip), f(vcoef), f(ecoef)
+    obs, h = np.asarray(obs, f), np.asarray(hxs, f)
+    masks = np.asarray(masks, f).reshape(-1)
     n, H = h.shape
     T = obs.shape[0] // n
     B = T * n
@@ -145,21 +150,21 @@ def minibatch_grad(sd, obs, hxs, masks, action, old_logp, adv, vpred, ret, clip,
     mean = a2 @ sd["dist.fc_mean.weight"].T + sd["dist.fc_mean.bias"]
     logstd = sd["dist.logstd._bias"].reshape(-1)
     var = np.exp(2.0 * logstd)
-    action = np.asarray(action, np.float64)
+    action = np.asarray(action, f)
     diff = action - mean
     logp = (-(diff * diff) / (2.0 * var) - logstd - HALF_LOG_2PI).sum(-1)
     ent = float(np.sum(0.5 + HALF_LOG_2PI + logstd))
-    old_logp, adv, vpred, ret = (np.asarray(q, np.float64).reshape(-1) for q in (old_logp, adv, vpred, ret))
+    old_logp, adv, vpred, ret = (np.asarray(q, f).reshape(-1) for q in (old_logp, adv, vpred, ret))
     ratio = np.exp(logp - old_logp)
-    s1, s2 = ratio * adv, np.clip(ratio, 1.0 - clip, 1.0 + clip) * adv
+    s1, s2 = ratio * adv, np.clip(ratio, f(1.0) - clip, f(1.0) + clip) * adv
     action_loss = -np.minimum(s1, s2).mean()
-    inside = ((ratio >= 1.0 - clip) & (ratio <= 1.0 + clip)).astype(np.float64)
+    inside = ((ratio >= f(1.0) - clip) & (ratio <= f(1.0) + clip)).astype(f)
     dlogp = -(np.where(s1 <= s2, adv, adv * inside) * ratio) / B
     if use_clipped:
         vc = vpred + np.clip(value - vpred, -clip, clip)
         u, w = (value - ret) ** 2, (vc - ret) ** 2
         value_loss = 0.5 * np.maximum(u, w).mean()
-        vin = (np.abs(value - vpred) <= clip).astype(np.float64)
+        vin = (np.abs(value - vpred) <= clip).astype(f)
         dv = vcoef * 0.5 * np.where(u >= w, 2.0 * (value - ret), 2.0 * (vc - ret) * vin) / B
     else:
         value_loss = 0.5 * ((ret - value) ** 2).mean()
@@ -170,11 +175,11 @@ def minibatch_grad(sd, obs, hxs, masks, action, old_logp, adv, vpred, ret, clip,
     g["dist.fc_mean.weight"] = dmean.T @ a2
     g["dist.fc_mean.bias"] = dmean.sum(0)
     g["base.critic_linear.weight"] = dv[None, :] @ c2
-    g["base.critic_linear.bias"] = np.array([dv.sum()])
+    g["base.critic_linear.bias"] = np.array([dv.sum()], f)
     dx = _trunk_bwd(sd, "base.actor", x, a1, a2, dmean @ sd["dist.fc_mean.weight"], g)
     dx = dx + _trunk_bwd(sd, "base.critic", x, c1, c2, dv[:, None] * sd["base.critic_linear.weight"], g)
     gWih, gWhh, gbih, gbhh = np.zeros_like(Wih), np.zeros_like(Whh), np.zeros_like(bih), np.zeros_like(bhh)
-    carry = np.zeros((n, H))
+    carry = np.zeros((n, H), f)
     for t in range(T - 1, -1, -1):
         sl = slice(t * n, (t + 1) * n)
         r, z, nn, hn, hm = saved[t]
@@ -194,9 +199,9 @@ def minibatch_grad(sd, obs, hxs, masks, action, old_logp, adv, vpred, ret, clip,
 
 
 def ppo_update(flat0, O, A, H, ro, hxs0, perms, ppo_epoch, num_mini_batch, clip, vcoef, ecoef, lr, eps, max_grad_norm, Hc=None,
-               adam=None):
+               adam=None, use_clipped=True):
     """ro: dict of the rollout's arrays (obs [T+1,N,O], actions, value_preds, returns, action_log_probs, masks); hxs0 [N, H];
-    perms [ppo_epoch, N] -> dict(params, losses, adam_m, adam_v, steps, advantages)"""
+    perms [ppo_epoch, N] -> dict(params, losses, adam_m, adam_v, steps, advantages, norms: every step's gradient norm before the clip)"""
     p = np.asarray(flat0, np.float64).copy()
     obs, act = np.asarray(ro["obs"], np.float64), np.asarray(ro["actions"], np.float64)
     vp, ret = np.asarray(ro["value_preds"], np.float64)[..., 0], np.asarray(ro["returns"], np.float64)[..., 0]
@@ -208,22 +213,23 @@ def ppo_update(flat0, O, A, H, ro, hxs0, perms, ppo_epoch, num_mini_batch, clip,
     assert N % per == 0
     m, v, step = (np.zeros_like(p), np.zeros_like(p), 0) if adam is None else (np.asarray(adam[0], np.float64).copy(),
                                                                                  np.asarray(adam[1], np.float64).copy(), int(adam[2]))
-    sums = np.zeros(3)
+    sums, norms = np.zeros(3), []
     for e in range(ppo_epoch):
         for start in range(0, N, per):
             envs = np.asarray(perms[e][start:start + per])
             tm = lambda a: a[:, envs].reshape(T * per, *a.shape[2:])  # noqa: E731
             sd = unflatten(p, O, A, H, Hc)
             g, losses = minibatch_grad(sd, tm(obs[:-1]), np.asarray(hxs0, np.float64)[envs], tm(mk[:-1]), tm(act), tm(olp), tm(adv),
-                                       tm(vp[:-1]), tm(ret[:-1]), clip, vcoef, ecoef)
+                                       tm(vp[:-1]), tm(ret[:-1]), clip, vcoef, ecoef, use_clipped)
             gf = flatten(g, O, A, H, Hc)
-            gf = gf * min(1.0, max_grad_norm / (np.sqrt((gf * gf).sum()) + 1e-6))
+            norms.append(float(np.sqrt((gf * gf).sum())))
+            gf = gf * min(1.0, max_grad_norm / (norms[-1] + 1e-6))
             step += 1
             m = 0.9 * m + 0.1 * gf
             v = 0.999 * v + 0.001 * gf * gf
             p = p - (lr / (1.0 - 0.9 ** step)) * m / (np.sqrt(v) / np.sqrt(1.0 - 0.999 ** step) + eps)
             sums += losses
-    return dict(params=p, losses=sums / (ppo_epoch * num_mini_batch), adam_m=m, adam_v=v, steps=step, advantages=adv[..., None])
+    return dict(params=p, losses=sums / (ppo_epoch * num_mini_batch), adam_m=m, adam_v=v, steps=step, advantages=adv[..., None], norms=norms)
 
 
 def load_ppo(name):

@@ -1,0 +1,445 @@
+"""Case builders for the numerical regimes the policy-side tests did not reach (tests/test_regimes_host.py on the CPU,
+tests/test_gpu_regimes.py on the GPU): rollouts that are OFF the behaviour policy, so that every branch of the clipped
+surrogate and of the clipped value loss holds rows (`off_policy`), rollouts on which every row's gradient is zero
+(`all_clipped`), and weights / observations scaled until the tanh units and the GRU's gates saturate (`saturated`).
+
+Nothing here touches the library.  A case is described in float64 by the arbiter (oracle/oracle64.py) or, for the recurrent
+policy, by tests/gru_ref.py; the builder ASSERTS on that description that the case reaches what it claims -- every class
+holds at least MIN_ROWS rows and no row lies within MARGIN of a branch boundary -- so a GPU test never runs on a case that
+means nothing, and no correct float32 evaluation (which moves a ratio or a value by ~1e-6) can flip a row.
+
+Parameters are laid out in state_dict order (simgan_amd Policy / SplitPolicy .param_shapes(), the oracle's flat vector)."""
+import functools
+
+import numpy as np
+
+import gru_ref
+from helpers import ATOL, RTOL
+
+CLIP, VCOEF = 0.2, 0.5
+MIN_ROWS = 8          # rows every class must hold
+JITTERS = 3          # jittered float32 evaluations behind every case's float32 distance (describe)
+MARGIN = 1e-4         # no row closer than this to a branch boundary (float32 evaluations differ by ~1e-6 there)
+T, N = 8, 16          # 128-row problems
+
+# (kind, O, A, H, num_feet)
+SHAPES = [("mlp", 47, 12, 64, 1), ("mlp", 5, 2, 8, 1), ("split", 14, 7, 100, 1), ("split", 64, 28, 100, 4),
+          ("gru", 13, 5, 20, 1), ("gru", 47, 12, 64, 1)]
+# every log-prob pass of k_ppo_bwd (tests/test_gpu_regimes.py, 2d): O = 20, H = 32 and the action width that picks the pass
+LOGP_SHAPES = [("mlp", 20, 12, 32, 1), ("mlp", 20, 40, 32, 1), ("mlp", 20, 70, 32, 1), ("mlp", 20, 130, 32, 1),
+               ("split", 14, 35, 32, 5)]
+SATURATIONS = [(4.0, 3.0), (8.0, 5.0)]
+
+# The seed of every (regime, shape): the first of 0, 1, 2, ... at which the builder's conditions hold (tools: run
+# `python tests/regimes.py` to search again after a change to the recipe).  A case that misses a condition gets another
+# seed here, never an exclusion list.
+SEEDS = {("off_policy", "gru", 47, 12, 64, 1): 2, ("off_policy", "mlp", 20, 12, 32, 1): 1,
+         ("saturated", "mlp", 47, 12, 64, 1, 8.0, 5.0): 7, ("saturated", "mlp", 5, 2, 8, 1, 8.0, 5.0): 6,
+         ("saturated", "split", 14, 7, 100, 1, 8.0, 5.0): 2, ("saturated", "split", 64, 28, 100, 4, 8.0, 5.0): 18,
+         ("saturated", "gru", 13, 5, 20, 1, 4.0, 3.0): 2, ("saturated", "gru", 13, 5, 20, 1, 8.0, 5.0): 58,
+         ("saturated", "gru", 47, 12, 64, 1, 4.0, 3.0): 6, ("saturated", "gru", 47, 12, 64, 1, 8.0, 5.0): 44}   # every other case: 0
+
+
+def param_shapes(kind, O, A, H, f=1):
+    if kind == "gru":
+        return gru_ref.param_shapes(O, A, H)
+    if kind == "mlp":
+        return [("base.actor.0.weight", (H, O)), ("base.actor.0.bias", (H,)), ("base.actor.2.weight", (H, H)), ("base.actor.2.bias", (H,)),
+                ("base.critic.0.weight", (H, O)), ("base.critic.0.bias", (H,)), ("base.critic.2.weight", (H, H)), ("base.critic.2.bias", (H,)),
+                ("base.critic_linear.weight", (1, H)), ("base.critic_linear.bias", (1,)),
+                ("dist.fc_mean.weight", (A, H)), ("dist.fc_mean.bias", (A,)), ("dist.logstd._bias", (A, 1))]
+    assert kind == "split" and A == 7 * f
+    out = []
+    for trunk in ("actor_contact", "actor_actuator", "critic_full"):
+        out += [(f"base.{trunk}.0.weight", (H, O)), (f"base.{trunk}.0.bias", (H,)), (f"base.{trunk}.2.weight", (H, H)), (f"base.{trunk}.2.bias", (H,))]
+    return out + [("base.critic_full.4.weight", (1, H)), ("base.critic_full.4.bias", (1,)),
+                  ("dist.contact_mean.weight", (4 * f, H)), ("dist.contact_mean.bias", (4 * f,)),
+                  ("dist.actuator_mean.weight", (3 * f, H)), ("dist.actuator_mean.bias", (3 * f,)),
+                  ("dist.contact_logstd.weight", (4 * f, H)), ("dist.contact_logstd.bias", (4 * f,)),
+                  ("dist.actuator_logstd.weight", (3 * f, H)), ("dist.actuator_logstd.bias", (3 * f,))]
+
+
+def blocks(kind, O, A, H, f, flat):
+    """[(name, slice of `flat`)] -- the GRU's four tensors gate by gate (r, z, n), so that a wrong gate shows up as one."""
+    out, off = [], 0
+    for name, shape in param_shapes(kind, O, A, H, f):
+        n = int(np.prod(shape))
+        if name.startswith("base.gru"):
+            for k, part in enumerate(np.array_split(np.arange(off, off + n), 3)):
+                out.append((f"{name}[{'rzn'[k]}]", flat[part[0]:part[-1] + 1]))
+        else:
+            out.append((name, flat[off:off + n]))
+        off += n
+    assert off == flat.size, (off, flat.size)
+    return out
+
+
+def _orthogonal(rng, rows, cols):
+    """a [rows, cols] matrix with orthonormal rows or columns (the reference initialises every weight this way): QR of a Gaussian"""
+    q, r = np.linalg.qr(rng.standard_normal((max(rows, cols), min(rows, cols))))
+    q = q * np.sign(np.diag(r))
+    return q if rows >= cols else q.T
+
+
+def _init_params(rng, kind, O, A, H, f, scale_w):
+    """Orthogonal weights of the reference's scale (trunks: gain sqrt 2; the GRU and the value head: gain 1; mean heads 0.05: 2.5 x the reference's initial gain), small
+    non-zero biases, log-stds spread over roughly [-2.5, 0.5].  scale_w multiplies every weight matrix but the log-std heads."""
+    parts = []
+    for name, shape in param_shapes(kind, O, A, H, f):
+        n = int(np.prod(shape))
+        if name == "dist.logstd._bias":
+            w = rng.permutation(np.linspace(-2.5, 0.5, n))
+        elif "logstd" in name:   # SplitPolicy: the log-std is a head of the actor trunks (|h| <= 1: the head adds about +-0.3)
+            w = rng.permutation(np.linspace(-2.2, 0.2, n)) if name.endswith("bias") else 0.3 * rng.standard_normal(n) / np.sqrt(shape[-1])
+        elif "bias" in name:
+            w = 0.1 * rng.standard_normal(n)
+        else:
+            gain = 1.0 if name.startswith("base.gru") or name.startswith("base.critic_linear") or name.endswith(".4.weight") else \
+                0.05 if "_mean" in name else np.sqrt(2.0)
+            w = scale_w * gain * _orthogonal(rng, *shape).reshape(-1)
+        parts.append(w)
+    return np.concatenate(parts).astype(np.float32)
+
+
+class Case(dict):
+    __getattr__ = dict.__getitem__
+
+
+def _dims(c, orc):
+    return orc.dims(orc.KIND_MLP if c.kind == "mlp" else orc.KIND_SPLIT, c.O, c.A, c.H, c.f)
+
+
+def forward64(c, params=None):
+    """float64 (value [B], mean [B, A], logstd [B, A]) of the T*N rows, time-major, from the case's float32 arrays"""
+    params = c.params if params is None else params
+    B = c.T * c.N
+    if c.kind == "gru":
+        sd = gru_ref.unflatten(params, c.O, c.A, c.H)
+        x, _ = gru_ref.gru_sequence(sd, c.obs[:-1].reshape(B, c.O), c.hxs0, c.masks[:-1].reshape(B))
+        v, mean, ls = gru_ref.heads(sd, x)
+        return v[:, 0], mean, np.broadcast_to(ls, mean.shape)
+    from oracle import oracle64 as o64
+    v, mean, ls = o64.policy_forward(_dims(c, o64), params, c.obs[:-1].reshape(B, c.O))
+    return v[:, 0], mean, ls
+
+
+def forward32(c, params=None, obs=None):
+    """the float32 evaluation's (value [B], logp [B]): oracle/sg_oracle.c, or gru_ref's cell and heads on float32 arrays"""
+    params = c.params if params is None else params
+    obs = c.obs if obs is None else obs
+    B, f = c.T * c.N, np.float32
+    if c.kind != "gru":
+        from oracle import oracle as o32
+        v, lp, _ = o32.policy_evaluate(_dims(c, o32), params, obs[:-1].reshape(B, c.O), c.actions.reshape(B, c.A))
+        return v[:, 0].astype(np.float64), lp[:, 0].astype(np.float64)
+    sd = gru_ref.unflatten(params, c.O, c.A, c.H, dtype=f)
+    h, xs, mk = c.hxs0.astype(f), [], c.masks[:-1].reshape(c.T, c.N, 1).astype(f)
+    for t in range(c.T):
+        h = gru_ref.gru_cell(sd, obs[t].astype(f), h * mk[t])
+        xs.append(h)
+    v, mean, ls = gru_ref.heads(sd, np.concatenate(xs))
+    diff = c.actions.reshape(B, c.A).astype(f) - mean
+    lp = (-(diff * diff) / (f(2.0) * np.exp(f(2.0) * ls)) - ls - f(gru_ref.HALF_LOG_2PI)).sum(-1)
+    assert v.dtype == f and lp.dtype == f
+    return v[:, 0].astype(np.float64), lp.astype(np.float64)
+
+
+def logp64(mean, ls, action):
+    action = np.asarray(action, np.float64)
+    return (-((action - mean) ** 2) / (2.0 * np.exp(2.0 * ls)) - ls - gru_ref.HALF_LOG_2PI).sum(-1)
+
+
+def advantages64(c):
+    adv = c.returns[:-1, :, 0].astype(np.float64) - c.value_preds[:-1, :, 0].astype(np.float64)
+    return (adv - adv.mean()) / (adv.std(ddof=1) + 1e-5)
+
+
+def grad(c, use_clipped=True, bits=64, entropy_coef=None, params=None):
+    """One-minibatch gradient of the whole rollout (ppo_epoch = 1, num_mini_batch = 1) -> (flat gradient, losses[3]).
+    bits = 64: the arbiter; bits = 32: the same algorithm carried out in float32 (the parity oracle; for the GRU,
+    gru_ref at float32)."""
+    ecoef = c.entropy_coef if entropy_coef is None else entropy_coef
+    params = c.params if params is None else params
+    B = c.T * c.N
+    if c.kind == "gru":
+        dt = np.float64 if bits == 64 else np.float32
+        sd = gru_ref.unflatten(params, c.O, c.A, c.H, dtype=dt)
+        adv = advantages64(c) if bits == 64 else _adv32(c)
+        g, losses = gru_ref.minibatch_grad(sd, c.obs[:-1].reshape(B, c.O), c.hxs0, c.masks[:-1].reshape(B), c.actions.reshape(B, c.A),
+                                           c.action_log_probs.reshape(B), adv.reshape(B), c.value_preds[:-1].reshape(B),
+                                           c.returns[:-1].reshape(B), CLIP, VCOEF, ecoef, use_clipped, dtype=dt)
+        return gru_ref.flatten(g, c.O, c.A, c.H), np.array(losses, np.float64)
+    if bits == 64:
+        from oracle import oracle64 as orc
+    else:
+        from oracle import oracle as orc
+    cfg = orc.ppo_cfg(CLIP, 1, 1, VCOEF, ecoef, 3e-4, 1e-5, 1e9, use_clipped)
+    vp, ret = c.value_preds[:-1].reshape(B), c.returns[:-1].reshape(B)
+    adv = orc.advantages(ret, vp)
+    G, sums = orc.ppo_grad_rows(_dims(c, orc), params, cfg, c.obs[:-1].reshape(B, c.O), c.actions.reshape(B, c.A), vp, ret,
+                                c.action_log_probs.reshape(B), adv, np.arange(B), 1.0 / B)
+    return np.asarray(G, np.float64), sums / B
+
+
+def _adv32(c):
+    adv = c.returns[:-1, :, 0] - c.value_preds[:-1, :, 0]
+    mean = np.float32(adv.astype(np.float64).mean())
+    std = np.float32(np.sqrt(((adv.astype(np.float64) - mean) ** 2).sum() / (adv.size - 1)))
+    return (adv - mean) / (std + np.float32(1e-5))
+
+
+def describe(c):
+    """The float64 description: per-row ratio / advantage / value terms, the class of every row, the margins to the branch
+    boundaries, and the one-step gradient norm under both value losses."""
+    v, mean, ls = forward64(c)
+    B = c.T * c.N
+    lp = logp64(mean, ls, c.actions.reshape(B, c.A))
+    ratio = np.exp(lp - c.action_log_probs.reshape(B).astype(np.float64))
+    adv = advantages64(c).reshape(B)
+    vo, R = c.value_preds[:-1].reshape(B).astype(np.float64), c.returns[:-1].reshape(B).astype(np.float64)
+    dvv = v - vo
+    vc = vo + np.clip(dvv, -CLIP, CLIP)
+    u, w = (v - R) ** 2, (vc - R) ** 2
+    above, below = ratio > 1.0 + CLIP, ratio < 1.0 - CLIP
+    outside = np.abs(dvv) > CLIP
+    d = Case(v=v, logp=lp, ratio=ratio, adv=adv, u=u, w=w)
+    d["classes"] = {"above_adv+": int((above & (adv > 0)).sum()), "above_adv-": int((above & (adv < 0)).sum()),
+                    "below_adv+": int((below & (adv > 0)).sum()), "below_adv-": int((below & (adv < 0)).sum()),
+                    "inside": int((~above & ~below).sum()),
+                    "u>w": int((outside & (u > w)).sum()), "w>u_outside": int((outside & (w > u)).sum()),
+                    "value_inside": int((~outside).sum())}
+    # rows whose gradient is zero in the reference: the surrogate's min picked the clipped (constant) term, the value loss's
+    # max picked the clipped value outside the clip
+    d["actor_zero"] = (above & (adv > 0)) | (below & (adv < 0))
+    d["value_zero"] = outside & (w > u)
+    d["margin_ratio"] = float(np.min(np.minimum(np.abs(ratio - (1.0 + CLIP)), np.abs(ratio - (1.0 - CLIP)))))
+    d["margin_value"] = float(np.min(np.abs(np.abs(dvv) - CLIP)))
+    d["margin_uw"] = float(np.min(np.abs(u - w)[outside])) if outside.any() else np.inf
+    d["margin_adv"] = float(np.min(np.abs(adv)))
+    # forward conditioning: the float32 evaluation's worst value / log-prob error in units of the project's tolerance
+    # (ATOL + RTOL |float64|), over the evaluation itself and JITTERS more with inputs moved by at most an ulp
+    fw = 0.0
+    for k in range(JITTERS + 1):
+        jr = np.random.default_rng([c.seed, k, 78])
+        jit = (lambda a: a) if k == 0 else (lambda a: (a * (1.0 + jr.uniform(-1.0, 1.0, a.shape) * 2.0 ** -24)).astype(np.float32))
+        v32, lp32 = forward32(c, jit(c.params), jit(c.obs))
+        fw = max(fw, float(np.max(np.abs(v32 - v) / (ATOL + RTOL * np.abs(v)))), float(np.max(np.abs(lp32 - lp) / (ATOL + RTOL * np.abs(lp)))))
+    d["fwd32"] = fw
+    d["saturation"] = _saturation(c)
+    for uc in (True, False):
+        g, losses = grad(c, uc, 64)
+        d["grad_clipped" if uc else "grad_plain"], d["losses_clipped" if uc else "losses_plain"] = g, losses
+        # the same algorithm in float32: its gradient, and its distance from float64 block by block.  One float32 evaluation is one
+        # draw of its round-off: where a block hangs on a few ill-conditioned units two evaluations differ severalfold, so the
+        # distance is the largest over the evaluation itself and JITTERS more with parameters and observations moved by at most
+        # an ulp (the size of the round-off inside any evaluation)
+        g32, _ = grad(c, uc, 32)
+        d["grad32_clipped" if uc else "grad32_plain"] = g32
+        o32 = block_distances(g32, g, c.kind, c.O, c.A, c.H, c.f, ATOL)
+        for k in range(JITTERS):
+            jr = np.random.default_rng([c.seed, k, 77])
+            cj = Case(c)
+            cj["params"] = (c.params * (1.0 + jr.uniform(-1.0, 1.0, c.params.shape) * 2.0 ** -24)).astype(np.float32)
+            cj["obs"] = (c.obs * (1.0 + jr.uniform(-1.0, 1.0, c.obs.shape) * 2.0 ** -24)).astype(np.float32)
+            for name, x in block_distances(grad(cj, uc, 32)[0], g, c.kind, c.O, c.A, c.H, c.f, ATOL).items():
+                o32[name] = max(o32[name], x)
+        d["o32_clipped" if uc else "o32_plain"] = o32
+    d["norm"] = float(np.sqrt((d["grad_clipped"] ** 2).sum()))
+    d["norm_plain"] = float(np.sqrt((d["grad_plain"] ** 2).sum()))
+    return d
+
+
+def _saturation(c):
+    """fraction of the first layer's units whose float64 activation is within 1e-3 of +-1 (GRU: of the r and z gates within 1e-3
+    of 0 or 1)"""
+    B = c.T * c.N
+    p = c.params.astype(np.float64)
+    x = c.obs[:-1].reshape(B, c.O).astype(np.float64)
+    if c.kind == "gru":
+        sd = gru_ref.unflatten(p, c.O, c.A, c.H)
+        hs, _ = gru_ref.gru_sequence(sd, x, c.hxs0, c.masks[:-1].reshape(B))
+        hprev = np.concatenate([c.hxs0.astype(np.float64), hs[:-c.N]]) * c.masks[:-1].reshape(B, 1)
+        gates = x @ sd["base.gru.weight_ih_l0"].T + sd["base.gru.bias_ih_l0"] + hprev @ sd["base.gru.weight_hh_l0"].T + sd["base.gru.bias_hh_l0"]
+        return float((np.abs(np.tanh(0.5 * gates[:, :2 * c.H])) > 1.0 - 2e-3).mean())   # r, z within 1e-3 of 0 or 1
+    name, shape = param_shapes(c.kind, c.O, c.A, c.H, c.f)[0]
+    W, b = p[:c.H * c.O].reshape(c.H, c.O), p[c.H * c.O:c.H * c.O + c.H]
+    return float((np.abs(np.tanh(x @ W.T + b)) > 1.0 - 1e-3).mean())
+
+
+def _check(c):
+    d, cl = c.desc, c.desc["classes"]
+    B = c.T * c.N
+    if c.regime == "all_clipped":
+        assert d["actor_zero"].all() and d["value_zero"].all(), f"{c.tag}: {int((~d['actor_zero']).sum())} actor rows / " \
+            f"{int((~d['value_zero']).sum())} value rows are not in a zero-gradient class"
+        assert min(cl["above_adv+"], cl["below_adv-"]) >= MIN_ROWS and cl["above_adv+"] + cl["below_adv-"] == B, (c.tag, cl)
+        assert d["margin_adv"] >= 1e-3, f"{c.tag}: a normalised advantage of {d['margin_adv']:.2e} has no safe sign"
+        assert not d["grad_clipped"].any(), f"{c.tag}: the float64 gradient is not exactly zero"
+    else:
+        short = {k: n for k, n in cl.items() if k != "value_inside" and n < MIN_ROWS}
+        assert not short, f"{c.tag}: classes with fewer than {MIN_ROWS} rows: {short} (all: {cl})"
+    for k in ("margin_ratio", "margin_value", "margin_uw"):
+        assert d[k] >= MARGIN, f"{c.tag}: {k} = {d[k]:.2e}: a row within {MARGIN} of a branch boundary"
+    assert np.isfinite(d["grad_clipped"]).all() and np.isfinite(d["grad_plain"]).all(), c.tag
+    # conditioning: the GPU tests hold the library to RTOL per block, so a case means something only where float32 evaluations
+    # themselves sit within RTOL of float64 in every block (in deep saturation 1 - h^2 and z (1 - z) are differences of nearly equal
+    # float32 numbers, in the reference as in any restatement of it; at saturated(8, 5) most seeds of the recurrent policy fail this)
+    # (forward: values and log-probs are held element by element to ATOL + RTOL |x|; a row whose log-prob terms cancel to ~0 is
+    # outside that in float32 itself, so float32 evaluations must use at most half of it)
+    assert d["fwd32"] <= 0.5, f"{c.tag}: float32 evaluations use {d['fwd32']:.2f} of the forward tolerance"
+    worst = max(max(d["o32_clipped"].values()), max(d["o32_plain"].values()))
+    # F >= 2 times that must still be inside the contract: RTOL / 2.  The recurrent policy at saturated(8, 5) has no such seed among
+    # 0..399 (its float32 evaluations sit 6e-5 .. 1.5e-4 from float64 whatever the seed); there the limit is the contract itself
+    limit = RTOL if (c.kind == "gru" and c.scale_w >= 8.0) else 0.5 * RTOL
+    assert worst <= limit, f"{c.tag}: float32 evaluations are up to {worst:.2e} from float64 in their worst block (limit {limit:g})"
+
+
+def build(regime, kind, O, A, H, f=1, T=T, N=N, seed=None, scale_w=1.0, scale_obs=1.0, check=True):
+    """-> Case: the shape, `params` (float32, flat), the rollout's float32 arrays (obs [T+1, N, O], actions [T, N, A],
+    value_preds / returns / masks [T+1, N, 1], action_log_probs [T, N, 1], hxs0 [N, H] for the GRU), entropy_coef, and `desc`
+    (describe()).  regime: "off_policy", "all_clipped" or "saturated" (= off_policy at scale_w, scale_obs)."""
+    assert regime in ("off_policy", "all_clipped", "saturated")
+    key = (regime, kind, O, A, H, f) + ((scale_w, scale_obs) if regime == "saturated" else ())
+    seed = SEEDS.get(key, 0) if seed is None else seed
+    rng = np.random.default_rng([seed, O, A, H, {"mlp": 0, "split": 1, "gru": 2}[kind]])
+    c = Case(regime=regime, kind=kind, O=O, A=A, H=H, f=f, T=T, N=N, seed=seed, scale_w=scale_w, scale_obs=scale_obs,
+             entropy_coef=0.0 if regime == "all_clipped" else 0.01,
+             tag=f"{regime}{(scale_w, scale_obs) if regime == 'saturated' else ''} {kind} ({O}, {A}, {H}, f={f}) seed {seed}")
+    c["params"] = _init_params(rng, kind, O, A, H, f, scale_w)
+    c["obs"] = (scale_obs * rng.standard_normal((T + 1, N, O))).astype(np.float32)
+    masks = np.ones((T + 1, N, 1), np.float32)
+    if kind == "gru":   # episode ends inside the sequence: the state reset and the cut in back-propagation through time
+        masks[1:T] = (rng.random((T - 1, N, 1)) > 0.08).astype(np.float32)
+        masks[T // 2, 0] = 0.0
+        c["hxs0"] = (0.5 * rng.standard_normal((N, H))).astype(np.float32)
+    c["masks"] = masks
+    B = T * N
+    c["actions"] = np.zeros((T, N, A), np.float32)
+    v, mean, ls = forward64(c)
+    c["actions"] = (mean + np.exp(ls) * rng.standard_normal((B, A))).reshape(T, N, A).astype(np.float32)
+    lp = logp64(mean, ls, c.actions.reshape(B, A))
+    vp, ret = np.zeros((T + 1, N, 1)), np.zeros((T + 1, N, 1))
+    if regime == "all_clipped":
+        vp[:T] = (v + rng.uniform(0.4, 0.8, B)).reshape(T, N, 1)     # v - v_old < -clip, and w > u:
+        ret[:T] = (v - rng.uniform(0.5, 1.5, B)).reshape(T, N, 1)    # the max picks the clipped value, whose gradient is zero
+    else:
+        vp[:T] = (v + rng.uniform(-0.5, 0.5, B)).reshape(T, N, 1)
+        ret[:T] = (v + 0.5 * rng.standard_normal(B)).reshape(T, N, 1)
+    c["value_preds"], c["returns"] = vp.astype(np.float32), ret.astype(np.float32)
+    if regime == "all_clipped":   # ratio 1.5 where adv > 0, 1 / 1.5 where adv < 0: the min picks the clipped, constant term
+        olp = lp - np.sign(advantages64(c).reshape(B)) * np.log(1.5)
+    else:
+        olp = lp + rng.uniform(-0.6, 0.6, B)
+    c["action_log_probs"] = olp.reshape(T, N, 1).astype(np.float32)
+    c["desc"] = describe(c)
+    if check:
+        _check(c)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def case(regime, kind, O, A, H, f=1, scale_w=1.0, scale_obs=1.0):
+    """build() at the committed seed, computed once per process and shared (callers must not write into it)"""
+    return build(regime, kind, O, A, H, f, scale_w=scale_w, scale_obs=scale_obs)
+
+
+def all_cases():
+    """every (regime, shape, scales) the GPU file uses"""
+    out = [("off_policy",) + s + (1.0, 1.0) for s in SHAPES + LOGP_SHAPES]
+    out += [("all_clipped",) + s + (1.0, 1.0) for s in SHAPES]
+    out += [("saturated",) + s + sc for s in SHAPES for sc in SATURATIONS]
+    return out
+
+
+def block_distances(got, ref, kind, O, A, H, f, atol=ATOL):
+    """{block: ||got - ref||_2 / (||ref||_2 + atol * max|ref| * sqrt(n))}: rel-L2 per parameter block, with a floor for a block
+    whose reference is near zero.  The floor is atol on the scale of the whole gradient's largest element, as helpers.ATOL is
+    on the scale of O(1) parameters: a block's own maximum vanishes with the block (a one-element bias gradient is a sum of 128
+    signed row terms that cancel to 1 / 150 of their size at saturated(8, 5)) and would floor nothing."""
+    out = {}
+    ref = np.asarray(ref, np.float64)
+    scale = atol * np.max(np.abs(ref))
+    for (name, g), (_, r) in zip(blocks(kind, O, A, H, f, np.asarray(got, np.float64)), blocks(kind, O, A, H, f, ref)):
+        out[name] = float(np.sqrt(((g - r) ** 2).sum()) / (np.sqrt((r ** 2).sum()) + scale * np.sqrt(r.size) + 1e-300))
+    return out
+
+
+# both sides of the gradient clip (tests/test_gpu_regimes.py, 2c): (shape, seed of the minibatch permutations) at which EVERY step of two
+# updates of E = 2, M = 2 has a float64 norm above 0.5 and below 5.0 by 10 % (tests/test_regimes_host.py asserts it)
+LR, EPS = 3e-4, 1e-5
+CLIP_CASES = [(("mlp", 5, 2, 8, 1), 2), (("gru", 13, 5, 20, 1), 1)]
+A2C_CLIP_CASE = ("mlp", 5, 2, 8, 1)
+
+
+def clip_perms(c, perm_seed, E=2):
+    rng = np.random.default_rng(perm_seed)
+    return np.stack([rng.permutation(c.N if c.kind == "gru" else c.T * c.N) for _ in range(E)]).astype(np.int64)
+
+
+def a2c_restated(c, max_grad_norm, lr=7e-4):
+    """test_a2c_host.a2c_update_restated on the case's rollout -> (params1, square_avg, losses, float64 gradient norm)"""
+    from test_a2c_host import a2c_loss_grad, a2c_update_restated
+    B, dims = c.T * c.N, (c.O, c.A, c.H, c.H)
+    _, g = a2c_loss_grad(c.params, c.obs[:-1].reshape(B, c.O), c.actions.reshape(B, c.A), c.returns[:-1].reshape(B), dims, VCOEF, c.entropy_coef)
+    out = a2c_update_restated(c.params, np.zeros_like(c.params), c.obs, c.actions, c.returns, dims, VCOEF, c.entropy_coef, lr, EPS, 0.99,
+                              max_grad_norm)
+    return out + (float(np.sqrt((g * g).sum())),)
+
+
+def ppo_update64(c, perms, E, M, lr, eps, max_grad_norm, use_clipped=True, adam=None, updates=1):
+    """`updates` PPO updates (E epochs x M minibatches each, the same `perms` every update) in float64 ->
+    dict(params, m, v, steps, norms, losses of the last update).  Feed-forward: perms [E, T*N] of rows; GRU: [E, N] of
+    environments (gru_ref.ppo_update)."""
+    if c.kind == "gru":
+        ro = {k: c[k] for k in ("obs", "actions", "value_preds", "returns", "action_log_probs", "masks")}
+        p, norms = c.params, []
+        for _ in range(updates):
+            r = gru_ref.ppo_update(p, c.O, c.A, c.H, ro, c.hxs0, perms, E, M, CLIP, VCOEF, c.entropy_coef, lr, eps, max_grad_norm,
+                                   adam=adam, use_clipped=use_clipped)
+            p, adam = r["params"], (r["adam_m"], r["adam_v"], r["steps"])
+            norms += r["norms"]
+        return dict(params=p, m=adam[0], v=adam[1], steps=adam[2], norms=norms, losses=r["losses"])
+    from oracle import oracle64 as orc
+    B = c.T * c.N
+    cfg = orc.ppo_cfg(CLIP, E, M, VCOEF, c.entropy_coef, lr, eps, max_grad_norm, use_clipped)
+    d = _dims(c, orc)
+    vp, ret = c.value_preds[:-1].reshape(B), c.returns[:-1].reshape(B)
+    adv = orc.advantages(ret, vp)
+    p = c.params.astype(np.float64)
+    m, v, step = (np.zeros_like(p), np.zeros_like(p), 0) if adam is None else (np.asarray(adam[0], np.float64).copy(),
+                                                                                 np.asarray(adam[1], np.float64).copy(), int(adam[2]))
+    mb, norms = B // M, []
+    for _ in range(updates):
+        tot = np.zeros(3)
+        for e in range(E):
+            for k in range(M):
+                G, sums = orc.ppo_grad_rows(d, p, cfg, c.obs[:-1].reshape(B, c.O), c.actions.reshape(B, c.A), vp, ret,
+                                            c.action_log_probs.reshape(B), adv, np.asarray(perms[e][k * mb:(k + 1) * mb]), 1.0 / mb)
+                norms.append(float(np.sqrt((G * G).sum())))
+                G = G * min(1.0, max_grad_norm / (norms[-1] + 1e-6))
+                step += 1
+                m = 0.9 * m + 0.1 * G
+                v = 0.999 * v + 0.001 * G * G
+                p = p - (lr / (1.0 - 0.9 ** step)) * m / (np.sqrt(v) / np.sqrt(1.0 - 0.999 ** step) + eps)
+                tot += sums / mb
+    return dict(params=p, m=m, v=v, steps=step, norms=norms, losses=tot / (E * M))
+
+
+if __name__ == "__main__":   # the seed search: prints the SEEDS table
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    for spec in all_cases():
+        regime, kind, O, A, H, f, sw, so = spec
+        for seed in range(400):
+            try:
+                c = build(regime, kind, O, A, H, f, seed=seed, scale_w=sw, scale_obs=so)
+            except AssertionError:
+                continue
+            key = (regime, kind, O, A, H, f) + ((sw, so) if regime == "saturated" else ())
+            d = c.desc
+            print(f"    {key}: {seed},   # norm {d['norm']:.3g} / {d['norm_plain']:.3g}, margins {d['margin_ratio']:.1e} {d['margin_value']:.1e} "
+                  f"{d['margin_uw']:.1e}, o32 {max(max(d['o32_clipped'].values()), max(d['o32_plain'].values())):.1e}, fwd32 {d['fwd32']:.2f}, saturated {d['saturation']:.2f}, {d['classes']}", flush=True)
+            break
+        else:
+            print("# NO SEED for", spec, flush=True)

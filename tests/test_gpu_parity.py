@@ -873,14 +873,14 @@ def test_injected_draws_are_validated(sg):
     assert a_ == b_ and np.array_equal(D.get_flat_params(), D2.get_flat_params())
 
 
-KNOBS = [{"SG_PPO_FUSED": "0"}, {"SG_PPO_ROWS": "16"}, {"SG_PPO_ROWS": "32"}, {"SG_PPO_WAVES": "4"}, {"SG_DISC_CHAIN": "wide"},
+KNOBS = [{"SG_PPO_FUSED": "0"}, {"SG_PPO_ROWS": "16"}, {"SG_PPO_ROWS": "32"}, {"SG_PPO_ROWS": "64"}, {"SG_PPO_WAVES": "4"}, {"SG_DISC_CHAIN": "wide"},
          {"SG_PPO_GRAPH": "0", "SG_DISC_GRAPH": "0"}, {"SG_WGRAD_XCD": "0"}]
 
 
 @pytest.mark.parametrize("knob", KNOBS, ids=[",".join(f"{k}={v}" for k, v in kn.items()) for kn in KNOBS])
 def test_every_launch_variant_keeps_parity(knob):
     """The library's environment knobs select other kernels / launch geometries for the same math (unfused PPO forward,
-    16- or 32-row PPO groups, 4-wave PPO workgroups, the 16-row discriminator chain kernel, direct launches instead of graph
+    16-, 32- or 64-row PPO groups, 4-wave PPO workgroups, the 16-row discriminator chain kernel, direct launches instead of graph
     replay, the linear weight-gradient tile order): the reference trajectories must hold under each of them."""
     import os
     import subprocess
