@@ -6,7 +6,7 @@
 //   k_kfac_stats     a^T a / g^T g of every distinct factor over the chunk's rows on the matrix cores (upper tiles only,
 //                    mirrored), added to the update's sums: scratch is one set of factors, whatever T*N is
 // then once per update:
-//   k_kfac_fold      running averages m <- (m 99 + f) 0.01 (update_running_stat, kfac.py:90-94; m = f on the first update)
+//   k_kfac_fold      running averages m <- m 0.99 + f 0.01 (update_running_stat, kfac.py:90-94; m = f on the first update)
 //   k_kfac_eig       cyclic Jacobi per distinct factor on the upper triangle (torch.symeig(upper=True), kfac.py:229-237),
 //                    only when the device step counter says steps % Tf == 0; eigenvalues <= 1e-6 set to 0
 //   k_kfac_gemm x4   v = Q_g ((Q_g^T grad Q_a) / (d_g d_a^T + damping)) Q_a^T per module, and the tiles' sums of v * grad
@@ -174,15 +174,17 @@ __global__ __launch_bounds__(64 * SG_KFAC_STATS_WAVES) void k_kfac_stats(KfacSta
 }
 
 // f = sums / B (A factors: a^T (a / B), kfac.py:72) or sums * B (G factors: (g B)^T (g B / B), kfac.py:87-88); m <- f on the
-// first update, then m <- ((m * 99) + f) * 0.01 in float32 (update_running_stat with stat_decay 0.99)
+// first update, then m <- m * stat_decay + f * (1 - stat_decay) (update_running_stat).  Not in the reference's form
+// ((m * 99) + f) * 0.01: in float32 neither 99.00009 (0.99f / (1 - 0.99f), rounded up by half an ulp) times 0.00999999 nor the
+// reference's own 99 times 0.01f makes the two weights sum to 1, so every factor drifts by 3.8e-8 (2.2e-8 there) of itself per
+// update, 3.8e-6 in the long run.  stat_decay and 1 - stat_decay are both float32 numbers (exactly, from 0.5 up): they sum to 1
 __global__ __launch_bounds__(256) void k_kfac_fold(float* m, const float* acc, int total, int g_start, float inv_b, float b,
-                                                   const KfacDevState* ks, float m_scale, float f_scale) {
+                                                   const KfacDevState* ks, float decay, float one_minus_decay) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const float f = acc[i] * (i < g_start ? inv_b : b);
-    float v = ks->steps == 0 ? f : m[i];
-    v = __fmul_rn(__fadd_rn(__fmul_rn(v, m_scale), f), f_scale);
-    m[i] = v;
+    const float v = ks->steps == 0 ? f : m[i];
+    m[i] = __fmaf_rn(v, decay, __fmul_rn(f, one_minus_decay));
 }
 
 // Cyclic Jacobi, round-robin pair order, in double.  a: [n][n] working matrix (the upper triangle of m is mirrored into it),

@@ -846,8 +846,7 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, uint64_t seed, float out3[3]) {
             const sg_acktr_config& kc = kf->cfg;
             const double sd = (double)kc.stat_decay;
             hipLaunchKernelGGL(k_kfac_fold, dim3((unsigned)((kf->fac_total + 255) / 256)), dim3(256), 0, ctx->stream, kf->d_m,
-                               kf->d_acc, kf->fac_total, kf->g_start, pa.inv_B, (float)TN, kf->d_ks, (float)(sd / (1.0 - sd)),
-                               (float)(1.0 - sd));
+                               kf->d_acc, kf->fac_total, kf->g_start, pa.inv_B, (float)TN, kf->d_ks, kc.stat_decay, (float)(1.0 - sd));
             hipLaunchKernelGGL(k_kfac_eig, dim3(SG_KFAC_NF), dim3(512), lds_eig, ctx->stream, ea);
             for (int st = 0; st < 4; ++st)
                 hipLaunchKernelGGL(k_kfac_gemm, dim3((unsigned)kf->max_tiles, SG_KFAC_MODULES), dim3(256), 0, ctx->stream,

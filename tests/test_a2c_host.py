@@ -34,23 +34,26 @@ def _trunk_bwd(g, sl, p, x, h1, h2, dout, wkey, w1, b1, w2, b2, bh):
     W = p[wkey]
     g[sl[wkey][0]] += (dout.T @ h2).reshape(-1)
     g[sl[bh][0]] += dout.sum(0)
-    dz2 = (dout @ W) * (1.0 - h2 * h2)
+    one = h2.dtype.type(1.0)
+    dz2 = (dout @ W) * (one - h2 * h2)
     g[sl[w2][0]] += (dz2.T @ h1).reshape(-1)
     g[sl[b2][0]] += dz2.sum(0)
-    dz1 = (dz2 @ p[w2]) * (1.0 - h1 * h1)
+    dz1 = (dz2 @ p[w2]) * (one - h1 * h1)
     g[sl[w1][0]] += (dz1.T @ x).reshape(-1)
     g[sl[b1][0]] += dz1.sum(0)
 
 
-def a2c_loss_grad(params, obs_rows, act_rows, ret_rows, dims, vcoef, ecoef):
-    """(value_loss, action_loss, dist_entropy), d loss / d params -- float64, all rows of the rollout at once."""
+def a2c_loss_grad(params, obs_rows, act_rows, ret_rows, dims, vcoef, ecoef, dtype=np.float64):
+    """(value_loss, action_loss, dist_entropy), d loss / d params -- all rows of the rollout at once, evaluated in `dtype`
+    (float64: the restatement; float32: the same arithmetic at the kernels' precision, for the conditioning of a case)."""
     O, A, H, Hc = dims
     sl, n = policy_slices(O, A, H, Hc)
-    flat = np.asarray(params, np.float64)
+    f = np.dtype(dtype).type
+    flat = np.asarray(params, dtype)
     p = {k: flat[s].reshape(shape) for k, (s, shape) in sl.items()}
-    x = np.asarray(obs_rows, np.float64)
-    act = np.asarray(act_rows, np.float64)
-    R = np.asarray(ret_rows, np.float64).reshape(-1)
+    x = np.asarray(obs_rows, dtype)
+    act = np.asarray(act_rows, dtype)
+    R = np.asarray(ret_rows, dtype).reshape(-1)
     B = x.shape[0]
     a1 = np.tanh(x @ p["aw1"].T + p["ab1"])
     a2 = np.tanh(a1 @ p["aw2"].T + p["ab2"])
@@ -59,18 +62,18 @@ def a2c_loss_grad(params, obs_rows, act_rows, ret_rows, dims, vcoef, ecoef):
     c2 = np.tanh(c1 @ p["cw2"].T + p["cb2"])
     v = (c2 @ p["vw"].T + p["vb"]).reshape(-1)
     ls = p["ls"]
-    var = np.exp(2.0 * ls)
+    var = np.exp(f(2.0) * ls)
     diff = act - mu
-    logp = (-(diff * diff) / (2.0 * var) - ls - HALF_LOG_2PI).sum(1)
-    ent = float(np.sum(0.5 + HALF_LOG_2PI + ls))
+    logp = (-(diff * diff) / (f(2.0) * var) - ls - f(HALF_LOG_2PI)).sum(1)
+    ent = float(np.sum(f(0.5) + f(HALF_LOG_2PI) + ls))
     adv = R - v
     value_loss = float(np.mean(adv * adv))
     action_loss = float(-np.mean(adv * logp))
-    g = np.zeros(n)
-    dv = vcoef * 2.0 * (v - R) / B                      # d(vcoef mean(adv^2)) / dv
-    dlogp = -adv / B                                    # adv detached
+    g = np.zeros(n, dtype)
+    dv = f(vcoef) * f(2.0) * (v - R) / f(B)             # d(vcoef mean(adv^2)) / dv
+    dlogp = -adv / f(B)                                 # adv detached
     dmu = dlogp[:, None] * diff / var
-    g[sl["ls"][0]] = (dlogp[:, None] * (diff * diff / var - 1.0)).sum(0) - ecoef
+    g[sl["ls"][0]] = (dlogp[:, None] * (diff * diff / var - f(1.0))).sum(0) - f(ecoef)
     _trunk_bwd(g, sl, p, x, a1, a2, dmu, "mw", "aw1", "ab1", "aw2", "ab2", "mb")
     _trunk_bwd(g, sl, p, x, c1, c2, dv[:, None], "vw", "cw1", "cb1", "cw2", "cb2", "vb")
     return (value_loss, action_loss, ent), g

@@ -14,7 +14,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from helpers import load  # noqa: E402
-from test_acktr_host import ACKTR_CASES, acktr_update_restated, dims_of, new_state, rel_l2  # noqa: E402
+import acktr_regimes as ar  # noqa: E402
+from test_acktr_host import ACKTR_CASES, acktr_update_restated, dims_of, new_state, rel_l2, restate_fixture  # noqa: E402
 from test_a2c_host import policy_slices  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -56,12 +57,31 @@ def _flat_factors(k):
     return (np.concatenate([m.reshape(-1) for m in k["m_aa"]]), np.concatenate([m.reshape(-1) for m in k["m_gg"]]))
 
 
+def _fixture_factors(m_aa, m_gg, dims):
+    """a fixture's packed m_aa / m_gg (13 modules) -> the 12 distinct factors"""
+    O, A, H, Hc = dims
+    aa, gg, ia, ig = [], [], 0, 0
+    for o, i in ((H, O), (H, 1), (H, H), (H, 1), (Hc, O), (Hc, 1), (Hc, Hc), (Hc, 1), (1, Hc), (1, 1), (A, H), (A, 1), (A, 1)):
+        aa.append(m_aa[ia:ia + i * i].reshape(i, i))
+        gg.append(m_gg[ig:ig + o * o].reshape(o, o))
+        ia, ig = ia + i * i, ig + o * o
+    return ar.distinct_factors(aa, gg)
+
+
 @pytest.mark.parametrize("name", ACKTR_CASES)
 def test_acktr_updates_match_the_reference_fixture(sg, name):
-    """Every update of the fixture: losses, the running factors, and Delta p against the reference's float64 and float32 runs."""
+    """Every update of the fixture: losses, the running factors, and Delta p against the reference's float64 and float32 runs.
+    Then the measures of tests/test_gpu_acktr_regimes.py against the fixture's float64 run (the restatement, which reproduces it
+    to 1e-10): each distinct factor relative to its own Frobenius norm, every module's block of the momentum buffer and of Delta p,
+    each within F x (the reference's own float32 run's distance) + FLOOR, and within DP_TOL wherever that float32 run is within
+    acktr_regimes.COND itself (its Delta p is not on dist.logstd, up to 3.6e-4: the step there is 1e-4 of the parameter, at
+    float32's resolution of it)."""
+    from test_gpu_acktr_regimes import F, FLOOR, _record, judge
+    rec, all_fails = {"case": f"fixture {name}: the float32 column is the reference's own float32 run", "updates": []}, []
     g = load(name)
     m = g["meta"]
     O, A, H, Hc = dims_of(m)
+    ref64 = restate_fixture(g)
     p = _policy(sg, O, A, H, Hc, g["it0_params0"])
     agent = _agent(sg, p)
     for j in range(m["iters"]):
@@ -84,6 +104,23 @@ def test_acktr_updates_match_the_reference_fixture(sg, name):
         e64 = rel_l2(dp, g[pre + "params1_f64"] - p0)
         e32 = rel_l2(dp, g[pre + "params1"] - p0)
         assert e64 <= DP_TOL and e32 <= DP_TOL, (j, e64, e32)
+        p1_64, _, st64 = ref64[j]
+        dims = (O, A, H, Hc)
+        f64 = [np.asarray(x) for x in st64["mA"] + st64["mG"]]
+        hip = {"factors": ar.factor_distances(ar.distinct_factors(k["m_aa"], k["m_gg"]), f64),
+               "nuv": ar.block_distances(k["momentum_buffer"], st64["buf"], dims), "dp": ar.block_distances(dp, p1_64 - p0, dims)}
+        o32 = {"factors": ar.factor_distances(_fixture_factors(g[pre + "m_aa"], g[pre + "m_gg"], dims), f64),
+               "nuv": ar.block_distances(g[pre + "momentum"], st64["buf"], dims),
+               "dp": ar.block_distances(g[pre + "params1"].astype(np.float64) - p0, p1_64 - p0, dims)}
+        fails = [f"{kind} {b}: HIP {x:.3e}, the reference's float32 run {o32[kind][b]:.3e}" for kind, d in hip.items() for b, x in d.items()
+                 if not (x <= F * o32[kind][b] + FLOOR[kind] and (x <= DP_TOL or o32[kind][b] > ar.COND))]
+        print(f"{name} update {j}: largest HIP distances", {kind: f"{max(d.values()):.2e}" for kind, d in hip.items()},
+              "float32 run", {kind: f"{max(d.values()):.2e}" for kind, d in o32.items()})
+        _, ratio, at = judge(name, hip, o32)
+        rec["updates"].append({"hip_vs_f64": hip, "float32_vs_f64": o32, "worst_ratio": ratio, "worst_ratio_at": at, "worst_hip": ar.worst(hip)})
+        all_fails += [(j, x) for x in fails]
+    _record("fixture_" + name, rec)
+    assert not all_fails, all_fails
     assert agent.optimizer.lr == 0.25
 
 
