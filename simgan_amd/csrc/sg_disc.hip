@@ -282,24 +282,35 @@ __global__ __launch_bounds__(256) void k_batch_stats(const float* rets, int N, d
 // Sequential Chan merge over t (float64 state) -> per-step scale = sqrt(var_t + 1e-7)
 // RunningMeanStd.update over the T batches in order (float64 Chan merge, running_mean_std.py:27-58): serial, so one
 // lane runs it -- from LDS, where the whole block first put the 2T batch statistics with parallel loads.
+// The 3T doubles of that staging are dynamic LDS, and no T-independent size holds them: HIP takes no opt-in for a larger
+// dynamic allocation on AMD devices (hipFuncAttributeMaxDynamicSharedMemorySize is ignored there), so a launch is bound by
+// the workgroup limit of the device, and a rollout long enough passes any such limit.  Beyond SG_RMS_SCAN_LDS_BYTES (the
+// 64 KiB every device offers: T >= 2731) the launcher asks for no LDS and passes staged = 0: the serial lane then reads the
+// statistics from global memory and writes the scales straight to scale[] -- the same arithmetic in the same order.
+constexpr size_t SG_RMS_SCAN_LDS_BYTES = 64 * 1024;
 __global__ __launch_bounds__(256) void k_rms_scan(const double* stats, int T, double n_global, double* rms /*[3] in/out*/,
-                                                  float* scale /*[T]*/) {
-    extern __shared__ __attribute__((aligned(16))) double sst[];   // [2T] statistics, then [T] scales
-    for (int i = threadIdx.x; i < 2 * T; i += blockDim.x) sst[i] = stats[i];
-    __syncthreads();
+                                                  float* scale /*[T]*/, int staged) {
+    extern __shared__ __attribute__((aligned(16))) double sst[];   // staged: [2T] statistics, then [T] scales
+    if (staged) {
+        for (int i = threadIdx.x; i < 2 * T; i += blockDim.x) sst[i] = stats[i];
+        __syncthreads();
+    }
     if (threadIdx.x == 0) {
+        const double* st = staged ? sst : stats;
         double mean = rms[0], var = rms[1], count = rms[2];
         for (int t = 0; t < T; ++t) {
-            const double bmean = (double)(float)(sst[t] / n_global);
-            const double bvar = (double)(float)(sst[T + t] / n_global);
+            const double bmean = (double)(float)(st[t] / n_global);
+            const double bvar = (double)(float)(st[T + t] / n_global);
             const double delta = bmean - mean, tot = count + n_global;
             const double new_mean = mean + delta * n_global / tot;
             const double M2 = var * count + bvar * n_global + delta * delta * count * n_global / tot;
             mean = new_mean; var = M2 / tot; count = tot;
-            sst[2 * T + t] = sqrt(var + 1e-7);
+            if (staged) sst[2 * T + t] = sqrt(var + 1e-7);
+            else scale[t] = (float)sqrt(var + 1e-7);
         }
         rms[0] = mean; rms[1] = var; rms[2] = count;
     }
+    if (!staged) return;
     __syncthreads();
     for (int t = threadIdx.x; t < T; t += blockDim.x) scale[t] = (float)sst[2 * T + t];
 }
@@ -1016,7 +1027,9 @@ static int relabel_core(sg_disc* d, sg_rollout* r, float gamma, float offset, co
     if (ctx->use_comm) SG_TRY(sg_comm_allreduce_f64(ctx, stats, T));            // per-step sums over all ranks
     hipLaunchKernelGGL(k_batch_stats, dim3(T), dim3(256), 0, ctx->stream, rets, N, n_global, stats, 1);
     if (ctx->use_comm) SG_TRY(sg_comm_allreduce_f64(ctx, stats + T, T));        // squares about the global mean
-    hipLaunchKernelGGL(k_rms_scan, dim3(1), dim3(256), sizeof(double) * 3 * T, ctx->stream, stats, T, n_global, rms, scale);
+    const size_t rms_lds = sizeof(double) * 3 * (size_t)T;
+    const int rms_staged = rms_lds <= SG_RMS_SCAN_LDS_BYTES ? 1 : 0;
+    hipLaunchKernelGGL(k_rms_scan, dim3(1), dim3(256), rms_staged ? rms_lds : 0, ctx->stream, stats, T, n_global, rms, scale, rms_staged);
     hipLaunchKernelGGL(k_normalize_rewards, dim3((unsigned)((TN + 255) / 256)), dim3(256), 0, ctx->stream, rewards, scale, T, N);
     SG_CHECK(hipGetLastError());
     if (rms_host) SG_TRY(sg_ctx_fetch_f64(ctx, rms, rms_host, 3));

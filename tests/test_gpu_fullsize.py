@@ -67,6 +67,34 @@ def test_gae_full_size_vs_oracle(world):
                                  ro.bad_masks.numpy()[..., 0], nv, 1, 0.99, 0.95, 1)
     assert_close(ro.returns.numpy()[:T, :, 0], ret[:T], rtol=1e-5, what="GAE returns, 65,536 rows")
     assert_close(ro.value_preds.numpy()[T, :, 0], nv, rtol=0, atol=0, what="value_preds[T] = next_value")
+    # per environment column against float64, in the distance and under both bounds of tests/test_gpu_rollout_regimes.py
+    import rollout_regimes as rr
+    from oracle import oracle64 as o64
+    from test_gpu_rollout_regimes import F as FAC, FLOOR
+
+    def columns(got, args, what):
+        r64 = np.asarray(o64.compute_returns(*args)[0], np.float64)[:T]
+        r32 = np.asarray(orc.compute_returns(*args)[0], np.float64)[:T]
+        hip, lim = rr.column_distances(got, r64), FAC * rr.column_distances(r32, r64) + FLOOR["returns"]
+        bad = ~((hip <= 1e-4) & (hip <= lim))
+        assert not bad.any(), f"{what}: {int(bad.sum())} of {N} columns outside; worst HIP distance {hip.max():.3e}, its limit {lim[int(np.argmax(hip))]:.3e}"
+
+    rewards, vp, masks = ro.rewards.numpy()[..., 0], ro.value_preds.numpy()[..., 0], ro.masks.numpy()[..., 0]
+    columns(ro.returns.numpy()[:T, :, 0], (rewards, vp, masks, ro.bad_masks.numpy()[..., 0], nv, 1, 0.99, 0.95, 1), "GAE returns")
+    # the synthetic rollout's bad_masks are all 1: once more on a copy with 20 % zeros (slot T included), so that the full shape
+    # runs the proper-time-limits branch
+    sg = world["sg"]
+    bad_masks = (np.random.default_rng(17).random((T + 1, N)) > 0.2).astype(np.float32)
+    assert (bad_masks[T] == 0).any() and (ro.bad_masks.numpy() == 1).all()
+    ro2 = sg.RolloutStorage(T, N, (O,), Box((A,)), 1, F)
+    for name, a in (("rewards", rewards), ("value_preds", vp), ("masks", masks), ("bad_masks", bad_masks)):
+        t = getattr(ro2, name)
+        t.copy_(t.new_tensor(np.ascontiguousarray(a)[..., None]))
+    ro2.compute_returns(nv, True, 0.99, 0.95, True)
+    args = (rewards, vp, masks, bad_masks, nv, 1, 0.99, 0.95, 1)
+    assert_close(ro2.returns.numpy()[:T, :, 0], orc.compute_returns(*args)[0][:T], what="GAE returns with bad_masks zeros, 65,536 rows")
+    columns(ro2.returns.numpy()[:T, :, 0], args, "GAE returns with bad_masks zeros")
+    assert np.abs(ro2.returns.numpy()[:T, :, 0] - ro.returns.numpy()[:T, :, 0]).max() > 0.1      # the branch was taken
 
 
 def test_disc_epoch_prefix_full_size_vs_oracle(world):

@@ -112,6 +112,15 @@ def test_compute_returns_golden(sg, use_gae, proper):
     upto = T if use_gae else T + 1
     assert_close(ro.returns.numpy()[:upto], g[f"returns_gae{use_gae}_proper{proper}"][:upto], rtol=1e-5, what="returns")
     assert_close(ro.value_preds.numpy(), g[f"value_preds_gae{use_gae}_proper{proper}"], what="value_preds")
+    # per environment column against float64, in the distance and under both bounds of tests/test_gpu_rollout_regimes.py
+    import rollout_regimes as rr
+    from test_gpu_rollout_regimes import F, FLOOR
+    args = (g["rewards"][..., 0], g["value_preds"][..., 0], g["masks"][..., 0], g["bad_masks"][..., 0], g["next_value"][:, 0], use_gae, 0.99, 0.95, proper)
+    from oracle import oracle as o32, oracle64 as o64
+    r64, r32 = np.asarray(o64.compute_returns(*args)[0], np.float64), np.asarray(o32.compute_returns(*args)[0], np.float64)
+    hip = rr.column_distances(ro.returns.numpy()[:upto, :, 0], r64[:upto])
+    lim = F * rr.column_distances(r32[:upto], r64[:upto]) + FLOOR["returns"]
+    assert (hip <= 1e-4).all() and (hip <= lim).all(), f"column distances {hip} against limits {lim}"
 
 
 # -------------------------------------------------------------------------- PPO
