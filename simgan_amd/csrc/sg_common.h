@@ -2,8 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 
 #include <string>
+#include <type_traits>
 #include <atomic>
 #include <vector>
 #include <mutex>
@@ -63,6 +66,29 @@ void sg_set_error(const char* fmt, ...);
         int _r = (expr);        \
         if (_r != 0) return _r; \
     } while (0)
+
+// The one way a learner object grows a device buffer: nothing while *cap >= need; otherwise the stream is drained (queued work
+// may still use the old block), the block released and a new one of `need` elements allocated.  Pointer and capacity are
+// cleared before the allocation, so a failed hipMalloc leaves an empty buffer in the object, never a released pointer with a
+// capacity beside it.  *grew (optional) is set when the buffer was reallocated: its contents and its address are new.
+template <typename T, typename C>
+static inline int ensure_cap(hipStream_t stream, T** ptr, C* cap, typename std::common_type<C>::type need, bool* grew = nullptr) {
+    if (*cap >= need) return 0;
+    SG_CHECK(hipStreamSynchronize(stream));
+    if (*ptr) SG_CHECK(sg_dev_free(*ptr));
+    *ptr = nullptr;
+    *cap = 0;
+    SG_CHECK(sg_dev_malloc((void**)ptr, sizeof(T) * (size_t)need));
+    *cap = need;
+    if (grew) *grew = true;
+    return 0;
+}
+
+// getenv(name) is "0": the switch that turns an optional path off
+static inline bool sg_env_is_off(const char* name) {
+    const char* e = getenv(name);
+    return e && !strcmp(e, "0");
+}
 
 // ----------------------------------------------------------------------------- padded layouts
 // Device parameter vectors are stored "tile padded": a weight [n_out, n_in] occupies
@@ -248,13 +274,28 @@ struct sg_rollout {
     uint64_t feat_version = sg_next_feat_version();
 };
 
+// A captured launch sequence and what it was captured for (sg_graph_run, below)
+#define SG_GRAPH_KEY_WORDS 18
+struct SgGraphCache {
+    hipGraphExec_t exec = nullptr;
+    bool refused = false;                        // a capture failed once: the object stays on direct launches
+    uint64_t key[SG_GRAPH_KEY_WORDS] = {0};      // addresses, geometry and coefficients baked into the captured launches
+};
+
+// The scratch layout an sg_ppo's buffers were last cleared for: padding columns / rows that the kernels never write must
+// read as zero, which holds for as long as the layout is the same.  Compared whole.  SG_LAYOUT_INVALID: clear before the next
+// update whatever its layout (after a reallocation, after sg_ppo_set_adam).
+enum { SG_LAYOUT_INVALID = 0, SG_LAYOUT_PPO, SG_LAYOUT_A2C, SG_LAYOUT_GRU };
+struct SgScratchLayout {
+    int64_t mode = SG_LAYOUT_INVALID;
+    int64_t dims[8] = {0};
+};
+
 #define SG_H0_SLOTS 8
 struct sg_ppo {
     int64_t opt_t = 0;           // completed Adam steps (mirrors SgOptState::t0 on the device)
-    uint64_t scratch_key = 0;    // layout the scratch buffers were last cleared for
-    hipGraphExec_t steps_graph = nullptr;   // the update's optimizer steps, captured once and replayed
-    bool graph_refused = false;             // a capture with collectives failed once: stay on direct launches
-    uint64_t steps_graph_key[18] = {0};
+    SgScratchLayout cleared;     // layout the scratch buffers were last cleared for
+    SgGraphCache steps_graph;    // the update's optimizer steps, captured once and replayed
     sg_ctx* ctx;
     sg_policy* policy;
     sg_ppo_config cfg;
@@ -288,7 +329,6 @@ struct sg_ppo {
     uint64_t h0_calls = 0;
     float* d_gru = nullptr;        // epoch copy of obs / masks / h0, GI, saved gates, gate gradients, dX, weight-gradient partials
     size_t gru_cap = 0;
-    int64_t gru_layout[8] = {0};   // the scratch layout the buffers were last cleared for
     // A2C (sg_a2c_create): one RMSprop step over the whole rollout per update; d_v holds square_avg, opt_t counts the steps
     bool a2c = false;
     float alpha = 0.f;
@@ -318,9 +358,7 @@ struct sg_disc {
     uint64_t gather_version = 0;
     int64_t n_gathers = 0;               // all-gathers issued so far (test hook)
     int64_t opt_t = 0;             // completed Adam steps (mirrors SgOptState::t0 on the device)
-    hipGraphExec_t epoch_graph = nullptr;   // one epoch of update steps, captured once and replayed
-    bool graph_refused = false;             // a capture with collectives failed once: stay on direct launches
-    uint64_t epoch_graph_key[12] = {0};
+    SgGraphCache epoch_graph;      // one epoch of update steps, captured once and replayed
     float* d_wT = nullptr;         // weight images W1 | W2 | W2^T | W1^T of k_disc_chain4, maintained by k_disc_wgrad
     float *d_erows = nullptr, *d_prows = nullptr;   // the epoch's expert / policy rows in consumption order
     int64_t erows_cap = 0, prows_cap = 0;
@@ -400,6 +438,27 @@ static inline int sg_try_capture(sg_ctx* ctx, hipGraphExec_t* exec, F&& enqueue)
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) { *exec = nullptr; return refuse("hipGraphInstantiate", e, 0); }
     return 0;
+}
+
+// One update's launch sequence through the object's graph cache.  allowed (the caller's own condition: environment switches,
+// communicator, profiling ...) and no earlier refusal: the sequence is captured again when `key` differs from the cached one,
+// then replayed; a refused capture is remembered and this and every later call enqueue the launches directly, as a call
+// with !allowed does (the cached exec is kept for the next allowed one).
+template <typename F>
+static inline int sg_graph_run(sg_ctx* ctx, SgGraphCache* c, bool allowed, const uint64_t (&key)[SG_GRAPH_KEY_WORDS], F&& enqueue) {
+    if (allowed && !c->refused) {
+        if (!c->exec || memcmp(key, c->key, sizeof c->key) != 0) {
+            if (c->exec) { SG_CHECK(hipGraphExecDestroy(c->exec)); c->exec = nullptr; }
+            if (sg_try_capture(ctx, &c->exec, enqueue) != 0) c->refused = true;   // reported once on stderr
+            else memcpy(c->key, key, sizeof c->key);
+        }
+        if (!c->refused) { SG_CHECK(hipGraphLaunch(c->exec, ctx->stream)); return 0; }
+    }
+    return enqueue();
+}
+static inline void sg_graph_release(SgGraphCache* c) {   // destroy calls: errors deliberately ignored
+    if (c->exec) (void)hipGraphExecDestroy(c->exec);
+    c->exec = nullptr;
 }
 
 // collectives (sg_comm.cpp): RCCL, or the one-host loopback transport

@@ -417,7 +417,7 @@ extern "C" int sg_disc_destroy(sg_disc* d) {
     if (d->d_pperm) (void)sg_dev_free(d->d_pperm);
     if (d->d_loss_acc) (void)sg_dev_free(d->d_loss_acc);
     if (d->d_scal) (void)sg_dev_free(d->d_scal);
-    if (d->epoch_graph) (void)hipGraphExecDestroy(d->epoch_graph);
+    sg_graph_release(&d->epoch_graph);
     delete d;
     return 0;
 }
@@ -481,22 +481,12 @@ extern "C" int sg_disc_set_adam(sg_disc* d, const float* m, const float* v, int6
 
 extern "C" int sg_disc_set_expert(sg_disc* d, const float* expert, int64_t n_rows) {
     SG_REQUIRE(d && expert && n_rows > 0, "sg_disc_set_expert: bad argument");
-    SG_CHECK(hipStreamSynchronize(d->ctx->stream));
-    if (d->d_expert) SG_CHECK(sg_dev_free(d->d_expert));
     const size_t bytes = sizeof(float) * (size_t)n_rows * d->desc.F;
-    SG_CHECK(sg_dev_malloc((void**)&d->d_expert, bytes));
+    size_t cap = 0;   // (none kept: a new block of exactly this size on every call)
+    d->n_expert = 0;
+    SG_TRY(ensure_cap(d->ctx->stream, &d->d_expert, &cap, bytes / sizeof(float)));
     SG_COPY_SYNC(d->ctx, d->d_expert, expert, bytes, hipMemcpyHostToDevice);
     d->n_expert = n_rows;
-    return 0;
-}
-
-template <typename T>
-static int ensure_cap(T** ptr, int64_t* cap, int64_t need, hipStream_t stream) {
-    if (*cap >= need) return 0;
-    SG_CHECK(hipStreamSynchronize(stream));
-    if (*ptr) SG_CHECK(sg_dev_free(*ptr));
-    SG_CHECK(sg_dev_malloc((void**)ptr, sizeof(T) * (size_t)need));
-    *cap = need;
     return 0;
 }
 
@@ -570,12 +560,11 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
         // instead of five.  "Same" = the same device rows at the same obs_feat version of the rollout (every entry point that
         // writes obs_feat bumps it); every rank runs the same call sequence, so every rank decides alike.  Rows the caller
         // assembled (sg_disc_update_rows) carry no version and are gathered every time.  SG_DISC_GATHER_CACHE=0: always gather.
-        const char* cenv = getenv("SG_DISC_GATHER_CACHE");
         const bool reuse = src_version && d->gather_version == src_version && d->gather_src == rows_local && d->gather_rows == TN_loc &&
-                           d->feat_all_cap >= TN * rowF && !(cenv && !strcmp(cenv, "0"));
+                           d->feat_all_cap >= TN * rowF && !sg_env_is_off("SG_DISC_GATHER_CACHE");
         if (!reuse) {
             d->gather_rows = 0;
-            SG_TRY(ensure_cap(&d->d_feat_all, &d->feat_all_cap, TN * rowF, ctx->stream));
+            SG_TRY(ensure_cap(ctx->stream, &d->d_feat_all, &d->feat_all_cap, TN * rowF));
             SG_TRY(sg_comm_allgather_f32(ctx, next_feat, d->d_feat_all, TN_loc * rowF));
             d->gather_src = rows_local; d->gather_rows = TN_loc; d->gather_version = src_version;
         }
@@ -613,11 +602,11 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
     }
     const int64_t rows_total = step_off[n_d];
 
-    SG_TRY(ensure_cap(&d->d_eperm, &d->eperm_cap, d->n_expert, ctx->stream));
-    SG_TRY(ensure_cap(&d->d_pperm, &d->pperm_cap, TN, ctx->stream));
-    SG_TRY(ensure_cap(&d->d_alpha, &d->alpha_cap, (int64_t)n_d * batch_size, ctx->stream));
-    SG_TRY(ensure_cap(&d->d_erows, &d->erows_cap, (rows_total + B_loc) * rowF, ctx->stream));   // + one step: the last step's
-    SG_TRY(ensure_cap(&d->d_prows, &d->prows_cap, (rows_total + B_loc) * rowF, ctx->stream));   // "next" pointers stay in range
+    SG_TRY(ensure_cap(ctx->stream, &d->d_eperm, &d->eperm_cap, d->n_expert));
+    SG_TRY(ensure_cap(ctx->stream, &d->d_pperm, &d->pperm_cap, TN));
+    SG_TRY(ensure_cap(ctx->stream, &d->d_alpha, &d->alpha_cap, (int64_t)n_d * batch_size));
+    SG_TRY(ensure_cap(ctx->stream, &d->d_erows, &d->erows_cap, (rows_total + B_loc) * rowF));   // + one step: the last step's
+    SG_TRY(ensure_cap(ctx->stream, &d->d_prows, &d->prows_cap, (rows_total + B_loc) * rowF));   // "next" pointers stay in range
     d->rng_calls += 1;
     d->last_draws[0] = d->n_expert; d->last_draws[1] = TN; d->last_draws[2] = (int64_t)n_d * batch_size;
     if (owned) {
@@ -658,9 +647,9 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
     // (two sets of partials: k_disc_step4 double-buffers them by step parity like the stacks; the two-launch forms use the first)
     const size_t ops_f = disc_ops_floats(dd, G), part_f = (size_t)12 * G * 4 * dd.Hp, grad_f = (size_t)dd.total + 8;
     if (d->n_slabs < G) {
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (d->d_slabs) SG_CHECK(sg_dev_free(d->d_slabs));
-        SG_CHECK(sg_dev_malloc((void**)&d->d_slabs, sizeof(float) * (2 * ops_f + part_f + grad_f)));
+        size_t cap = 0;   // (the capacity is kept in row groups: n_slabs)
+        d->n_slabs = 0;
+        SG_TRY(ensure_cap(ctx->stream, &d->d_slabs, &cap, 2 * ops_f + part_f + grad_f));
         d->n_slabs = G;
         // ld-padding entries of the flat gradient are never written by k_disc_wgrad: they must read as zero
         SG_CHECK(hipMemsetAsync(d->d_slabs, 0, sizeof(float) * (2 * ops_f + part_f + grad_f), ctx->stream));
@@ -687,8 +676,7 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
     const int nblk = (dd.total + 255) / 256;
     const int n_vec = (3 * dd.Hp + 4 + 63) / 64;
     const int th_ = dd.Hp / 16, tf_ = dd.Fp / 16;
-    const char* xenv = getenv("SG_WGRAD_XCD");
-    wa.xcd_map = (th_ <= 7 && n_vec <= (8 - th_) * (th_ + tf_) && !(xenv && !strcmp(xenv, "0"))) ? 1 : 0;
+    wa.xcd_map = (th_ <= 7 && n_vec <= (8 - th_) * (th_ + tf_) && !sg_env_is_off("SG_WGRAD_XCD")) ? 1 : 0;
     // blocks that copy the next step's rows: 2G beside the 4-row chain blocks (they have the time), else 2G in k_disc_wgrad,
     // which then only keeps one spare block when no tile slot is free for the lane that evaluates the next Adam scalars
     const int n_gather_wgrad = !thin ? 2 * G : (wa.xcd_map && (8 - th_) * (th_ + tf_) > n_vec) ? 0 : 1;
@@ -766,28 +754,15 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
     };
     // Sharded mode has one RCCL all-reduce per step inside the sequence: captured with it (see sg_ppo_update), unless
     // SG_DISC_GRAPH_COMM=0 or the RCCL build refuses the capture.
-    const char* genv = getenv("SG_DISC_GRAPH");
-    const char* gcenv = getenv("SG_DISC_GRAPH_COMM");
-    const bool comm_ok = !d->graph_refused && (!sharded || (sg_comm_graph_ok(ctx) && !(gcenv && !strcmp(gcenv, "0"))));
-    bool use_graph = comm_ok && !owned && !ctx->profile && !d->d_dbg && !(genv && !strcmp(genv, "0"));
-    if (use_graph) {
-        const uint64_t key[12] = {(uint64_t)(uintptr_t)d->d_slabs, (uint64_t)(uintptr_t)d->d_eperm, (uint64_t)(uintptr_t)d->d_pperm,
-                                  (uint64_t)(uintptr_t)d->d_alpha, (uint64_t)(uintptr_t)next_feat, (uint64_t)(uintptr_t)d->d_expert,
-                                  (uint64_t)n_d, (uint64_t)B_loc, (uint64_t)batch_size,
-                                  (uint64_t)thin | (sharded ? 2u : 0u) | (gw ? 4u : 0u) | (fused ? 8u : 0u) | (sg_comm_peer_on(ctx) ? 16u : 0u) | ((uint64_t)((replicated && world > 1) ? n_cols : 0) << 8), (uint64_t)ops_f | ((uint64_t)sg_comm_peer_generation(ctx) << 40),
-                                  (uint64_t)(uintptr_t)d->d_erows ^ ((uint64_t)(uintptr_t)d->d_prows << 1)};
-        if (!d->epoch_graph || memcmp(key, d->epoch_graph_key, sizeof key) != 0) {
-            if (d->epoch_graph) { SG_CHECK(hipGraphExecDestroy(d->epoch_graph)); d->epoch_graph = nullptr; }
-            if (sg_try_capture(ctx, &d->epoch_graph, enqueue_epoch) != 0) {
-                d->graph_refused = true;   // reported once on stderr; this object launches kernel by kernel from now on
-                use_graph = false;
-            } else {
-                memcpy(d->epoch_graph_key, key, sizeof key);
-            }
-        }
-        if (use_graph) SG_CHECK(hipGraphLaunch(d->epoch_graph, ctx->stream));
-    }
-    if (!use_graph) SG_TRY(enqueue_epoch());
+    const bool comm_ok = !sharded || (sg_comm_graph_ok(ctx) && !sg_env_is_off("SG_DISC_GRAPH_COMM"));
+    const bool use_graph = comm_ok && !owned && !ctx->profile && !d->d_dbg && !sg_env_is_off("SG_DISC_GRAPH");
+    const uint64_t key[SG_GRAPH_KEY_WORDS] = {   // (12 words in use, the rest zero)
+            (uint64_t)(uintptr_t)d->d_slabs, (uint64_t)(uintptr_t)d->d_eperm, (uint64_t)(uintptr_t)d->d_pperm,
+            (uint64_t)(uintptr_t)d->d_alpha, (uint64_t)(uintptr_t)next_feat, (uint64_t)(uintptr_t)d->d_expert,
+            (uint64_t)n_d, (uint64_t)B_loc, (uint64_t)batch_size,
+            (uint64_t)thin | (sharded ? 2u : 0u) | (gw ? 4u : 0u) | (fused ? 8u : 0u) | (sg_comm_peer_on(ctx) ? 16u : 0u) | ((uint64_t)((replicated && world > 1) ? n_cols : 0) << 8), (uint64_t)ops_f | ((uint64_t)sg_comm_peer_generation(ctx) << 40),
+            (uint64_t)(uintptr_t)d->d_erows ^ ((uint64_t)(uintptr_t)d->d_prows << 1)};
+    SG_TRY(sg_graph_run(ctx, &d->epoch_graph, use_graph, key, enqueue_epoch));
     SG_CHECK(hipGetLastError());
     const auto t_enq1 = std::chrono::steady_clock::now();
     d->opt_t += n_d;
@@ -836,7 +811,7 @@ extern "C" int sg_disc_update_rows(sg_disc* d, const float* policy_rows, int64_t
     SG_REQUIRE(d && policy_rows && n_rows > 0, "sg_disc_update_rows: bad argument");
     sg_ctx* ctx = d->ctx;
     SG_CHECK(hipSetDevice(ctx->device));
-    SG_TRY(ensure_cap(&d->d_rows, &d->rows_cap, n_rows * d->desc.F, ctx->stream));
+    SG_TRY(ensure_cap(ctx->stream, &d->d_rows, &d->rows_cap, n_rows * d->desc.F));
     SG_CHECK(hipMemcpyAsync(d->d_rows, policy_rows, sizeof(float) * (size_t)n_rows * d->desc.F, hipMemcpyHostToDevice, ctx->stream));
     return disc_update_core(d, d->d_rows, n_rows, n_cols, batch_size, expert_perm, n_expert_perm, policy_perm, n_policy_perm, alpha,
                             n_alpha, seed, out3, n_steps);
@@ -861,9 +836,8 @@ static int ensure_returns(sg_disc* d, int n) {
     if (d->d_returns && d->returns_n == n) return 0;
     SG_REQUIRE(d->returns_none || d->returns_n == n,
                "Discriminator.returns holds %d rows but %d were passed (the reference would broadcast-fail)", d->returns_n, n);
-    SG_CHECK(hipStreamSynchronize(d->ctx->stream));
-    if (d->d_returns) SG_CHECK(sg_dev_free(d->d_returns));
-    SG_CHECK(sg_dev_malloc((void**)&d->d_returns, sizeof(float) * n));
+    int cap = 0;   // (none kept: exactly n rows, returns_n is the tensor's length)
+    SG_TRY(ensure_cap(d->ctx->stream, &d->d_returns, &cap, n));
     SG_CHECK(hipMemsetAsync(d->d_returns, 0, sizeof(float) * n, d->ctx->stream));
     d->returns_n = n;
     return 0;

@@ -422,7 +422,7 @@ __global__ void k_kfac_tick(KfacDevState* ks, const float* grad, int total, floa
     }
 }
 
-// ------------------------------------------------------------------------- host-side state (sg_ppo.hip)
+// ------------------------------------------------------------------------- host-side state (set up and read by sg_kfac_host.hpp)
 // module m of KFACOptimizer.modules (a2c/algo/kfac.py:144-150 after split_bias: state_dict order): its gradient block in the
 // padded vector and the distinct factors it reads (a_f < 0: an AddBias, A = [[1]])
 struct KfacModule {

@@ -25,6 +25,12 @@
 //   k_a2c_gather
 //   per chunk:  k_ppo_fwd -> k_a2c_bwd -> k_a2c_reduce -> k_acktr_fisher -> k_kfac_stats (adds to the factor sums)
 //   then        k_kfac_fold -> k_kfac_eig (exits unless steps % Tf == 0) -> k_kfac_gemm x4 -> k_kfac_step -> k_kfac_tick
+// (its host-side state: sg_kfac_host.hpp)
+//
+// The file reads: launch helpers and kernel-instance tables, API, A2C / ACKTR, PPO through time, PPO, results ring.  The three
+// updates stay three functions; what they share lies underneath them: ensure_cap (growing a scratch buffer), sg_graph_run (the
+// capture / replay cache; each update builds its own key and its own "may I use a graph"), both in sg_common.h, and here
+// ppo_bwd_tiles_lds, ppo_row_tiles, ppo_launch, enqueue_adv_stats and clear_for_layout.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -35,7 +41,7 @@
 #include "sg_common.h"
 #include "sg_rng.hpp"
 #include "sg_ppo_kernels.hpp"
-#include "sg_kfac.hpp"
+#include "sg_kfac_host.hpp"
 #include "sg_gru_kernels.hpp"
 
 __global__ void k_fill_perm(int64_t* perm, int64_t n, int half_bits, uint64_t key) {
@@ -72,36 +78,42 @@ static size_t ppo_fwd_lds(const SgPolicyDesc& d, int MT, bool gw) {
     const int R = 16 * MT;
     return sizeof(float) * ((gw ? 0 : (size_t)max_trunk_floats(d)) + R * d.ldO + 2 * R * d.ldH);
 }
+// LDS bytes of every kernel built on sg_ppo_bwd_body (k_ppo_bwd, k_ppo_bwd_sym, k_a2c_bwd, k_ppo_pair, k_ppo_fwd_critic).  It
+// MIRRORS the carve-up at the head of sg_ppo_bwd_body (sg_ppo_kernels.hpp): Wimg | X H1 H2 | O0 O1 [OM] | ACT | SC[4][R]
+// ROWL[2][R] VALID[R] | [MA] -- change the two together.
+//   w_floats  the weight image in front of the tiles: 0 (global-weight instances), the whole trunk (max_trunk_floats: the
+//             fused forms recompute the forward) or the trunk from w2 on (max_bwd_floats: the two-launch backward)
+//   n_out     [R][ldP] head-output tiles: 2, or 3 with the other actor column's (k_ppo_bwd_sym)
+//   ma        the [A][A] action mirror M_a behind everything (k_ppo_bwd_sym)
+static size_t ppo_bwd_tiles_lds(const SgPolicyDesc& d, int MT, size_t w_floats, int n_out, bool ma) {
+    const int R = 16 * MT;
+    return sizeof(float) * (w_floats + R * d.ldO + 2 * R * d.ldH + (size_t)n_out * R * stack_ldP(d) + ((R * d.A + 3) & ~3) + 7 * R +
+                            (ma ? (d.A * d.A + 3) & ~3 : 0));
+}
 static bool ppo_fused(const SgPolicyDesc& d, int MT) {
-    const char* e = getenv("SG_PPO_FUSED");
-    return d.kind == SG_POLICY_MLP && MT <= 2 && !(e && !strcmp(e, "0"));
-}
-static size_t ppo_bwd_lds(const SgPolicyDesc& d, int MT, bool gw) {
-    const int R = 16 * MT;
-    return sizeof(float) * ((gw ? 0 : (size_t)(ppo_fused(d, MT) ? max_trunk_floats(d) : max_bwd_floats(d))) + R * d.ldO + 2 * R * d.ldH + 2 * R * stack_ldP(d) +
-                            ((R * d.A + 3) & ~3) + 7 * R);
-}
-// k_ppo_bwd_sym: the unfused backward's tiles + the other actor column's head tile + M_a
-static size_t ppo_bwd_sym_lds(const SgPolicyDesc& d, int MT, bool gw) {
-    const int R = 16 * MT;
-    return sizeof(float) * ((gw ? 0 : (size_t)max_bwd_floats(d)) + R * d.ldO + 2 * R * d.ldH + 3 * R * stack_ldP(d) +
-                            ((R * d.A + 3) & ~3) + 7 * R + ((d.A * d.A + 3) & ~3));
-}
-
-// k_a2c_bwd: the unfused backward's tiles (w2 on in LDS), whatever ppo_fused says
-static size_t a2c_bwd_lds(const SgPolicyDesc& d, int MT, bool gw) {
-    const int R = 16 * MT;
-    return sizeof(float) * ((gw ? 0 : (size_t)max_bwd_floats(d)) + R * d.ldO + 2 * R * d.ldH + 2 * R * stack_ldP(d) +
-                            ((R * d.A + 3) & ~3) + 7 * R);
+    return d.kind == SG_POLICY_MLP && MT <= 2 && !sg_env_is_off("SG_PPO_FUSED");
 }
 // rows of the rollout one A2C forward / backward / reduce pass covers: the slabs and row stacks are sized for this many rows
 // whatever T*N is (the north-star PPO minibatch: 65,536 rows / 16)
 #define SG_A2C_CHUNK_ROWS 4096
 
-// shape-specialised instances for the shipped configurations at the row-group
-// size the launch heuristic picks for them, plus run-time-shape fallbacks
-#define SG_PPO_SHAPES(X) X(1, 3, 4) X(2, 3, 4) /* north-star: obs 47, h64 */ X(2, 1, 7) /* HopperCombined: obs 14, h100 */ \
-                         X(2, 4, 7) /* LaikagoCombined: obs 64, h100 */ X(2, 7, 4) /* Laikago refinement: obs 111, h64 */
+// Row-group size of a step on `mb` rows and `ncols` grid columns, in 16-row tiles.  32-row groups as long as they still give
+// every CU a workgroup (half the gradient slabs for k_ppo_reduce to stream: -1.8 us per step at the north-star shape against
+// +0.6 us in k_ppo_bwd), or (slab_rule) when the 16-row slabs would exceed 24 MB; otherwise 16-row groups (more workgroups in
+// flight hide the phases' latencies).  SG_PPO_ROWS (tuning knob) overrides with 16, 32 or 64 rows as far as the mode has
+// instances for them: env_max_mt tiles, 0 = the mode does not read the knob.  Then at most cap_mt, then halved until fits(MT).
+template <typename Fits>
+static int ppo_row_tiles(const sg_ctx* ctx, const SgPolicyDesc& d, int mb, int ncols, bool slab_rule, int env_max_mt, int cap_mt, Fits&& fits) {
+    int MT = ((slab_rule && (size_t)((mb + 15) / 16) * (size_t)(d.total + 8) * sizeof(float) > ((size_t)24 << 20)) ||
+              ((mb + 31) / 32) * ncols >= ctx->num_cu) ? 2 : 1;
+    if (const char* e = env_max_mt ? getenv("SG_PPO_ROWS") : nullptr) {
+        const int v = atoi(e);
+        if ((v == 16 || v == 32 || v == 64) && v / 16 <= env_max_mt) MT = v / 16;
+    }
+    if (MT > cap_mt) MT = cap_mt;
+    while (MT > 1 && !fits(MT)) MT /= 2;
+    return MT;
+}
 
 // 8 waves once a workgroup has two row tiles to deal out (SG_PPO_WAVES=4: tuning knob, 4 waves always)
 static int ppo_block_threads(int MT) {
@@ -109,232 +121,66 @@ static int ppo_block_threads(int MT) {
     return (MT >= 2 && !(we && atoi(we) == 4)) ? 512 : 256;
 }
 
-// (the shape-specialised instances fold ONE hidden width into the code: a policy whose critic was rebuilt at another width
-// -- Policy.reset_critic, d.Hc != d.H -- takes the run-time-shape instances, kh = 0 matches none of them)
-static void launch_ppo_fwd(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 grid, size_t lds, const PpoArgs& pa, bool gw) {
-    const int ko = d.Op / 16, kh = d.Hc == d.H ? d.Hp / 16 : 0;
-    const dim3 block(ppo_block_threads(MT));
-    if (gw) {   // general-shape instances: run-time extents, weights through L2
-        if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd<2, 0, 0, true>), grid, block, lds, pa);
-        else SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd<1, 0, 0, true>), grid, block, lds, pa);
-        return;
-    }
-#define SG_CASE(mt, o, h) \
-    if (MT == mt && ko == o && kh == h) { SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd<mt, o, h>), grid, block, lds, pa); return; }
-    SG_PPO_SHAPES(SG_CASE)
-#undef SG_CASE
-    if (MT == 4) SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd<4, 0, 0>), grid, block, lds, pa);
-    else if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd<2, 0, 0>), grid, block, lds, pa);
-    else SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd<1, 0, 0>), grid, block, lds, pa);
-}
-static void launch_ppo_fwd_critic(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 grid, size_t lds, const PpoArgs& pa) {
-    const int ko = d.Op / 16, kh = d.Hc == d.H ? d.Hp / 16 : 0;
-    const dim3 block(ppo_block_threads(MT));
-    if (MT == 2 && ko == 4 && kh == 7) { SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_critic<2, 4, 7>), grid, block, lds, pa); return; }   // LaikagoCombined
-    if (MT == 2 && ko == 1 && kh == 7) { SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_critic<2, 1, 7>), grid, block, lds, pa); return; }   // HopperCombined
-    if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_critic<2, 0, 0>), grid, block, lds, pa);
-    else SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_critic<1, 0, 0>), grid, block, lds, pa);
-}
-// SplitPolicy, one launch per step (k_ppo_pair): grid = 3 G workgroups, trunk index fastest
-static void launch_ppo_pair(sg_ctx* ctx, int MT, const SgPolicyDesc& d, int G, size_t lds, const PpoArgs& pa) {
-    const int ko = d.Op / 16, kh = d.Hc == d.H ? d.Hp / 16 : 0;
-    const dim3 block(ppo_block_threads(MT)), grid(3 * G);
-    if (MT == 2 && ko == 1 && kh == 7) { SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_pair<2, 1, 7>), grid, block, lds, pa); return; }   // HopperCombined
-    if (MT == 2 && ko == 4 && kh == 7) { SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_pair<2, 4, 7>), grid, block, lds, pa); return; }   // LaikagoCombined at <= 2720-row minibatches
-    if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_pair<2, 0, 0>), grid, block, lds, pa);
-    else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_pair<1, 0, 0>), grid, block, lds, pa);
-}
-static void launch_ppo_bwd(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 grid, size_t lds, const PpoArgs& pa, bool fused, bool gw) {
-    const int ko = d.Op / 16, kh = d.Hc == d.H ? d.Hp / 16 : 0;
-    const dim3 block(ppo_block_threads(MT));
-    if (gw) {
-        if (fused && MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<2, 0, 0, true, true>), grid, block, lds, pa);
-        else if (fused) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<1, 0, 0, true, true>), grid, block, lds, pa);
-        else if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<2, 0, 0, false, true>), grid, block, lds, pa);
-        else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<1, 0, 0, false, true>), grid, block, lds, pa);
-        return;
-    }
-    if (fused) {   // Policy (independent actor / critic trunks): forward recomputed inside, no k_ppo_fwd launch
-        if (MT == 1 && ko == 3 && kh == 4) { SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<1, 3, 4, true>), grid, block, lds, pa); return; }
-        if (MT == 2 && ko == 3 && kh == 4) { SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<2, 3, 4, true>), grid, block, lds, pa); return; }
-        if (MT == 2 && ko == 7 && kh == 4) { SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<2, 7, 4, true>), grid, block, lds, pa); return; }   // Laikago refinement: obs 111, h64
-        if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<2, 0, 0, true>), grid, block, lds, pa);
-        else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<1, 0, 0, true>), grid, block, lds, pa);
-        return;
-    }
-#define SG_CASE(mt, o, h) \
-    if (MT == mt && ko == o && kh == h) { SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<mt, o, h>), grid, block, lds, pa); return; }
-    SG_PPO_SHAPES(SG_CASE)
-#undef SG_CASE
-    if (MT == 4) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<4, 0, 0>), grid, block, lds, pa);
-    else if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<2, 0, 0>), grid, block, lds, pa);
-    else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<1, 0, 0>), grid, block, lds, pa);
-}
+// ------------------------------------------------------------------------- kernel instances
+// Every family of row-group kernels exists in a few instances: shape-specialised ones X(MT, Op/16, Hp/16) for the shipped
+// configurations at the row-group size the launch heuristic picks for them, run-time-shape ones
+// X(MT, 0, 0), and global-weight ones (run-time shapes, weights through L2).  A family is its list of each; the lists are
+// what gets compiled.
+#define SG_PPO_SHAPES(X, K) X(K, 1, 3, 4) X(K, 2, 3, 4) /* north-star: obs 47, h64 */ X(K, 2, 1, 7) /* HopperCombined: obs 14, h100 */ \
+                            X(K, 2, 4, 7) /* LaikagoCombined: obs 64, h100 */ X(K, 2, 7, 4) /* Laikago refinement: obs 111, h64 */
+#define SG_SPLIT_SHAPES(X, K) X(K, 2, 4, 7) /* LaikagoCombined (k_ppo_pair: at <= 2720-row minibatches) */ X(K, 2, 1, 7) /* HopperCombined */
+#define SG_FUSED_SHAPES(X, K) X(K, 1, 3, 4) X(K, 2, 3, 4) X(K, 2, 7, 4)   // Policy: north-star, Laikago refinement
+#define SG_SYM_SHAPES(X, K) X(K, 2, 7, 4)                                 // the Laikago refinement
+#define SG_A2C_SHAPES(X, K) X(K, 2, 3, 4) X(K, 1, 3, 4)                   // north-star
+#define SG_NONE(X, K)
+#define SG_MT_421(X, K) X(K, 4, 0, 0) X(K, 2, 0, 0) X(K, 1, 0, 0)
+#define SG_MT_21(X, K) X(K, 2, 0, 0) X(K, 1, 0, 0)
 
-// Policy with the mirror-symmetry loss: grid (row groups, 3), the Laikago refinement shape specialised
-static void launch_ppo_fwd_sym(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 grid, size_t lds, const PpoArgs& pa, bool gw) {
-    const int ko = d.Op / 16, kh = d.Hc == d.H ? d.Hp / 16 : 0;
-    const dim3 block(ppo_block_threads(MT));
-    if (gw) {
-        if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_sym<2, 0, 0, true>), grid, block, lds, pa);
-        else SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_sym<1, 0, 0, true>), grid, block, lds, pa);
-    } else if (MT == 2 && ko == 7 && kh == 4) {
-        SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_sym<2, 7, 4>), grid, block, lds, pa);
-    } else if (MT == 2) {
-        SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_sym<2, 0, 0>), grid, block, lds, pa);
-    } else {
-        SG_LAUNCH(ctx, SG_PROF_PPO_FWD, (k_ppo_fwd_sym<1, 0, 0>), grid, block, lds, pa);
-    }
-}
-static void launch_ppo_bwd_sym(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 grid, size_t lds, const PpoArgs& pa, bool gw) {
-    const int ko = d.Op / 16, kh = d.Hc == d.H ? d.Hp / 16 : 0;
-    const dim3 block(ppo_block_threads(MT));
-    if (gw) {
-        if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd_sym<2, 0, 0, true>), grid, block, lds, pa);
-        else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd_sym<1, 0, 0, true>), grid, block, lds, pa);
-    } else if (MT == 2 && ko == 7 && kh == 4) {
-        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd_sym<2, 7, 4>), grid, block, lds, pa);
-    } else if (MT == 2) {
-        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd_sym<2, 0, 0>), grid, block, lds, pa);
-    } else {
-        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd_sym<1, 0, 0>), grid, block, lds, pa);
-    }
-}
+struct PpoInstance {
+    int mt, ko, kh;
+    bool gw;
+    void (*kernel)(PpoArgs);
+};
+#define SG_INST(K, mt, o, h) {mt, o, h, false, K(mt, o, h, false)},
+#define SG_INST_GW(K, mt, o, h) {mt, o, h, true, K(mt, o, h, true)},
+// SHAPES first: ppo_launch takes the first instance that matches
+#define SG_PPO_FAMILY(name, K, SHAPES, RUNTIME_MT, GW_MT) \
+    static const PpoInstance name[] = {SHAPES(SG_INST, K) RUNTIME_MT(SG_INST, K) GW_MT(SG_INST_GW, K)}
 
-// A2C's backward: the north-star shape (obs 47, h64) specialised, run-time shapes and the global-weight instances otherwise
-static void launch_a2c_bwd(sg_ctx* ctx, int MT, const SgPolicyDesc& d, dim3 grid, size_t lds, const PpoArgs& pa, bool gw) {
+#define SG_K_FWD(mt, o, h, gw) k_ppo_fwd<mt, o, h, gw>
+#define SG_K_FWD_CRITIC(mt, o, h, gw) k_ppo_fwd_critic<mt, o, h>
+#define SG_K_PAIR(mt, o, h, gw) k_ppo_pair<mt, o, h>
+#define SG_K_BWD(mt, o, h, gw) k_ppo_bwd<mt, o, h, false, gw>
+#define SG_K_BWD_FUSED(mt, o, h, gw) k_ppo_bwd<mt, o, h, true, gw>
+#define SG_K_BWD_FUSED_DX(mt, o, h, gw) k_ppo_bwd<mt, o, h, true, gw, true>
+#define SG_K_FWD_SYM(mt, o, h, gw) k_ppo_fwd_sym<mt, o, h, gw>
+#define SG_K_BWD_SYM(mt, o, h, gw) k_ppo_bwd_sym<mt, o, h, gw>
+#define SG_K_A2C_BWD(mt, o, h, gw) k_a2c_bwd<mt, o, h, gw>
+SG_PPO_FAMILY(ppo_fwd_family, SG_K_FWD, SG_PPO_SHAPES, SG_MT_421, SG_MT_21);
+SG_PPO_FAMILY(ppo_fwd_critic_family, SG_K_FWD_CRITIC, SG_SPLIT_SHAPES, SG_MT_21, SG_NONE);   // SplitPolicy, critic in the forward launch
+SG_PPO_FAMILY(ppo_pair_family, SG_K_PAIR, SG_SPLIT_SHAPES, SG_MT_21, SG_NONE);               // SplitPolicy, one launch per step
+SG_PPO_FAMILY(ppo_bwd_family, SG_K_BWD, SG_PPO_SHAPES, SG_MT_421, SG_MT_21);
+// Policy (independent actor / critic trunks): forward recomputed inside, no k_ppo_fwd launch
+SG_PPO_FAMILY(ppo_bwd_fused_family, SG_K_BWD_FUSED, SG_FUSED_SHAPES, SG_MT_21, SG_MT_21);
+SG_PPO_FAMILY(ppo_bwd_fused_dx_family, SG_K_BWD_FUSED_DX, SG_NONE, SG_MT_21, SG_MT_21);      // the recurrent policy's heads: + d loss / d h_t
+SG_PPO_FAMILY(ppo_fwd_sym_family, SG_K_FWD_SYM, SG_SYM_SHAPES, SG_MT_21, SG_MT_21);               // mirror-symmetry loss: grid (row groups, 3)
+SG_PPO_FAMILY(ppo_bwd_sym_family, SG_K_BWD_SYM, SG_SYM_SHAPES, SG_MT_21, SG_MT_21);
+SG_PPO_FAMILY(a2c_bwd_family, SG_K_A2C_BWD, SG_A2C_SHAPES, SG_MT_21, SG_MT_21);
+
+// Launches the family's instance for (MT, the policy's shape, gw): with gw a global-weight instance, else the one specialised
+// for the shape, else the run-time-shape one.  (The specialised instances fold ONE hidden width into the code: a policy whose
+// critic was rebuilt at another width -- Policy.reset_critic, d.Hc != d.H -- has kh = 0 here, which matches none of them.)
+// A row-group size the family has no instance for is an error: grid and LDS size were computed for MT, no other fits them.
+template <size_t NI>
+static int ppo_launch(sg_ctx* ctx, const PpoInstance (&family)[NI], const char* what, int prof, int MT, const SgPolicyDesc& d, dim3 grid,
+                      size_t lds, const PpoArgs& pa, bool gw) {
     const int ko = d.Op / 16, kh = d.Hc == d.H ? d.Hp / 16 : 0;
-    const dim3 block(ppo_block_threads(MT));
-    if (gw) {
-        if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<2, 0, 0, true>), grid, block, lds, pa);
-        else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<1, 0, 0, true>), grid, block, lds, pa);
-    } else if (MT == 2 && ko == 3 && kh == 4) {
-        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<2, 3, 4>), grid, block, lds, pa);
-    } else if (MT == 1 && ko == 3 && kh == 4) {
-        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<1, 3, 4>), grid, block, lds, pa);
-    } else if (MT == 2) {
-        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<2, 0, 0>), grid, block, lds, pa);
-    } else {
-        SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_a2c_bwd<1, 0, 0>), grid, block, lds, pa);
-    }
-}
-
-// ---------------------------------------------------------------------------------- ACKTR (K-FAC) state
-static void kfac_free(sg_ppo* a) {
-    SgKfac* k = a->kfac;
-    if (!k) return;
-    void* ptrs[] = {k->d_acc, k->d_m, k->d_Q, k->d_d, k->d_work, k->d_ks, k->d_vec, k->d_t0, k->d_t1, k->d_one, k->d_vpart,
-                    k->d_jobs, k->d_tiles, k->d_eps, k->d_fish};
-    for (void* q : ptrs) if (q) (void)sg_dev_free(q);
-    delete k;
-    a->kfac = nullptr;
-}
-
-static int kfac_setup(sg_ctx* ctx, SgKfac* k, const SgPolicyDesc& d, float* d_grad) {
-    const SgTrunk& ac = d.trunk[0];
-    const SgTrunk& cr = d.trunk[1];
-    const int O = d.O, A = d.A, H = ac.H, Hc = cr.H;
-    const int nf[SG_KFAC_NF] = {O, H, H, Hc, Hc, H, H, Hc, Hc, 1, A, A};
-    int fo = 0, vo = 0;
-    int64_t wo = 0;
-    k->lds_n = 0;
-    while (16 * (k->lds_n + 1) * (k->lds_n + 1) + 8192 <= ctx->lds_bytes) ++k->lds_n;
-    for (int f = 0; f < SG_KFAC_NF; ++f) {
-        if (f == SG_KFAC_NA) k->g_start = fo;
-        k->n[f] = nf[f]; k->off[f] = fo; k->voff[f] = vo; k->woff[f] = wo;
-        fo += nf[f] * nf[f]; vo += nf[f];
-        if (nf[f] > k->lds_n) wo += 2 * (int64_t)nf[f] * nf[f];
-        SG_REQUIRE(nf[f] <= 512, "sg_acktr_create: a %d-wide Kronecker factor is larger than the eigensolver's 512", nf[f]);
-    }
-    k->fac_total = fo; k->vec_total = vo; k->work_doubles = wo;
-    const KfacModule mods[SG_KFAC_MODULES] = {
-        {0, 5, ac.off + ac.w1, d.ldO, H, O, 0},     {-1, 5, ac.off + ac.b1, 1, H, 1, 0},
-        {1, 6, ac.off + ac.w2, ac.ldH, H, H, 0},    {-1, 6, ac.off + ac.b2, 1, H, 1, 0},
-        {0, 7, cr.off + cr.w1, d.ldO, Hc, O, 0},    {-1, 7, cr.off + cr.b1, 1, Hc, 1, 0},
-        {3, 8, cr.off + cr.w2, cr.ldH, Hc, Hc, 0},  {-1, 8, cr.off + cr.b2, 1, Hc, 1, 0},
-        {4, 9, cr.off + cr.wh, cr.ldH, 1, Hc, 0},   {-1, 9, cr.off + cr.bh, 1, 1, 1, 0},
-        {2, 10, ac.off + ac.wh, ac.ldH, A, H, 0},   {-1, 10, ac.off + ac.bh, 1, A, 1, 0},
-        {-1, 11, ac.off + ac.ex, 1, A, 1, 0}};
-    int to = 0;
-    k->max_tiles = 0;
-    for (int m = 0; m < SG_KFAC_MODULES; ++m) {
-        k->mod[m] = mods[m];
-        k->mod[m].toff = to;
-        to += mods[m].out * mods[m].in;
-        k->max_tiles = std::max(k->max_tiles, ((mods[m].out + 31) / 32) * ((mods[m].in + 31) / 32));
-    }
-    k->tmp_total = to;
-    SG_CHECK(sg_dev_malloc((void**)&k->d_acc, sizeof(float) * fo));
-    SG_CHECK(sg_dev_malloc((void**)&k->d_m, sizeof(float) * fo));
-    SG_CHECK(sg_dev_malloc((void**)&k->d_Q, sizeof(float) * fo));
-    SG_CHECK(sg_dev_malloc((void**)&k->d_d, sizeof(float) * vo));
-    if (wo) SG_CHECK(sg_dev_malloc((void**)&k->d_work, sizeof(double) * wo));
-    SG_CHECK(sg_dev_malloc((void**)&k->d_ks, sizeof(KfacDevState)));
-    SG_CHECK(sg_dev_malloc((void**)&k->d_vec, sizeof(float) * (d.total + 8)));
-    SG_CHECK(sg_dev_malloc((void**)&k->d_t0, sizeof(float) * to));
-    SG_CHECK(sg_dev_malloc((void**)&k->d_t1, sizeof(float) * to));
-    SG_CHECK(sg_dev_malloc((void**)&k->d_one, sizeof(float) * 4));
-    SG_CHECK(sg_dev_malloc((void**)&k->d_vpart, sizeof(float) * SG_KFAC_MODULES * k->max_tiles));
-    SG_CHECK(hipMemsetAsync(k->d_m, 0, sizeof(float) * fo, ctx->stream));
-    SG_CHECK(hipMemsetAsync(k->d_Q, 0, sizeof(float) * fo, ctx->stream));
-    SG_CHECK(hipMemsetAsync(k->d_d, 0, sizeof(float) * vo, ctx->stream));
-    SG_CHECK(hipMemsetAsync(k->d_ks, 0, sizeof(KfacDevState), ctx->stream));
-    SG_CHECK(hipMemsetAsync(k->d_vec, 0, sizeof(float) * (d.total + 8), ctx->stream));
-    const float one[4] = {1.f, 1.f, 1.f, 1.f};
-    SG_COPY_SYNC(ctx, k->d_one, one, sizeof one, hipMemcpyHostToDevice);
-    // the four preconditioning stages of every module (see k_kfac_gemm): t0 = Q_g^T grad; t1 = (t0 Q_a) / (d_g d_a^T + la);
-    // t0 = Q_g t1; v = t0 Q_a^T (with the tile sums of v * grad)
-    std::vector<KfacJob> jobs(4 * SG_KFAC_MODULES);
-    for (int m = 0; m < SG_KFAC_MODULES; ++m) {
-        const KfacModule& md = k->mod[m];
-        const float* Qa = md.a_f >= 0 ? k->d_Q + k->off[md.a_f] : k->d_one;
-        const float* da = md.a_f >= 0 ? k->d_d + k->voff[md.a_f] : k->d_one;
-        const float* Qg = k->d_Q + k->off[md.g_f];
-        const float* dg = k->d_d + k->voff[md.g_f];
-        float* t0 = k->d_t0 + md.toff;
-        float* t1 = k->d_t1 + md.toff;
-        const int M = md.out, N = md.in;
-        KfacJob j;
-        memset(&j, 0, sizeof j);
-        j.M = M; j.N = N;
-        KfacJob s1 = j, s2 = j, s3 = j, s4 = j;
-        s1.K = M; s1.A = Qg; s1.lda = M; s1.ta = 1; s1.B = d_grad + md.goff; s1.ldb = md.gld; s1.C = t0; s1.ldc = N;
-        s2.K = N; s2.A = t0; s2.lda = N; s2.B = Qa; s2.ldb = N; s2.C = t1; s2.ldc = N; s2.epi = 1; s2.dg = dg; s2.da = da;
-        s3.K = M; s3.A = Qg; s3.lda = M; s3.B = t1; s3.ldb = N; s3.C = t0; s3.ldc = N;
-        s4.K = N; s4.A = t0; s4.lda = N; s4.B = Qa; s4.ldb = N; s4.tb = 1; s4.C = k->d_vec + md.goff; s4.ldc = md.gld; s4.epi = 2;
-        s4.G = d_grad + md.goff; s4.ldg = md.gld;
-        jobs[0 * SG_KFAC_MODULES + m] = s1;
-        jobs[1 * SG_KFAC_MODULES + m] = s2;
-        jobs[2 * SG_KFAC_MODULES + m] = s3;
-        jobs[3 * SG_KFAC_MODULES + m] = s4;
-    }
-    SG_CHECK(sg_dev_malloc((void**)&k->d_jobs, sizeof(KfacJob) * jobs.size()));
-    SG_COPY_SYNC(ctx, k->d_jobs, jobs.data(), sizeof(KfacJob) * jobs.size(), hipMemcpyHostToDevice);
-    std::vector<int4> tiles;
-    for (int f = 0; f < SG_KFAC_NF; ++f) {
-        const int T = (k->n[f] + 15) / 16;
-        for (int ti = 0; ti < T; ++ti)
-            for (int tj = ti; tj < T; ++tj) tiles.push_back(make_int4(f, ti, tj, 0));
-    }
-    k->n_tiles = (int)tiles.size();
-    SG_CHECK(sg_dev_malloc((void**)&k->d_tiles, sizeof(int4) * tiles.size()));
-    SG_COPY_SYNC(ctx, k->d_tiles, tiles.data(), sizeof(int4) * tiles.size(), hipMemcpyHostToDevice);
+    const PpoInstance* inst = nullptr;
+    for (const PpoInstance& i : family)
+        if (!inst && i.mt == MT && i.gw == gw && ((i.ko == 0 && i.kh == 0) || (!gw && i.ko == ko && i.kh == kh))) inst = &i;
+    SG_REQUIRE(inst, "sg_ppo_update: %s has no instance for %d-row groups%s", what, 16 * MT, gw ? " with global weights" : "");
+    SG_LAUNCH(ctx, prof, inst->kernel, grid, dim3(ppo_block_threads(MT)), lds, pa);
     return 0;
-}
-
-static KfacEigArgs kfac_eig_args(const SgKfac* k) {
-    KfacEigArgs e;
-    memset(&e, 0, sizeof e);
-    e.m = k->d_m; e.Q = k->d_Q; e.dv = k->d_d; e.work = k->d_work;
-    for (int f = 0; f < SG_KFAC_NF; ++f) { e.n[f] = k->n[f]; e.off[f] = k->off[f]; e.voff[f] = k->voff[f]; e.woff[f] = k->woff[f]; }
-    e.lds_n = k->lds_n; e.tf = k->cfg.Tf; e.ks = k->d_ks;
-    return e;
-}
-
-static size_t kfac_eig_lds(const SgKfac* k) {
-    int nl = 0;
-    for (int f = 0; f < SG_KFAC_NF; ++f) if (k->n[f] <= k->lds_n) nl = std::max(nl, k->n[f]);
-    return sizeof(double) * 2 * (size_t)nl * nl;
 }
 
 // ---------------------------------------------------------------------------------- PPO API
@@ -345,9 +191,10 @@ extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg
                "context has a communicator of world %d (data-parallel PPO through time is not implemented)", ctx->world);
     SG_REQUIRE(cfg->ppo_epoch > 0 && cfg->num_mini_batch > 0, "sg_ppo_create: ppo_epoch and num_mini_batch must be positive");
     // a policy whose trunk does not fit a CU's LDS runs on the global-weight instances; only the 16-row tiles must fit
-    SG_REQUIRE(ppo_fwd_lds(p->desc, 1, true) <= (size_t)ctx->lds_bytes && ppo_bwd_lds(p->desc, 1, true) <= (size_t)ctx->lds_bytes,
-               "sg_ppo_create: the 16-row activation tiles of this policy do not fit LDS (%zu / %zu > %d bytes)",
-               ppo_fwd_lds(p->desc, 1, true), ppo_bwd_lds(p->desc, 1, true), ctx->lds_bytes);
+    const size_t tiles_f = ppo_fwd_lds(p->desc, 1, true), tiles_b = ppo_bwd_tiles_lds(p->desc, 1, 0, 2, false);
+    SG_REQUIRE(tiles_f <= (size_t)ctx->lds_bytes && tiles_b <= (size_t)ctx->lds_bytes,
+               "sg_ppo_create: the 16-row activation tiles of this policy do not fit LDS (%zu / %zu > %d bytes)", tiles_f, tiles_b,
+               ctx->lds_bytes);
     SG_CHECK(hipSetDevice(ctx->device));
     sg_ppo* a = new sg_ppo();
     a->ctx = ctx; a->policy = p; a->cfg = *cfg;
@@ -430,60 +277,6 @@ extern "C" int sg_acktr_create(sg_ctx* ctx, sg_policy* p, const sg_acktr_config*
     return 0;
 }
 
-extern "C" int sg_acktr_set_value_noise(sg_ppo* a, const float* eps, int64_t n) {
-    SG_REQUIRE(a, "sg_acktr_set_value_noise: NULL argument");
-    SG_REQUIRE(a->kfac, "sg_acktr_set_value_noise: not an ACKTR handle");
-    SgKfac* k = a->kfac;
-    if (!eps) {
-        k->eps_pending = false;
-        k->eps_host.clear();
-        return 0;
-    }
-    SG_REQUIRE(n > 0 && n < (1ll << 30), "sg_acktr_set_value_noise: %lld values", (long long)n);
-    k->eps_host.assign(eps, eps + n);
-    k->eps_pending = true;
-    return 0;
-}
-
-extern "C" int sg_acktr_get_state(sg_ppo* a, float* m_aa, int64_t n_aa, float* m_gg, int64_t n_gg, float* momentum_buf,
-                                  int64_t n, int64_t* steps) {
-    SG_REQUIRE(a && m_aa && m_gg && momentum_buf && steps, "sg_acktr_get_state: NULL argument");
-    SG_REQUIRE(a->kfac, "sg_acktr_get_state: not an ACKTR handle");
-    const SgKfac* k = a->kfac;
-    const SgPolicyDesc& d = a->policy->desc;
-    SG_REQUIRE(n == sg_policy_flat_count(d), "sg_acktr_get_state: bad momentum length");
-    int64_t want_aa = 0, want_gg = 0;
-    for (int m = 0; m < SG_KFAC_MODULES; ++m) {
-        want_aa += (int64_t)k->mod[m].in * k->mod[m].in;
-        want_gg += (int64_t)k->mod[m].out * k->mod[m].out;
-    }
-    SG_REQUIRE(n_aa == want_aa && n_gg == want_gg, "sg_acktr_get_state: m_aa / m_gg take %lld / %lld floats", (long long)want_aa,
-               (long long)want_gg);
-    std::vector<float> fac(k->fac_total), buf(d.total);
-    KfacDevState ks;
-    SG_CHECK(hipSetDevice(a->ctx->device));
-    SG_CHECK(hipStreamSynchronize(a->ctx->stream));
-    SG_COPY_SYNC(a->ctx, fac.data(), k->d_m, sizeof(float) * k->fac_total, hipMemcpyDeviceToHost);
-    SG_COPY_SYNC(a->ctx, buf.data(), a->d_m, sizeof(float) * d.total, hipMemcpyDeviceToHost);
-    SG_COPY_SYNC(a->ctx, &ks, k->d_ks, sizeof ks, hipMemcpyDeviceToHost);
-    SG_REQUIRE(!ks.err, "sg_acktr_get_state: k_kfac_eig hit its sweep cap (%d) on an earlier update", SG_KFAC_SWEEPS);
-    float *pa = m_aa, *pg = m_gg;
-    for (int m = 0; m < SG_KFAC_MODULES; ++m) {
-        const KfacModule& md = k->mod[m];
-        if (md.a_f >= 0) {
-            memcpy(pa, fac.data() + k->off[md.a_f], sizeof(float) * md.in * md.in);
-        } else {
-            pa[0] = ks.steps > 0 ? 1.f : 0.f;   // ones^T ones / B
-        }
-        pa += (int64_t)md.in * md.in;
-        memcpy(pg, fac.data() + k->off[md.g_f], sizeof(float) * md.out * md.out);
-        pg += (int64_t)md.out * md.out;
-    }
-    sg_policy_unpad(d, buf.data(), momentum_buf);
-    *steps = ks.steps;
-    return 0;
-}
-
 extern "C" int sg_ppo_destroy(sg_ppo* a) {
     SG_DEVICE_WIDE();
     if (!a) return 0;
@@ -499,7 +292,7 @@ extern "C" int sg_ppo_destroy(sg_ppo* a) {
     if (a->d_pair) (void)sg_dev_free(a->d_pair);
     if (a->h_h0) (void)sg_host_release(a->h_h0);
     for (hipEvent_t ev : a->h0_ev) if (ev) (void)hipEventDestroy(ev);
-    if (a->steps_graph) (void)hipGraphExecDestroy(a->steps_graph);
+    sg_graph_release(&a->steps_graph);
     kfac_free(a);
     delete a;
     return 0;
@@ -534,9 +327,9 @@ extern "C" int sg_ppo_set_symmetry(sg_ppo* a, float coef, const float* m_obs, co
                "not for SplitPolicy");
     SG_REQUIRE(!a->policy->recurrent, "sg_ppo_set_symmetry: the mirror-symmetry loss is implemented for feed-forward policies only, "
                "not for a recurrent Policy");
-    SG_REQUIRE(ppo_bwd_sym_lds(d, 1, true) <= (size_t)ctx->lds_bytes,
-               "sg_ppo_set_symmetry: the 16-row tiles of the symmetric step do not fit LDS (%zu > %d bytes)", ppo_bwd_sym_lds(d, 1, true),
-               ctx->lds_bytes);
+    SG_REQUIRE(ppo_bwd_tiles_lds(d, 1, 0, 3, true) <= (size_t)ctx->lds_bytes,
+               "sg_ppo_set_symmetry: the 16-row tiles of the symmetric step do not fit LDS (%zu > %d bytes)",
+               ppo_bwd_tiles_lds(d, 1, 0, 3, true), ctx->lds_bytes);
     if (!a->d_mact) SG_CHECK(sg_dev_malloc((void**)&a->d_mact, sizeof(float) * d.A * d.A));
     SG_COPY_SYNC(ctx, a->d_mact, m_act, sizeof(float) * d.A * d.A, hipMemcpyHostToDevice);
     if (m_obs) {
@@ -560,11 +353,7 @@ extern "C" int sg_ppo_set_mirrored_obs(sg_ppo* a, const float* host, int64_t cou
     sg_ctx* ctx = a->ctx;
     SG_CHECK(hipSetDevice(ctx->device));
     SG_CHECK(hipStreamSynchronize(ctx->stream));   // a queued update may still read the previous rows
-    if (a->mrows_cap < count) {
-        if (a->d_mrows) SG_CHECK(sg_dev_free(a->d_mrows));
-        SG_CHECK(sg_dev_malloc((void**)&a->d_mrows, sizeof(float) * count));
-        a->mrows_cap = count;
-    }
+    SG_TRY(ensure_cap(ctx->stream, &a->d_mrows, &a->mrows_cap, count));
     SG_COPY_SYNC(ctx, a->d_mrows, host, sizeof(float) * count, hipMemcpyHostToDevice);
     a->mrows_host = count;
     return 0;
@@ -638,7 +427,7 @@ extern "C" int sg_ppo_set_adam(sg_ppo* a, const float* m, const float* v, int64_
     SG_COPY_SYNC(a->ctx, &reinterpret_cast<SgOptState*>(a->d_state)->t0, &t0, sizeof t0, hipMemcpyHostToDevice);
     // the words k_ppo_pair's actor workgroups swap carry Adam step numbers: a step count set from outside may repeat old ones,
     // so the row stacks they live in are cleared before the next update
-    a->scratch_key = 0;
+    a->cleared.mode = SG_LAYOUT_INVALID;
     a->pair_primed = false;
     a->opt_t = step;
     return 0;
@@ -676,6 +465,34 @@ extern "C" int sg_a2c_set_rmsprop(sg_ppo* a, const float* square_avg, int64_t n,
     return 0;
 }
 
+// ------------------------------------------------------------------- shared by the three updates
+// advantages of the rollout's T*N rows (global mean / unbiased std) into its advantage field
+static int enqueue_adv_stats(sg_ctx* ctx, sg_rollout* r, sg_ppo* a, bool with_comm) {
+    const int64_t TN = (int64_t)r->T * r->N;
+    double* stats = a->d_loss_acc + 4;
+    for (int pass = 0; pass < 3; ++pass) {
+        hipLaunchKernelGGL(k_adv_stats, dim3(pass == 2 ? 64 : 1), dim3(1024), 0, ctx->stream, r->d_field[SG_F_RETURNS],
+                           r->d_field[SG_F_VALUE_PREDS], TN, r->d_field[SG_F_ADVANTAGES], stats, pass);
+        if (with_comm && pass == 0) SG_TRY(sg_comm_allreduce_f64(ctx, stats, 3));       // sum and n are linear
+        if (with_comm && pass == 1) SG_TRY(sg_comm_allreduce_f64(ctx, stats + 1, 1));   // squares about the global mean
+    }
+    SG_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ld-padding columns of the slabs and rows past the minibatch are never written by the kernels and must read as zero; the
+// epoch copy's slack rows must be finite.  Both hold for as long as the scratch layout is unchanged, so the buffers (35 MB at
+// the north-star shape) are cleared when the layout differs from the one they were last cleared for, not on every update.
+// gru_f: floats of d_gru the mode uses (0: none).
+static int clear_for_layout(sg_ppo* a, const SgScratchLayout& layout, size_t slab_f, size_t stack_f, size_t gru_f) {
+    if (memcmp(&a->cleared, &layout, sizeof layout) == 0) return 0;
+    SG_CHECK(hipMemsetAsync(a->d_slabs, 0, sizeof(float) * slab_f, a->ctx->stream));
+    SG_CHECK(hipMemsetAsync(a->d_stacks, 0, sizeof(float) * stack_f, a->ctx->stream));
+    if (gru_f) SG_CHECK(hipMemsetAsync(a->d_gru, 0, sizeof(float) * gru_f, a->ctx->stream));
+    a->cleared = layout;
+    return 0;
+}
+
 // A2C_ACKTR.update(rollouts), acktr=False (a2c/algo/a2c_acktr.py:52-102): evaluate_actions on all T*N rows with the current
 // parameters, adv = returns[:-1] - values, loss = vcoef mean(adv^2) + (-mean(adv.detach() logp)) - ecoef mean(ent), one
 // clip_grad_norm_ + RMSprop step.  The rows are taken in chunks of SG_A2C_CHUNK_ROWS; each chunk's slabs are added to the
@@ -689,18 +506,13 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, uint64_t seed, float out3[3]) {
     SG_CHECK(hipSetDevice(ctx->device));
     const int chunk = (int)std::min<int64_t>(TN, SG_A2C_CHUNK_ROWS);
     const int n_chunks = (int)((TN + chunk - 1) / chunk);
-    // row-group size: PPO's heuristic at a minibatch of `chunk` rows (two grid columns: actor, critic)
-    int MT = ((size_t)((chunk + 15) / 16) * (size_t)(d.total + 8) * sizeof(float) > ((size_t)24 << 20) ||
-              ((chunk + 31) / 32) * d.n_trunks >= ctx->num_cu) ? 2 : 1;
-    if (const char* e = getenv("SG_PPO_ROWS")) {   // tuning knob
-        const int v = atoi(e);
-        if (v == 16 || v == 32) MT = v / 16;
-    }
-    const bool gw = sg_policy_needs_gw(ctx, d) || ppo_fwd_lds(d, 1, false) > (size_t)ctx->lds_bytes ||
-                    a2c_bwd_lds(d, 1, false) > (size_t)ctx->lds_bytes;
-    SG_REQUIRE(ppo_fwd_lds(d, 1, gw) <= (size_t)ctx->lds_bytes && a2c_bwd_lds(d, 1, gw) <= (size_t)ctx->lds_bytes,
-               "sg_ppo_update: the 16-row tiles of the A2C step do not fit LDS");
-    while (MT > 1 && (ppo_fwd_lds(d, MT, gw) > (size_t)ctx->lds_bytes || a2c_bwd_lds(d, MT, gw) > (size_t)ctx->lds_bytes)) MT /= 2;
+    // k_a2c_bwd: the unfused backward's tiles (w2 on in LDS), whatever ppo_fused says
+    auto bwd_lds = [&](int mt, bool g) { return ppo_bwd_tiles_lds(d, mt, g ? 0 : max_bwd_floats(d), 2, false); };
+    auto fits = [&](int mt, bool g) { return ppo_fwd_lds(d, mt, g) <= (size_t)ctx->lds_bytes && bwd_lds(mt, g) <= (size_t)ctx->lds_bytes; };
+    const bool gw = sg_policy_needs_gw(ctx, d) || !fits(1, false);
+    SG_REQUIRE(fits(1, gw), "sg_ppo_update: the 16-row tiles of the A2C step do not fit LDS");
+    // row-group size: PPO's heuristic at a minibatch of `chunk` rows (two grid columns: actor, critic); SG_PPO_ROWS: 16 or 32
+    const int MT = ppo_row_tiles(ctx, d, chunk, d.n_trunks, true, 2, 2, [&](int mt) { return fits(mt, gw); });
     const int R = 16 * MT;
     const int G = (chunk + R - 1) / R;   // row groups of a full chunk: the slab count
     const int mbp = G * R;
@@ -710,24 +522,11 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, uint64_t seed, float out3[3]) {
     const size_t slab_f = (size_t)G * slab_stride;
     const size_t epoch_f = (size_t)TNp * (d.ldO + d.A + 4);
     const size_t stack_f = (size_t)d.n_trunks * mbp * (2 * (size_t)d.ldH + ldP);
-    if (a->slabs_cap < slab_f || a->stacks_cap < epoch_f + stack_f) {
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (a->d_slabs) SG_CHECK(sg_dev_free(a->d_slabs));
-        if (a->d_stacks) SG_CHECK(sg_dev_free(a->d_stacks));
-        SG_CHECK(sg_dev_malloc((void**)&a->d_slabs, sizeof(float) * slab_f));
-        SG_CHECK(sg_dev_malloc((void**)&a->d_stacks, sizeof(float) * (epoch_f + stack_f)));
-        a->slabs_cap = slab_f;
-        a->stacks_cap = epoch_f + stack_f;
-        a->scratch_key = 0;
-    }
-    // as for PPO: slab padding columns must read as zero, the copy's slack rows must be finite
-    const uint64_t key = ((uint64_t)G << 40) ^ ((uint64_t)slab_stride << 20) ^ ((uint64_t)mbp << 8) ^ (uint64_t)TNp ^ ((uint64_t)MT << 60) ^
-                         (1ull << 62);
-    if (a->scratch_key != key) {
-        SG_CHECK(hipMemsetAsync(a->d_slabs, 0, sizeof(float) * slab_f, ctx->stream));
-        SG_CHECK(hipMemsetAsync(a->d_stacks, 0, sizeof(float) * (epoch_f + stack_f), ctx->stream));
-        a->scratch_key = key;
-    }
+    bool grew = false;
+    SG_TRY(ensure_cap(ctx->stream, &a->d_slabs, &a->slabs_cap, slab_f, &grew));
+    SG_TRY(ensure_cap(ctx->stream, &a->d_stacks, &a->stacks_cap, epoch_f + stack_f, &grew));
+    if (grew) a->cleared.mode = SG_LAYOUT_INVALID;
+    SG_TRY(clear_for_layout(a, {SG_LAYOUT_A2C, {G, slab_stride, mbp, TNp, MT}}, slab_f, epoch_f + stack_f, 0));
     hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 4);
 
     float* epX = a->d_stacks;
@@ -754,7 +553,7 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, uint64_t seed, float out3[3]) {
         pa.OUT[t] = stk; stk += (size_t)mbp * ldP;
     }
     const int wb_f = gw ? 0 : max_trunk_floats(d), wb_b = gw ? 0 : max_bwd_floats(d);
-    const size_t lds_f = ppo_fwd_lds(d, MT, gw), lds_b = a2c_bwd_lds(d, MT, gw);
+    const size_t lds_f = ppo_fwd_lds(d, MT, gw), lds_b = bwd_lds(MT, gw);
     const int nblk = (d.total + 8 + 255) / 256;
     const int nblk_r = (d.total + 8 + SG_PPO_REDUCE_PARAMS - 1) / SG_PPO_REDUCE_PARAMS;
     const double oma = 1.0 - (double)a->alpha;   // torch: value = 1 - alpha in Python doubles
@@ -775,19 +574,8 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, uint64_t seed, float out3[3]) {
         const int frows = (chunk + 63) & ~63;
         const int ldZ = d.ldH;
         const size_t fish_f = (size_t)frows * (4 * (size_t)ldZ + 2 * (size_t)d.A + 1);
-        if (kf->eps_cap < TN || kf->fish_cap < fish_f) {
-            SG_CHECK(hipStreamSynchronize(ctx->stream));
-            if (kf->eps_cap < TN) {
-                if (kf->d_eps) SG_CHECK(sg_dev_free(kf->d_eps));
-                SG_CHECK(sg_dev_malloc((void**)&kf->d_eps, sizeof(float) * TN));
-                kf->eps_cap = TN;
-            }
-            if (kf->fish_cap < fish_f) {
-                if (kf->d_fish) SG_CHECK(sg_dev_free(kf->d_fish));
-                SG_CHECK(sg_dev_malloc((void**)&kf->d_fish, sizeof(float) * fish_f));
-                kf->fish_cap = fish_f;
-            }
-        }
+        SG_TRY(ensure_cap(ctx->stream, &kf->d_eps, &kf->eps_cap, TN));
+        SG_TRY(ensure_cap(ctx->stream, &kf->d_fish, &kf->fish_cap, fish_f));
         if (kf->eps_pending) {
             SG_COPY_SYNC(ctx, kf->d_eps, kf->eps_host.data(), sizeof(float) * TN, hipMemcpyHostToDevice);
             kf->eps_pending = false;
@@ -829,9 +617,9 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, uint64_t seed, float out3[3]) {
             pa.mb = cnt;
             pa.X = epX + rb * d.ldO; pa.ACT = epACT + rb * d.A; pa.SC = epSC + rb;
             pa.wbuf_floats = wb_f;
-            launch_ppo_fwd(ctx, MT, d, dim3(Gc, d.n_trunks), lds_f, pa, gw);
+            SG_TRY(ppo_launch(ctx, ppo_fwd_family, "k_ppo_fwd", SG_PROF_PPO_FWD, MT, d, dim3(Gc, d.n_trunks), lds_f, pa, gw));
             pa.wbuf_floats = wb_b;
-            launch_a2c_bwd(ctx, MT, d, dim3(Gc, d.n_trunks), lds_b, pa, gw);
+            SG_TRY(ppo_launch(ctx, a2c_bwd_family, "k_a2c_bwd", SG_PROF_PPO_BWD, MT, d, dim3(Gc, d.n_trunks), lds_b, pa, gw));
             SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_a2c_reduce, dim3(nblk_r), dim3(256), 0, a->d_slabs, Gc, slab_stride, d.total, a->d_grad,
                       a->d_part, c > 0 ? 1 : 0);
             if (kf) {
@@ -863,32 +651,20 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, uint64_t seed, float out3[3]) {
                   nblk_r, d.total, pa.st, a->alpha, (float)oma, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B, a->d_loss_acc);
         return 0;
     };
-    const char* genv = getenv("SG_PPO_GRAPH");
-    bool use_graph = !a->graph_refused && !ctx->use_comm && !ctx->profile && !(genv && !strcmp(genv, "0"));
-    if (use_graph) {
-        uint32_t fbits[6];
-        const float fv[6] = {a->alpha, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B};
-        memcpy(fbits, fv, sizeof fbits);
-        const uint64_t key[18] = {(uint64_t)(uintptr_t)a->d_slabs, (uint64_t)(uintptr_t)a->d_stacks, 0,
-                                  (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
-                                  (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)a->policy->d_params,
-                                  (uint64_t)TN, ((uint64_t)n_chunks << 32) | (uint64_t)chunk, ((uint64_t)MT << 32) | (uint64_t)G,
-                                  ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
-                                  ((uint64_t)fbits[4] << 32) | fbits[5], kf ? (uint64_t)(uintptr_t)kf->d_eps : 0,
-                                  kf ? (uint64_t)(uintptr_t)kf->d_fish : 0, 0x413243ull + (gw ? 8 : 0) + (1ull << 7) + (kf ? (1ull << 9) : 0),
-                                  0, 0};
-        if (!a->steps_graph || memcmp(key, a->steps_graph_key, sizeof key) != 0) {
-            if (a->steps_graph) { SG_CHECK(hipGraphExecDestroy(a->steps_graph)); a->steps_graph = nullptr; }
-            if (sg_try_capture(ctx, &a->steps_graph, enqueue_step) != 0) {
-                a->graph_refused = true;
-                use_graph = false;
-            } else {
-                memcpy(a->steps_graph_key, key, sizeof key);
-            }
-        }
-        if (use_graph) SG_CHECK(hipGraphLaunch(a->steps_graph, ctx->stream));
-    }
-    if (!use_graph) SG_TRY(enqueue_step());
+    const bool use_graph = !ctx->use_comm && !ctx->profile && !sg_env_is_off("SG_PPO_GRAPH");
+    uint32_t fbits[6];
+    const float fv[6] = {a->alpha, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B};
+    memcpy(fbits, fv, sizeof fbits);
+    const uint64_t key[SG_GRAPH_KEY_WORDS] = {
+            (uint64_t)(uintptr_t)a->d_slabs, (uint64_t)(uintptr_t)a->d_stacks, 0,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
+            (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)a->policy->d_params,
+            (uint64_t)TN, ((uint64_t)n_chunks << 32) | (uint64_t)chunk, ((uint64_t)MT << 32) | (uint64_t)G,
+            ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
+            ((uint64_t)fbits[4] << 32) | fbits[5], kf ? (uint64_t)(uintptr_t)kf->d_eps : 0,
+            kf ? (uint64_t)(uintptr_t)kf->d_fish : 0, 0x413243ull + (gw ? 8 : 0) + (1ull << 7) + (kf ? (1ull << 9) : 0),
+            0, 0};
+    SG_TRY(sg_graph_run(ctx, &a->steps_graph, use_graph, key, enqueue_step));
     SG_CHECK(hipGetLastError());
     a->opt_t += 1;
     if (!out3) return 0;   // queued: the losses come through the results ring (step count 1)
@@ -979,21 +755,10 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
     SG_CHECK(hipSetDevice(ctx->device));
 
     // advantages (global mean / unbiased std over all T*N, as for the feed-forward update)
-    float* adv = r->d_field[SG_F_ADVANTAGES];
-    double* stats = a->d_loss_acc + 4;
-    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(1024), 0, ctx->stream, r->d_field[SG_F_RETURNS], r->d_field[SG_F_VALUE_PREDS], TN, adv, stats, 0);
-    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(1024), 0, ctx->stream, r->d_field[SG_F_RETURNS], r->d_field[SG_F_VALUE_PREDS], TN, adv, stats, 1);
-    hipLaunchKernelGGL(k_adv_stats, dim3(64), dim3(1024), 0, ctx->stream, r->d_field[SG_F_RETURNS], r->d_field[SG_F_VALUE_PREDS], TN, adv, stats, 2);
-    SG_CHECK(hipGetLastError());
+    SG_TRY(enqueue_adv_stats(ctx, r, a, false));
 
     // permutations of the environments: [E][N]
-    if (a->perms_cap < (int64_t)E * N) {
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (a->d_perms) SG_CHECK(sg_dev_free(a->d_perms));
-        a->d_perms = nullptr; a->perms_cap = 0;
-        SG_CHECK(sg_dev_malloc((void**)&a->d_perms, sizeof(int64_t) * (size_t)E * N));
-        a->perms_cap = (int64_t)E * N;
-    }
+    SG_TRY(ensure_cap(ctx->stream, &a->d_perms, &a->perms_cap, (int64_t)E * N));
     a->last_perm_count = (int64_t)E * N;
     if (perms) {
         SG_CHECK(hipMemcpyAsync(a->d_perms, perms, sizeof(int64_t) * (size_t)E * N, hipMemcpyHostToDevice, ctx->stream));
@@ -1007,12 +772,9 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
     const int mb = T * per;
     const bool gw = sg_policy_needs_gw(ctx, d) || ppo_fwd_lds(d, 1, false) > (size_t)ctx->lds_bytes;
     const int ldP = stack_ldP(d);
-    auto bwd_lds = [&](int mt) {
-        const int R = 16 * mt;
-        return sizeof(float) * ((gw ? 0 : (size_t)max_trunk_floats(d)) + R * d.ldO + 2 * R * d.ldH + 2 * R * ldP + ((R * d.A + 3) & ~3) + 7 * R);
-    };
-    int MT = ((mb + 31) / 32) * d.n_trunks >= ctx->num_cu ? 2 : 1;
-    if (MT == 2 && bwd_lds(2) > (size_t)ctx->lds_bytes) MT = 1;
+    auto bwd_lds = [&](int mt) { return ppo_bwd_tiles_lds(d, mt, gw ? 0 : max_trunk_floats(d), 2, false); };   // the fused form
+    // (neither SG_PPO_ROWS nor the 24 MB slab rule here; 32-row groups fall back to 16-row ones only)
+    const int MT = ppo_row_tiles(ctx, d, mb, d.n_trunks, false, 0, 2, [&](int mt) { return bwd_lds(mt) <= (size_t)ctx->lds_bytes; });
     SG_REQUIRE(bwd_lds(MT) <= (size_t)ctx->lds_bytes, "sg_ppo_update: the heads' 16-row tiles do not fit LDS (%zu bytes)", bwd_lds(MT));
     const int R = 16 * MT, G = (mb + R - 1) / R, mbp = G * R;
     const int slab_stride = (d.total + 8 + 63) & ~63;
@@ -1036,29 +798,13 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
     const size_t o_shn = o_sn + (size_t)rows_p * Hp, o_hm = o_shn + (size_t)rows_p * Hp, o_dgi = o_hm + (size_t)rows_p * g.ldH;
     const size_t o_dgh = o_dgi + (size_t)rows_p * G3, o_dxa = o_dgh + (size_t)rows_p * G3, o_dxc = o_dxa + (size_t)mbp * d.ldO;
     const size_t o_part = o_dxc + (size_t)mbp * d.ldO, gru_f = o_part + (size_t)KS * g.total;
-    if (a->slabs_cap < slab_f || a->stacks_cap < stack_f || a->gru_cap < gru_f) {
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (a->d_slabs) SG_CHECK(sg_dev_free(a->d_slabs));
-        if (a->d_stacks) SG_CHECK(sg_dev_free(a->d_stacks));
-        if (a->d_gru) SG_CHECK(sg_dev_free(a->d_gru));
-        a->d_slabs = a->d_stacks = a->d_gru = nullptr;
-        a->slabs_cap = a->stacks_cap = a->gru_cap = 0;
-        SG_CHECK(sg_dev_malloc((void**)&a->d_slabs, sizeof(float) * slab_f));
-        SG_CHECK(sg_dev_malloc((void**)&a->d_stacks, sizeof(float) * stack_f));
-        SG_CHECK(sg_dev_malloc((void**)&a->d_gru, sizeof(float) * gru_f));
-        a->slabs_cap = slab_f; a->stacks_cap = stack_f; a->gru_cap = gru_f;
-        a->scratch_key = 0;
-    }
-    // padding columns / rows past the minibatch are never written and must read as zero: cleared when the layout changes (the
-    // whole tuple is compared, not a hash of it)
-    const int64_t layout[8] = {G, slab_stride, mbp, TNp, MT, KS, per, ((int64_t)g.total << 32) | (int64_t)rows_p};
-    if (a->scratch_key != 0x475255ull || memcmp(layout, a->gru_layout, sizeof layout) != 0) {
-        SG_CHECK(hipMemsetAsync(a->d_slabs, 0, sizeof(float) * slab_f, ctx->stream));
-        SG_CHECK(hipMemsetAsync(a->d_stacks, 0, sizeof(float) * stack_f, ctx->stream));
-        SG_CHECK(hipMemsetAsync(a->d_gru, 0, sizeof(float) * gru_f, ctx->stream));
-        memcpy(a->gru_layout, layout, sizeof layout);
-        a->scratch_key = 0x475255ull;   // (0 after a reallocation or sg_ppo_set_adam: clear again)
-    }
+    bool grew = false;
+    SG_TRY(ensure_cap(ctx->stream, &a->d_slabs, &a->slabs_cap, slab_f, &grew));
+    SG_TRY(ensure_cap(ctx->stream, &a->d_stacks, &a->stacks_cap, stack_f, &grew));
+    SG_TRY(ensure_cap(ctx->stream, &a->d_gru, &a->gru_cap, gru_f, &grew));
+    if (grew) a->cleared.mode = SG_LAYOUT_INVALID;
+    SG_TRY(clear_for_layout(a, {SG_LAYOUT_GRU, {G, slab_stride, mbp, TNp, MT, KS, per, ((int64_t)g.total << 32) | (int64_t)rows_p}},
+                            slab_f, stack_f, gru_f));
     hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 4);
 
     float* hX = a->d_stacks;
@@ -1067,7 +813,8 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
     float* gb = a->d_gru;
 
     GruGatherArgs ga;
-    ga.obs = r->d_field[SG_F_OBS]; ga.actions = r->d_field[SG_F_ACTIONS]; ga.old_logp = r->d_field[SG_F_LOGP]; ga.adv = adv;
+    ga.obs = r->d_field[SG_F_OBS]; ga.actions = r->d_field[SG_F_ACTIONS]; ga.old_logp = r->d_field[SG_F_LOGP];
+    ga.adv = r->d_field[SG_F_ADVANTAGES];
     ga.vpred = r->d_field[SG_F_VALUE_PREDS]; ga.ret = r->d_field[SG_F_RETURNS]; ga.masks = r->d_field[SG_F_MASKS]; ga.h0 = a->d_h0;
     ga.T = T; ga.N = N; ga.per = per; ga.O = g.O; ga.ldO = g.ldO; ga.A = d.A; ga.H = g.H; ga.sc_stride = TNp;
     ga.X = gb + o_x; ga.ACT = epACT; ga.SC = epSC; ga.MK = gb + o_mk; ga.H0 = gb + o_h0;
@@ -1097,7 +844,6 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
                          sg_gru_bwd_lds(g, false) > (size_t)ctx->lds_bytes - 1024;
     const int n_tiles = (G3 / 16) * (g.Op / 16 + Hp / 16) + 2 * (G3 / 16);
     const size_t lds_b = bwd_lds(MT);
-    const dim3 hblock(ppo_block_threads(MT));
     SgOptState* st = reinterpret_cast<SgOptState*>(a->d_state);
 
     auto enqueue_steps = [&]() -> int {
@@ -1113,12 +859,8 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
                                              gb + o_gi, hX, d.ldO, nullptr, &tr));
                 pa.ACT = epACT + rb * d.A; pa.SC = epSC + rb;
                 pa.k1 = e * S + k + 1;
-                const dim3 grid(G, 2);
-                if (gw) {
-                    if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<2, 0, 0, true, true, true>), grid, hblock, lds_b, pa);
-                    else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<1, 0, 0, true, true, true>), grid, hblock, lds_b, pa);
-                } else if (MT == 2) SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<2, 0, 0, true, false, true>), grid, hblock, lds_b, pa);
-                else SG_LAUNCH(ctx, SG_PROF_PPO_BWD, (k_ppo_bwd<1, 0, 0, true, false, true>), grid, hblock, lds_b, pa);
+                SG_TRY(ppo_launch(ctx, ppo_bwd_fused_dx_family, "k_ppo_bwd (fused, with d loss / d h)", SG_PROF_PPO_BWD, MT, d, dim3(G, 2),
+                                  lds_b, pa, gw));
                 SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_ppo_reduce, dim3(nblk_r), dim3(256), 0, a->d_slabs, G, slab_stride, d.total, a->d_grad,
                           a->d_part);
                 ba.masks = mk;
@@ -1136,33 +878,21 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
         SG_CHECK(hipGetLastError());
         return 0;
     };
-    const char* genv = getenv("SG_PPO_GRAPH");
-    bool use_graph = !a->graph_refused && !ctx->profile && !(genv && !strcmp(genv, "0"));
-    if (use_graph) {
-        uint32_t fbits[6];
-        const float fv[6] = {a->cfg.clip_param, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B};
-        memcpy(fbits, fv, sizeof fbits);
-        const uint64_t gkey[18] = {(uint64_t)(uintptr_t)a->d_slabs, (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_perms,
-                                   (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
-                                   (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)pol->d_params,
-                                   (uint64_t)TN, ((uint64_t)E << 32) | (uint64_t)M, ((uint64_t)MT << 32) | (uint64_t)G,
-                                   ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
-                                   ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)a->cfg.use_clipped_value_loss,
-                                   (uint64_t)(uintptr_t)r->d_field[SG_F_LOGP],
-                                   0x475255ull + (gw ? 8 : 0) + (gw_scan ? 16 : 0) + ((uint64_t)N << 32),   // 'GRU': the recurrent step sequence
-                                   (uint64_t)(uintptr_t)a->d_gru, (uint64_t)(uintptr_t)a->d_h0 ^ ((uint64_t)(uintptr_t)r->d_field[SG_F_MASKS] << 1)};
-        if (!a->steps_graph || memcmp(gkey, a->steps_graph_key, sizeof gkey) != 0) {
-            if (a->steps_graph) { SG_CHECK(hipGraphExecDestroy(a->steps_graph)); a->steps_graph = nullptr; }
-            if (sg_try_capture(ctx, &a->steps_graph, enqueue_steps) != 0) {
-                a->graph_refused = true;
-                use_graph = false;
-            } else {
-                memcpy(a->steps_graph_key, gkey, sizeof gkey);
-            }
-        }
-        if (use_graph) SG_CHECK(hipGraphLaunch(a->steps_graph, ctx->stream));
-    }
-    if (!use_graph) SG_TRY(enqueue_steps());
+    const bool use_graph = !ctx->profile && !sg_env_is_off("SG_PPO_GRAPH");
+    uint32_t fbits[6];
+    const float fv[6] = {a->cfg.clip_param, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B};
+    memcpy(fbits, fv, sizeof fbits);
+    const uint64_t key[SG_GRAPH_KEY_WORDS] = {
+            (uint64_t)(uintptr_t)a->d_slabs, (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_perms,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
+            (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)pol->d_params,
+            (uint64_t)TN, ((uint64_t)E << 32) | (uint64_t)M, ((uint64_t)MT << 32) | (uint64_t)G,
+            ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
+            ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)a->cfg.use_clipped_value_loss,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_LOGP],
+            0x475255ull + (gw ? 8 : 0) + (gw_scan ? 16 : 0) + ((uint64_t)N << 32),   // 'GRU': the recurrent step sequence
+            (uint64_t)(uintptr_t)a->d_gru, (uint64_t)(uintptr_t)a->d_h0 ^ ((uint64_t)(uintptr_t)r->d_field[SG_F_MASKS] << 1)};
+    SG_TRY(sg_graph_run(ctx, &a->steps_graph, use_graph, key, enqueue_steps));
     SG_CHECK(hipGetLastError());
     a->opt_t += (int64_t)E * S;
     if (!out3) return 0;
@@ -1254,12 +984,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     const bool sym = a->sym_coef > 0.f;
     if (sym) {
         if (a->d_mobs_mat) {
-            if (a->mrows_cap < TN * d.O) {
-                SG_CHECK(hipStreamSynchronize(ctx->stream));
-                if (a->d_mrows) SG_CHECK(sg_dev_free(a->d_mrows));
-                SG_CHECK(sg_dev_malloc((void**)&a->d_mrows, sizeof(float) * TN * d.O));
-                a->mrows_cap = TN * d.O;
-            }
+            SG_TRY(ensure_cap(ctx->stream, &a->d_mrows, &a->mrows_cap, TN * d.O));
             hipLaunchKernelGGL(k_mirror_rows, dim3((unsigned)((TN * d.O + 255) / 256)), dim3(256), 0, ctx->stream,
                                r->d_field[SG_F_OBS], a->d_mobs_mat, a->d_mrows, TN, d.O);
             SG_CHECK(hipGetLastError());
@@ -1271,26 +996,10 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
         }
     }
 
-    // advantages (global mean / unbiased std)
-    float* adv = r->d_field[SG_F_ADVANTAGES];
-    double* stats = a->d_loss_acc + 4;
-    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(1024), 0, ctx->stream, r->d_field[SG_F_RETURNS],
-                       r->d_field[SG_F_VALUE_PREDS], TN, adv, stats, 0);
-    if (ctx->use_comm) SG_TRY(sg_comm_allreduce_f64(ctx, stats, 3));       // sum and n are linear
-    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(1024), 0, ctx->stream, r->d_field[SG_F_RETURNS],
-                       r->d_field[SG_F_VALUE_PREDS], TN, adv, stats, 1);
-    if (ctx->use_comm) SG_TRY(sg_comm_allreduce_f64(ctx, stats + 1, 1));   // squares about the global mean
-    hipLaunchKernelGGL(k_adv_stats, dim3(64), dim3(1024), 0, ctx->stream, r->d_field[SG_F_RETURNS],
-                       r->d_field[SG_F_VALUE_PREDS], TN, adv, stats, 2);
-    SG_CHECK(hipGetLastError());
+    SG_TRY(enqueue_adv_stats(ctx, r, a, ctx->use_comm));
 
     // permutations
-    if (a->perms_cap < (int64_t)E * TN) {
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (a->d_perms) SG_CHECK(sg_dev_free(a->d_perms));
-        SG_CHECK(sg_dev_malloc((void**)&a->d_perms, sizeof(int64_t) * (size_t)E * TN));
-        a->perms_cap = (int64_t)E * TN;
-    }
+    SG_TRY(ensure_cap(ctx->stream, &a->d_perms, &a->perms_cap, (int64_t)E * TN));
     a->last_perm_count = owned ? 0 : (int64_t)E * TN;   // owned mode: the device holds this rank's share only
     if (owned) {
         SG_CHECK(hipMemcpyAsync(a->d_perms, own_perm.data(), sizeof(int64_t) * (size_t)E * TN, hipMemcpyHostToDevice, ctx->stream));
@@ -1304,22 +1013,19 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
             SG_TRY(sg_fill_perm(ctx, a->d_perms + (size_t)e * TN, TN, seed, (uint64_t)e * 2654435761ull + (uint64_t)ctx->rank));
     }
 
-    // launch geometry: 32-row groups as long as they still give every CU a workgroup (half the gradient slabs for
-    // k_ppo_reduce to stream: -1.8 us per step at the north-star shape against +0.6 us in k_ppo_bwd), or when the
-    // 16-row slabs would exceed 24 MB; otherwise 16-row groups (more workgroups in flight hide the phases' latencies)
+    // launch geometry (ppo_row_tiles).  The backward launch: the fused form keeps the whole trunk in LDS, the two-launch form
+    // the trunk from w2 on; k_ppo_bwd_sym is the two-launch backward + the other actor column's head tile + M_a
     const int ncols = d.n_trunks + (sym ? 1 : 0);   // grid columns: the trunks, + the mirrored actor
-    int MT = ((size_t)((mb + 15) / 16) * (size_t)(d.total + 8) * sizeof(float) > ((size_t)24 << 20) ||
-              ((mb + 31) / 32) * ncols >= ctx->num_cu) ? 2 : 1;
-    if (const char* e = getenv("SG_PPO_ROWS")) {   // tuning knob
-        const int v = atoi(e);
-        if (v == 16 || v == 32 || v == 64) MT = v / 16;
-    }
+    auto bwd_lds = [&](int mt, bool g) { return ppo_bwd_tiles_lds(d, mt, g ? 0 : ppo_fused(d, mt) ? max_trunk_floats(d) : max_bwd_floats(d), 2, false); };
+    auto bwd_sym_lds = [&](int mt, bool g) { return ppo_bwd_tiles_lds(d, mt, g ? 0 : max_bwd_floats(d), 3, true); };
+    auto fits = [&](int mt, bool g) {
+        return ppo_fwd_lds(d, mt, g) <= (size_t)ctx->lds_bytes && bwd_lds(mt, g) <= (size_t)ctx->lds_bytes &&
+               (!sym || bwd_sym_lds(mt, g) <= (size_t)ctx->lds_bytes);
+    };
     // global-weight instances when a trunk (+ one 16-row tile) does not fit LDS: in the forward, or in the backward launch
-    const bool gw = sg_policy_needs_gw(ctx, d) || ppo_fwd_lds(d, 1, false) > (size_t)ctx->lds_bytes ||
-                    ppo_bwd_lds(d, 1, false) > (size_t)ctx->lds_bytes || (sym && ppo_bwd_sym_lds(d, 1, false) > (size_t)ctx->lds_bytes);
-    if ((gw || sym) && MT > 2) MT = 2;
-    while (MT > 1 && (ppo_fwd_lds(d, MT, gw) > (size_t)ctx->lds_bytes || ppo_bwd_lds(d, MT, gw) > (size_t)ctx->lds_bytes ||
-                      (sym && ppo_bwd_sym_lds(d, MT, gw) > (size_t)ctx->lds_bytes))) MT /= 2;
+    const bool gw = sg_policy_needs_gw(ctx, d) || !fits(1, false);
+    // (SG_PPO_ROWS may ask for 64-row groups; the global-weight and the symmetric instances stop at 32)
+    const int MT = ppo_row_tiles(ctx, d, mb, ncols, true, 4, (gw || sym) ? 2 : 4, [&](int mt) { return fits(mt, gw); });
     const int R = 16 * MT;
     const int G = (mb + R - 1) / R;
     const int mbp = G * R;
@@ -1337,26 +1043,11 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     const size_t xm_off = ((size_t)TNp * (d.ldO + d.A + 4) + 3) & ~(size_t)3;
     const size_t epoch_f = sym ? xm_off + (size_t)TNp * d.ldO : (size_t)TNp * (d.ldO + d.A + 4);
     const size_t stack_f = (size_t)ncols * mbp * (2 * (size_t)d.ldH + ldP);
-    if (a->slabs_cap < slab_f || a->stacks_cap < epoch_f + stack_f) {
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (a->d_slabs) SG_CHECK(sg_dev_free(a->d_slabs));
-        if (a->d_stacks) SG_CHECK(sg_dev_free(a->d_stacks));
-        SG_CHECK(sg_dev_malloc((void**)&a->d_slabs, sizeof(float) * slab_f));
-        SG_CHECK(sg_dev_malloc((void**)&a->d_stacks, sizeof(float) * (epoch_f + stack_f)));
-        a->slabs_cap = slab_f;
-        a->stacks_cap = epoch_f + stack_f;
-        a->scratch_key = 0;
-    }
-    // ld-padding columns of the slabs are never written by the kernels and must read as zero; the epoch copy's
-    // slack rows must be finite.  Both hold for as long as the scratch layout is unchanged, so the 35 MB are
-    // cleared when the layout changes, not on every update.
-    const uint64_t key = ((uint64_t)G << 40) ^ ((uint64_t)slab_stride << 20) ^ ((uint64_t)mbp << 8) ^ (uint64_t)TNp ^ ((uint64_t)MT << 60) ^
-                         ((uint64_t)sym << 63);
-    if (a->scratch_key != key) {
-        SG_CHECK(hipMemsetAsync(a->d_slabs, 0, sizeof(float) * slab_f, ctx->stream));
-        SG_CHECK(hipMemsetAsync(a->d_stacks, 0, sizeof(float) * (epoch_f + stack_f), ctx->stream));
-        a->scratch_key = key;
-    }
+    bool grew = false;
+    SG_TRY(ensure_cap(ctx->stream, &a->d_slabs, &a->slabs_cap, slab_f, &grew));
+    SG_TRY(ensure_cap(ctx->stream, &a->d_stacks, &a->stacks_cap, epoch_f + stack_f, &grew));
+    if (grew) a->cleared.mode = SG_LAYOUT_INVALID;
+    SG_TRY(clear_for_layout(a, {SG_LAYOUT_PPO, {G, slab_stride, mbp, TNp, MT, sym}}, slab_f, epoch_f + stack_f, 0));
     hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 4);
 
     float* epX = a->d_stacks;
@@ -1367,7 +1058,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
 
     EpochGatherArgs ga;
     ga.obs = r->d_field[SG_F_OBS]; ga.actions = r->d_field[SG_F_ACTIONS]; ga.old_logp = r->d_field[SG_F_LOGP];
-    ga.adv = adv; ga.vpred = r->d_field[SG_F_VALUE_PREDS]; ga.ret = r->d_field[SG_F_RETURNS];
+    ga.adv = r->d_field[SG_F_ADVANTAGES]; ga.vpred = r->d_field[SG_F_VALUE_PREDS]; ga.ret = r->d_field[SG_F_RETURNS];
     ga.TN = TN; ga.O = d.O; ga.Op = d.Op; ga.ldO = d.ldO; ga.A = d.A; ga.sc_stride = TNp;
     ga.X = epX; ga.ACT = epACT; ga.SC = epSC;
     ga.mobs = sym ? a->d_mrows : nullptr; ga.Xm = epXm;
@@ -1392,7 +1083,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     const bool fused = !sym && ppo_fused(d, MT);
     // SplitPolicy with more (row group, trunk) workgroups than CUs: the critic's whole fused forward + backward rides in the
     // forward launch (k_ppo_fwd_critic), the backward launch covers the two actor trunks.  SG_PPO_CRITIC_FIRST=0/1 forces it.
-    const size_t lds_fc = sizeof(float) * ((size_t)wb_f + R * d.ldO + 2 * R * d.ldH + 2 * R * ldP + ((R * d.A + 3) & ~3) + 7 * R);
+    const size_t lds_fc = ppo_bwd_tiles_lds(d, MT, wb_f, 2, false);   // a fused body: the whole trunk
     const char* cfenv = getenv("SG_PPO_CRITIC_FIRST");
     const bool crit_first = !gw && !fused && d.kind == SG_POLICY_SPLIT && MT <= 2 && lds_fc <= (size_t)ctx->lds_bytes &&
                             (cfenv ? cfenv[0] == '1' : G * d.n_trunks > ctx->num_cu);
@@ -1408,7 +1099,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     // and a bit pattern must never be mistaken for a tagged word -- clear them whenever the mode is (re-)entered
     if (pair && !a->pair_primed) SG_CHECK(hipMemsetAsync(a->d_stacks, 0, sizeof(float) * (epoch_f + stack_f), ctx->stream));
     a->pair_primed = pair;
-    const size_t lds_f = ppo_fwd_lds(d, MT, gw), lds_b = sym ? ppo_bwd_sym_lds(d, MT, gw) : ppo_bwd_lds(d, MT, gw);
+    const size_t lds_f = ppo_fwd_lds(d, MT, gw), lds_b = sym ? bwd_sym_lds(MT, gw) : bwd_lds(MT, gw);
     const int nblk = (d.total + 8 + 255) / 256;
     const int nblk_r = (d.total + 8 + SG_PPO_REDUCE_PARAMS - 1) / SG_PPO_REDUCE_PARAMS;
     SgOptState* st = reinterpret_cast<SgOptState*>(a->d_state);
@@ -1431,24 +1122,27 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
                 pa.k1 = e * M + k + 1;
                 if (sym) {
                     pa.wbuf_floats = wb_f;
-                    launch_ppo_fwd_sym(ctx, MT, d, dim3(G, 3), lds_f, pa, gw);
+                    SG_TRY(ppo_launch(ctx, ppo_fwd_sym_family, "k_ppo_fwd_sym", SG_PROF_PPO_FWD, MT, d, dim3(G, 3), lds_f, pa, gw));
                     pa.wbuf_floats = wb_b;
-                    launch_ppo_bwd_sym(ctx, MT, d, dim3(G, 3), lds_b, pa, gw);
-                } else if (pair) {
+                    SG_TRY(ppo_launch(ctx, ppo_bwd_sym_family, "k_ppo_bwd_sym", SG_PROF_PPO_BWD, MT, d, dim3(G, 3), lds_b, pa, gw));
+                } else if (pair) {   // grid = 3 G workgroups, trunk index fastest
                     pa.wbuf_floats = wb_f;
-                    launch_ppo_pair(ctx, MT, d, G, lds_fc, pa);
+                    SG_TRY(ppo_launch(ctx, ppo_pair_family, "k_ppo_pair", SG_PROF_PPO_BWD, MT, d, dim3(3 * G), lds_fc, pa, false));
                 } else if (crit_first) {
                     pa.wbuf_floats = wb_f;
-                    launch_ppo_fwd_critic(ctx, MT, d, dim3(G, d.n_trunks), lds_fc > lds_f ? lds_fc : lds_f, pa);
+                    SG_TRY(ppo_launch(ctx, ppo_fwd_critic_family, "k_ppo_fwd_critic", SG_PROF_PPO_FWD, MT, d, dim3(G, d.n_trunks),
+                                      lds_fc > lds_f ? lds_fc : lds_f, pa, false));
                     pa.wbuf_floats = wb_b;
-                    launch_ppo_bwd(ctx, MT, d, dim3(G, d.n_trunks - 1), lds_b, pa, false, false);   // trunks 0, 1: the actors
+                    SG_TRY(ppo_launch(ctx, ppo_bwd_family, "k_ppo_bwd", SG_PROF_PPO_BWD, MT, d, dim3(G, d.n_trunks - 1), lds_b, pa,
+                                      false));   // trunks 0, 1: the actors
+                } else if (fused) {
+                    pa.wbuf_floats = wb_f;
+                    SG_TRY(ppo_launch(ctx, ppo_bwd_fused_family, "k_ppo_bwd (fused)", SG_PROF_PPO_BWD, MT, d, dim3(G, d.n_trunks), lds_b, pa, gw));
                 } else {
-                    if (!fused) {
-                        pa.wbuf_floats = wb_f;
-                        launch_ppo_fwd(ctx, MT, d, dim3(G, d.n_trunks), lds_f, pa, gw);
-                    }
-                    pa.wbuf_floats = fused ? wb_f : wb_b;
-                    launch_ppo_bwd(ctx, MT, d, dim3(G, d.n_trunks), lds_b, pa, fused, gw);
+                    pa.wbuf_floats = wb_f;
+                    SG_TRY(ppo_launch(ctx, ppo_fwd_family, "k_ppo_fwd", SG_PROF_PPO_FWD, MT, d, dim3(G, d.n_trunks), lds_f, pa, gw));
+                    pa.wbuf_floats = wb_b;
+                    SG_TRY(ppo_launch(ctx, ppo_bwd_family, "k_ppo_bwd", SG_PROF_PPO_BWD, MT, d, dim3(G, d.n_trunks), lds_b, pa, gw));
                 }
                 if (sym) SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_ppo_reduce_sym, dim3(nblk_r), dim3(256), 0, a->d_slabs, G, slab_stride,
                                    d.total, a->d_grad, a->d_part, d.trunk[0].off, d.trunk[0].off + d.trunk[0].ex);
@@ -1469,36 +1163,23 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     // With a communicator the RCCL all-reduces are part of the captured sequence (RCCL enqueues them on the capturing
     // stream like any kernel), so N > 1 keeps the one-call-per-update property; SG_PPO_GRAPH_COMM=0 or a capture the
     // RCCL build refuses falls back to direct launches.
-    const char* genv = getenv("SG_PPO_GRAPH");
-    const char* gcenv = getenv("SG_PPO_GRAPH_COMM");
-    const bool comm_ok = !a->graph_refused && (!ctx->use_comm || (sg_comm_graph_ok(ctx) && !(gcenv && !strcmp(gcenv, "0"))));
-    bool use_graph = comm_ok && !owned && !ctx->profile && !a->d_dbg && !(genv && !strcmp(genv, "0"));
-    if (use_graph) {
-        uint32_t fbits[6];
-        const float fv[6] = {a->cfg.clip_param, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B};
-        memcpy(fbits, fv, sizeof fbits);
-        uint32_t cbits;
-        memcpy(&cbits, &a->sym_coef, sizeof cbits);
-        const uint64_t key[18] = {(uint64_t)(uintptr_t)a->d_slabs, (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_perms,
-                                  (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
-                                  (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)a->policy->d_params,
-                                  (uint64_t)TN, ((uint64_t)E << 32) | (uint64_t)M, ((uint64_t)MT << 32) | (uint64_t)G,
-                                  ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
-                                  ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)a->cfg.use_clipped_value_loss,
-                                  (uint64_t)(uintptr_t)r->d_field[SG_F_LOGP], 0x50504full + (fused ? 1 : 0) + (ctx->use_comm ? 2 : 0) + (crit_first ? 4 : 0) + (gw ? 8 : 0) + (pair ? 16 : 0) + (sg_comm_peer_on(ctx) ? 32 : 0) + (sym ? 64 : 0) + ((uint64_t)sg_comm_peer_generation(ctx) << 32),
-                                  sym ? (uint64_t)(uintptr_t)a->d_mrows : 0, sym ? (uint64_t)cbits : 0};   // (M_a lives at one address for the object's life: read at run time)
-        if (!a->steps_graph || memcmp(key, a->steps_graph_key, sizeof key) != 0) {
-            if (a->steps_graph) { SG_CHECK(hipGraphExecDestroy(a->steps_graph)); a->steps_graph = nullptr; }
-            if (sg_try_capture(ctx, &a->steps_graph, enqueue_steps) != 0) {
-                a->graph_refused = true;   // reported once on stderr: direct launches from now on
-                use_graph = false;
-            } else {
-                memcpy(a->steps_graph_key, key, sizeof key);
-            }
-        }
-        if (use_graph) SG_CHECK(hipGraphLaunch(a->steps_graph, ctx->stream));
-    }
-    if (!use_graph) SG_TRY(enqueue_steps());
+    const bool comm_ok = !ctx->use_comm || (sg_comm_graph_ok(ctx) && !sg_env_is_off("SG_PPO_GRAPH_COMM"));
+    const bool use_graph = comm_ok && !owned && !ctx->profile && !a->d_dbg && !sg_env_is_off("SG_PPO_GRAPH");
+    uint32_t fbits[6];
+    const float fv[6] = {a->cfg.clip_param, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B};
+    memcpy(fbits, fv, sizeof fbits);
+    uint32_t cbits;
+    memcpy(&cbits, &a->sym_coef, sizeof cbits);
+    const uint64_t key[SG_GRAPH_KEY_WORDS] = {
+            (uint64_t)(uintptr_t)a->d_slabs, (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_perms,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
+            (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)a->policy->d_params,
+            (uint64_t)TN, ((uint64_t)E << 32) | (uint64_t)M, ((uint64_t)MT << 32) | (uint64_t)G,
+            ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
+            ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)a->cfg.use_clipped_value_loss,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_LOGP], 0x50504full + (fused ? 1 : 0) + (ctx->use_comm ? 2 : 0) + (crit_first ? 4 : 0) + (gw ? 8 : 0) + (pair ? 16 : 0) + (sg_comm_peer_on(ctx) ? 32 : 0) + (sym ? 64 : 0) + ((uint64_t)sg_comm_peer_generation(ctx) << 32),
+            sym ? (uint64_t)(uintptr_t)a->d_mrows : 0, sym ? (uint64_t)cbits : 0};   // (M_a lives at one address for the object's life: read at run time)
+    SG_TRY(sg_graph_run(ctx, &a->steps_graph, use_graph, key, enqueue_steps));
     SG_CHECK(hipGetLastError());
     a->opt_t += (int64_t)E * M;
     if (!out3) return 0;   // the caller reads the losses later (sg_results_publish): the update stays queued, no host wait

@@ -485,8 +485,8 @@ extern "C" int sg_test_fetch_probe(sg_ctx* ctx, int n_blocks, int waves, int mod
 
 extern "C" int sg_test_graph_state(sg_ppo* a, sg_disc* d, int out[2]) {
     SG_REQUIRE(out, "sg_test_graph_state: NULL argument");
-    out[0] = a ? (a->graph_refused ? 2 : (a->steps_graph ? 1 : 0)) : -1;
-    out[1] = d ? (d->graph_refused ? 2 : (d->epoch_graph ? 1 : 0)) : -1;
+    out[0] = a ? (a->steps_graph.refused ? 2 : (a->steps_graph.exec ? 1 : 0)) : -1;
+    out[1] = d ? (d->epoch_graph.refused ? 2 : (d->epoch_graph.exec ? 1 : 0)) : -1;
     return 0;
 }
 
