@@ -247,9 +247,7 @@ bool sg_gru_fits(const sg_ctx* ctx, const SgGruDesc& g);   // sg_gru.hip: the GR
 // 128-byte line per chain workgroup) and its sticky time-out word; sg_ppo::d_pair: k_ppo_pair's time-out word.
 #define SG_STEP4_FLAG_WORD0 64
 #define SG_STEP4_MAX_FLAGS 1024
-#ifndef SG_STEP4_FLAG_STRIDE
 #define SG_STEP4_FLAG_STRIDE 32           // words between two workgroups' flags: one 128-byte line each
-#endif
 #define SG_STEP4_ERR_WORD (SG_STEP4_FLAG_WORD0 + SG_STEP4_MAX_FLAGS * SG_STEP4_FLAG_STRIDE)
 #define SG_STEP4_STATE_BYTES (4 * (SG_STEP4_ERR_WORD + 16))
 #define SG_PAIR_ERR_WORD 0
@@ -371,7 +369,6 @@ struct sg_disc {
     int returns_n = 0;
     bool returns_none = true;
     uint64_t rng_calls = 0;
-    long long* d_dbg_step4 = nullptr;   // k_disc_step4's stamps (SG_STEP4_STAMPS builds, tools/step4_times.py)
     long long* d_dbg = nullptr;    // phase-timestamp buffer (test hook)
 };
 

@@ -364,51 +364,14 @@ extern "C" int sg_disc_create(sg_ctx* ctx, int input_dim, int hidden_dim, sg_dis
     SG_CHECK(hipMemcpyAsync(d->d_state, &st, sizeof st, hipMemcpyHostToDevice, ctx->stream));
     SG_CHECK(hipStreamSynchronize(ctx->stream));
     sg_ctx_learner_born(ctx);
-#if SG_STEP4_VERIFY
-    SG_CHECK(sg_dev_malloc((void**)&d->d_dbg_step4, sizeof(long long) * 8 * 512 + sizeof(float) * 128 * 8 * 32 * 64 + 4 * 96 * 8 * 8 * 64 + 8 * 4 * 512));
-    SG_CHECK(hipMemset(d->d_dbg_step4, 0, sizeof(long long) * 8 * 512 + sizeof(float) * 128 * 8 * 32 * 64 + 4 * 96 * 8 * 8 * 64 + 8 * 4 * 512));
-#endif
     *out = d;
     return 0;
 }
 
-#if SG_STEP4_VERIFY
-// debug builds only (not in include/simgan_hip.h): the operand words the tile workgroups of the last step consumed
-extern "C" SG_API int sg_debug_step4_log(sg_disc* d, float* out, long long n_floats) {
-    SG_CHECK(hipStreamSynchronize(d->ctx->stream));
-    SG_CHECK(hipMemcpy(out, reinterpret_cast<float*>(d->d_dbg_step4 + 8 * 512), sizeof(float) * n_floats, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" SG_API int sg_debug_step4_stamps(sg_disc* d, long long* out) {   // [512][4]
-    SG_CHECK(hipStreamSynchronize(d->ctx->stream));
-    SG_CHECK(hipMemcpy(out, reinterpret_cast<unsigned*>(reinterpret_cast<float*>(d->d_dbg_step4 + 8 * 512) + (size_t)128 * 8 * 32 * 64) + 96 * 8 * 8 * 64, 8 * 4 * 512, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" SG_API int sg_debug_step4_chainlog(sg_disc* d, unsigned* out) {   // [96][8][8][64]
-    SG_CHECK(hipStreamSynchronize(d->ctx->stream));
-    SG_CHECK(hipMemcpy(out, reinterpret_cast<float*>(d->d_dbg_step4 + 8 * 512) + (size_t)128 * 8 * 32 * 64, 4 * 96 * 8 * 8 * 64, hipMemcpyDeviceToHost));
-    return 0;
-}
-#endif
 extern "C" int sg_disc_destroy(sg_disc* d) {
     SG_DEVICE_WIDE();
     if (!d) return 0;
     (void)hipStreamSynchronize(d->ctx->stream);
-#if SG_STEP4_VERIFY
-    if (d->d_dbg_step4) {
-        std::vector<long long> h(8 * 512);
-        (void)hipMemcpy(h.data(), d->d_dbg_step4, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[step4 verify] %lld operand words differed on re-read (steps so far %lld)\n", h[0], (long long)d->opt_t);
-        for (long long i = 0; i < h[0] && i < 100; ++i) {
-            const long long* o = h.data() + 8 + 4 * i;
-            fprintf(stderr, "  block %lld wave %lld lane %lld half %lld cc %lld s %lld side %lld: consumed %08llx re-read %08llx step %lld off %lld\n",
-                    o[0] >> 32, (o[0] >> 16) & 0xffff, (o[0] >> 8) & 0xff, (o[0] >> 4) & 1, (o[0] >> 3) & 1, (o[0] >> 1) & 3, o[0] & 1,
-                    (unsigned long long)o[1] >> 32, (unsigned long long)o[1] & 0xffffffffull, o[2], o[3]);
-        }
-        (void)sg_dev_free(d->d_dbg_step4);
-        d->d_dbg_step4 = nullptr;
-    }
-#endif
     sg_ctx_learner_gone(d->ctx);
     for (auto& q : d->ctx->res_d) if (q == d) q = nullptr;
     float* ptrs[] = {d->d_params, d->d_m, d->d_v, d->d_slabs, d->d_state, d->d_expert, d->d_alpha, d->d_returns, d->d_feat_all, d->d_rows, d->d_wT, d->d_erows, d->d_prows};
@@ -734,7 +697,6 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
             if (fused) {
                 Step4Args sa;
                 sa.next = pg; sa.loss_acc = d->d_loss_acc;
-                sa.dbg = (SG_STEP4_VERIFY || k == n_d - 2 || n_d < 2) ? d->d_dbg_step4 : nullptr;   // stamps: one representative step
                 launch_disc_step4(ctx, dd, d, a.ops, a.B, G, wa.k1, sa);
                 continue;
             }

@@ -23,37 +23,17 @@
 // Round 5 tried the hand-off WITHOUT flags (every operand word poisoned one launch ahead and validated by its reader, no drain, no
 // flag: `SG_STEP4_POISON`): measured negative (profiles/r05_step4_poison_handoff_negative.txt) and removed from the library in
 // round 6 (git show 9df2324:simgan_amd/csrc/sg_disc_step4.hpp has it).
+//
+// The kernel carries no build switches.  The experiment switches of rounds 3-6 (ablations of the waits and of the chain's
+// publication, a re-read verifier of the operands, the hand-off without its drain, the poll without its sleep, the store and
+// load flavours below) were measured and removed; `git show b28af2c:simgan_amd/csrc/sg_disc_step4.hpp` has them.  The one
+// diagnostic that is still of use, the wall-clock stamps behind tools/step4_times.py, is tools/diag/step4_stamps.patch.
 #pragma once
-#ifndef SG_ABL
-#define SG_ABL 0
-#endif
 
 struct Step4Args {          // not preloaded: read by the workgroups that copy the next step's rows and by one vector lane at its end
     PregatherArgs next;
     double* loss_acc;
-    long long* dbg;         // SG_STEP4_STAMPS builds only (tools/step4_times.py): wall-clock stamps of a few workgroups
 };
-#define SG_STEP4_STAMP_SLOTS 16   // long longs per workgroup in Step4Args::dbg (SG_STEP4_STAMPS builds)
-#ifndef SG_STEP4_VERIFY
-#define SG_STEP4_VERIFY 0     // 1 (debug builds, batch 128): every tile wave re-reads its operands ~2 us after it consumed them and records differences
-#endif
-#ifndef SG_STEP4_NO_DRAIN
-#define SG_STEP4_NO_DRAIN 0   // 1: the hand-off WITHOUT its store drain (to see tests/test_gpu_fullsize.py::..._under_load fail)
-#endif
-#ifndef SG_STEP4_NOSLEEP
-#define SG_STEP4_NOSLEEP 0
-#endif
-#ifndef SG_STEP4_STAMPS
-#define SG_STEP4_STAMPS 0
-#endif
-#ifndef SG_STEP4_WSTORE
-#define SG_STEP4_WSTORE 0     // how the tile blocks store the new weights: 0 streaming (kept), 1 write-through, 2 plain (A/B, round 4)
-#endif
-#if SG_STEP4_STAMPS
-#define SG_STAMP(var) const long long var = wall_clock64()
-#else
-#define SG_STAMP(var) const long long var = 0
-#endif
 
 // (SG_STEP4_FLAG_WORD0 / _MAX_FLAGS / _FLAG_STRIDE / _ERR_WORD / _STATE_BYTES: sg_common.h, next to sg_disc::d_state)
 #define SG_STEP4_TIMEOUT_TICKS 300000000ll   // 3 s of the 100 MHz wall clock
@@ -61,21 +41,9 @@ struct Step4Args {          // not preloaded: read by the workgroups that copy t
 __device__ __forceinline__ float sg_ld_sc1(__amdgpu_buffer_rsrc_t r, int byte_off) {
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 16 /* sc1: served past this CU's L1 */));
 }
-// How the flag form's tile workgroups read the operand stacks once the flags are up (A/B, round 5): 16 = sc1 (past this
-// XCD's L2: every tile workgroup pulls its 64 KB through the fabric), 0 = plain (the 13 tiles of an XCD share a 32 KB slab
-// through its L2), 1 = sc0.
-#ifndef SG_STEP4_OPLOAD
-#define SG_STEP4_OPLOAD 16
-#endif
-__device__ __forceinline__ float sg_ld_op(__amdgpu_buffer_rsrc_t r, int byte_off) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, SG_STEP4_OPLOAD));
-}
-#ifndef SG_STEP4_FIRST_PLAIN
-#define SG_STEP4_FIRST_PLAIN 1   // the timed FIRST request of an operand word is a plain load (shared through the XCD's L2); 0: sc1 like the re-requests
-#endif
-__device__ __forceinline__ float sg_ld_first(__amdgpu_buffer_rsrc_t r, int byte_off) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, SG_STEP4_FIRST_PLAIN ? 0 : 16));
-}
+// The tile workgroups read the operand stacks with it too once the flags are up: past this XCD's L2, so every tile workgroup
+// pulls its 64 KB through the fabric.  A/B, round 5, against plain loads (the 13 tiles of an XCD share a 32 KB slab through
+// its L2) and sc0 loads: measured and removed; `git show b28af2c:simgan_amd/csrc/sg_disc_step4.hpp` has the switch.
 
 // One wave waits until the flags of workgroups [lo, hi) all hold `want`; false on time-out.
 // Measured and removed, round 4 (north-star, ms per update; 26.19-26.24 with this plain loop):
@@ -96,9 +64,7 @@ __device__ __forceinline__ bool sg_step4_wait(const unsigned* flags, int lo, int
         for (int j = lo + lane; j < hi; j += 64) ok = ok & (__hip_atomic_load(flags + j * SG_STEP4_FLAG_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == want);
         if (__all(ok)) return true;
         if ((it & 31) == 31 && wall_clock64() > deadline) return false;
-#if !SG_STEP4_NOSLEEP
         __builtin_amdgcn_s_sleep(1);
-#endif
     }
 }
 
@@ -122,29 +88,15 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
         if (wave >= NWC) return;   // the launch has 8 waves per workgroup for the tile blocks; the chain uses one per column tile
         int t0 = 0;
         if (tid == 0) t0 = c_st->t0;
-        SG_STAMP(ts0);
         Chain4Args ca{c_params, c_wT, c_ops, c_part, nullptr, c_B, c_G, 1.0f / (float)c_B, 10.0f};   // (time stamps: the two-launch path)
-#if SG_STEP4_VERIFY
-        if (a.dbg) ca.vlog = reinterpret_cast<unsigned*>(reinterpret_cast<float*>(a.dbg + 8 * 512) + (size_t)128 * 8 * 32 * 64);
-        long long* vst = a.dbg ? reinterpret_cast<long long*>(ca.vlog + 96 * 8 * 8 * 64) + 4 * blockIdx.x : nullptr;
-        if (vst && tid == 0) vst[0] = wall_clock64();
-#endif
-        sg_chain4_body<KF, KH, (SG_ABL & 2) ? false : true>(ca, sm);
-        SG_STAMP(ts1);
-#if SG_STEP4_VERIFY
-        if (vst && tid == 0) vst[1] = wall_clock64();
-#endif
+        sg_chain4_body<KF, KH, true>(ca, sm);
         // every wave drains its write-through stores BEFORE the barrier the flag store sits behind.  The wait has to be spelt
         // out: __syncthreads() is a workgroup-scope fence, for which gfx950 needs no vmcnt wait (the waves of a workgroup share
         // their CU's L1), and the compiler emits none -- the flag then overtakes the data under load (replicas of 8 contexts
         // sharing one GPU diverged in the 6th digit: tests/test_gpu_world.py).
-#if !SG_STEP4_NO_DRAIN
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
         __syncthreads();
-        SG_STAMP(ts2);
         if (tid == 0) __hip_atomic_store(flags + blockIdx.x * SG_STEP4_FLAG_STRIDE, (unsigned)(t0 + c_k1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (SG_STEP4_STAMPS && tid == 0 && a.dbg) { long long* o = a.dbg + SG_STEP4_STAMP_SLOTS * blockIdx.x; o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = wall_clock64(); }
         return;
     }
     const int wb = (int)blockIdx.x - w_base;
@@ -152,10 +104,7 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
     static_assert((8 - th) * (th + tf) > NV, "k_disc_step4: a spare slot must exist for the Adam-scalar lane");
     if (wb < 0) return;            // padding up to a multiple of 8: the tile map below counts XCDs from w_base
     if (wb >= ntv) {               // the next step's rows (see k_disc_chain4)
-        SG_STAMP(tg0);
         if (a.next.ops) sg_disc_pregather(a.next, wb - ntv);
-        if (SG_STEP4_STAMPS && a.dbg) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (SG_STEP4_STAMPS && tid == 0 && a.dbg) { long long* o = a.dbg + SG_STEP4_STAMP_SLOTS * blockIdx.x; o[0] = tg0; o[1] = wall_clock64(); }
         return;
     }
     SgDiscDesc d;
@@ -195,7 +144,6 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
         int img0 = 0, img1 = 0;
         sg_disc_img_pos(d, w2, tm * 16 + ((tid & 255) >> 4), tn * 16 + (tid & 15), img0, img1);
         if (tid == 0) *sh_ok = 1;
-        SG_STAMP(ts0);
         __syncthreads();
         // The stacked rows [0, 32G) come from the BCE workgroups (chain blocks [4G, 12G)), which finish ~0.7 us before the mixup
         // workgroups ([0, 4G): seven dependent GEMMs against three): their half of the two slabs is requested and contracted
@@ -204,7 +152,7 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
         const unsigned want = (unsigned)(t0 + c_k1);
         // (a time-out is sticky: once the error word is up, the waiting workgroups of every later launch give up at once instead
         // of spinning out their own three seconds -- the update ends in its normal time, with NaN losses and the error reported)
-        if (!(SG_ABL & 1) && wave == 7 && (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 || !sg_step4_wait(flags, 4 * c_G, n_chain, want, lane)) && lane == 0) *sh_ok = 0;
+        if (wave == 7 && (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 || !sg_step4_wait(flags, 4 * c_G, n_chain, want, lane)) && lane == 0) *sh_ok = 0;
         __syncthreads();
         if (!*sh_ok) { if (tid == 0) { atomicOr(err, 1u); a.loss_acc[0] = __builtin_nanf(""); } return; }   // the host sees NaN losses, then the error word
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f}, alt = acc;
@@ -221,8 +169,8 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
                     for (int s = 0; s < 4; ++s) {
                         const int c = c0 + cc * nw;
                         const int r = c < c_hi ? 16 * c + 4 * s + lq : Kt;   // past this half: the buffer's range check returns zero
-                        x[cc][s] = sg_ld_op(rL, (r * 16 + li) * 4);
-                        y[cc][s] = sg_ld_op(rR, (r * 16 + li) * 4);
+                        x[cc][s] = sg_ld_sc1(rL, (r * 16 + li) * 4);
+                        y[cc][s] = sg_ld_sc1(rR, (r * 16 + li) * 4);
                     }
                 if (first) { between(); first = false; }
 #pragma unroll
@@ -235,18 +183,15 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
             }
         };
         contract(0, half_chunks, [&]() {
-            if (!(SG_ABL & 1) && wave == 7 && !sg_step4_wait(flags, 0, 4 * c_G, want, lane) && lane == 0) *sh_ok = 0;
+            if (wave == 7 && !sg_step4_wait(flags, 0, 4 * c_G, want, lane) && lane == 0) *sh_ok = 0;
         });
         __syncthreads();
-        SG_STAMP(ts1);
         if (!*sh_ok) { if (tid == 0) { atomicOr(err, 1u); a.loss_acc[0] = __builtin_nanf(""); } return; }   // the host sees NaN losses, then the error word
         contract(half_chunks, n_chunks, []() {});
         acc += alt;
 #pragma unroll
         for (int r = 0; r < 4; ++r) red[wave][(4 * lq + r) * 16 + li] = acc[r];
-        SG_STAMP(ts2);
         __syncthreads();
-        if (SG_STEP4_STAMPS && tid == 0 && a.dbg) { long long* o = a.dbg + SG_STEP4_STAMP_SLOTS * blockIdx.x; o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = wall_clock64(); }
         if (tid < 256) {
             float g = 0.f;
             {
@@ -263,21 +208,14 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
             const float denom = sqrtf(v0) / bc2_sqrt + SG_DISC_ADAM_EPS;
             p0 = p0 - step_size * (m0 / denom);
             __builtin_amdgcn_sched_barrier(0);
-#if SG_STEP4_WSTORE == 1      // write-through (sc1) stores for what the next launch's chain blocks read
-            __hip_atomic_store(c_params + idx, p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_nontemporal_store(m0, c_m + idx);
-            __builtin_nontemporal_store(v0, c_v + idx);
-            __hip_atomic_store(c_wT + img0, p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(c_wT + img1, p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#elif SG_STEP4_WSTORE == 2    // plain stores: written back by the end-of-kernel release
-            c_params[idx] = p0; c_m[idx] = m0; c_v[idx] = v0; c_wT[img0] = p0; c_wT[img1] = p0;
-#else
+            // streaming stores for what the next launch's chain blocks read.  A/B, round 4: write-through (agent-scope atomic)
+            // stores of the parameters and images, and plain stores written back by the end-of-kernel release -- neither beat
+            // these.  Measured and removed; `git show b28af2c:simgan_amd/csrc/sg_disc_step4.hpp` has the switch.
             __builtin_nontemporal_store(p0, c_params + idx);
             __builtin_nontemporal_store(m0, c_m + idx);
             __builtin_nontemporal_store(v0, c_v + idx);
             __builtin_nontemporal_store(p0, c_wT + img0);
             __builtin_nontemporal_store(p0, c_wT + img1);
-#endif
         }
         return;
     }
@@ -300,10 +238,9 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
         float pv = 0.f, pm = 0.f, pvv = 0.f;
         if (is_param) { pv = c_params[pidx]; pm = c_m[pidx]; pvv = c_v[pidx]; }
         const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc(c_part, 0, nparts * stride * 4, 0x00020000);
-        SG_STAMP(tv0); (void)tv0;
         if (tid == 0) *sh_ok = 1;
         __syncthreads();
-        if (!(SG_ABL & 1) && wave == 7 && (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 || !sg_step4_wait(flags, 0, n_chain, (unsigned)(t0 + c_k1), lane)) && lane == 0) *sh_ok = 0;
+        if (wave == 7 && (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 || !sg_step4_wait(flags, 0, n_chain, (unsigned)(t0 + c_k1), lane)) && lane == 0) *sh_ok = 0;
         __syncthreads();
         if (!*sh_ok) { if (tid == 0) { atomicOr(err, 1u); a.loss_acc[0] = __builtin_nanf(""); } return; }   // the host sees NaN losses, then the error word
         float g = 0.f;
@@ -348,10 +285,6 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
                 a.loss_acc[1] += (double)el;
                 a.loss_acc[2] += (double)pl;
             }
-        }
-        if (SG_STEP4_STAMPS && a.dbg) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (tid == 0) a.dbg[SG_STEP4_STAMP_SLOTS * blockIdx.x + 3] = wall_clock64();
         }
     }
 }

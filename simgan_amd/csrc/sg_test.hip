@@ -570,27 +570,13 @@ extern "C" int sg_test_disc_phase_times(sg_disc* d, int enable, long long* out, 
     return 0;
 }
 
-// Test hook: per-phase shader-clock timestamps of k_ppo_fwd, row groups [0, n_blocks) (tools/ppo_phase_times.py).
-// k_disc_step4's wall-clock stamps (library built with -DSG_STEP4_STAMPS=1): 16 per workgroup, of the epoch's last-but-one step (the last has no next step's rows to copy)
-extern "C" int sg_test_disc_step4_times(sg_disc* d, int enable, long long* out, int n_blocks) {
-    SG_REQUIRE(d && n_blocks >= 0 && n_blocks <= 512, "sg_test_disc_step4_times: bad argument");
-    SG_CHECK(hipSetDevice(d->ctx->device));
-    SG_CHECK(hipStreamSynchronize(d->ctx->stream));
-    if (enable && !d->d_dbg_step4) {
-        SG_CHECK(hipMalloc((void**)&d->d_dbg_step4, sizeof(long long) * 16 * 512));
-        SG_CHECK(hipMemset(d->d_dbg_step4, 0, sizeof(long long) * 16 * 512));
-    }
-    if (out && d->d_dbg_step4) SG_CHECK(hipMemcpy(out, d->d_dbg_step4, sizeof(long long) * 16 * n_blocks, hipMemcpyDeviceToHost));
-    if (!enable && d->d_dbg_step4) { SG_CHECK(hipFree(d->d_dbg_step4)); d->d_dbg_step4 = nullptr; }
-    return 0;
-}
-
 extern "C" int sg_test_disc_gathers(sg_disc* d, long long* out) {
     SG_REQUIRE(d && out, "sg_test_disc_gathers: NULL argument");
     *out = (long long)d->n_gathers;
     return 0;
 }
 
+// Test hook: per-phase shader-clock timestamps of k_ppo_fwd, row groups [0, n_blocks) (tools/ppo_phase_times.py).
 extern "C" int sg_test_ppo_phase_times(sg_ppo* a, int enable, long long* out, int n_blocks) {
     SG_REQUIRE(a, "sg_test_ppo_phase_times: NULL argument");
     SG_CHECK(hipStreamSynchronize(a->ctx->stream));

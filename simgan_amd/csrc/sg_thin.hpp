@@ -39,19 +39,9 @@ __host__ __device__ __forceinline__ int sg4_img_index(int n, int k, int K) {
 // This lane's B operand for the whole kernel: wave-th 16-column slice of an image.
 template <int K>
 __device__ __forceinline__ void sg4_load_w(float4 (&w)[SG4_NW(K)], const float* img, int wave, int lane) {
-#if defined(SG4_W_SC1) && SG4_W_SC1   // diagnostic builds: the weight slices past the CU's L1 (and, with sc1, past stale L2 copies)
-    typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(img), 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-    for (int t = 0; t < SG4_NW(K); ++t) {
-        const u32x4_ v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)((((size_t)wave * SG4_NW(K) + t) * 64 + lane) * 16), 0, 16);
-        w[t] = float4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
-    }
-#else
     const float4* p = reinterpret_cast<const float4*>(img) + (size_t)wave * SG4_NW(K) * 64 + lane;
 #pragma unroll
     for (int t = 0; t < SG4_NW(K); ++t) w[t] = p[t * 64];
-#endif
 }
 
 // A operand of RG row groups from X (LDS or global, leading dimension ldx, 16-byte aligned rows).
@@ -70,13 +60,8 @@ __device__ __forceinline__ void sg4_load_a(float4 (&a)[RG][SG4_NCH(K)], const fl
         }
 }
 
-#ifndef SG4_TIMING_SKIP
-#define SG4_TIMING_SKIP 0        // diagnostic builds (WRONG results, timing only): 1 = every other group of four MFMAs is not issued
-#endif
 #define SG4_STEP(CC)                                                                 \
-    if (SG4_TIMING_SKIP && ((CC) & 1)) {   /* the registers stay loaded, the MFMAs are not issued */ \
-        if (4 * tc + (CC) < SG4_NW(K)) { const float4 wk = w[4 * tc + (CC) < SG4_NW(K) ? 4 * tc + (CC) : 0]; asm volatile("" ::"v"(wk.x), "v"(wk.y), "v"(wk.z), "v"(wk.w)); } \
-    } else if (4 * tc + (CC) < SG4_NW(K)) {                                          \
+    if (4 * tc + (CC) < SG4_NW(K)) {                                                 \
         const float4 wq = w[4 * tc + (CC) < SG4_NW(K) ? 4 * tc + (CC) : 0];          \
         _Pragma("unroll") for (int rg = 0; rg < RG; ++rg) {                          \
             acc[rg][0] = sg4_mfma<CC>(a[rg][tc].x, wq.x, acc[rg][0]);                \

@@ -101,3 +101,46 @@ def test_no_kernel_of_the_product_library_spills_to_scratch():
     assert len(ks) > 50, len(ks)
     bad = [(k["name"], k["vgpr_spill"], k["scratch"]) for k in ks if k["vgpr_spill"] or k["scratch"]]
     assert not bad, bad
+
+
+CSRC = os.path.join(ROOT, "simgan_amd", "csrc")
+RETIRED_SWITCHES = ("SG_ABL", "SG_STEP4_VERIFY", "SG_STEP4_NO_DRAIN", "SG_STEP4_NOSLEEP", "SG_STEP4_STAMPS", "SG_STEP4_WSTORE",
+                    "SG_STEP4_OPLOAD", "SG_STEP4_FIRST_PLAIN", "SG4_W_SC1", "SG4_TIMING_SKIP")
+
+
+def product_sources():
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)
+                  if f.endswith((".h", ".hpp", ".hip", ".cpp")) and not f.startswith("sg_test"))
+
+
+def test_product_sources_have_no_build_switches():
+    """The product sources compile one way: every preprocessor conditional asks only whether the compiler is hipcc / C++.  An
+    experiment switch one -D away from a silently wrong library (the hand-off without its drain, half the MFMAs) has no place
+    in them; a diagnostic build is a patch under tools/diag/."""
+    assert len(product_sources()) > 15
+    bad = []
+    for path in product_sources():
+        src = open(path).read().replace("\\\n", " ")
+        for m in re.finditer(r"^[ \t]*#[ \t]*(if|ifdef|ifndef|elif)\b(.*)$", src, flags=re.M):
+            macros = set(re.findall(r"[A-Za-z_]\w*", re.sub(r"//.*|/\*.*?\*/", "", m.group(2)))) - {"defined"}
+            if not macros or not macros <= {"__HIPCC__", "__cplusplus"}:
+                bad.append((os.path.basename(path), m.group(0).strip()))
+    assert not bad, bad
+
+
+def test_retired_switch_names_are_gone():
+    hits = [(os.path.basename(path), name) for path in product_sources() + [os.path.join(CSRC, "Makefile")]
+            for name in RETIRED_SWITCHES if re.search(rf"\b{name}\b", open(path).read())]
+    assert not hits, hits
+
+
+def test_stamps_patch_applies(tmp_path):
+    """tools/diag/step4_stamps.patch (the surviving diagnostic build of k_disc_step4) still applies to csrc/: a patch that
+    has rotted fails here and not on the day someone needs it."""
+    import shutil
+    import subprocess
+    shutil.copytree(CSRC, tmp_path / "simgan_amd" / "csrc", ignore=shutil.ignore_patterns("build"))
+    patch = os.path.join(ROOT, "tools", "diag", "step4_stamps.patch")
+    r = subprocess.run(["git", "apply", "--check", "--verbose", patch], cwd=tmp_path, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert "sg_disc_step4.hpp" in r.stderr and "sg_test.hip" in r.stderr, r.stderr   # (checked, not skipped as outside a repository)

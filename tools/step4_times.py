@@ -1,5 +1,6 @@
 """Wall-clock timeline of k_disc_step4 (one launch per discriminator step): chain blocks, hand-off, weight-gradient blocks.
-Needs a library built with -DSG_STEP4_STAMPS=1 (make -C simgan_amd/csrc CXXFLAGS+=...); run on the GPU box."""
+Needs the stamps variant of BOTH libraries (bash tools/build_variant.sh stamps "" tools/diag/step4_stamps.patch) in place of
+simgan_amd/libsimgan_hip.so and simgan_amd/libsimgan_hip_test.so -- in a copy of the tree; run on the GPU box."""
 import ctypes as C
 import os
 import sys
@@ -16,17 +17,30 @@ w = WORKLOADS[sys.argv[1] if len(sys.argv) > 1 else "northstar"]
 pol, disc, agent, ro, loader, expert, learner = build_problem(sg, w, 0)
 lib = _lib.load()
 _lib.check(lib.sg_rollout_fill_synthetic(ro.h, pol.h, 1234, 0.01))
-fn = _lib.load_test().sg_test_disc_step4_times
+# the hook exists in the stamps variant only, so it is bound here and not through _lib.TEST_PROTOTYPES (the in-tree test library's table)
+tlib = C.CDLL(_lib.TEST_LIB_PATH)
+if not hasattr(tlib, "sg_test_disc_step4_times"):
+    sys.exit(f"{_lib.TEST_LIB_PATH} has no sg_test_disc_step4_times: build the stamps variant (see tools/README.md)")
+tlib.sg_test_disc_step4_times.restype = C.c_int
+tlib.sg_test_disc_step4_times.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_int]
+tlib.sg_test_last_error.restype = C.c_char_p
+
+
+def fn(*args):
+    if tlib.sg_test_disc_step4_times(*args) != 0:
+        raise RuntimeError(tlib.sg_test_last_error().decode(errors="replace"))
+
+
 disc.update_gail_dyn(loader, ro)  # warm
-_lib.check_test(fn(disc.h, 1, None, 0))
+fn(disc.h, 1, None, 0)
 disc.update_gail_dyn(loader, ro)
 G = (w["B"] + 15) // 16
 kf, kh = (w["F"] + 15) // 16, (w["Hd"] + 15) // 16
 nc, wb = 12 * G, (12 * G + 7) & ~7
 n = wb + 8 * (kf + kh) + 2 * G
-S = 16   # stamp slots per workgroup (SG_STEP4_STAMP_SLOTS)
+S = 16   # stamp slots per workgroup (SG_STEP4_STAMP_SLOTS in the patch)
 buf = (C.c_longlong * (S * 512))()
-_lib.check_test(fn(disc.h, 1, buf, 512))
+fn(disc.h, 1, buf, 512)
 raw = np.array(buf, dtype=np.int64).reshape(512, S)[:n]
 t = raw * 10  # ns
 c = t[:nc]
@@ -52,10 +66,7 @@ if len(vt):
     print(f"vector blocks ({len(vt)}): start {rng(vt[:, 0])}, partials in {rng(vt[:, 1])}, reduce barrier {rng(vt[:, 2])}, stores acknowledged {rng(vt[:, 3])}")
 if len(gt):
     print(f"row-copy blocks ({len(gt)}): start {rng(gt[:, 0])}, stores acknowledged {rng(gt[:, 1])}")
-rounds = raw[wb + np.nonzero(xcd < kh)[0]][:, 7]
-print(f"tile blocks ({len(tt)}), wave 0: ready {rng(tt[:, 0])}")
-print(f"  BCE half:   requested {rng(tt[:, 1])}, first answer {rng(tt[:, 2])}, contracted {rng(tt[:, 3])}, re-request rounds {np.bincount(rounds & 0xffff)}")
-print(f"  mixup half: requested {rng(tt[:, 4])}, first answer {rng(tt[:, 5])}, contracted {rng(tt[:, 6])}, re-request rounds {np.bincount(rounds >> 16)}")
-print(f"  past the reduce barrier {rng(tt[:, 8])}, Adam done and stores acknowledged {rng(tt[:, 9])}")
-print(f"last chain body done -> median tile wave 0 has its operands contracted: {int(np.median(tt[:, 6])) - c[:, 1].max()} ns; -> last tile block's stores acknowledged: {tt[:, 9].max() - c[:, 1].max()} ns")
-_lib.check_test(fn(disc.h, 0, None, 0))
+print(f"tile blocks ({len(tt)}), wave 0: ready {rng(tt[:, 0])}, BCE half contracted and mixup flags seen {rng(tt[:, 1])}, "
+      f"all contracted {rng(tt[:, 2])}, past the reduce barrier {rng(tt[:, 3])}")
+print(f"last chain body done -> median tile wave 0 has its operands contracted: {int(np.median(tt[:, 2])) - c[:, 1].max()} ns")
+fn(disc.h, 0, None, 0)
