@@ -6,7 +6,10 @@ import os
 
 import numpy as np
 
-HALF_LOG_2PI = 0.5 * np.log(2.0 * np.pi)
+# The reference's float32 constants at their float32 VALUE, as in every float64 arbiter (the convention is stated once, in
+# tests/autograd_ref.py): torch subtracts the double log(sqrt(2 pi)) from a float32 tensor, PPO.update adds 1e-5 to a float32 std.
+HALF_LOG_2PI = float(np.float32(0.5 * np.log(2.0 * np.pi)))
+ADV_EPS = float(np.float32(1e-5))
 
 
 def param_shapes(O, A, H, Hc=None):
@@ -121,7 +124,7 @@ def minibatch_grad(sd, obs, hxs, masks, action, old_logp, adv, vpred, ret, clip,
     unflattened at float32) carries every array in float32: the same algorithm at the library's precision, for tests that
     measure the library's distance from float64 against a float32 evaluation's own."""
     f = dtype
-    HALF_LOG_2PI = f(0.5 * np.log(2.0 * np.pi))  # noqa: N806  (a float32 scalar must not promote the arrays)
+    half_log_2pi = f(HALF_LOG_2PI)  # (a float32 scalar must not promote the arrays)
     clip, vcoef, ecoef = f(clip), f(vcoef), f(ecoef)
     obs, h = np.asarray(obs, f), np.asarray(hxs, f)
     masks = np.asarray(masks, f).reshape(-1)
@@ -152,8 +155,8 @@ def minibatch_grad(sd, obs, hxs, masks, action, old_logp, adv, vpred, ret, clip,
     var = np.exp(2.0 * logstd)
     action = np.asarray(action, f)
     diff = action - mean
-    logp = (-(diff * diff) / (2.0 * var) - logstd - HALF_LOG_2PI).sum(-1)
-    ent = float(np.sum(0.5 + HALF_LOG_2PI + logstd))
+    logp = (-(diff * diff) / (2.0 * var) - logstd - half_log_2pi).sum(-1)
+    ent = float(np.sum(0.5 + half_log_2pi + logstd))
     old_logp, adv, vpred, ret = (np.asarray(q, f).reshape(-1) for q in (old_logp, adv, vpred, ret))
     ratio = np.exp(logp - old_logp)
     s1, s2 = ratio * adv, np.clip(ratio, f(1.0) - clip, f(1.0) + clip) * adv
@@ -208,7 +211,7 @@ def ppo_update(flat0, O, A, H, ro, hxs0, perms, ppo_epoch, num_mini_batch, clip,
     olp, mk = np.asarray(ro["action_log_probs"], np.float64)[..., 0], np.asarray(ro["masks"], np.float64)[..., 0]
     T, N = act.shape[:2]
     adv = ret[:-1] - vp[:-1]
-    adv = (adv - adv.mean()) / (adv.std(ddof=1) + 1e-5)
+    adv = (adv - adv.mean()) / (adv.std(ddof=1) + ADV_EPS)
     per = N // num_mini_batch
     assert N % per == 0
     m, v, step = (np.zeros_like(p), np.zeros_like(p), 0) if adam is None else (np.asarray(adam[0], np.float64).copy(),

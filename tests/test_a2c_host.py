@@ -13,7 +13,7 @@ sys.path.insert(0, ROOT)
 from helpers import ATOL, RTOL, assert_close, load  # noqa: E402
 
 A2C_CASES = ["a2c_tiny", "a2c_default", "a2c_critic64"]
-HALF_LOG_2PI = 0.5 * np.log(2.0 * np.pi)
+HALF_LOG_2PI = float(np.float32(0.5 * np.log(2.0 * np.pi)))   # the float32 value, as in every float64 arbiter (tests/autograd_ref.py)
 
 
 # ------------------------------------------------------------------ restatement
@@ -43,9 +43,10 @@ def _trunk_bwd(g, sl, p, x, h1, h2, dout, wkey, w1, b1, w2, b2, bh):
     g[sl[b1][0]] += dz1.sum(0)
 
 
-def a2c_loss_grad(params, obs_rows, act_rows, ret_rows, dims, vcoef, ecoef, dtype=np.float64):
+def a2c_loss_grad(params, obs_rows, act_rows, ret_rows, dims, vcoef, ecoef, dtype=np.float64, half_log_2pi=HALF_LOG_2PI):
     """(value_loss, action_loss, dist_entropy), d loss / d params -- all rows of the rollout at once, evaluated in `dtype`
-    (float64: the restatement; float32: the same arithmetic at the kernels' precision, for the conditioning of a case)."""
+    (float64: the restatement; float32: the same arithmetic at the kernels' precision, for the conditioning of a case).
+    half_log_2pi: log(sqrt(2 pi)) as the run compared with had it (the reference after .double(): the exact double)."""
     O, A, H, Hc = dims
     sl, n = policy_slices(O, A, H, Hc)
     f = np.dtype(dtype).type
@@ -64,8 +65,8 @@ def a2c_loss_grad(params, obs_rows, act_rows, ret_rows, dims, vcoef, ecoef, dtyp
     ls = p["ls"]
     var = np.exp(f(2.0) * ls)
     diff = act - mu
-    logp = (-(diff * diff) / (f(2.0) * var) - ls - f(HALF_LOG_2PI)).sum(1)
-    ent = float(np.sum(f(0.5) + f(HALF_LOG_2PI) + ls))
+    logp = (-(diff * diff) / (f(2.0) * var) - ls - f(half_log_2pi)).sum(1)
+    ent = float(np.sum(f(0.5) + f(half_log_2pi) + ls))
     adv = R - v
     value_loss = float(np.mean(adv * adv))
     action_loss = float(-np.mean(adv * logp))
