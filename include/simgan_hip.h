@@ -172,6 +172,25 @@ SG_API int sg_rollout_compute_returns_policy(sg_rollout *r, sg_policy *p, int us
 /* Synthetic rollout fill on device for benchmarks: obs, obs_feat ~ N(0,1);
  * actions/logp/value_preds from policy.act; masks ~ Bernoulli(1-p_done); bad_masks = 1. */
 SG_API int sg_rollout_fill_synthetic(sg_rollout *r, sg_policy *p, uint64_t seed, float p_done);
+/* Mirror-augmented rollouts, a2c/main.py:171-245 (--dup-sym): the rollout has N = 2n columns, [0, n) the environments and
+ * column n + j the mirror image of column j.  The reference mirrors every step's rows on the host and inserts 2n rows
+ * (:181-185, :231-242); here the mirrored half is made on the device.  m_obs [O*O] and m_act [A*A] are row-major linear
+ * maps, mirrored = M x (what mirror_obsact_batch's per-row callable computes, my_pybullet_envs/utils.py:334-357), uploaded
+ * once.  m_act is required; m_obs NULL (the convention of sg_ppo_set_symmetry): the caller mirrors observations itself and
+ * uploads OBS full-width, and sg_rollout_dup_sym leaves OBS alone.  Odd N and non-finite entries are errors. */
+SG_API int sg_rollout_set_mirrors(sg_rollout *r, const float *m_obs, const float *m_act);
+/* The mirrored half of every slot in ONE launch, queued on the context's stream (the host does not wait): a2c/main.py:232-242
+ * for all T steps at once and :181-185 for slot 0.  OBS and ACTIONS go through M_obs / M_act (double accumulation over
+ * ascending j, zero entries skipped, one cast: sg_ppo_set_symmetry's arithmetic, exact for a signed permutation); OBS_FEAT,
+ * REWARDS, VALUE_PREDS, LOGP, MASKS and BAD_MASKS are repeated (.repeat(2, 1), obs_feat included although it is a copy of the
+ * observation).  Slots 0..T of OBS, OBS_FEAT, MASKS, BAD_MASKS and slots 0..T-1 of ACTIONS, REWARDS, LOGP, VALUE_PREDS are
+ * written; VALUE_PREDS[T], RETURNS, ADVANTAGES and columns [0, n) of every field are left alone (the bootstrap value of a
+ * mirrored column is get_value(obs[-1]) = V(mirror(s_T)), :247-250, not a repeat).  An error before sg_rollout_set_mirrors. */
+SG_API int sg_rollout_dup_sym(sg_rollout *r);
+/* Columns [0, n_cols) of every slot of a field, host -> device, as one strided copy: what crosses the link of a rollout whose
+ * other columns the device makes itself (the first half of a2c/main.py:241-242's insert).  host is the FULL-width field
+ * (count = its size, as for sg_rollout_upload), e.g. the page-locked host tensor; its other columns are not read. */
+SG_API int sg_rollout_upload_columns(sg_rollout *r, int field, int n_cols, const float *host, int64_t count);
 
 /* ---------------------------------------------------------------------- PPO */
 typedef struct {

@@ -85,6 +85,9 @@ PROTOTYPES = {
     "sg_rollout_compute_returns_policy": (C.c_int, [H, H, C.c_int, C.c_float, C.c_float, C.c_int]),
     "sg_rollout_fill_synthetic": (C.c_int, [H, H, C.c_uint64, C.c_float]),
     "sg_rollout_count_dones": (C.c_int, [H, c_double_p]),
+    "sg_rollout_set_mirrors": (C.c_int, [H, c_float_p, c_float_p]),
+    "sg_rollout_dup_sym": (C.c_int, [H]),
+    "sg_rollout_upload_columns": (C.c_int, [H, C.c_int, C.c_int, c_float_p, C.c_int64]),
     "sg_ppo_create": (C.c_int, [H, H, C.POINTER(PPOConfig), C.POINTER(H)]),
     "sg_ppo_destroy": (C.c_int, [H]),
     "sg_ppo_set_lr": (C.c_int, [H, C.c_float]),

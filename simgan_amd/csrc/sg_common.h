@@ -270,6 +270,10 @@ struct sg_rollout {
     // stamp is never shared by two rollouts -- a destroyed rollout's successor at the same address with the same upload history
     // cannot be mistaken for it by a cache keyed on (pointer, rows, stamp) (sg_disc.hip: the replicated-mode all-gather cache)
     uint64_t feat_version = sg_next_feat_version();
+    // mirror-augmented rollout (sg_rollout_set_mirrors, sg_dup_sym.hip): columns [N/2, N) are the mirror images of [0, N/2)
+    bool mirrors_set = false;
+    float* d_mobs = nullptr;             // [O][O] linear obs mirror, or NULL: the caller uploads OBS full-width
+    float* d_mact = nullptr;             // [A][A] action mirror
 };
 
 // A captured launch sequence and what it was captured for (sg_graph_run, below)

@@ -48,6 +48,8 @@ extern "C" int sg_rollout_destroy(sg_rollout* r) {
     for (int f = 0; f < SG_F_COUNT; ++f)
         if (r->d_field[f]) (void)sg_dev_free(r->d_field[f]);
     if (r->d_perm) (void)sg_dev_free(r->d_perm);
+    if (r->d_mobs) (void)sg_dev_free(r->d_mobs);
+    if (r->d_mact) (void)sg_dev_free(r->d_mact);
     delete r;
     return 0;
 }

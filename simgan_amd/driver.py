@@ -206,6 +206,13 @@ def _returns_resident(self):
     host wait per update, the only one -- and the scan runs on the device's rewards / values / masks."""
     ro, lib = self.rollouts, self.rollouts.lib
     if self.actor_critic.is_recurrent:
+        if getattr(ro, "dup_sym", False):
+            # mirror-augmented rollout: the host mirrors hold columns [0, n) only, the device made the rest -- slot T of obs and
+            # masks comes back first (this path waits for the device anyway), so that the bootstrap value of a mirrored column
+            # is V(mirror(s_T)) (a2c/main.py:247-250 over all 2n columns)
+            for f in (_lib.F_OBS, _lib.F_MASKS):
+                a = ro._host_np(f)
+                _lib.check(lib.sg_rollout_download_step(ro.h, f, ro.num_steps, _lib.fptr(a[-1]), a[-1].size))
         nv = _lib.as_f32(self.actor_critic.get_value(ro.obs[-1], ro.recurrent_hidden_states[-1], ro.masks[-1])).reshape(-1)
         _lib.check(lib.sg_rollout_compute_returns(ro.h, _lib.fptr(nv), 1 if self.use_gae else 0, float(self.gamma), float(self.gae_lambda),
                                                   1 if self.use_proper_time_limits else 0))
@@ -248,8 +255,16 @@ class PpoLearner(object):
     a2c/main.py:168-169,218, my_pybullet_envs/utils.py:310-331)."""
 
     def __init__(self, actor_critic, agent, rollouts, gamma=0.99, gae_lambda=0.95, use_gae=True,
-                 use_proper_time_limits=True, use_linear_lr_decay=False, lr=None, num_updates=None):
+                 use_proper_time_limits=True, use_linear_lr_decay=False, lr=None, num_updates=None, dup_sym=None):
         self.actor_critic, self.agent, self.rollouts = actor_critic, agent, rollouts
+        # a2c/main.py:171-245 (--dup-sym): dup_sym = (mirror_obs, mirror_act) makes `rollouts` mirror-augmented -- it must have
+        # 2 * envs.num_envs columns; collect() acts on the first half and inserts through insert_dup_sym, update() is unchanged
+        # (get_value, compute_returns, the agent's update and after_update run over all 2n columns).  With a communicator of
+        # world > 1 the duplication is local to each rank's column shard, and injected permutations number the rank's 2n
+        # columns as they lie (environments first, their mirror images behind them).
+        self.dup_sym = dup_sym is not None
+        if self.dup_sym:
+            rollouts.enable_dup_sym(*dup_sym)
         self.gamma, self.gae_lambda, self.use_gae = gamma, gae_lambda, use_gae
         self.use_proper_time_limits = use_proper_time_limits
         self.use_linear_lr_decay, self.lr, self.num_updates = use_linear_lr_decay, lr, num_updates
@@ -272,13 +287,23 @@ class PpoLearner(object):
     # ---------------------------------------------------------------- rollout fill (:207-244)
     def collect(self, envs, feat_select_func=None):
         ro, pol = self.rollouts, self.actor_critic
+        n = ro.num_processes
+        if self.dup_sym:
+            n = ro.num_processes // 2
+            if ro.num_processes != 2 * envs.num_envs:
+                raise ValueError(f"PpoLearner(dup_sym=...): the rollout has {ro.num_processes} columns; {envs.num_envs} environments "
+                                 f"and their mirror images need 2 * num_envs = {2 * envs.num_envs}")
+        insert = ro.insert_dup_sym if self.dup_sym else ro.insert
         for step in range(ro.num_steps):
-            value, action, logp, hxs = pol.act(ro.obs[step], ro.recurrent_hidden_states[step], ro.masks[step])
+            if self.dup_sym:   # :211-214 -- act on the environments' columns only
+                value, action, logp, hxs = pol.act(ro.obs[step, :n], ro.recurrent_hidden_states[step, :n], ro.masks[step, :n])
+            else:
+                value, action, logp, hxs = pol.act(ro.obs[step], ro.recurrent_hidden_states[step], ro.masks[step])
             obs, reward, done, infos = envs.step(action)
             feat = obs if feat_select_func is None else feat_select_func(obs)
             masks = np.array([[0.0] if d else [1.0] for d in done], np.float32)
             bad = np.array([[0.0] if 'bad_transition' in info.keys() else [1.0] for info in infos], np.float32)
-            ro.insert(obs, hxs, action, logp, value, reward, to_host_tensor(masks), to_host_tensor(bad), feat)
+            insert(obs, hxs, action, logp, value, reward, to_host_tensor(masks), to_host_tensor(bad), feat)
         if ro.device_resident:
             ro.sync_to_device()
 

@@ -84,6 +84,7 @@ class RolloutStorage(object):
         self._synced = {}            # field -> (weakref of the host tensor, its _version) when the device copy last matched it
         self._crcs = {}              # SG_ROLLOUT_VERIFY=1: field -> crc32 of the host content at that moment
         self.bytes_uploaded = 0      # host -> device traffic of this rollout so far (bench.py's `dropin` leg reads it)
+        self._dup = None             # enable_dup_sym: {"n", "m_obs" | None, "m_act", "obs_fn" | None}
 
         h = _lib.H()
         _lib.check(self.lib.sg_rollout_create(self.ctx.h, T, N, O, A, F, C.byref(h)))
@@ -139,6 +140,8 @@ class RolloutStorage(object):
         return zlib.crc32(self._host_np(field))
 
     def sync_to_device(self, fields=None):
+        if self._dup is not None and self.device_resident:
+            return self._sync_to_device_dup_sym(fields)
         for f in (fields if fields is not None else _FIELD_ATTR):
             a = self._host_np(f)
             if a.size:
@@ -208,6 +211,115 @@ class RolloutStorage(object):
         put(self.bad_masks[s + 1], bad_masks)
         self.step = (self.step + 1) % self.num_steps
         self._host_written = True
+
+    # ------------------------------------------------- mirror-augmented rollouts (a2c/main.py:171-245, --dup-sym)
+    def enable_dup_sym(self, mirror_obs, mirror_act):
+        """The rollout's N = 2n columns are n environments and their n mirror images: column n + j mirrors column j.
+        mirror_act: [A, A] matrix or a per-row callable, which must be linear (probed into its matrix; ValueError otherwise).
+        mirror_obs: [O, O] matrix (the mirrored observations are made where the rollout lives) or any per-row callable,
+        applied on the host row by row in both modes, as PPO applies it for the symmetry loss.  Matrices act on rows:
+        mirrored = M @ x.  Fill the rollout through set_initial_obs_dup_sym / insert_dup_sym afterwards."""
+        from . import symmetry as _sym
+        N = self.num_processes
+        if N % 2:
+            raise ValueError(f"enable_dup_sym: the rollout has num_processes = {N}, an odd number: a mirror-augmented rollout "
+                             "holds n environments and their n mirror images (num_processes = 2n)")
+        if mirror_act is None:
+            raise ValueError("enable_dup_sym: mirror_act is required")
+        A, O = self.act_dim, self.obs_dim
+        m_act = _sym.probe_linear(mirror_act, A, "mirror_act") if callable(mirror_act) else _sym.as_matrix(mirror_act, A, "mirror_act")
+        if callable(mirror_obs):
+            obs_fn, m_obs = mirror_obs, None
+        else:
+            obs_fn, m_obs = None, _sym.as_matrix(mirror_obs, O, "mirror_obs")
+        _lib.check(self.lib.sg_rollout_set_mirrors(self.h, None if m_obs is None else _lib.fptr(m_obs), _lib.fptr(m_act)))
+        self._dup = {"n": N // 2, "m_obs": m_obs, "m_act": m_act, "obs_fn": obs_fn}
+
+    @property
+    def dup_sym(self):
+        """True once enable_dup_sym made the rollout mirror-augmented."""
+        return self._dup is not None
+
+    def _dup_state(self, who):
+        if self._dup is None:
+            raise RuntimeError(f"{who}: the rollout is not mirror-augmented: call enable_dup_sym(mirror_obs, mirror_act) first")
+        return self._dup
+
+    def _dup_rows(self, x, width, who, what):
+        a = _lib.as_f32(x).reshape(-1, width) if width else np.zeros((self._dup["n"], 0), np.float32)
+        if a.shape[0] != self._dup["n"]:
+            raise ValueError(f"{who}: {what} must hold n = {self._dup['n']} rows (one per environment), got {a.shape[0]}")
+        return a
+
+    def _dup_mirror_obs(self, rows):
+        from . import symmetry as _sym
+        d = self._dup
+        return _sym.mirror_rows(d["obs_fn"], rows) if d["obs_fn"] is not None else _sym.matrix_rows(d["m_obs"], rows)
+
+    def _dup_put(self, dst, rows, mirrored=None, both=False):
+        """rows -> columns [0, n) of the slot `dst`; columns [n, 2n) get `mirrored` (default: the rows again) in host mode,
+        or when `both` is set; on a device-resident rollout they are left to sg_rollout_dup_sym."""
+        n = self._dup["n"]
+        full = both or not self.device_resident
+        src = np.concatenate([rows, rows if mirrored is None else mirrored]) if full else rows
+        tgt = dst if full else dst[:n]
+        if torch is not None and hasattr(tgt, "copy_"):
+            tgt.copy_(torch.as_tensor(np.ascontiguousarray(src)).reshape(tgt.shape))
+        else:
+            tgt[...] = src.reshape(tgt.shape)
+
+    def set_initial_obs_dup_sym(self, obs, obs_feat=None):
+        """a2c/main.py:181-185: obs[0] = cat(obs, mirror_obs(obs)), obs_feat[0] = obs_feat repeated; obs / obs_feat hold n rows."""
+        d = self._dup_state("set_initial_obs_dup_sym")
+        rows = self._dup_rows(obs, self.obs_dim, "set_initial_obs_dup_sym", "obs")
+        host_obs = d["obs_fn"] is not None     # a callable mirror: OBS is mirrored here and crosses the link full-width
+        self._dup_put(self.obs[0], rows, self._dup_mirror_obs(rows) if (host_obs or not self.device_resident) else None, both=host_obs)
+        if obs_feat is not None:
+            self._dup_put(self.obs_feat[0], self._dup_rows(obs_feat, self.feat_len, "set_initial_obs_dup_sym", "obs_feat"))
+        self._host_written = True
+
+    def insert_dup_sym(self, obs, recurrent_hidden_states, actions, action_log_probs,
+                       value_preds, rewards, masks, bad_masks, obs_feat=None):
+        """a2c/main.py:231-242: insert()'s arguments with n rows each; observations and actions are mirrored into columns
+        [n, 2n), everything else (obs_feat included) is repeated.  Host (drop-in) mode writes both halves of the host tensors, the
+        mirrored half in the device kernel's arithmetic (symmetry.matrix_rows).  On a device-resident rollout only columns
+        [0, n) are written -- recurrent_hidden_states, which has no device twin, in both halves -- and sync_to_device() sends
+        those columns and has the device make the rest."""
+        from . import symmetry as _sym
+        d = self._dup_state("insert_dup_sym")
+        who, s = "insert_dup_sym", self.step
+        resident, host_obs = self.device_resident, d["obs_fn"] is not None
+        rows = self._dup_rows(obs, self.obs_dim, who, "obs")
+        self._dup_put(self.obs[s + 1], rows, self._dup_mirror_obs(rows) if (host_obs or not resident) else None, both=host_obs)
+        if obs_feat is not None:
+            self._dup_put(self.obs_feat[s + 1], self._dup_rows(obs_feat, self.feat_len, who, "obs_feat"))
+        hx = self.recurrent_hidden_states
+        self._dup_put(hx[s + 1], self._dup_rows(recurrent_hidden_states, hx.shape[-1], who, "recurrent_hidden_states"), both=True)
+        act = self._dup_rows(actions, self.act_dim, who, "actions")
+        self._dup_put(self.actions[s], act, None if resident else _sym.matrix_rows(d["m_act"], act))
+        self._dup_put(self.action_log_probs[s], self._dup_rows(action_log_probs, 1, who, "action_log_probs"))
+        self._dup_put(self.value_preds[s], self._dup_rows(value_preds, 1, who, "value_preds"))
+        self._dup_put(self.rewards[s], self._dup_rows(rewards, 1, who, "rewards"))
+        self._dup_put(self.masks[s + 1], self._dup_rows(masks, 1, who, "masks"))
+        self._dup_put(self.bad_masks[s + 1], self._dup_rows(bad_masks, 1, who, "bad_masks"))
+        self.step = (self.step + 1) % self.num_steps
+        self._host_written = True
+
+    def _sync_to_device_dup_sym(self, fields=None):
+        """sync_to_device() of a device-resident mirror-augmented rollout: columns [0, n) of every field cross the link (OBS
+        full-width when mirror_obs is a callable), then one launch makes columns [n, 2n) on the device."""
+        d = self._dup
+        for f in (fields if fields is not None else _FIELD_ATTR):
+            a = self._host_np(f)
+            if a.size:
+                if f == _lib.F_OBS and d["obs_fn"] is not None:
+                    _lib.check(self.lib.sg_rollout_upload(self.h, f, _lib.fptr(a), a.size))
+                    self.bytes_uploaded += a.nbytes
+                else:
+                    _lib.check(self.lib.sg_rollout_upload_columns(self.h, f, d["n"], _lib.fptr(a), a.size))
+                    self.bytes_uploaded += a.nbytes // 2
+            self._synced[f] = self._stamp(f)
+        _lib.check(self.lib.sg_rollout_dup_sym(self.h))
 
     def mod_reward(self, offset, reverse_l):
         """a2c/storage.py:86-94 (called by no shipped script): add the per-environment `offset` [N] to the rewards of the

@@ -84,6 +84,22 @@ def probe_linear(fn, n, what, trials=8, seed=0):
     return as_matrix(m, n, what)
 
 
+def matrix_rows(m, rows):
+    """M x for every row of `rows` ([R, n] float32) with the device kernels' arithmetic (k_mirror_rows, k_dup_sym): the float32
+    entries widened to float64, the products summed over ascending j, zero entries of M skipped, one cast to float32.  A
+    signed permutation is exact; a dense M gives the bits the device gives."""
+    m = np.asarray(m, np.float32)
+    x = np.asarray(rows, np.float32)
+    x = x.reshape(-1, m.shape[1]).astype(np.float64)
+    out = np.zeros((x.shape[0], m.shape[0]), np.float64)
+    for j in range(m.shape[1]):
+        col = m[:, j].astype(np.float64)
+        nz = col != 0.0
+        if nz.any():
+            out[:, nz] = out[:, nz] + x[:, j:j + 1] * col[nz]
+    return np.ascontiguousarray(out.astype(np.float32))
+
+
 def mirror_rows(fn, rows):
     """mirror_obsact_batch(rows, ..., fn, augment=False) (my_pybullet_envs/utils.py:334-357): fn on every row, float32."""
     out = np.asarray([np.asarray(fn(r), np.float64).reshape(-1) for r in rows], np.float32)
