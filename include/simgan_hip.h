@@ -96,6 +96,18 @@ SG_API int sg_policy_create(sg_ctx *ctx, int kind, int obs_dim, int act_dim, int
  * state_dict order and entry points are unchanged; base.critic.* and base.critic_linear take the critic's width. */
 SG_API int sg_policy_create2(sg_ctx *ctx, int kind, int obs_dim, int act_dim, int hidden, int num_feet, int critic_hidden,
                              sg_policy **out);
+/* Policy on a Discrete / MultiBinary action space (a2c/model.py:52-62, a2c/distributions.py:33-88,157-168): sg_policy_create2's
+ * arguments plus the distribution and its head width.  dist SG_DIST_GAUSSIAN: n_out is ignored and the call is
+ * sg_policy_create2.  SG_DIST_CATEGORICAL (Discrete(n_out)): act_dim must be 1 -- an action row holds the class index as a
+ * float, which is why n_out < 2^24 -- and the head is Linear(hidden, n_out).  SG_DIST_BERNOULLI (MultiBinary(n_out)): act_dim
+ * == n_out, an action row holds n_out 0/1 floats.  Neither has a log-std: the flat order ends with dist.linear.weight
+ * [n_out, hidden], dist.linear.bias [n_out].  kind must be SG_POLICY_MLP.  `noise` of sg_policy_act is then UNIFORM draws in
+ * [0, 1): one per row (categorical: inverse CDF over ascending class index) or one per bit (Bernoulli: bit = u < p).
+ * sg_ppo_create (any world) and sg_a2c_create take such a policy; sg_acktr_create, sg_ppo_set_symmetry (coef > 0) and
+ * sg_policy_act_ensemble refuse it. */
+enum { SG_DIST_GAUSSIAN = 0, SG_DIST_CATEGORICAL = 1, SG_DIST_BERNOULLI = 2 };
+SG_API int sg_policy_create3(sg_ctx *ctx, int kind, int obs_dim, int act_dim, int hidden, int num_feet, int critic_hidden,
+                             int dist, int n_out, sg_policy **out);
 SG_API int sg_policy_destroy(sg_policy *p);
 SG_API int sg_policy_num_params(const sg_policy *p, int64_t *n);
 /* nn.Module.load_state_dict / state_dict, flattened. */

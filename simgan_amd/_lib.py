@@ -23,6 +23,7 @@ H = C.c_void_p  # opaque handle
 F_OBS, F_OBS_FEAT, F_ACTIONS, F_REWARDS, F_VALUE_PREDS, F_RETURNS, F_LOGP, F_MASKS, F_BAD_MASKS, \
     F_ADVANTAGES = range(10)
 POLICY_MLP, POLICY_SPLIT, POLICY_GRU = 0, 1, 2
+DIST_GAUSSIAN, DIST_CATEGORICAL, DIST_BERNOULLI = 0, 1, 2
 PROF_DISC_CHAIN, PROF_DISC_WGRAD, PROF_PPO_FWD, PROF_PPO_BWD, PROF_PPO_REDUCE, PROF_RELABEL, PROF_PPO_ADAM = range(7)
 
 
@@ -60,6 +61,7 @@ PROTOTYPES = {
     "sg_ctx_set_disc_dp": (C.c_int, [H, C.c_int]),
     "sg_policy_create": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(H)]),
     "sg_policy_create2": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(H)]),
+    "sg_policy_create3": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(H)]),
     "sg_policy_destroy": (C.c_int, [H]),
     "sg_policy_num_params": (C.c_int, [H, c_i64_p]),
     "sg_policy_set_params": (C.c_int, [H, c_float_p, C.c_int64]),

@@ -76,6 +76,9 @@ class A2C_ACKTR():
         if getattr(actor_critic, "is_recurrent", False):
             raise NotImplementedError("A2C_ACKTR: implemented for feed-forward policies only, not for a recurrent Policy "
                                       "(the reference allows --recurrent-policy with a2c and refuses it with acktr)")
+        if acktr and getattr(actor_critic, "dist_kind", 0):
+            raise NotImplementedError("A2C_ACKTR(acktr=True): K-FAC's Fisher sampling is built for the Gaussian head (Box action spaces) "
+                                      "only, not for a Discrete / MultiBinary policy; acktr=False (A2C) runs")
         if acktr:
             self._init_acktr(actor_critic, value_loss_coef, entropy_coef, seed)
             return

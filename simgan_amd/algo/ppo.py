@@ -71,6 +71,9 @@ class PPO():
         if self.recurrent and getattr(actor_critic.ctx, "world", 1) > 1:
             raise NotImplementedError("PPO with a recurrent Policy runs on one rank: data-parallel PPO through time is not implemented "
                                       f"(this context's communicator has world {actor_critic.ctx.world})")
+        if getattr(actor_critic, "dist_kind", 0) and mirror_obs is not None and symmetry_coef > 0:
+            raise NotImplementedError("mirror-symmetry loss: it compares action means, which a Categorical / Bernoulli head (Discrete / "
+                                      "MultiBinary action space) does not have; symmetry_coef > 0 needs a Box action space")
         self.ctx = actor_critic.ctx
         self.lib = self.ctx.lib
         cfg = _lib.PPOConfig(float(clip_param), int(ppo_epoch), int(num_mini_batch), float(value_loss_coef),

@@ -163,7 +163,30 @@ def _rms_state(rms):
     return {"mean": np.asarray(rms.mean, np.float64), "var": np.asarray(rms.var, np.float64), "count": float(rms.count)}
 
 
-def _policy_dims(class_name, sd):
+# the distribution modules of a2c/distributions.py that hold one `linear` (a2c/model.py:58-62) -> (kind suffix, SG_DIST_* value)
+_LINEAR_DISTS = {"Categorical": ("mlp_categorical", 1), "Bernoulli": ("mlp_bernoulli", 2)}
+
+
+def _dist_class(actor_critic):
+    """Class name of the policy object's `dist` module (None when it has none)."""
+    d = (getattr(actor_critic, "_modules", None) or {}).get("dist")
+    return None if d is None else type(d).__name__
+
+
+def _policy_dims(class_name, sd, dist_class=None):
+    if class_name == "Policy" and "dist.linear.weight" in sd:
+        # Discrete / MultiBinary action space: the two heads have the same parameters, the dist module's class tells them apart
+        if dist_class not in _LINEAR_DISTS:
+            raise ValueError(f"checkpoint policy has a dist.linear head inside a {dist_class} module: Categorical or Bernoulli expected")
+        H, O = sd["base.actor.0.weight"].shape
+        K = sd["dist.linear.weight"].shape[0]
+        Hc = sd["base.critic.0.weight"].shape[0]
+        assert "base.gru.weight_ih_l0" not in sd, "a recurrent policy with a Categorical / Bernoulli head is not built"
+        assert sd["base.critic.0.weight"].shape == (Hc, O) and sd["base.critic.2.weight"].shape == (Hc, Hc) and \
+            sd["base.critic_linear.weight"].shape == (1, Hc), "inconsistent critic shapes in the checkpoint"
+        kind, dist = _LINEAR_DISTS[dist_class]
+        return dict(kind=kind, obs_dim=int(O), act_dim=1 if dist == 1 else int(K), hidden=int(H), num_feet=1, critic_hidden=int(Hc),
+                    dist=dist, n_out=int(K))
     if class_name == "Policy":
         H, O = sd["base.actor.0.weight"].shape
         A = sd["dist.fc_mean.weight"].shape[0]
@@ -190,7 +213,7 @@ def policy_from_module_state(class_name, state):
     holder = _RefStub()
     holder.__setstate__(state)
     sd = _normalise_split_bias(_walk(holder, "", collections.OrderedDict()))
-    return _policy_dims(class_name, sd), sd
+    return _policy_dims(class_name, sd, _dist_class(holder)), sd
 
 
 def read_reference_checkpoint(path):
@@ -200,7 +223,7 @@ def read_reference_checkpoint(path):
     actor_critic, ob_rms = (obj[0], obj[1]) if isinstance(obj, (list, tuple)) else (obj, None)
     sd = _normalise_split_bias(_walk(actor_critic, "", collections.OrderedDict()))
     name = type(actor_critic).__name__
-    out = _policy_dims(name, sd)
+    out = _policy_dims(name, sd, _dist_class(actor_critic))
     out.update(class_name=name, state_dict=sd, ob_rms=_rms_state(ob_rms))
     return out
 
@@ -249,7 +272,7 @@ class _RefModules(object):
     previous attributes restored afterwards."""
 
     NAMES = {"model": ["Policy", "MLPBase"], "model_split": ["SplitPolicy", "SplitPolicyBaseNew", "StateDiagGaussianNew"],
-             "distributions": ["DiagGaussian"], "utils": ["AddBias"]}
+             "distributions": ["DiagGaussian", "Categorical", "Bernoulli"], "utils": ["AddBias"]}
 
     def __enter__(self):
         import torch
@@ -314,18 +337,22 @@ def save_reference_checkpoint(path, kind, state_dict, ob_rms=None):
     import torch
     sd = {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32) for k, v in state_dict.items()}
     with _RefModules() as ref:
-        if kind == "mlp":
+        if kind in ("mlp", "mlp_categorical", "mlp_bernoulli"):
             base = ref.new("MLPBase")
             base._hidden_size = int(sd["base.actor.0.weight"].shape[0])
             base._recurrent = False
             base.actor = _trunk(sd, "base.actor")
             base.critic = _trunk(sd, "base.critic")
             base.critic_linear = _linear(sd["base.critic_linear.weight"], sd["base.critic_linear.bias"])
-            dist = ref.new("DiagGaussian")
-            dist.fc_mean = _linear(sd["dist.fc_mean.weight"], sd["dist.fc_mean.bias"])
-            bias = ref.new("AddBias")
-            bias._bias = torch.nn.Parameter(torch.from_numpy(sd["dist.logstd._bias"].reshape(-1, 1).copy()))
-            dist.logstd = bias
+            if kind == "mlp":
+                dist = ref.new("DiagGaussian")
+                dist.fc_mean = _linear(sd["dist.fc_mean.weight"], sd["dist.fc_mean.bias"])
+                bias = ref.new("AddBias")
+                bias._bias = torch.nn.Parameter(torch.from_numpy(sd["dist.logstd._bias"].reshape(-1, 1).copy()))
+                dist.logstd = bias
+            else:   # a2c/distributions.py:74-88,157-168: one Linear called `linear`
+                dist = ref.new("Categorical" if kind == "mlp_categorical" else "Bernoulli")
+                dist.linear = _linear(sd["dist.linear.weight"], sd["dist.linear.bias"])
             pol = ref.new("Policy")
         elif kind == "split":
             base = ref.new("SplitPolicyBaseNew")
@@ -387,7 +414,13 @@ def reference_module_state(kind, sd):
     CPU (my_pybullet_envs/utils.py:24-57, hopper_env_combined_policy.py:113-140), with no GPU and without this package."""
     import torch
     sd = {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32) for k, v in sd.items()}
-    if kind == "mlp":
+    if kind in ("mlp_categorical", "mlp_bernoulli"):
+        base = _holder("model", "MLPBase", modules=[("actor", _trunk(sd, "base.actor")), ("critic", _trunk(sd, "base.critic")),
+                                                    ("critic_linear", _linear(sd["base.critic_linear.weight"], sd["base.critic_linear.bias"]))],
+                       _hidden_size=int(sd["base.actor.0.weight"].shape[0]), _recurrent=False)
+        dist = _holder("distributions", "Categorical" if kind == "mlp_categorical" else "Bernoulli",
+                       modules=[("linear", _linear(sd["dist.linear.weight"], sd["dist.linear.bias"]))])
+    elif kind == "mlp":
         base = _holder("model", "MLPBase", modules=[("actor", _trunk(sd, "base.actor")), ("critic", _trunk(sd, "base.critic")),
                                                     ("critic_linear", _linear(sd["base.critic_linear.weight"], sd["base.critic_linear.bias"]))],
                        _hidden_size=int(sd["base.actor.0.weight"].shape[0]), _recurrent=False)
@@ -424,12 +457,32 @@ class _Box(object):
 _Box.__name__ = "Box"
 
 
+class _Discrete(object):
+    def __init__(self, n):
+        self.n = int(n)
+
+
+_Discrete.__name__ = "Discrete"
+
+
+class _MultiBinary(object):
+    def __init__(self, n):
+        self.shape = (int(n),)
+
+
+_MultiBinary.__name__ = "MultiBinary"
+
+
 def load_policy(path, ctx=None):
     """my_pybullet_envs/utils.py:24-57 / a2c/main.py:78-84: -> (Policy | SplitPolicy on the GPU, ob_rms dict or None)."""
     from .model import Policy
     from .model_split import SplitPolicy
     ck = read_reference_checkpoint(path)
-    if ck["kind"] == "mlp":
+    if ck["kind"] in ("mlp_categorical", "mlp_bernoulli"):
+        space = _Discrete(ck["n_out"]) if ck["kind"] == "mlp_categorical" else _MultiBinary(ck["n_out"])
+        pol = Policy((ck["obs_dim"],), space, base_kwargs={"recurrent": False, "hidden_size": ck["hidden"]}, ctx=ctx,
+                     critic_hidden=ck.get("critic_hidden"))
+    elif ck["kind"] == "mlp":
         pol = Policy((ck["obs_dim"],), _Box(ck["act_dim"]), base_kwargs={"recurrent": bool(ck.get("recurrent")), "hidden_size": ck["hidden"]}, ctx=ctx,
                      critic_hidden=ck.get("critic_hidden"))
     else:
@@ -443,7 +496,8 @@ def save_policy(path, policy, ob_rms=None):
     """a2c/main.py:260-269: a file the reference's `torch.load(path)` turns back into `[actor_critic, ob_rms]`."""
     if policy.is_recurrent:
         raise NotImplementedError(RECURRENT_SAVE_MSG)
-    save_reference_checkpoint(path, "mlp" if policy.KIND == 0 else "split", policy.state_dict(), ob_rms)
+    kind = {1: "mlp_categorical", 2: "mlp_bernoulli"}.get(getattr(policy, "dist_kind", 0), "mlp")
+    save_reference_checkpoint(path, kind if policy.KIND == 0 else "split", policy.state_dict(), ob_rms)
 
 
 def load_discriminator(path, ctx=None):

@@ -113,6 +113,9 @@ struct SgPolicyDesc {
     SgTrunk trunk[3];
     int total;            // padded parameter count
     int nc, na;           // split: 4*feet, 3*feet
+    // Discrete / MultiBinary action spaces (sg_policy_create3): A stays the width of an ACTION ROW (1 for a class index, n_out
+    // for MultiBinary) -- ACT tiles, gathers, rollout checks; n_out is the head's output count -- trunk[0].P, weights, slabs
+    int dist, n_out;      // SG_DIST_*; n_out == A for the Gaussian
 };
 
 struct SgDiscDesc {
@@ -121,7 +124,8 @@ struct SgDiscDesc {
     int total;
 };
 
-SgPolicyDesc sg_make_policy_desc(int kind, int O, int A, int H, int num_feet, int Hc = 0);   // Hc 0: critic as wide as the actors
+SgPolicyDesc sg_make_policy_desc(int kind, int O, int A, int H, int num_feet, int Hc = 0,   // Hc 0: critic as wide as the actors
+                                 int dist = SG_DIST_GAUSSIAN, int n_out = 0);
 int64_t sg_policy_flat_count(const SgPolicyDesc& d);
 void sg_policy_pad(const SgPolicyDesc& d, const float* flat, float* padded);    // padded must be zeroed
 void sg_policy_unpad(const SgPolicyDesc& d, const float* padded, float* flat);

@@ -30,18 +30,20 @@ static SgTrunk make_trunk(int& cursor, int H, int ldO, int P, int EX) {
     return t;
 }
 
-SgPolicyDesc sg_make_policy_desc(int kind, int O, int A, int H, int num_feet, int Hc) {
+SgPolicyDesc sg_make_policy_desc(int kind, int O, int A, int H, int num_feet, int Hc, int dist, int n_out) {
     SgPolicyDesc d;
     memset(&d, 0, sizeof d);
     if (Hc <= 0) Hc = H;
     d.kind = kind; d.O = O; d.A = A; d.H = H; d.num_feet = num_feet; d.Hc = Hc;
+    d.dist = dist; d.n_out = dist == SG_DIST_GAUSSIAN ? A : n_out;
     d.Op = SG_PAD16(O); d.ldO = SG_LD(O);
     const int Hmax = H > Hc ? H : Hc;
     d.Hp = SG_PAD16(Hmax); d.ldH = SG_LD(Hmax);
     int cur = 0;
     if (kind == SG_POLICY_MLP) {
         d.n_trunks = 2;
-        d.trunk[0] = make_trunk(cur, H, d.ldO, A, A);    // actor: fc_mean head + logstd
+        if (dist == SG_DIST_GAUSSIAN) d.trunk[0] = make_trunk(cur, H, d.ldO, A, A);   // actor: fc_mean head + logstd
+        else d.trunk[0] = make_trunk(cur, H, d.ldO, d.n_out, 0);                      // actor: dist.linear (logits), no log-std
         d.trunk[1] = make_trunk(cur, Hc, d.ldO, 1, 0);   // critic: critic_linear head
     } else {
         d.n_trunks = 3;
@@ -74,9 +76,9 @@ static int64_t policy_segments(const SgPolicyDesc& d, const SegFn& f) {
     mat(cr.off + cr.bh, 1, 1, 1);
     if (d.kind == SG_POLICY_MLP) {
         const SgTrunk& ac = d.trunk[0];
-        mat(ac.off + ac.wh, A, H, ac.ldH);   // fc_mean
-        mat(ac.off + ac.bh, 1, A, A);
-        mat(ac.off + ac.ex, 1, A, A);       // logstd._bias [A,1]
+        mat(ac.off + ac.wh, ac.P, H, ac.ldH);   // fc_mean (Categorical / Bernoulli: dist.linear)
+        mat(ac.off + ac.bh, 1, ac.P, ac.P);
+        if (ac.EX) mat(ac.off + ac.ex, 1, A, A);   // logstd._bias [A,1]
     } else {
         const SgTrunk& c = d.trunk[0];
         const SgTrunk& a = d.trunk[1];

@@ -142,6 +142,77 @@ __global__ void k_gauss_head(HeadArgs a) {
     if (a.ent) a.ent[row] = ent;
 }
 
+// Categorical / Bernoulli head (a2c/distributions.py:33-88,157-168; Discrete / MultiBinary action spaces): value, action
+// (sampled / mode / given), log-prob, per-row entropy from the n_out logits of the actor trunk.  One thread per row, the
+// logits read in ascending k.  `noise` / the library's draws are UNIFORM in [0, 1): one per row (categorical) or per bit.
+//   categorical: m = max_k z_k (first k on ties), S = sum_{k != argmax} exp(z_k - m), log p_k = (z_k - m) - log1p(S): the
+//     log-prob of a near-certain class comes from the OTHER classes' mass S, not from log(1 - ...) of a rounded 1.  A sample
+//     is the first k whose float32 running sum of p_k (ascending k) exceeds u, clamped to K - 1; the mode is the argmax.
+//   Bernoulli: e = exp(-|z|), p = sigmoid(z) = z >= 0 ? 1 / (1 + e) : e / (1 + e); log p(a) = a z - softplus(z) with
+//     softplus(z) = max(z, 0) + log1p(e); entropy = log1p(e) + |z| e / (1 + e) (softplus(z) - p z without its
+//     cancellation).  A sample is u < p, the mode z > 0 (p > 0.5).
+// An action row holds the class index as a float (d.A == 1) or the n_out bits (d.A == n_out).
+__global__ void k_discrete_head(HeadArgs a) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= a.n) return;
+    const SgPolicyDesc& d = a.d;
+    const size_t hs = (size_t)a.n * a.hld;
+    const float* z = a.heads + (size_t)row * a.hld;
+    const float* hc = a.heads + (size_t)(d.n_trunks - 1) * hs + (size_t)row * a.hld;
+    if (a.value) a.value[row] = hc[0];
+    if (!a.logp && !a.action && !a.ent) return;
+    const int K = d.n_out;
+    float logp = 0.f, ent = 0.f;
+    if (d.dist == SG_DIST_CATEGORICAL) {
+        float m = z[0];
+        int am = 0;
+        for (int k = 1; k < K; ++k)
+            if (z[k] > m) { m = z[k]; am = k; }
+        float S = 0.f;
+        for (int k = 0; k < K; ++k)
+            if (k != am) S += expf(z[k] - m);
+        const float l1p = log1pf(S);
+        int act = am;
+        if (a.mode == 2) {
+            act = (int)a.action_in[row];
+            act = act < 0 ? 0 : (act > K - 1 ? K - 1 : act);   // (a class index outside [0, K) has no logit to read)
+        } else if (a.mode == 0) {
+            const float u = a.noise ? a.noise[row] : sg_uniform(a.seed, a.stream, (uint64_t)row);
+            float cum = 0.f;
+            act = K - 1;
+            for (int k = 0; k < K; ++k) {
+                cum += expf((z[k] - m) - l1p);
+                if (cum > u) { act = k; break; }
+            }
+        }
+        for (int k = 0; k < K; ++k) {
+            const float lp = (z[k] - m) - l1p;
+            ent -= expf(lp) * lp;
+        }
+        logp = (z[act] - m) - l1p;
+        if (a.action) a.action[row] = (float)act;
+    } else {
+        for (int k = 0; k < K; ++k) {
+            const float zk = z[k], az = fabsf(zk);
+            const float e = expf(-az), l1p = log1pf(e);
+            const float p = zk >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+            float act;
+            if (a.mode == 2) act = a.action_in[(size_t)row * K + k];
+            else if (a.mode == 1) act = zk > 0.f ? 1.f : 0.f;
+            else {
+                const float u = a.noise ? a.noise[(size_t)row * K + k] : sg_uniform(a.seed, a.stream, (uint64_t)row * K + k);
+                act = u < p ? 1.f : 0.f;
+            }
+            if (a.action) a.action[(size_t)row * K + k] = act;
+            // a z - softplus(z), a in [0, 1] (the reference evaluates float actions as they are)
+            logp += act * zk - (fmaxf(zk, 0.f) + l1p);
+            ent += l1p + az * (e / (1.f + e));
+        }
+    }
+    if (a.logp) a.logp[row] = logp;
+    if (a.ent) a.ent[row] = ent;
+}
+
 // LDS floats needed by the forward kernel / the PPO gradient kernel for a given MT.
 static int max_trunk_size(const SgPolicyDesc& d, int t0, int nt) {
     int m = 0;
@@ -212,7 +283,8 @@ int sg_policy_forward_device(sg_policy* p, const float* d_obs, int n, int mode, 
     h.d = p->desc; h.params = p->d_params; h.heads = scratch; h.hld = hld; h.n = n; h.mode = mode;
     h.noise = d_noise; h.seed = seed; h.stream = SG_ACT_STREAM + (uint64_t)ctx->rank; h.action_in = d_action_in;
     h.value = d_value; h.action = d_action; h.logp = d_logp; h.ent = d_ent;
-    hipLaunchKernelGGL(k_gauss_head, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, h);
+    if (p->desc.dist == SG_DIST_GAUSSIAN) hipLaunchKernelGGL(k_gauss_head, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, h);
+    else hipLaunchKernelGGL(k_discrete_head, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, h);
     SG_CHECK(hipGetLastError());
     return 0;
 }
@@ -226,11 +298,27 @@ extern "C" int sg_policy_create(sg_ctx* ctx, int kind, int obs_dim, int act_dim,
 
 extern "C" int sg_policy_create2(sg_ctx* ctx, int kind, int obs_dim, int act_dim, int hidden, int num_feet, int critic_hidden,
                                  sg_policy** out) {
+    return sg_policy_create3(ctx, kind, obs_dim, act_dim, hidden, num_feet, critic_hidden, SG_DIST_GAUSSIAN, 0, out);
+}
+
+extern "C" int sg_policy_create3(sg_ctx* ctx, int kind, int obs_dim, int act_dim, int hidden, int num_feet, int critic_hidden,
+                                 int dist, int n_out, sg_policy** out) {
     SG_DEVICE_WIDE();
     SG_REQUIRE(ctx && out, "sg_policy_create: NULL argument");
     SG_REQUIRE(critic_hidden >= 0, "sg_policy_create2: bad critic_hidden");
     SG_REQUIRE(kind == SG_POLICY_MLP || kind == SG_POLICY_SPLIT || kind == SG_POLICY_GRU, "sg_policy_create: unknown kind %d", kind);
     SG_REQUIRE(obs_dim > 0 && act_dim > 0 && hidden > 0, "sg_policy_create: bad dims");
+    SG_REQUIRE(dist == SG_DIST_GAUSSIAN || dist == SG_DIST_CATEGORICAL || dist == SG_DIST_BERNOULLI,
+               "sg_policy_create3: unknown dist %d", dist);
+    if (dist != SG_DIST_GAUSSIAN) {
+        SG_REQUIRE(kind == SG_POLICY_MLP, "sg_policy_create3: a Categorical / Bernoulli head is built on the feed-forward Policy "
+                   "(kind SG_POLICY_MLP) only, not on kind %d", kind);
+        SG_REQUIRE(n_out > 0 && n_out < (1 << 24), "sg_policy_create3: n_out = %d: need 0 < n_out < 2^24 (a class index travels as a "
+                   "float)", n_out);
+        SG_REQUIRE(act_dim == (dist == SG_DIST_CATEGORICAL ? 1 : n_out), "sg_policy_create3: act_dim (%d) must be %s", act_dim,
+                   dist == SG_DIST_CATEGORICAL ? "1 for a Categorical head (an action row is one class index)"
+                                               : "n_out for a Bernoulli head (an action row is n_out bits)");
+    }
     if (kind == SG_POLICY_SPLIT)
         SG_REQUIRE(num_feet > 0 && act_dim == 7 * num_feet,
                    "SplitPolicy: num_outputs (%d) must equal (4+3)*num_feet (%d)", act_dim, 7 * num_feet);
@@ -249,7 +337,7 @@ extern "C" int sg_policy_create2(sg_ctx* ctx, int kind, int obs_dim, int act_dim
             return -2;
         }
     } else
-        p->desc = sg_make_policy_desc(kind, obs_dim, act_dim, hidden, num_feet, critic_hidden);
+        p->desc = sg_make_policy_desc(kind, obs_dim, act_dim, hidden, num_feet, critic_hidden, dist, n_out);
     // any width the reference's constructor accepts (a2c/arguments.py:107-109, a2c/model.py:233-253): a trunk that fits a
     // CU's LDS runs on the LDS-resident kernels, a larger one on the global-weight instances; only one 16-row activation
     // tile has to fit
@@ -493,6 +581,8 @@ extern "C" int sg_policy_act_ensemble(sg_policy* const* policies, int n_policies
         SG_REQUIRE(!policies[k]->recurrent, "sg_policy_act_ensemble: member %d is a recurrent policy; the ensemble launch carries no hidden "
                    "state (feed-forward policies only)", k);
         const SgPolicyDesc& e = policies[k]->desc;
+        SG_REQUIRE(e.dist == SG_DIST_GAUSSIAN, "sg_policy_act_ensemble: member %d has a Categorical / Bernoulli head; the ensemble "
+                   "launch carries the Gaussian head only (Box action spaces)", k);
         SG_REQUIRE(e.kind == d.kind && e.O == d.O && e.A == d.A && e.H == d.H && e.Hc == d.Hc && e.num_feet == d.num_feet,
                    "sg_policy_act_ensemble: member %d has a different shape", k);
         a.params[k] = policies[k]->d_params;

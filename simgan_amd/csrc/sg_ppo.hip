@@ -90,8 +90,9 @@ static size_t ppo_bwd_tiles_lds(const SgPolicyDesc& d, int MT, size_t w_floats, 
     return sizeof(float) * (w_floats + R * d.ldO + 2 * R * d.ldH + (size_t)n_out * R * stack_ldP(d) + ((R * d.A + 3) & ~3) + 7 * R +
                             (ma ? (d.A * d.A + 3) & ~3 : 0));
 }
+// (a Categorical / Bernoulli policy has the fused form only -- LDS-resident or global-weight: SG_PPO_FUSED does not apply)
 static bool ppo_fused(const SgPolicyDesc& d, int MT) {
-    return d.kind == SG_POLICY_MLP && MT <= 2 && !sg_env_is_off("SG_PPO_FUSED");
+    return d.kind == SG_POLICY_MLP && MT <= 2 && (d.dist != SG_DIST_GAUSSIAN || !sg_env_is_off("SG_PPO_FUSED"));
 }
 // rows of the rollout one A2C forward / backward / reduce pass covers: the slabs and row stacks are sized for this many rows
 // whatever T*N is (the north-star PPO minibatch: 65,536 rows / 16)
@@ -156,6 +157,10 @@ struct PpoInstance {
 #define SG_K_FWD_SYM(mt, o, h, gw) k_ppo_fwd_sym<mt, o, h, gw>
 #define SG_K_BWD_SYM(mt, o, h, gw) k_ppo_bwd_sym<mt, o, h, gw>
 #define SG_K_A2C_BWD(mt, o, h, gw) k_a2c_bwd<mt, o, h, gw>
+#define SG_K_BWD_FUSED_CAT(mt, o, h, gw) k_ppo_bwd_dist<mt, gw, SG_DIST_CATEGORICAL>
+#define SG_K_BWD_FUSED_BER(mt, o, h, gw) k_ppo_bwd_dist<mt, gw, SG_DIST_BERNOULLI>
+#define SG_K_A2C_BWD_CAT(mt, o, h, gw) k_a2c_bwd_dist<mt, gw, SG_DIST_CATEGORICAL>
+#define SG_K_A2C_BWD_BER(mt, o, h, gw) k_a2c_bwd_dist<mt, gw, SG_DIST_BERNOULLI>
 SG_PPO_FAMILY(ppo_fwd_family, SG_K_FWD, SG_PPO_SHAPES, SG_MT_421, SG_MT_21);
 SG_PPO_FAMILY(ppo_fwd_critic_family, SG_K_FWD_CRITIC, SG_SPLIT_SHAPES, SG_MT_21, SG_NONE);   // SplitPolicy, critic in the forward launch
 SG_PPO_FAMILY(ppo_pair_family, SG_K_PAIR, SG_SPLIT_SHAPES, SG_MT_21, SG_NONE);               // SplitPolicy, one launch per step
@@ -166,6 +171,11 @@ SG_PPO_FAMILY(ppo_bwd_fused_dx_family, SG_K_BWD_FUSED_DX, SG_NONE, SG_MT_21, SG_
 SG_PPO_FAMILY(ppo_fwd_sym_family, SG_K_FWD_SYM, SG_SYM_SHAPES, SG_MT_21, SG_MT_21);               // mirror-symmetry loss: grid (row groups, 3)
 SG_PPO_FAMILY(ppo_bwd_sym_family, SG_K_BWD_SYM, SG_SYM_SHAPES, SG_MT_21, SG_MT_21);
 SG_PPO_FAMILY(a2c_bwd_family, SG_K_A2C_BWD, SG_A2C_SHAPES, SG_MT_21, SG_MT_21);
+// Policy on a Discrete / MultiBinary action space: PPO in the fused form, A2C in the two-launch form; run-time shapes
+SG_PPO_FAMILY(ppo_bwd_fused_cat_family, SG_K_BWD_FUSED_CAT, SG_NONE, SG_MT_21, SG_MT_21);
+SG_PPO_FAMILY(ppo_bwd_fused_ber_family, SG_K_BWD_FUSED_BER, SG_NONE, SG_MT_21, SG_MT_21);
+SG_PPO_FAMILY(a2c_bwd_cat_family, SG_K_A2C_BWD_CAT, SG_NONE, SG_MT_21, SG_MT_21);
+SG_PPO_FAMILY(a2c_bwd_ber_family, SG_K_A2C_BWD_BER, SG_NONE, SG_MT_21, SG_MT_21);
 
 // Launches the family's instance for (MT, the policy's shape, gw): with gw a global-weight instance, else the one specialised
 // for the shape, else the run-time-shape one.  (The specialised instances fold ONE hidden width into the code: a policy whose
@@ -253,6 +263,8 @@ extern "C" int sg_acktr_create(sg_ctx* ctx, sg_policy* p, const sg_acktr_config*
     SG_REQUIRE(!p->recurrent, "sg_acktr_create: ACKTR is not defined for a recurrent Policy (the reference refuses it too: "
                "a2c/arguments.py:253-255)");
     SG_REQUIRE(p->desc.kind == SG_POLICY_MLP, "sg_acktr_create: ACKTR is implemented for Policy (MLP) only, not for SplitPolicy");
+    SG_REQUIRE(p->desc.dist == SG_DIST_GAUSSIAN, "sg_acktr_create: ACKTR is implemented for Box action spaces only: this policy has a "
+               "%s head (its Fisher sampling is not built)", p->desc.dist == SG_DIST_CATEGORICAL ? "Categorical" : "Bernoulli");
     SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_acktr_create: ACKTR runs on one rank: this context has a communicator of "
                "world %d (data-parallel ACKTR is not implemented)", ctx->world);
     SG_REQUIRE(cfg->lr > 0.f && cfg->momentum >= 0.f && cfg->momentum < 1.f && cfg->stat_decay > 0.f && cfg->stat_decay < 1.f &&
@@ -325,6 +337,8 @@ extern "C" int sg_ppo_set_symmetry(sg_ppo* a, float coef, const float* m_obs, co
     SG_REQUIRE(m_act, "sg_ppo_set_symmetry: symmetry_coef > 0 needs the action mirror m_act");
     SG_REQUIRE(d.kind == SG_POLICY_MLP, "sg_ppo_set_symmetry: the mirror-symmetry loss is implemented for Policy (MLP) only, "
                "not for SplitPolicy");
+    SG_REQUIRE(d.dist == SG_DIST_GAUSSIAN, "sg_ppo_set_symmetry: the mirror-symmetry loss compares action means: it is defined for "
+               "Box action spaces only, not for a %s head", d.dist == SG_DIST_CATEGORICAL ? "Categorical" : "Bernoulli");
     SG_REQUIRE(!a->policy->recurrent, "sg_ppo_set_symmetry: the mirror-symmetry loss is implemented for feed-forward policies only, "
                "not for a recurrent Policy");
     SG_REQUIRE(ppo_bwd_tiles_lds(d, 1, 0, 3, true) <= (size_t)ctx->lds_bytes,
@@ -619,7 +633,12 @@ static int a2c_update(sg_ppo* a, sg_rollout* r, uint64_t seed, float out3[3]) {
             pa.wbuf_floats = wb_f;
             SG_TRY(ppo_launch(ctx, ppo_fwd_family, "k_ppo_fwd", SG_PROF_PPO_FWD, MT, d, dim3(Gc, d.n_trunks), lds_f, pa, gw));
             pa.wbuf_floats = wb_b;
-            SG_TRY(ppo_launch(ctx, a2c_bwd_family, "k_a2c_bwd", SG_PROF_PPO_BWD, MT, d, dim3(Gc, d.n_trunks), lds_b, pa, gw));
+            if (d.dist == SG_DIST_CATEGORICAL)
+                SG_TRY(ppo_launch(ctx, a2c_bwd_cat_family, "k_a2c_bwd (categorical)", SG_PROF_PPO_BWD, MT, d, dim3(Gc, d.n_trunks), lds_b, pa, gw));
+            else if (d.dist == SG_DIST_BERNOULLI)
+                SG_TRY(ppo_launch(ctx, a2c_bwd_ber_family, "k_a2c_bwd (Bernoulli)", SG_PROF_PPO_BWD, MT, d, dim3(Gc, d.n_trunks), lds_b, pa, gw));
+            else
+                SG_TRY(ppo_launch(ctx, a2c_bwd_family, "k_a2c_bwd", SG_PROF_PPO_BWD, MT, d, dim3(Gc, d.n_trunks), lds_b, pa, gw));
             SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_a2c_reduce, dim3(nblk_r), dim3(256), 0, a->d_slabs, Gc, slab_stride, d.total, a->d_grad,
                       a->d_part, c > 0 ? 1 : 0);
             if (kf) {
@@ -1025,7 +1044,8 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     // global-weight instances when a trunk (+ one 16-row tile) does not fit LDS: in the forward, or in the backward launch
     const bool gw = sg_policy_needs_gw(ctx, d) || !fits(1, false);
     // (SG_PPO_ROWS may ask for 64-row groups; the global-weight and the symmetric instances stop at 32)
-    const int MT = ppo_row_tiles(ctx, d, mb, ncols, true, 4, (gw || sym) ? 2 : 4, [&](int mt) { return fits(mt, gw); });
+    // (... and so do the Categorical / Bernoulli instances, which have the fused form only)
+    const int MT = ppo_row_tiles(ctx, d, mb, ncols, true, 4, (gw || sym || d.dist != SG_DIST_GAUSSIAN) ? 2 : 4, [&](int mt) { return fits(mt, gw); });
     const int R = 16 * MT;
     const int G = (mb + R - 1) / R;
     const int mbp = G * R;
@@ -1137,7 +1157,12 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
                                       false));   // trunks 0, 1: the actors
                 } else if (fused) {
                     pa.wbuf_floats = wb_f;
-                    SG_TRY(ppo_launch(ctx, ppo_bwd_fused_family, "k_ppo_bwd (fused)", SG_PROF_PPO_BWD, MT, d, dim3(G, d.n_trunks), lds_b, pa, gw));
+                    if (d.dist == SG_DIST_CATEGORICAL)
+                        SG_TRY(ppo_launch(ctx, ppo_bwd_fused_cat_family, "k_ppo_bwd (fused, categorical)", SG_PROF_PPO_BWD, MT, d, dim3(G, d.n_trunks), lds_b, pa, gw));
+                    else if (d.dist == SG_DIST_BERNOULLI)
+                        SG_TRY(ppo_launch(ctx, ppo_bwd_fused_ber_family, "k_ppo_bwd (fused, Bernoulli)", SG_PROF_PPO_BWD, MT, d, dim3(G, d.n_trunks), lds_b, pa, gw));
+                    else
+                        SG_TRY(ppo_launch(ctx, ppo_bwd_fused_family, "k_ppo_bwd (fused)", SG_PROF_PPO_BWD, MT, d, dim3(G, d.n_trunks), lds_b, pa, gw));
                 } else {
                     pa.wbuf_floats = wb_f;
                     SG_TRY(ppo_launch(ctx, ppo_fwd_family, "k_ppo_fwd", SG_PROF_PPO_FWD, MT, d, dim3(G, d.n_trunks), lds_f, pa, gw));

@@ -228,6 +228,28 @@ __global__ __launch_bounds__(512) void k_ppo_fwd_sym(PpoArgs a) {
 }
 
 // -------------------------------------------------------------------------------- backward
+// d loss / d logp and the action loss of one valid row from its log-prob (a2c/algo/ppo.py:92-97; A2C: a2c/algo/a2c_acktr.py:69-73):
+// the clipped surrogate's three branches, or -adv logp.  The Categorical / Bernoulli loss block calls it; the Gaussian block
+// carries the same lines inline (with the hardware exp on its fast path).
+template <bool A2C>
+__device__ __forceinline__ void sg_ppo_row_weight(const PpoArgs& a, const float* SC, const int R, const int r, const float logp,
+                                                  float& dlogp, float& la) {
+    if (A2C) {
+        const float adv = SC[3 * R + r] - SC[0 * R + r];   // R - v
+        dlogp = -a.inv_B * adv;
+        la = -adv * logp;
+    } else {
+        const float adv = SC[1 * R + r];
+        const float ratio = expf(logp - SC[0 * R + r]);
+        const float surr1 = ratio * adv;
+        const float surr2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * adv;
+        const float w1 = surr1 < surr2 ? 1.f : (surr1 > surr2 ? 0.f : 0.5f);  // torch.min tie -> 1/2, 1/2
+        const float inr = (ratio >= 1.f - a.clip && ratio <= 1.f + a.clip) ? 1.f : 0.f;
+        dlogp = -a.inv_B * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
+        la = -fminf(surr1, surr2);
+    }
+}
+
 // FUSED (Policy: the actor and critic trunks do not depend on each other's outputs): the workgroup stages the
 // whole trunk, recomputes the forward on its own rows in LDS and goes straight on to the loss -- no k_ppo_fwd
 // launch, no activation stacks written, flushed and read back (5 MB per step at the north-star shape).
@@ -253,8 +275,13 @@ __global__ __launch_bounds__(512) void k_ppo_fwd_sym(PpoArgs a) {
 // A2C (Policy, two-launch form, a2c/algo/a2c_acktr.py:56-91): loss = vcoef mean(adv^2) - mean(adv.detach() logp) - ecoef
 // mean(ent), adv = R - v with v the critic's head output of the SAME forward (k_ppo_fwd's critic OUT stack; the actor columns
 // read it in place of old_logp).  No ratio, no clip, no clipped value loss; the entropy term is PPO's.
-template <int MT, int KO, int KH, bool FUSED, bool GW = false, bool PAIR = false, bool SYM = false, bool A2C = false, bool DX = false>
+// DIST (SG_DIST_*): the action distribution the actor column's loss block evaluates.  The default keeps the Gaussian code;
+// the Categorical / Bernoulli instances (Policy on Discrete / MultiBinary action spaces, kind MLP) exist in the fused and the
+// A2C forms.
+template <int MT, int KO, int KH, bool FUSED, bool GW = false, bool PAIR = false, bool SYM = false, bool A2C = false, bool DX = false,
+          int DIST = SG_DIST_GAUSSIAN>
 __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, const int bx) {
+    static_assert(DIST == SG_DIST_GAUSSIAN || (!PAIR && !SYM && !DX), "Categorical / Bernoulli heads: plain Policy only");
     static_assert(!(SYM && (FUSED || PAIR)), "the symmetric step runs the two-launch form");
     static_assert(!DX || ((FUSED || GW) && !PAIR && !SYM && !A2C), "d loss / d X needs w1 at hand: the fused or the global-weight form");
     static_assert(!(A2C && (FUSED || PAIR || SYM)), "the A2C step runs the two-launch form");
@@ -458,6 +485,67 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
             O0[r * ldP] = dv;
             ROWL[r] = lv;
         }
+    } else if (DIST != SG_DIST_GAUSSIAN) {
+        // Categorical / Bernoulli (a2c/distributions.py:33-88,157-168): log-prob and entropy of every row from its K logits in
+        // O0, then d(loss)/d(logits) written over them.  Rows get lanes as in the Gaussian branch: L = blockDim / R consecutive
+        // lanes (8 or 16, one wave), a lane walks the columns sub, sub + L, ... -- any K, nothing per thread sized by it.
+        // The arithmetic is k_discrete_head's (sg_policy.hip): row maximum subtracted, the log-prob taken from the other
+        // classes' mass.
+        const int K = tr.P;
+        const int L = blockDim.x / R;
+        const int r = tid / L, sub = tid - r * L;
+        float* o0 = O0 + r * ldP;
+        const float* arow = ACT + r * A;
+        float logp = 0.f, ent = 0.f, m = 0.f, l1p = 0.f;
+        int act = 0;
+        if (DIST == SG_DIST_CATEGORICAL) {
+            int am = K;
+            m = -INFINITY;
+            for (int k = sub; k < K; k += L) { const float z = o0[k]; if (z > m) { m = z; am = k; } }
+            for (int o = 1; o < L; o <<= 1) {   // the row's maximum, the first index on ties
+                const float m2 = __shfl_xor(m, o);
+                const int a2 = __shfl_xor(am, o);
+                if (m2 > m || (m2 == m && a2 < am)) { m = m2; am = a2; }
+            }
+            float S = 0.f;
+            for (int k = sub; k < K; k += L) if (k != am) S += expf(o0[k] - m);
+            for (int o = 1; o < L; o <<= 1) S += __shfl_xor(S, o);
+            l1p = log1pf(S);
+            for (int k = sub; k < K; k += L) { const float lp = (o0[k] - m) - l1p; ent -= expf(lp) * lp; }
+            for (int o = 1; o < L; o <<= 1) ent += __shfl_xor(ent, o);
+            act = (int)arow[0];
+            act = act < 0 ? 0 : (act > K - 1 ? K - 1 : act);
+            logp = (o0[act] - m) - l1p;
+        } else {
+            for (int k = sub; k < K; k += L) {
+                const float z = o0[k], az = fabsf(z);
+                const float e = expf(-az), l = log1pf(e);
+                logp += arow[k] * z - (fmaxf(z, 0.f) + l);
+                ent += l + az * (e / (1.f + e));
+            }
+            for (int o = 1; o < L; o <<= 1) { logp += __shfl_xor(logp, o); ent += __shfl_xor(ent, o); }
+        }
+        const bool valid = VALID[r];
+        float dlogp = 0.f, la = 0.f;
+        if (valid) sg_ppo_row_weight<A2C>(a, SC, R, r, logp, dlogp, la);
+        const float dent = valid ? a.ecoef * a.inv_B : 0.f;
+        for (int k = sub; k < tr.Pp; k += L) {   // the padding columns too: the head GEMMs read them
+            float g = 0.f;
+            if (k < K && valid) {
+                const float z = o0[k];
+                if (DIST == SG_DIST_CATEGORICAL) {
+                    const float lp = (z - m) - l1p, p = expf(lp);
+                    g = dlogp * ((k == act ? 1.f : 0.f) - p) + dent * p * (lp + ent);
+                } else {
+                    // q = the rarer outcome's probability: a - p and p (1 - p) without forming 1 - p from a rounded p
+                    const float e = expf(-fabsf(z)), q = e / (1.f + e);
+                    const float amp = z >= 0.f ? (arow[k] - 1.f) + q : arow[k] - q;
+                    g = dlogp * amp + dent * z * (q / (1.f + e));
+                }
+            }
+            o0[k] = g;
+        }
+        if (sub == 0) { ROWL[r] = la; ROWL[R + r] = valid ? ent : 0.f; }
     } else {
         // Gaussian log-prob / entropy of every row and d(loss)/d(mean, log-std).  All R rows in ONE pass: a row gets
         // L = blockDim / R lanes (16, 8 or 4), a lane takes action dimensions sub, sub + L, ... (at most 8 of them: A <= 8 L
@@ -650,6 +738,12 @@ template <int MT, int KO, int KH, bool FUSED = false, bool GW = false, bool DX =
 __global__ __launch_bounds__(512) void k_ppo_bwd(PpoArgs a) {
     sg_ppo_bwd_body<MT, KO, KH, FUSED, GW, false, false, false, DX>(a, blockIdx.y, blockIdx.x);
 }
+// Policy on a Discrete / MultiBinary action space (DIST = SG_DIST_CATEGORICAL / SG_DIST_BERNOULLI): the fused form, run-time
+// shapes.  Kernels of their own, so that the Gaussian instances keep their names.
+template <int MT, bool GW, int DIST>
+__global__ __launch_bounds__(512) void k_ppo_bwd_dist(PpoArgs a) {
+    sg_ppo_bwd_body<MT, 0, 0, true, GW, false, false, false, false, DIST>(a, blockIdx.y, blockIdx.x);
+}
 // Policy with the mirror-symmetry loss: grid (row groups, 3), after k_ppo_fwd_sym
 template <int MT, int KO, int KH, bool GW = false>
 __global__ __launch_bounds__(512) void k_ppo_bwd_sym(PpoArgs a) {
@@ -660,6 +754,11 @@ __global__ __launch_bounds__(512) void k_ppo_bwd_sym(PpoArgs a) {
 template <int MT, int KO, int KH, bool GW = false>
 __global__ __launch_bounds__(512) void k_a2c_bwd(PpoArgs a) {
     sg_ppo_bwd_body<MT, KO, KH, false, GW, false, false, true>(a, blockIdx.y, blockIdx.x);
+}
+// ... with a Categorical / Bernoulli head (run-time shapes)
+template <int MT, bool GW, int DIST>
+__global__ __launch_bounds__(512) void k_a2c_bwd_dist(PpoArgs a) {
+    sg_ppo_bwd_body<MT, 0, 0, false, GW, false, false, true, false, DIST>(a, blockIdx.y, blockIdx.x);
 }
 
 // SplitPolicy, ONE launch per step when its 3 G workgroups fit the chip together: every trunk's fused forward + loss + backward,

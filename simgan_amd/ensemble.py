@@ -21,6 +21,9 @@ class PolicyEnsemble(object):
         self.policies = list(policies)
         if any(getattr(p, "is_recurrent", False) for p in self.policies):
             raise NotImplementedError("PolicyEnsemble: feed-forward members only (the one-launch act carries no hidden state)")
+        if any(getattr(p, "dist_kind", 0) for p in self.policies):
+            raise NotImplementedError("PolicyEnsemble: members with Box action spaces only (the one-launch act carries the Gaussian "
+                                      "head; a Discrete / MultiBinary policy acts through Policy.act)")
         shapes = {(type(p), p.obs_dim, p.act_dim, p.hidden_size, p.critic_hidden, p.num_feet) for p in self.policies}
         assert len(shapes) == 1, "ensemble members must share kind, observation, action and hidden sizes"
         self.obs_dim, self.act_dim = self.policies[0].obs_dim, self.policies[0].act_dim

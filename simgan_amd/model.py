@@ -1,5 +1,5 @@
-"""Policy -- host mirror of a2c/model.py:37-114 (MLPBase + DiagGaussian, Box actions; feed-forward, or
-recurrent with the GRU base of a2c/model.py:117-201).  Parameters live in HBM inside libsimgan_hip.so; this class keeps the
+"""Policy -- host mirror of a2c/model.py:37-114 (MLPBase + DiagGaussian on Box actions, Categorical on Discrete, Bernoulli on
+MultiBinary, a2c/model.py:52-62; feed-forward, or -- Box only -- recurrent with the GRU base of a2c/model.py:117-201).  Parameters live in HBM inside libsimgan_hip.so; this class keeps the
 reference's constructor and method signatures and hands host tensors across the C ABI."""
 import ctypes as C
 
@@ -19,7 +19,11 @@ MATERIALISE_CTX = None
 class _PolicyBase(object):
     KIND = None
 
-    def _create(self, obs_dim, act_dim, hidden, num_feet, ctx, critic_hidden=None, recurrent=False):
+    def _create(self, obs_dim, act_dim, hidden, num_feet, ctx, critic_hidden=None, recurrent=False, dist=0, n_out=None):
+        # dist_kind: _lib.DIST_GAUSSIAN (Box), DIST_CATEGORICAL (Discrete(n_out): act_dim 1, the class index) or DIST_BERNOULLI
+        # (MultiBinary(n_out): act_dim n_out); n_out: the head's outputs
+        self.__dict__["_dist_kind"] = int(dist or 0)
+        self.__dict__["n_out"] = int(n_out) if self.__dict__["_dist_kind"] else int(act_dim)
         self.__dict__["recurrent"] = bool(recurrent)   # GRU base (a2c/model.py:117-131): the device kind is POLICY_GRU, the class stays Policy
         self.ctx = ctx or _lib.Context.default()
         self.lib = self.ctx.lib
@@ -28,8 +32,13 @@ class _PolicyBase(object):
         # width of the critic trunk: the actors' unless reset_critic rebuilt it (a2c/model.py:80-87: always 64 units)
         self.critic_hidden = int(critic_hidden) if critic_hidden else self.hidden_size
         h = _lib.H()
-        _lib.check(self.lib.sg_policy_create2(self.ctx.h, _lib.POLICY_GRU if self._rec() else self.KIND, self.obs_dim, self.act_dim, self.hidden_size, self.num_feet,
-                                              0 if self.critic_hidden == self.hidden_size else self.critic_hidden, C.byref(h)))
+        ch = 0 if self.critic_hidden == self.hidden_size else self.critic_hidden
+        if self.dist_kind:
+            _lib.check(self.lib.sg_policy_create3(self.ctx.h, self.KIND, self.obs_dim, self.act_dim, self.hidden_size, self.num_feet, ch,
+                                                  self.dist_kind, self.n_out, C.byref(h)))
+        else:
+            _lib.check(self.lib.sg_policy_create2(self.ctx.h, _lib.POLICY_GRU if self._rec() else self.KIND, self.obs_dim, self.act_dim, self.hidden_size, self.num_feet,
+                                                  ch, C.byref(h)))
         self.h = h
         n = C.c_int64(0)
         _lib.check(self.lib.sg_policy_num_params(self.h, C.byref(n)))
@@ -43,6 +52,14 @@ class _PolicyBase(object):
         if "recurrent" not in self.__dict__ and self.__dict__.get("_pending") is not None:
             self._materialise()
         return self.__dict__.get("recurrent", False)
+
+    @property
+    def dist_kind(self):
+        """_lib.DIST_GAUSSIAN / DIST_CATEGORICAL / DIST_BERNOULLI.  Like _rec(): an object still pending materialises first, one
+        assembled without the constructor counts as Gaussian."""
+        if "_dist_kind" not in self.__dict__ and self.__dict__.get("_pending") is not None:
+            self._materialise()
+        return self.__dict__.get("_dist_kind", 0)
 
     def _register_handle_user(self, obj):
         """Objects that keep this policy's device handle (PPO, PolicyEnsemble) announce themselves: reset_critic refuses to
@@ -75,7 +92,8 @@ class _PolicyBase(object):
             # the context an unpickled policy lands on: `simgan_amd.model.MATERIALISE_CTX` when the caller set one,
             # the process default otherwise (see the module-level comment)
             self._create(dims["obs_dim"], dims["act_dim"], dims["hidden"], dims["num_feet"], MATERIALISE_CTX,
-                         critic_hidden=dims.get("critic_hidden"), recurrent=dims.get("recurrent", False))
+                         critic_hidden=dims.get("critic_hidden"), recurrent=dims.get("recurrent", False),
+                         dist=dims.get("dist", 0), n_out=dims.get("n_out"))
             self.seed = derive_seed(0, 0x5EED, per_instance=True)
             self.load_state_dict(sd)
         except BaseException:
@@ -141,7 +159,7 @@ class _PolicyBase(object):
     def __getstate__(self):
         return {"obs_dim": self.obs_dim, "act_dim": self.act_dim, "hidden": self.hidden_size,
                 "num_feet": self.num_feet, "critic_hidden": self.critic_hidden, "recurrent": self._rec(),
-                "flat": self.get_flat_params()}
+                "dist": self.dist_kind, "n_out": self.n_out, "flat": self.get_flat_params()}
 
     def __reduce_ex__(self, protocol):
         """A policy built through the reference's import path (`third_party.a2c_ppo_acktr.model[_split]`, i.e. by the
@@ -155,7 +173,8 @@ class _PolicyBase(object):
                 raise NotImplementedError(RECURRENT_SAVE_MSG)
             import copyreg
             from .checkpoint import reference_module_state
-            return (copyreg.__newobj__, (type(self),), reference_module_state("mlp" if self.KIND == _lib.POLICY_MLP else "split", self.state_dict()))
+            kind = {_lib.DIST_CATEGORICAL: "mlp_categorical", _lib.DIST_BERNOULLI: "mlp_bernoulli"}.get(self.dist_kind, "mlp")
+            return (copyreg.__newobj__, (type(self),), reference_module_state(kind if self.KIND == _lib.POLICY_MLP else "split", self.state_dict()))
         return object.__reduce_ex__(self, protocol)
 
     def __setstate__(self, st):
@@ -165,7 +184,7 @@ class _PolicyBase(object):
             self.__dict__["_pending"] = st
             return
         self._create(st["obs_dim"], st["act_dim"], st["hidden"], st["num_feet"], None, critic_hidden=st.get("critic_hidden"),
-                     recurrent=st.get("recurrent", False))
+                     recurrent=st.get("recurrent", False), dist=st.get("dist", 0), n_out=st.get("n_out"))
         self.seed = derive_seed(0, 0x5EED, per_instance=True)
         self.set_flat_params(st["flat"])
 
@@ -181,7 +200,9 @@ class _PolicyBase(object):
     # ---- the three calls on the hot path
     def act(self, inputs, rnn_hxs, masks, deterministic=False, noise=None):
         """a2c/model.py:89-101 -> (value [n,1], action [n,A], action_log_probs [n,1], rnn_hxs).
-        `noise` ([n,A] standard normal) injects the sampling draw; default = library RNG."""
+        `noise` ([n,A] standard normal) injects the sampling draw; default = library RNG.
+        Discrete: action is int64 [n,1] and `noise` [n,1] UNIFORM draws in [0,1) (inverse CDF over ascending class index);
+        MultiBinary: action is float32 0/1 [n,n_bits] and `noise` [n,n_bits] uniform draws (bit = u < p)."""
         obs = _lib.as_f32(inputs).reshape(-1, self.obs_dim)
         n = obs.shape[0]
         value = np.empty((n, 1), np.float32)
@@ -201,6 +222,8 @@ class _PolicyBase(object):
                                           None if nz is None else _lib.fptr(nz), (self.seed + self._act_calls) & (2 ** 64 - 1),
                                           1 if deterministic else 0, _lib.fptr(value),
                                           _lib.fptr(action), _lib.fptr(logp)))
+        if self.dist_kind == _lib.DIST_CATEGORICAL:   # the class index crossed the ABI as a float
+            action = action.astype(np.int64)
         return to_host_tensor(value), to_host_tensor(action), to_host_tensor(logp), rnn_hxs
 
     def get_value(self, inputs, rnn_hxs, masks):
@@ -246,16 +269,38 @@ class Policy(_PolicyBase):
             base_kwargs = {}
         if base is not None or len(obs_shape) != 1:
             raise NotImplementedError("only the MLP base on 1-D observations is built (SURVEY.md section 2, row 3)")
-        if action_space.__class__.__name__ != "Box":
-            raise NotImplementedError("only Box action spaces (a2c/model.py:55-57)")
+        # a2c/model.py:52-62
+        space = action_space.__class__.__name__
+        if space == "Box":
+            dist, act_dim, n_out = _lib.DIST_GAUSSIAN, action_space.shape[0], None
+        elif space == "Discrete":
+            dist, act_dim, n_out = _lib.DIST_CATEGORICAL, 1, int(action_space.n)
+            if not 0 < n_out < 2 ** 24:
+                raise ValueError(f"Discrete({n_out}): the class index crosses the C ABI as a float32, exact below 2^24 only")
+        elif space == "MultiBinary":
+            n_out = int(action_space.shape[0])
+            dist, act_dim = _lib.DIST_BERNOULLI, n_out
+        else:
+            raise NotImplementedError(f"action space {space}: Box, Discrete and MultiBinary are built (a2c/model.py:52-62)")
+        if dist != _lib.DIST_GAUSSIAN and base_kwargs.get("recurrent", False):
+            raise NotImplementedError(f"Policy on a {space} action space with base_kwargs={{'recurrent': True}}: the GRU base is built "
+                                      "with the Gaussian head (Box actions) only")
         hidden = base_kwargs.get("hidden_size", 64)
-        self._create(obs_shape[0], action_space.shape[0], hidden, 1, ctx, critic_hidden=critic_hidden,
-                     recurrent=base_kwargs.get("recurrent", False))
+        self._create(obs_shape[0], act_dim, hidden, 1, ctx, critic_hidden=critic_hidden,
+                     recurrent=base_kwargs.get("recurrent", False), dist=dist, n_out=n_out)
         self.seed = derive_seed(seed, 0x5EED, per_instance=True)
         self._init_params(np.random.default_rng(seed))
 
     def param_shapes(self):
         O, A, Hh, Hc = self.obs_dim, self.act_dim, self.hidden_size, self.critic_hidden
+        if getattr(self, "dist_kind", 0):   # a2c/distributions.py:74-88,157-168: Categorical / Bernoulli hold one Linear, no log-std
+            K = self.n_out
+            return [("base.actor.0.weight", (Hh, O)), ("base.actor.0.bias", (Hh,)),
+                    ("base.actor.2.weight", (Hh, Hh)), ("base.actor.2.bias", (Hh,)),
+                    ("base.critic.0.weight", (Hc, O)), ("base.critic.0.bias", (Hc,)),
+                    ("base.critic.2.weight", (Hc, Hc)), ("base.critic.2.bias", (Hc,)),
+                    ("base.critic_linear.weight", (1, Hc)), ("base.critic_linear.bias", (1,)),
+                    ("dist.linear.weight", (K, Hh)), ("dist.linear.bias", (K,))]
         gru = []
         if self._rec():   # a2c/model.py:124-131: nn.GRU's four tensors come first and the trunks read its H-wide state
             gru = [("base.gru.weight_ih_l0", (3 * Hh, O)), ("base.gru.weight_hh_l0", (3 * Hh, Hh)),
@@ -271,7 +316,7 @@ class Policy(_PolicyBase):
 
     def _init_params(self, rng):
         """a2c/model.py:240-251 (orthogonal, gain sqrt2, zero bias), a2c/distributions.py:95-104
-        (fc_mean gain 1 then /50, logstd -0.5); the GRU, a2c/model.py:126-130: orthogonal (gain 1) on each whole [3H, .]
+        (fc_mean gain 1 then /50, logstd -0.5), :78-84 (Categorical: dist.linear gain 0.01), :161-164 (Bernoulli: gain 1); the GRU, a2c/model.py:126-130: orthogonal (gain 1) on each whole [3H, .]
         weight, zero biases."""
         sd = {}
         for name, shape in self.param_shapes():
@@ -283,12 +328,16 @@ class Policy(_PolicyBase):
                 sd[name] = orthogonal(rng, *shape, gain=1.0)
             elif name.startswith("dist.fc_mean"):
                 sd[name] = orthogonal(rng, *shape, gain=1.0) / 50.0
+            elif name.startswith("dist.linear"):
+                sd[name] = orthogonal(rng, *shape, gain=0.01 if self.dist_kind == _lib.DIST_CATEGORICAL else 1.0)
             else:
                 sd[name] = orthogonal(rng, *shape, gain=np.sqrt(2))
         self.load_state_dict(sd)
 
     def reset_variance(self, action_space, log_std):
         """a2c/model.py:76-78"""
+        if self.dist_kind:   # (the reference dies with an AttributeError: Categorical / Bernoulli have no reset_variance)
+            raise ValueError("reset_variance: a Categorical / Bernoulli head has no log-std to reset (Box action spaces only)")
         sd = self.state_dict()
         sd["dist.logstd._bias"] = np.full((action_space.shape[0], 1), log_std, np.float32)
         self.load_state_dict(sd)
@@ -315,7 +364,7 @@ class Policy(_PolicyBase):
                                    "(a2c/main.py:85 precedes :149) or rebuild them afterwards")
             old, seed_, calls_ = self.h, self.seed, self._act_calls
             self._create(self.obs_dim, self.act_dim, self.hidden_size, self.num_feet, self.ctx, critic_hidden=64,
-                         recurrent=self._rec())
+                         recurrent=self._rec(), dist=self.dist_kind, n_out=self.__dict__.get("n_out"))
             self.seed, self._act_calls = seed_, calls_     # the action-noise stream goes on where it was
             self.lib.sg_policy_destroy(old)
         for name, shape in self.param_shapes():

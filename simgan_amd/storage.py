@@ -51,11 +51,12 @@ class RolloutStorage(object):
     def __init__(self, num_steps, num_processes, obs_shape, action_space,
                  recurrent_hidden_state_size, feat_len=0, ctx=None):
         T, N = int(num_steps), int(num_processes)
-        if action_space.__class__.__name__ == 'Discrete':
-            raise NotImplementedError("discrete action spaces never occur in SimGAN configs")
         if len(obs_shape) != 1:
             raise NotImplementedError("1-D observations only")
-        O, A, F = int(obs_shape[0]), int(action_space.shape[0]), int(feat_len)
+        # a2c/storage.py:42-48: Discrete -> actions [T, N, 1] int64 (the class index; float32 on the device), else [T, N, shape[0]]
+        self.discrete = action_space.__class__.__name__ == 'Discrete'
+        self.box_actions = action_space.__class__.__name__ == 'Box'
+        O, A, F = int(obs_shape[0]), 1 if self.discrete else int(action_space.shape[0]), int(feat_len)
         self.ctx = ctx or _lib.Context.default()   # (first: creating the context is what initialises the HIP runtime, with its settings)
         self.lib = self.ctx.lib
         # the host tensors live in page-locked memory (sg_host_alloc): ordinary CPU tensors to whoever slices them, one DMA
@@ -70,6 +71,8 @@ class RolloutStorage(object):
         self.returns = z(T + 1, N, 1)
         self.action_log_probs = z(T, N, 1)
         self.actions = z(T, N, A)
+        if self.discrete:
+            self.actions = self.actions.long() if hasattr(self.actions, "long") else self.actions.astype(np.int64)
         self.masks = o(T + 1, N, 1)
         # Masks that indicate whether it's a true terminal state or time limit end state
         self.bad_masks = o(T + 1, N, 1)
@@ -105,6 +108,10 @@ class RolloutStorage(object):
     def _host_np(self, field):
         t = getattr(self, _FIELD_ATTR[field])
         a = t.numpy() if hasattr(t, "numpy") else t
+        if field == _lib.F_ACTIONS and self.__dict__.get("discrete"):
+            if a.dtype != np.int64 or not a.flags["C_CONTIGUOUS"]:
+                raise TypeError("rollouts.actions of a Discrete action space must stay a contiguous int64 host tensor")
+            return a
         if a.dtype != np.float32 or not a.flags["C_CONTIGUOUS"]:
             raise TypeError(f"rollouts.{_FIELD_ATTR[field]} must stay a contiguous float32 host tensor")
         return a
@@ -145,8 +152,9 @@ class RolloutStorage(object):
         for f in (fields if fields is not None else _FIELD_ATTR):
             a = self._host_np(f)
             if a.size:
-                _lib.check(self.lib.sg_rollout_upload(self.h, f, _lib.fptr(a), a.size))
-                self.bytes_uploaded += a.nbytes
+                up = a.astype(np.float32) if a.dtype == np.int64 else a   # Discrete actions: int64 on the host, float32 on the device
+                _lib.check(self.lib.sg_rollout_upload(self.h, f, _lib.fptr(up), up.size))
+                self.bytes_uploaded += up.nbytes
             self._synced[f] = self._stamp(f)
             if _VERIFY:
                 self._crcs[f] = self._crc(f)
@@ -154,7 +162,11 @@ class RolloutStorage(object):
     def sync_from_device(self, fields=None):
         for f in (fields if fields is not None else _FIELD_ATTR):
             a = self._host_np(f)
-            if a.size:
+            if a.size and a.dtype == np.int64:   # Discrete actions: the device's float32 class indices back into the int64 host tensor
+                down = np.empty(a.shape, np.float32)
+                _lib.check(self.lib.sg_rollout_download(self.h, f, _lib.fptr(down), down.size))
+                a[...] = down
+            elif a.size:
                 _lib.check(self.lib.sg_rollout_download(self.h, f, _lib.fptr(a), a.size))
             self._synced[f] = self._stamp(f)   # (written through the numpy view: the version counter did not move)
             if _VERIFY:
@@ -195,9 +207,9 @@ class RolloutStorage(object):
 
         def put(dst, src):
             if torch is not None and hasattr(dst, "copy_"):
-                dst.copy_(src if hasattr(src, "dim") else torch.as_tensor(np.asarray(src, np.float32)))
+                dst.copy_(src if hasattr(src, "dim") else torch.as_tensor(np.asarray(src, np.int64 if dst.dtype == torch.int64 else np.float32)))
             else:
-                dst[...] = np.asarray(src, np.float32)
+                dst[...] = np.asarray(src, dst.dtype)
 
         put(self.obs[s + 1], obs)
         if obs_feat is not None:
@@ -220,6 +232,9 @@ class RolloutStorage(object):
         applied on the host row by row in both modes, as PPO applies it for the symmetry loss.  Matrices act on rows:
         mirrored = M @ x.  Fill the rollout through set_initial_obs_dup_sym / insert_dup_sym afterwards."""
         from . import symmetry as _sym
+        if not self.__dict__.get("box_actions", True):
+            raise NotImplementedError("enable_dup_sym: a mirror-augmented rollout mirrors actions through a linear map, which a class "
+                                      "index or a bit vector (Discrete / MultiBinary action space) does not have; Box action spaces only")
         N = self.num_processes
         if N % 2:
             raise ValueError(f"enable_dup_sym: the rollout has num_processes = {N}, an odd number: a mirror-augmented rollout "
