@@ -155,9 +155,7 @@ TEST_PROTOTYPES = {
     "sg_test_pmc_calibrate": (C.c_int, [H, C.c_int64]),
     "sg_test_pstep_probe": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ll_p, c_int_p]),
     "sg_test_graph_state": (C.c_int, [H, H, c_int_p]),
-    "sg_test_disc_phase_times": (C.c_int, [H, C.c_int, c_ll_p, C.c_int]),
     "sg_test_disc_gathers": (C.c_int, [H, c_ll_p]),
-    "sg_test_ppo_phase_times": (C.c_int, [H, C.c_int, c_ll_p, C.c_int]),
     "sg_test_rng": (C.c_int, [H, C.c_int, C.c_int64, C.c_uint64, C.c_void_p]),
     "sg_test_kfac_eig": (C.c_int, [H, C.c_int, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_int)]),
     "sg_test_acktr_noise": (C.c_int, [H, C.c_int64, C.c_uint64, C.c_int64, c_float_p]),

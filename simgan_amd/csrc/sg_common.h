@@ -316,7 +316,6 @@ struct sg_ppo {
     int64_t last_perm_count = 0;   // entries of d_perms the last update consumed (sg_ppo_last_perms)
     double* d_loss_acc = nullptr;  // [3] running loss sums over the update
     float* d_part = nullptr;       // per-block partial sums (sumsq, losses)
-    long long* d_dbg = nullptr;    // phase-timestamp buffer (test hook)
     unsigned* d_pair = nullptr;    // k_ppo_pair: error word
     bool self_wait_failed = false; // a k_ppo_pair hand-off timed out on this object: its later updates run the two-launch step
     bool pair_primed = false;      // the row stacks were cleared for k_ppo_pair's tagged words and no other mode has run since
@@ -377,7 +376,6 @@ struct sg_disc {
     int returns_n = 0;
     bool returns_none = true;
     uint64_t rng_calls = 0;
-    long long* d_dbg = nullptr;    // phase-timestamp buffer (test hook)
 };
 
 // Device-side optimizer scalars: kept in device memory so queued / graph-replayed launches never depend on

@@ -31,7 +31,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <chrono>
 #include <vector>
 
 #include "sg_common.h"
@@ -74,8 +73,8 @@ static void launch_disc_chain4(sg_ctx* ctx, const SgDiscDesc& dd, dim3 grid, con
     const int kf = dd.Fp / 16, kh = dd.Hp / 16;
     const dim3 block(64 * (kf > kh ? kf : kh));   // one wave per 16 output columns: no idle wave to launch and drain
 #define SG_CHAIN4(KF_, KH_)                                                                                         \
-    SG_LAUNCH(ctx, SG_PROF_DISC_CHAIN, (k_disc_chain4<KF_, KH_>), grid, block, 0, a.params, a.wT, a.ops, a.part, a.dbg, \
-              a.B, a.G, a.inv_B, a.lambda_, next)
+    SG_LAUNCH(ctx, SG_PROF_DISC_CHAIN, (k_disc_chain4<KF_, KH_>), grid, block, 0, a.params, a.wT, a.ops, a.part, a.B, \
+              a.G, a.inv_B, a.lambda_, next)
     if (kf == 6 && kh == 7) SG_CHAIN4(6, 7);
     else if (kf == 2 && kh == 7) SG_CHAIN4(2, 7);
     else SG_CHAIN4(1, 1);
@@ -626,14 +625,13 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
     // stacks[k&1], its spare workgroups gather step k+1's input rows into stacks[(k+1)&1]
     float* stacks[2] = {d->d_slabs, d->d_slabs + ops_f};
     a.part = d->d_slabs + 2 * ops_f; a.st = reinterpret_cast<SgOptState*>(d->d_state);
-    a.dbg = d->d_dbg;
     a.wT = d->d_wT;
     float* grad = d->d_slabs + 2 * ops_f + part_f;
     WgradArgs wa;
     wa.d = dd; wa.part = a.part; wa.G = G; wa.params = d->d_params; wa.m = d->d_m; wa.v = d->d_v;
     wa.grad_out = sharded ? grad : nullptr; wa.st = a.st; wa.eps = 1e-8f; wa.inv_B = a.inv_B; wa.lambda_ = a.lambda_;
     wa.loss_acc = d->d_loss_acc;
-    wa.nparts = n_chain_wg; wa.wT = d->d_wT; wa.dbg = d->d_dbg;
+    wa.nparts = n_chain_wg; wa.wT = d->d_wT;
     const size_t lds = disc_chain_lds_bytes(dd, gw);
     const int n_tiles = (dd.Hp / 16) * (dd.Hp / 16) + (dd.Hp / 16) * (dd.Fp / 16);
     const int nblk = (dd.total + 255) / 256;
@@ -648,10 +646,8 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
     const char* fenv = getenv("SG_DISC_FUSED");
     // ... and the device is this context's alone (sg_ctx_exclusive: a launch that waits inside itself needs all its workgroups
     // resident); SG_DISC_FUSED=1 forces it (tests), =0 forbids it
-    const bool fused = thin && !sharded && !owned && !d->d_dbg && wa.xcd_map && 12 * G <= SG_STEP4_MAX_FLAGS && !d->self_wait_failed &&
+    const bool fused = thin && !sharded && !owned && wa.xcd_map && 12 * G <= SG_STEP4_MAX_FLAGS && !d->self_wait_failed &&
                        (fenv ? strcmp(fenv, "0") != 0 : sg_ctx_exclusive(ctx));
-    const bool dbg_timing = getenv("SG_DEBUG_TIMING") != nullptr;
-    const auto t_enq0 = std::chrono::steady_clock::now();
     // One epoch = zero the loss sums, gather step 0's rows, then (chain, weight gradient) per step, then commit
     // the step count.  No argument of these ~2 n_d launches depends on anything but buffer addresses and the
     // batch geometry (the Adam step number lives on the device), so the sequence is captured into a hipGraph
@@ -704,7 +700,7 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
             else launch_disc_chain(ctx, dd, dim3(n_chain_wg), lds, a, gw);
             SG_LAUNCH(ctx, SG_PROF_DISC_WGRAD, k_disc_wgrad, dim3(n_wgrad_blocks), dim3(SG_WGRAD_THREADS), 0, wa.ops, wa.params, wa.m,
                       wa.v, wa.st, wa.wT, dd.Hp | (dd.Fp << 16),
-                      sg_wgrad_pack(wa.G, (wa.xcd_map ? 1 : 0) | (wa.grad_out ? 2 : 0) | (wa.dbg ? 4 : 0) | (thin ? 8 : 0), wa.k1), wa);
+                      sg_wgrad_pack(wa.G, (wa.xcd_map ? 1 : 0) | (wa.grad_out ? 2 : 0) | (thin ? 8 : 0), wa.k1), wa);
             if (sharded) {
                 SG_TRY(sg_comm_allreduce_f32(ctx, grad, (int64_t)grad_f));
                 hipLaunchKernelGGL(k_disc_adam_flat, dim3(nblk), dim3(256), 0, ctx->stream, d->d_params, d->d_m, d->d_v, grad,
@@ -717,7 +713,7 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
     // Sharded mode has one RCCL all-reduce per step inside the sequence: captured with it (see sg_ppo_update), unless
     // SG_DISC_GRAPH_COMM=0 or the RCCL build refuses the capture.
     const bool comm_ok = !sharded || (sg_comm_graph_ok(ctx) && !sg_env_is_off("SG_DISC_GRAPH_COMM"));
-    const bool use_graph = comm_ok && !owned && !ctx->profile && !d->d_dbg && !sg_env_is_off("SG_DISC_GRAPH");
+    const bool use_graph = comm_ok && !owned && !ctx->profile && !sg_env_is_off("SG_DISC_GRAPH");
     const uint64_t key[SG_GRAPH_KEY_WORDS] = {   // (12 words in use, the rest zero)
             (uint64_t)(uintptr_t)d->d_slabs, (uint64_t)(uintptr_t)d->d_eperm, (uint64_t)(uintptr_t)d->d_pperm,
             (uint64_t)(uintptr_t)d->d_alpha, (uint64_t)(uintptr_t)next_feat, (uint64_t)(uintptr_t)d->d_expert,
@@ -726,7 +722,6 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
             (uint64_t)(uintptr_t)d->d_erows ^ ((uint64_t)(uintptr_t)d->d_prows << 1)};
     SG_TRY(sg_graph_run(ctx, &d->epoch_graph, use_graph, key, enqueue_epoch));
     SG_CHECK(hipGetLastError());
-    const auto t_enq1 = std::chrono::steady_clock::now();
     d->opt_t += n_d;
     d->last_n_d = n_d;
     // out3 == NULL: the caller does not want this epoch's losses (the reference's main keeps only the last epoch's,
@@ -735,12 +730,6 @@ static int disc_update_core(sg_disc* d, const float* rows_local, int64_t TN_loc,
     if (!out3) return 0;
     double acc[3];
     SG_TRY(sg_ctx_fetch_f64(ctx, d->d_loss_acc, acc, 3));
-    if (dbg_timing) {
-        const auto t_done = std::chrono::steady_clock::now();
-        fprintf(stderr, "[sg] disc epoch: %d steps, enqueue %.3f ms, enqueue->done %.3f ms\n", n_d,
-                std::chrono::duration<double, std::milli>(t_enq1 - t_enq0).count(),
-                std::chrono::duration<double, std::milli>(t_done - t_enq1).count());
-    }
     if (fused && acc[0] != acc[0]) {   // NaN: either the data, or a weight-gradient workgroup of k_disc_step4 gave up waiting
         unsigned err = 0;
         SG_COPY_SYNC(ctx, &err, reinterpret_cast<unsigned*>(d->d_state) + SG_STEP4_ERR_WORD, sizeof err, hipMemcpyDeviceToHost);

@@ -47,16 +47,8 @@ struct DiscArgs {
     float* ops;              // operand stacks: L2 | R2 | L1 [Kt][ldH] each, then R1 [Kt][ldF]
     float* part;             // [2G][4*Hp]: db1 | db2 | dw3 | {db3, loss_expert, loss_policy, loss_gp, 0...}
     SgOptState* st;
-    long long* dbg;          // optional phase timestamps [block][32] (test hook), NULL in production
     const float* wT;         // k_disc_chain4: weight images W1 | W2 | W2^T | W1^T (sg4_img_index), kept in step by k_disc_wgrad
 };
-
-// barrier + (test hook) shader-clock timestamp of the phase that just ended
-#define SG_PHASE_SYNC(n)                                                         \
-    do {                                                                         \
-        __syncthreads();                                                         \
-        if (a.dbg && threadIdx.x == 0) a.dbg[blockIdx.x * 32 + (n)] = clock64(); \
-    } while (0)
 
 __device__ __forceinline__ float sg_log_sigmoid(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
 __device__ __forceinline__ float sg_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
@@ -212,7 +204,6 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
     float* R1s = stk.R1;     // row-major: pre-gathered input rows
     float* R1t = stk.R1t;    // tiled: gb rows for the weight gradient
     float* part = a.part + (size_t)blockIdx.x * (4 * Hp);   // db1 | db2 | dw3 | scalars
-    if (a.dbg && tid == 0) a.dbg[blockIdx.x * 32] = clock64();
 
     const int li = tid & 15, lq = (tid & 63) >> 4;
     if ((int)blockIdx.x < a.G) {
@@ -235,15 +226,15 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
             *reinterpret_cast<float4*>(X + r * ldF + c) = *reinterpret_cast<const float4*>(R1s + (size_t)(row0 + r) * ldF + c);
         }
         if (!GW) sg_stage_commit<12>(smem, wv, a.params, d.total / 4);
-        SG_PHASE_SYNC(1);
+        __syncthreads();
         sg_layer_nt<2, GW>(X, ldF, W1, ldF, Fp, Hp, [&](int r, int c, float v) {
             const float h = sg_tanh(v + b1[c]);
             H1[r * ldH + c] = h;
             R2s[SG_STK(Kt, row0 + r, c)] = h;
         });
-        SG_PHASE_SYNC(2);
+        __syncthreads();
         sg_layer_nt<2, GW>(H1, ldH, W2, ldH, Hp, Hp, [&](int r, int c, float v) { H2[r * ldH + c] = sg_tanh(v + b2[c]); });
-        SG_PHASE_SYNC(3);
+        __syncthreads();
         {   // logits, BCE losses and dL/dd: blockDim/32 lanes per row   (a2c/algo/gail.py:168-176)
             const int L = blockDim.x / R, r = tid / L, sub = tid % L;
             float s = 0.f;
@@ -261,7 +252,7 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
                 LOSS[r] = loss;
             }
         }
-        SG_PHASE_SYNC(4);
+        __syncthreads();
         // dw3, db2, db3 and dZ2 (in place over H2, and into the left stack), one thread per hidden column
         for (int c = tid; c < Hp; c += blockDim.x) {
             const float w = w3[c];
@@ -284,7 +275,7 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
             if (tid == 258) for (int r = 16; r < 32; ++r) s += LOSS[r];           // sum policy BCE
             part[3 * Hp + tid - 256] = s;
         }
-        SG_PHASE_SYNC(5);
+        __syncthreads();
         // dZ1 = (dZ2 W2) * (1 - h1^2) straight to the left stack; db1 from the epilogue registers
         sg_layer_nn_t<2>(H2, ldH, W2, ldH, Hp, Hp, [&](int tn, f32x4 (&acc)[2][1]) {
             const int c = tn * 16 + li;
@@ -323,13 +314,13 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
             *reinterpret_cast<float4*>(XM + r * ldF + c) = *reinterpret_cast<const float4*>(R1s + (size_t)(rowB + r) * ldF + c);
         }
         if (!GW) sg_stage_commit<12>(smem, wv, a.params, d.total / 4);
-        SG_PHASE_SYNC(8);
+        __syncthreads();
         sg_layer_nt<1, GW>(XM, ldF, W1, ldF, Fp, Hp, [&](int r, int c, float v) {
             const float h = sg_tanh(v + b1[c]);
             H1[r * ldH + c] = h;
             R2s[SG_STK(Kt, rowB + r, c)] = h;
         });
-        SG_PHASE_SYNC(9);
+        __syncthreads();
         sg_layer_nt<1, GW>(H1, ldH, W2, ldH, Hp, Hp, [&](int r, int c, float v) {
             const float h = sg_tanh(v + b2[c]);
             const float d2 = w3[c] * (1.f - h * h);
@@ -337,7 +328,7 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
             D2[r * ldH + c] = d2;
             L2s[SG_STK(Kt, rowA + r, c)] = d2;
         });
-        SG_PHASE_SYNC(10);
+        __syncthreads();
         sg_layer_nn<1>(D2, ldH, W2, ldH, Hp, Hp, [&](int r, int c, float v) {      // u1 = d2 W2
             const float h = H1[r * ldH + c];
             const float d1 = v * (1.f - h * h);
@@ -345,9 +336,9 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
             D1[r * ldH + c] = d1;
             L1s[SG_STK(Kt, rowA + r, c)] = d1;
         });
-        SG_PHASE_SYNC(11);
+        __syncthreads();
         sg_layer_nn<1>(D1, ldH, W1, ldF, Hp, Fp, [&](int r, int c, float v) { GX[r * ldF + c] = v; });  // g = d1 W1
-        SG_PHASE_SYNC(12);
+        __syncthreads();
         {   // per-row |g|, penalty and gb = c_r * g: blockDim/16 lanes per row   (a2c/algo/gail.py:88)
             const int L = blockDim.x / R, r = tid / L, sub = tid % L;
             float s = 0.f;
@@ -363,7 +354,7 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
             }
             if (sub == 0) ROWL[r] = valid ? (nn - 1.f) * (nn - 1.f) : 0.f;
         }
-        SG_PHASE_SYNC(13);
+        __syncthreads();
         sg_layer_nt<1, GW>(GX, ldF, W1, ldF, Fp, Hp, [&](int r, int c, float v) {      // bd1 = gb W1^T
             const float h = H1[r * ldH + c];
             const float bu1 = v * (1.f - h * h);
@@ -371,7 +362,7 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
             R2s[SG_STK(Kt, rowA + r, c)] = bu1;
             U1[r * ldH + c] = v * U1[r * ldH + c];                                  // sb1 = bd1*u1
         });
-        SG_PHASE_SYNC(14);
+        __syncthreads();
         sg_layer_nt_t<1, GW>(BU1, ldH, W2, ldH, Hp, Hp, [&](int tn, f32x4 (&acc)[1][1]) {  // bd2 = bu1 W2^T
             const int c = tn * 16 + li;
             const float w = w3[c];
@@ -388,7 +379,7 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
             const float sw = sg_tile_colsum<1>(t3), sb = sg_tile_colsum<1>(z);
             if (lq == 0) { part[2 * Hp + c] = sw; part[Hp + c] = sb; }
         });
-        SG_PHASE_SYNC(15);
+        __syncthreads();
         sg_layer_nn_t<1>(Z2B, ldH, W2, ldH, Hp, Hp, [&](int tn, f32x4 (&acc)[1][1]) {  // h1b = z2b W2
             const int c = tn * 16 + li;
             float z[1][4];
@@ -408,7 +399,7 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
             part[3 * Hp + tid - 448] = s;
         }
     }
-    SG_PHASE_SYNC(31);
+    __syncthreads();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -422,7 +413,7 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
 //   k_disc_chain the step uses 4x the CUs and a phase costs 28 MFMA issues per wave instead of 56
 //   16x16x4 issues (4x the cycles each).  Operand stacks, partials and math are identical.
 //   Requires compile-time KF, KH <= 8 (one wave per 16 columns, at most 8 waves; launched with exactly max(KF,KH) waves).
-// Arguments are individual scalars / pointers (14 dwords), not a struct: the code object asks the command
+// Arguments are individual scalars / pointers (12 dwords), not a struct: the code object asks the command
 // processor to preload them into SGPRs (-amdgpu-kernarg-preload-count), so the first global loads do not wait
 // for a kernarg fetch from memory (~1 us after a fresh launch).
 // A wave cannot run ahead of the vector-memory instructions it has issued, and a CU's memory pipe moves ~64 B per clock:
@@ -440,7 +431,6 @@ __global__ __launch_bounds__(SG_DISC_THREADS) void k_disc_chain(DiscArgs a) {
 struct Chain4Args {
     const float *params, *wT;
     float *ops, *part;
-    long long* dbg;
     int B, G;
     float inv_B, lambda_;
 };
@@ -481,7 +471,6 @@ __device__ __forceinline__ void sg_chain4_body(const Chain4Args& a, float* sm) {
     float* R1s = stk.R1;     // row-major: pre-gathered input rows
     float* R1t = stk.R1t;    // tiled: gb rows for the weight gradient
     float* part = a.part + (size_t)blockIdx.x * (4 * Hp);   // db1 | db2 | dw3 | scalars
-    if (a.dbg && tid == 0) { a.dbg[blockIdx.x * 32] = clock64(); a.dbg[blockIdx.x * 32 + 28] = wall_clock64(); }
     float4 w1[SG4_NW(Fp)], w2[SG4_NW(Hp)], w2t[SG4_NW(Hp)];
     float b1c = 0.f, b2c = 0.f, w3c = 0.f;
 
@@ -517,7 +506,7 @@ __device__ __forceinline__ void sg_chain4_body(const Chain4Args& a, float* sm) {
             H1[s * ldAH + col] = h1;
             sg_pub<WT>(&R2s[SG_STK(Kt, r0 + s, col)], h1);
         }
-        SG_PHASE_SYNC(1);
+        __syncthreads();
         if (actH) {
             float4 ah[1][SG4_NCH(Hp)];
             float o[1];
@@ -527,7 +516,7 @@ __device__ __forceinline__ void sg_chain4_body(const Chain4Args& a, float* sm) {
             const float pl = sg4_rowsum16(h2 * w3c);
             if (cl == 0) LP[tile * 4 + s] = pl;
         }
-        SG_PHASE_SYNC(2);
+        __syncthreads();
         {   // logit, BCE loss and dL/dd of this lane's row   (a2c/algo/gail.py:168-176)
             const bool valid = bi0 + s < a.B;
             float dd = b3;
@@ -553,7 +542,7 @@ __device__ __forceinline__ void sg_chain4_body(const Chain4Args& a, float* sm) {
                 if (lane < 4) sg_pub<WT>(&part[3 * Hp + lane], lane == 0 ? db3 : (lane == 1 && !is_policy) || (lane == 2 && is_policy) ? ls : 0.f);
             }
         }
-        SG_PHASE_SYNC(3);
+        __syncthreads();
         if (actH) {   // dZ1 = (dZ2 W2) * (1 - h1^2) straight to the left stack; db1 = its column sums
             float4 ad[1][SG4_NCH(Hp)];
             float o[1];
@@ -595,7 +584,7 @@ __device__ __forceinline__ void sg_chain4_body(const Chain4Args& a, float* sm) {
             H1[s * ldAH + col] = h1;
             sg_pub<WT>(&R2s[SG_STK(Kt, rowB + s, col)], h1);
         }
-        SG_PHASE_SYNC(8);
+        __syncthreads();
         if (actH) {
             float4 av[1][SG4_NCH(Hp)];
             float o[1];
@@ -609,7 +598,7 @@ __device__ __forceinline__ void sg_chain4_body(const Chain4Args& a, float* sm) {
             D2[s * ldAH + col] = d2;
             sg_pub<WT>(&L2s[SG_STK(Kt, rowA + s, col)], d2);
         }
-        SG_PHASE_SYNC(9);
+        __syncthreads();
         if (actH) {   // u1 = d2 W2
             float4 av[1][SG4_NCH(Hp)];
             float o[1];
@@ -620,7 +609,7 @@ __device__ __forceinline__ void sg_chain4_body(const Chain4Args& a, float* sm) {
             D1[s * ldAH + col] = d1;
             sg_pub<WT>(&L1s[SG_STK(Kt, rowA + s, col)], d1);
         }
-        SG_PHASE_SYNC(10);
+        __syncthreads();
         if (actF) {   // g = d1 W1
             float4 av[1][SG4_NCH(Hp)];
             float o[1];
@@ -629,7 +618,7 @@ __device__ __forceinline__ void sg_chain4_body(const Chain4Args& a, float* sm) {
             gown = o[0];
             GX[s * ldAF + col] = gown;
         }
-        SG_PHASE_SYNC(11);
+        __syncthreads();
         {   // per-row |g|, penalty coefficient c_r (a2c/algo/gail.py:88) and bd1 = (c_r g) W1^T.  The row scale
             // commutes with the GEMM, so g W1^T is issued straight after the barrier and scaled by this lane's own
             // c_r in the epilogue; the norms (every wave recomputes the four of them from LDS rather than spending a
@@ -660,7 +649,7 @@ __device__ __forceinline__ void sg_chain4_body(const Chain4Args& a, float* sm) {
                 sb1 = bd1 * u1;
             }
         }
-        SG_PHASE_SYNC(13);
+        __syncthreads();
         if (actH) {   // bd2 = bu1 W2^T
             float4 av[1][SG4_NCH(Hp)];
             float o[1];
@@ -674,7 +663,7 @@ __device__ __forceinline__ void sg_chain4_body(const Chain4Args& a, float* sm) {
             const float sw = sg4_colsum(t3), sb = sg4_colsum(z2b);
             if (s == 0) { sg_pub<WT>(&part[2 * Hp + col], sw); sg_pub<WT>(&part[Hp + col], sb); }
         }
-        SG_PHASE_SYNC(14);
+        __syncthreads();
         if (actH) {   // h1b = z2b W2
             float4 av[1][SG4_NCH(Hp)];
             float o[1];
@@ -686,14 +675,13 @@ __device__ __forceinline__ void sg_chain4_body(const Chain4Args& a, float* sm) {
             if (s == 0) sg_pub<WT>(&part[col], sb);
         }
     }
-    SG_PHASE_SYNC(31);
-    if (a.dbg && tid == 0) a.dbg[blockIdx.x * 32 + 29] = wall_clock64();
+    __syncthreads();
 }
 #define SG_CHAIN4_LDS_FLOATS(KF, KH) (5 * 4 * (16 * (KH) + 8) + 4 * (16 * (KF) + 8) + 64)
 
 template <int KF, int KH>
-__global__ __launch_bounds__(512) void k_disc_chain4(const float* params, const float* wT, float* ops, float* part_base,
-                                                    long long* dbg, int B, int G, float inv_B, float lambda_, PregatherArgs next) {
+__global__ __launch_bounds__(512) void k_disc_chain4(const float* params, const float* wT, float* ops, float* part_base, int B, int G,
+                                                    float inv_B, float lambda_, PregatherArgs next) {
     // Workgroups past the 12G chain blocks copy the NEXT step's rows into the other parity's operand stacks (nothing of this
     // step touches those).  Such a block is one round trip to the epoch's row copies in HBM + the write-back of its stores,
     // ~2.5 us: riding in k_disc_wgrad (rounds 1-3) it was as long as that kernel's tile blocks (round 4: the weight-gradient
@@ -704,7 +692,7 @@ __global__ __launch_bounds__(512) void k_disc_chain4(const float* params, const 
         return;
     }
     __shared__ __attribute__((aligned(16))) float sm[SG_CHAIN4_LDS_FLOATS(KF, KH)];
-    const Chain4Args a{params, wT, ops, part_base, dbg, B, G, inv_B, lambda_};
+    const Chain4Args a{params, wT, ops, part_base, B, G, inv_B, lambda_};
     sg_chain4_body<KF, KH, false>(a, sm);
 }
 
@@ -750,7 +738,6 @@ struct WgradArgs {
     int nparts;               // workgroups of the chain kernel (rows of `part`)
     int k1;                   // 1-based step index within the epoch: Adam step t = st->t0 + k1, scalars in slot t & 1
     float* wT;                // k_disc_chain4's weight images to keep in step (NULL: not maintained)
-    long long* dbg;           // optional wall-clock stamps per block (test hook), NULL in production
     int xcd_map;              // tiles grouped by row panel per XCD (grid = align8(2G) + 8 * (th + tf) blocks)
 };
 
@@ -783,7 +770,7 @@ __host__ __device__ __forceinline__ int sg_wgrad_pack(int G, int flags, int k1) 
 constexpr float SG_DISC_ADAM_EPS = 1e-8f;   // a2c/algo/gail.py:48 (torch.optim.Adam default)
 __global__ __launch_bounds__(SG_WGRAD_THREADS) void k_disc_wgrad(const float* c_ops, float* c_params, float* c_m, float* c_v,
                                                                 const SgOptState* c_st, float* c_wT, int c_HpFp /* Hp | Fp << 16 */,
-                                                                int c_pack /* G | flags << 10 | k1 << 14; flags 1: xcd_map, 2: grad_out set, 4: dbg set, 8: 4-row chain */,
+                                                                int c_pack /* G | flags << 10 | k1 << 14; flags 1: xcd_map, 2: grad_out set, 8: 4-row chain */,
                                                                 WgradArgs a) {
     __shared__ float red[8][256];
     SgDiscDesc d;   // same arithmetic as sg_make_disc_desc, from the preloaded extents
@@ -792,15 +779,12 @@ __global__ __launch_bounds__(SG_WGRAD_THREADS) void k_disc_wgrad(const float* c_
     d.w1 = 0; d.b1 = d.Hp * d.ldF; d.w2 = d.b1 + d.Hp; d.b2 = d.w2 + d.Hp * d.ldH;
     d.w3 = d.b2 + d.Hp; d.b3 = d.w3 + d.Hp; d.total = d.b3 + 16;
     const int c_G = c_pack & 1023, c_flags = (c_pack >> 10) & 15, c_k1 = (int)((unsigned)c_pack >> 14);
-    const bool xcd_map = c_flags & 1, has_grad_out = c_flags & 2, has_dbg = c_flags & 4;
+    const bool xcd_map = c_flags & 1, has_grad_out = c_flags & 2;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lq = lane >> 4;
     constexpr int nw = SG_WGRAD_THREADS / 64;
     const int th = d.Hp >> 4, tf = d.Fp >> 4;
     const int T2 = th * th, T1 = th * tf;
     const int Kt = 64 * c_G;
-    // test hook: wall clock (100 MHz) at block start / after the operand loads / after the LDS reduce / end
-    long long* stamp = (has_dbg && threadIdx.x == 0) ? a.dbg + 32 * 256 + 4 * blockIdx.x : nullptr;
-    if (stamp) stamp[0] = wall_clock64();
     // Role of this workgroup: 0 weight tile b, 1 vector block b, 2 everything short (copy the next step's rows and / or
     // evaluate the next step's Adam scalars, or nothing); the double-precision pow() of the Adam scalars is instantiated once.
     int role, b = 0, j = 0;
@@ -830,7 +814,6 @@ __global__ __launch_bounds__(SG_WGRAD_THREADS) void k_disc_wgrad(const float* c_
     if (__builtin_expect(role == 2, 0)) {
         if (prepare && tid == 0) {
             sg_opt_prepare(const_cast<SgOptState*>(c_st), c_st->t0 + c_k1 + 1);
-            if (stamp) stamp[3] = wall_clock64();
         }
         if (gather && a.next.ops) sg_disc_pregather(a.next, j);
         return;
@@ -882,9 +865,7 @@ __global__ __launch_bounds__(SG_WGRAD_THREADS) void k_disc_wgrad(const float* c_
         acc += alt;
 #pragma unroll
         for (int r = 0; r < 4; ++r) red[wave][(4 * lq + r) * 16 + li] = acc[r];
-        if (stamp) stamp[1] = wall_clock64();
         __syncthreads();
-        if (stamp) stamp[2] = wall_clock64();
         if (tid < 256) {
             // every address is formed before the first store: an index computed after a store would reuse the store's
             // data registers and make the compiler wait for the store to be acknowledged (a memory round trip)
@@ -913,7 +894,6 @@ __global__ __launch_bounds__(SG_WGRAD_THREADS) void k_disc_wgrad(const float* c_
                 if (c_wT) { __builtin_nontemporal_store(p0, c_wT + img0); __builtin_nontemporal_store(p0, c_wT + img1); }
             }
         }
-        if (stamp) stamp[3] = wall_clock64();
     } else {
         // vectors: db1 | db2 | dw3 | db3 and the three loss sums from the per-workgroup partials.  Vector block vb
         // owns elements [64 vb, 64 vb + 64); its 8 waves each sum an eighth of the partials (independent

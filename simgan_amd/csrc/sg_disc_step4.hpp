@@ -88,7 +88,7 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
         if (wave >= NWC) return;   // the launch has 8 waves per workgroup for the tile blocks; the chain uses one per column tile
         int t0 = 0;
         if (tid == 0) t0 = c_st->t0;
-        Chain4Args ca{c_params, c_wT, c_ops, c_part, nullptr, c_B, c_G, 1.0f / (float)c_B, 10.0f};   // (time stamps: the two-launch path)
+        Chain4Args ca{c_params, c_wT, c_ops, c_part, c_B, c_G, 1.0f / (float)c_B, 10.0f};
         sg_chain4_body<KF, KH, true>(ca, sm);
         // every wave drains its write-through stores BEFORE the barrier the flag store sits behind.  The wait has to be spelt
         // out: __syncthreads() is a workgroup-scope fence, for which gfx950 needs no vmcnt wait (the waves of a workgroup share

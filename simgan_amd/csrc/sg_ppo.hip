@@ -300,7 +300,6 @@ extern "C" int sg_ppo_destroy(sg_ppo* a) {
     for (float* q : ptrs) if (q) (void)sg_dev_free(q);
     if (a->d_perms) (void)sg_dev_free(a->d_perms);
     if (a->d_loss_acc) (void)sg_dev_free(a->d_loss_acc);
-    if (a->d_dbg) (void)sg_dev_free(a->d_dbg);
     if (a->d_pair) (void)sg_dev_free(a->d_pair);
     if (a->h_h0) (void)sg_host_release(a->h_h0);
     for (hipEvent_t ev : a->h0_ev) if (ev) (void)hipEventDestroy(ev);
@@ -843,7 +842,7 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
     pa.sc_stride = TNp; pa.mb = mb; pa.mbp = mbp; pa.inv_B = 1.0f / (float)mb;
     pa.clip = a->cfg.clip_param; pa.vcoef = a->cfg.value_loss_coef; pa.ecoef = a->cfg.entropy_coef;
     pa.use_clipped = a->cfg.use_clipped_value_loss;
-    pa.slabs = a->d_slabs; pa.slab_stride = slab_stride; pa.ldP = ldP; pa.dbg = nullptr;
+    pa.slabs = a->d_slabs; pa.slab_stride = slab_stride; pa.ldP = ldP;
     pa.st = reinterpret_cast<SgOptState*>(a->d_state); pa.G = G; pa.k1 = 0;
     pa.pair = a->d_pair; pa.Xm = nullptr; pa.MA = nullptr; pa.sym_c = 0.f;
     for (int t = 0; t < 3; ++t) { pa.H1[t] = hX; pa.H2[t] = hX; pa.OUT[t] = hX; }   // the fused form keeps its activations in LDS
@@ -1088,7 +1087,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     pa.sc_stride = TNp; pa.mb = mb; pa.mbp = mbp; pa.inv_B = 1.0f / (float)mb_global;
     pa.clip = a->cfg.clip_param; pa.vcoef = a->cfg.value_loss_coef; pa.ecoef = a->cfg.entropy_coef;
     pa.use_clipped = a->cfg.use_clipped_value_loss;
-    pa.slabs = a->d_slabs; pa.slab_stride = slab_stride; pa.ldP = ldP; pa.dbg = a->d_dbg;
+    pa.slabs = a->d_slabs; pa.slab_stride = slab_stride; pa.ldP = ldP;
     pa.st = reinterpret_cast<SgOptState*>(a->d_state); pa.G = G; pa.k1 = 0;
     pa.pair = a->d_pair;
     pa.Xm = nullptr; pa.MA = a->d_mact;
@@ -1111,7 +1110,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     // the two actor workgroups of a row group exchanging their head outputs inside it (k_ppo_pair).  SG_PPO_PAIR=0: two launches.
     const char* penv = getenv("SG_PPO_PAIR");
     const bool pair = !gw && !fused && !crit_first && d.kind == SG_POLICY_SPLIT && d.n_trunks == 3 && MT <= 2 &&
-                      lds_fc <= (size_t)ctx->lds_bytes && 3 * G <= ctx->num_cu && 2 * ldP + 2 <= std::min(d.trunk[0].ldH, d.trunk[1].ldH) && !a->d_dbg &&
+                      lds_fc <= (size_t)ctx->lds_bytes && 3 * G <= ctx->num_cu && 2 * ldP + 2 <= std::min(d.trunk[0].ldH, d.trunk[1].ldH) &&
                       !a->self_wait_failed && (penv ? strcmp(penv, "0") != 0 : sg_ctx_exclusive(ctx));   // (=1 forces it on a shared device: tests)
     // (the tagged words live in the ACTOR trunks' H1 rows, indexed with the trunk's own ldH: d.ldH is the widest trunk's, which a
     // critic rebuilt wider than the actors -- sg_policy_create2 -- would make too generous a bound)
@@ -1189,7 +1188,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     // stream like any kernel), so N > 1 keeps the one-call-per-update property; SG_PPO_GRAPH_COMM=0 or a capture the
     // RCCL build refuses falls back to direct launches.
     const bool comm_ok = !ctx->use_comm || (sg_comm_graph_ok(ctx) && !sg_env_is_off("SG_PPO_GRAPH_COMM"));
-    const bool use_graph = comm_ok && !owned && !ctx->profile && !a->d_dbg && !sg_env_is_off("SG_PPO_GRAPH");
+    const bool use_graph = comm_ok && !owned && !ctx->profile && !sg_env_is_off("SG_PPO_GRAPH");
     uint32_t fbits[6];
     const float fv[6] = {a->cfg.clip_param, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B};
     memcpy(fbits, fv, sizeof fbits);

@@ -45,7 +45,6 @@ struct PpoArgs {
     int slab_stride;
     int ldP;              // stride of the OUT stacks (max over trunks)
     int wbuf_floats;
-    long long* dbg;       // optional phase timestamps [block][16] (test hook), NULL in production
     SgOptState* st;       // optimizer scalars (read by k_ppo_adam; prepared one step ahead by the previous k_ppo_adam)
     int k1, G;            // 1-based step index within the update; row groups
     unsigned* pair;       // k_ppo_pair: the error word an actor workgroup raises when its partner never shows up
@@ -68,9 +67,6 @@ struct PpoArgs {
 // the acknowledgement of the gradient-slab stores the phase has just issued -- a memory round trip per phase for data no
 // later phase of the kernel reads.
 #define SG_LDS_SYNC() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
-#define SG_PPO_STAMP(n) do { if (a.dbg && threadIdx.x == 0 && blockIdx.y == 0) a.dbg[blockIdx.x * 16 + (n)] = clock64(); } while (0)
-#define SG_PPO_WALL(n) do { if (a.dbg && threadIdx.x == 0 && blockIdx.y < 2) a.dbg[(blockIdx.x + 512 * blockIdx.y) * 16 + (n)] = wall_clock64(); } while (0)
 
 struct EpochGatherArgs {
     const float *obs, *actions, *old_logp, *adv, *vpred, *ret;
@@ -180,7 +176,6 @@ __device__ __forceinline__ void sg_ppo_fwd_body(const PpoArgs& a, const int t, c
     float* H2 = H1 + R * ldH;
     const int row0 = bx * R;
 
-    SG_PPO_STAMP(0);
     float4 wv[12];
     if (!GW) sg_stage_issue<12>(wv, a.params + tr.off, tr.size / 4);
     {   // the row tile: contiguous in the epoch's permuted copy
@@ -188,10 +183,8 @@ __device__ __forceinline__ void sg_ppo_fwd_body(const PpoArgs& a, const int t, c
         float4* lx = reinterpret_cast<float4*>(X);
         for (int i = tid; i < R * ldO / 4; i += blockDim.x) lx[i] = gx[i];
     }
-    SG_PPO_STAMP(1);
     if (!GW) sg_stage_commit<12>(smem, wv, a.params + tr.off, tr.size / 4);
     __syncthreads();
-    SG_PPO_STAMP(2);
     const float* b1 = W + tr.b1;
     const float* b2 = W + tr.b2;
     const float* bh = W + tr.bh;
@@ -204,17 +197,14 @@ __device__ __forceinline__ void sg_ppo_fwd_body(const PpoArgs& a, const int t, c
         gH1[r * ldH + c] = h;
     });
     __syncthreads();
-    SG_PPO_STAMP(3);
     sg_layer_nt_u<MT, GW>(H1, ldH, W + tr.w2, ldH, Hp, Hp, [&](int r, int c, float v) {
         const float h = sg_tanh(v + b2[c]);
         H2[r * ldH + c] = h;
         gH2[r * ldH + c] = h;
     });
     __syncthreads();
-    SG_PPO_STAMP(4);
     sg_layer_nt_u<MT, GW>(H2, ldH, W + tr.wh, ldH, Hp, tr.Pp, [&](int r, int c, float v) { gOUT[r * ldP + c] = v + bh[c]; });
     __syncthreads();
-    SG_PPO_STAMP(5);
 }
 
 template <int MT, int KO, int KH, bool GW = false>
@@ -319,8 +309,6 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
     const int row0 = bx * R;
     float* slab = a.slabs + (size_t)(mirror ? a.G + bx : bx) * a.slab_stride;
 
-    SG_PPO_STAMP(8);
-    SG_PPO_WALL(6);
     unsigned pair_tag = 0;
     bool pair_failed = false;
     if (PAIR && !critic) pair_tag = (unsigned)(a.st->t0 + a.k1);
@@ -382,24 +370,19 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
 #pragma unroll
         for (int q = 0; q < 4; ++q) SC[q * R + tid] = scv[q];
     }
-    SG_PPO_STAMP(0);
     if (!GW) sg_stage_commit<12>(Wimg, wv, a.params + tr.off + w_first, wfl / 4);
     __syncthreads();
-    SG_PPO_STAMP(1);
     if (FUSED) {   // forward on this row group (a2c/model.py:255-264, a2c/distributions.py:109-118), activations stay in LDS
         const float* b1 = W + tr.b1;
         const float* b2 = W + tr.b2;
         const float* bh = W + tr.bh;
         sg_layer_nt_u<MT, GW>(X, ldO, W + tr.w1, ldO, Op, Hp, [&](int r, int c, float v) { H1[r * ldH + c] = sg_tanh(v + b1[c]); });
         __syncthreads();
-        SG_PPO_STAMP(2);
         sg_layer_nt_u<MT, GW>(H1, ldH, W + tr.w2, ldH, Hp, Hp, [&](int r, int c, float v) { H2[r * ldH + c] = sg_tanh(v + b2[c]); });
         __syncthreads();
-        SG_PPO_STAMP(3);
         float* Oown = (PAIR && t == 1) ? O1 : O0;
         sg_layer_nt_u<MT, GW>(H2, ldH, W + tr.wh, ldH, Hp, tr.Pp, [&](int r, int c, float v) { Oown[r * ldP + c] = v + bh[c]; });
         __syncthreads();
-        SG_PPO_STAMP(4);
         if (PAIR && !critic) {
             // The swap, low-latency form: every head output travels as an 8-byte {value, step tag} word (one aligned 8-byte
             // write-through store: the pair arrives together or not at all), and the partner polls the words it needs until they
@@ -434,7 +417,6 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
             pair_failed = __syncthreads_or(!ok) != 0;
         }
     }
-    SG_PPO_STAMP(9);
 
     if (SYM && !critic) {
         // e = M_a mu(s) - mu(s_m), zero on rows past the minibatch.  The actor column keeps e in OM; the mirrored column turns
@@ -679,7 +661,6 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
         }
     }
     __syncthreads();
-    SG_PPO_STAMP(10);
     float* dout = (critic || t == 0 || mirror) ? O0 : O1;     // this trunk's d loss / d head outputs
     // loss sums of this row group (recorded once: by the critic and by actor trunk 0)
     if (tid < 64 && (critic || t == 0)) {   // first wave: R <= 64 row losses, one per lane
@@ -703,21 +684,16 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
     sg_colsum(dout, ldP, R, tr.Pp, g + tr.bh, false);
     if (tr.EX && !mirror) sg_colsum(O1, ldP, R, SG_PAD16(tr.EX), g + tr.ex, false);
     SG_LDS_SYNC();
-    SG_PPO_STAMP(11);
     {
         // per-tile tasks; dZ = (dY W) * (1 - h^2) in place over h, the bias gradient from column sums of the finished tile
         auto dz_u = [&](float* h) { return [=](int r, int c, float v) { float* ph = h + r * ldH + c; const float hv = *ph; *ph = v * (1.f - hv * hv); }; };
         sg_layer_nn_u<MT>(dout, ldP, W + tr.wh, ldH, tr.Pp, Hp, dz_u(H2));
         SG_LDS_SYNC();
-        SG_PPO_STAMP(12);
         sg_grad_tn<MT, (MT >= 2 ? 8 : 0), true>(H2, ldH, H1, ldH, Hp, Hp, g + tr.w2, ldH, false);
-        SG_PPO_STAMP(5);
         sg_colsum(H2, ldH, R, Hp, g + tr.b2, false);
         SG_LDS_SYNC();
-        SG_PPO_STAMP(13);
         sg_layer_nn_u<MT>(H2, ldH, W + tr.w2, ldH, Hp, Hp, dz_u(H1));
         SG_LDS_SYNC();
-        SG_PPO_STAMP(14);
         sg_grad_tn<MT, (MT >= 2 ? 8 : 0), true>(H1, ldH, X, ldO, Hp, Op, g + tr.w1, ldO, false);
         sg_colsum(H1, ldH, R, Hp, g + tr.b1, false);
         SG_LDS_SYNC();
@@ -726,8 +702,6 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
         float* gdx = a.DX[t] + (size_t)row0 * ldO;
         sg_layer_nn_u<MT>(H1, ldH, W + tr.w1, ldO, Hp, Op, [&](int r, int c, float v) { gdx[r * ldO + c] = v; });
     }
-    SG_PPO_STAMP(15);
-    SG_PPO_WALL(7);
     if (PAIR && pair_failed && tid == 0) {   // the partner never published: the host sees NaN losses, then the error word
         atomicOr(a.pair + SG_PAIR_ERR_WORD, 1u);
         slab[d.total + 1] = __builtin_nanf("");

@@ -1,4 +1,4 @@
-// sg_test.hip -- libsimgan_hip_test.so: test hooks and probe kernels (engine unit tests, phase-timestamp switches, RNG
+// sg_test.hip -- libsimgan_hip_test.so: test hooks and probe kernels (engine unit tests, RNG
 // dumps, latency / fetch / counter-calibration probes).  Built from this file alone and loaded only by tests/ and tools/
 // (simgan_amd/_lib.py:load_test); the product library exports none of it.  The hooks reach into handles created by the
 // product library through the struct definitions of sg_common.h -- both libraries are built from the same headers and
@@ -554,41 +554,9 @@ extern "C" int sg_test_pmc_calibrate(sg_ctx* ctx, int64_t mbytes) {
     return 0;
 }
 
-// Test hook: enable/read per-phase shader-clock timestamps of k_disc_chain (tools/phase_times.py).
-extern "C" int sg_test_disc_phase_times(sg_disc* d, int enable, long long* out, int n_blocks) {
-    SG_REQUIRE(d, "sg_test_disc_phase_times: NULL argument");
-    SG_CHECK(hipStreamSynchronize(d->ctx->stream));
-    if (enable && !d->d_dbg) {
-        SG_CHECK(hipMalloc((void**)&d->d_dbg, sizeof(long long) * 32 * 512));
-        SG_CHECK(hipMemsetAsync(d->d_dbg, 0, sizeof(long long) * 32 * 512, d->ctx->stream)); SG_CHECK(hipStreamSynchronize(d->ctx->stream));
-    }
-    if (out && d->d_dbg) {
-        SG_REQUIRE(n_blocks <= 512, "sg_test_disc_phase_times: at most 512 blocks");
-        SG_COPY_SYNC(d->ctx, out, d->d_dbg, sizeof(long long) * 32 * n_blocks, hipMemcpyDeviceToHost);   // n_blocks = 512: + k_disc_wgrad stamps
-    }
-    if (!enable && d->d_dbg) { SG_CHECK(hipFree(d->d_dbg)); d->d_dbg = nullptr; }
-    return 0;
-}
-
 extern "C" int sg_test_disc_gathers(sg_disc* d, long long* out) {
     SG_REQUIRE(d && out, "sg_test_disc_gathers: NULL argument");
     *out = (long long)d->n_gathers;
-    return 0;
-}
-
-// Test hook: per-phase shader-clock timestamps of k_ppo_fwd, row groups [0, n_blocks) (tools/ppo_phase_times.py).
-extern "C" int sg_test_ppo_phase_times(sg_ppo* a, int enable, long long* out, int n_blocks) {
-    SG_REQUIRE(a, "sg_test_ppo_phase_times: NULL argument");
-    SG_CHECK(hipStreamSynchronize(a->ctx->stream));
-    if (enable && !a->d_dbg) {
-        SG_CHECK(hipMalloc((void**)&a->d_dbg, sizeof(long long) * 16 * 1024));
-        SG_CHECK(hipMemsetAsync(a->d_dbg, 0, sizeof(long long) * 16 * 1024, a->ctx->stream)); SG_CHECK(hipStreamSynchronize(a->ctx->stream));
-    }
-    if (out && a->d_dbg) {
-        SG_REQUIRE(n_blocks <= 1024, "sg_test_ppo_phase_times: at most 1024 blocks");
-        SG_COPY_SYNC(a->ctx, out, a->d_dbg, sizeof(long long) * 16 * n_blocks, hipMemcpyDeviceToHost);
-    }
-    if (!enable && a->d_dbg) { SG_CHECK(hipFree(a->d_dbg)); a->d_dbg = nullptr; }
     return 0;
 }
 

@@ -19,8 +19,6 @@ SG_API int sg_test_pstep_probe(sg_ctx *ctx, int mode, int S, int NW, int cyc_pha
 SG_API int sg_test_pmc_calibrate(sg_ctx *ctx, int64_t mbytes);
 /* out[0] / out[1]: how the last PPO update / discriminator epoch was issued: 0 direct, 1 replayed graph, 2 capture refused */
 SG_API int sg_test_graph_state(sg_ppo *a, sg_disc *d, int out[2]);
-SG_API int sg_test_disc_phase_times(sg_disc *d, int enable, long long *out, int n_blocks);
-SG_API int sg_test_ppo_phase_times(sg_ppo *a, int enable, long long *out, int n_blocks);
 /* all-gathers the discriminator's replicated data-parallel mode has issued so far (it reuses the union across the epochs of an update) */
 SG_API int sg_test_disc_gathers(sg_disc *d, long long *out);
 /* kind 0: permutation of [0, n) -> int64 out; 1: uniform [0,1) -> float out; 2: standard normal -> float out */

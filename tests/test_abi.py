@@ -5,6 +5,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -134,13 +136,52 @@ def test_retired_switch_names_are_gone():
     assert not hits, hits
 
 
-def test_stamps_patch_applies(tmp_path):
-    """tools/diag/step4_stamps.patch (the surviving diagnostic build of k_disc_step4) still applies to csrc/: a patch that
-    has rotted fails here and not on the day someone needs it."""
+RETIRED_STAMP_NAMES = ("SG_PPO_STAMP", "SG_PPO_WALL", "SG_PHASE_SYNC", "d_dbg", "SG_DEBUG_TIMING", "sg_test_ppo_phase_times",
+                       "sg_test_disc_phase_times")
+
+
+def test_phase_stamp_hooks_are_gone():
+    """The phase-stamp hooks of the PPO and discriminator kernels live in tools/diag/*.patch only: their names appear nowhere in
+    csrc/ (test sources and Makefile included), include/ or the ctypes tables."""
+    paths = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if os.path.isfile(os.path.join(CSRC, f))]
+    inc = os.path.join(ROOT, "include")
+    paths += [os.path.join(inc, f) for f in sorted(os.listdir(inc))] + [os.path.join(ROOT, "simgan_amd", "_lib.py")]
+    assert len(paths) > 20 and os.path.join(CSRC, "sg_test.hip") in paths and os.path.join(CSRC, "Makefile") in paths
+    hits = [(os.path.basename(path), name) for path in paths for name in RETIRED_STAMP_NAMES
+            if name in open(path, errors="replace").read()]
+    assert not hits, hits
+
+
+def test_product_sources_carry_no_diagnostic_pointer_or_shader_clock():
+    """No product source has an identifier `dbg` (the kernels' optional stamp buffers were all called that), and none reads the
+    shader clock: clock64() served the stamps alone.  wall_clock64() stays -- the hand-off time-outs use it."""
+    hits = []
+    for path in product_sources():
+        src = open(path).read()
+        hits += [(os.path.basename(path), m.group(0)) for m in re.finditer(r"\bdbg\b|(?<!wall_)clock64", src)]
+    assert not hits, hits
+
+
+DIAG = os.path.join(ROOT, "tools", "diag")
+DIAG_PATCHES = sorted(f for f in os.listdir(DIAG) if f.endswith(".patch"))
+
+
+def test_the_three_diagnostic_patches_exist():
+    assert DIAG_PATCHES == ["disc_stamps.patch", "ppo_stamps.patch", "step4_stamps.patch"], DIAG_PATCHES
+
+
+@pytest.mark.parametrize("name", DIAG_PATCHES)
+def test_stamps_patch_applies(tmp_path, name):
+    """Every tools/diag/*.patch (the surviving diagnostic builds: stamps of the PPO kernels, of the two-launch discriminator
+    step and of k_disc_step4) still applies, on its own, to a fresh copy of csrc/: a patch that has rotted fails here and not on
+    the day someone needs it."""
     import shutil
     import subprocess
     shutil.copytree(CSRC, tmp_path / "simgan_amd" / "csrc", ignore=shutil.ignore_patterns("build"))
-    patch = os.path.join(ROOT, "tools", "diag", "step4_stamps.patch")
+    patch = os.path.join(DIAG, name)
+    assert len(re.findall(r"^@@ ", open(patch).read(), flags=re.M)) >= 5, "a patch without hunks proves nothing"
     r = subprocess.run(["git", "apply", "--check", "--verbose", patch], cwd=tmp_path, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    assert "sg_disc_step4.hpp" in r.stderr and "sg_test.hip" in r.stderr, r.stderr   # (checked, not skipped as outside a repository)
+    # (checked, not skipped as outside a repository: a kernel header and the test library's source are among the files named)
+    assert re.search(r"Checking patch simgan_amd/csrc/sg_(ppo_kernels|disc_kernels|disc_step4)\.hpp", r.stderr), r.stderr
+    assert "Checking patch simgan_amd/csrc/sg_test.hip" in r.stderr and "Skipped" not in r.stderr, r.stderr

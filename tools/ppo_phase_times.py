@@ -1,5 +1,8 @@
-"""Per-phase shader-clock breakdown of k_ppo_fwd (test hook sg_test_ppo_phase_times).
-Run on the GPU box:  python tools/ppo_phase_times.py [workload]"""
+"""Per-phase shader-clock breakdown of k_ppo_fwd / k_ppo_bwd in their multi-launch, ungraphed form (the stamped build never
+runs k_ppo_pair or the replayed graph).
+Needs the ppo_stamps variant of BOTH libraries (bash tools/build_variant.sh ppo_stamps "" tools/diag/ppo_stamps.patch) in place
+of simgan_amd/libsimgan_hip.so and simgan_amd/libsimgan_hip_test.so -- in a copy of the tree; run on the GPU box:
+python tools/ppo_phase_times.py [workload]"""
 import ctypes as C
 import os
 import sys
@@ -16,13 +19,26 @@ pol, disc, agent, ro, loader, expert, learner = build_problem(sg, w, 0)
 lib = _lib.load()
 _lib.check(lib.sg_rollout_fill_synthetic(ro.h, pol.h, 1234, 0.01))
 _lib.check(lib.sg_rollout_compute_returns_policy(ro.h, pol.h, 1, 0.99, 0.95, 1))
-fn = _lib.load_test().sg_test_ppo_phase_times
+# the hook exists in the ppo_stamps variant only, so it is bound here and not through _lib.TEST_PROTOTYPES (the in-tree test library's table)
+tlib = C.CDLL(_lib.TEST_LIB_PATH)
+if not hasattr(tlib, "sg_test_ppo_phase_times"):
+    sys.exit(f"{_lib.TEST_LIB_PATH} has no sg_test_ppo_phase_times: build the ppo_stamps variant (see tools/README.md)")
+tlib.sg_test_ppo_phase_times.restype = C.c_int
+tlib.sg_test_ppo_phase_times.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_int]
+tlib.sg_test_last_error.restype = C.c_char_p
+
+
+def fn(*args):
+    if tlib.sg_test_ppo_phase_times(*args) != 0:
+        raise RuntimeError(tlib.sg_test_last_error().decode(errors="replace"))
+
+
 agent.update(ro)
-_lib.check_test(fn(agent.h, 1, None, 0))
+fn(agent.h, 1, None, 0)
 agent.update(ro)
-nb = 1024
+nb = 1024   # rows [0, 512): grid column 0, [512, 1024): column 1 (SG_PPO_STAMP_ROWS in the patch)
 buf = (C.c_longlong * (16 * nb))()
-_lib.check_test(fn(agent.h, 1, buf, nb))
+fn(agent.h, 1, buf, nb)
 t = np.array(buf, dtype=np.int64).reshape(nb, 16)
 names = ["rows->LDS (fused bwd: until the weight commit)", "commit+sync", "L1", "L2", "head"]
 t1 = t[512:]
@@ -42,7 +58,7 @@ print("k_ppo_bwd phases (trunk 0), median cycles over", nb, "row groups:")
 for i, n in enumerate(names):
     print(f"   {n:12s} {int(np.median(d[:, i])):8d}   (min {int(d[:, i].min())}, max {int(d[:, i].max())})")
 print("   total       ", int(np.median(t[:, 15] - t[:, 8])))
-_lib.check_test(fn(agent.h, 0, None, 0))
+fn(agent.h, 0, None, 0)
 
 st, en = t[:, 6], t[:, 7]     # wall clock, 100 MHz, comparable across CUs
 ok = st > 0
