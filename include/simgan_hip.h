@@ -203,6 +203,18 @@ SG_API int sg_rollout_dup_sym(sg_rollout *r);
  * other columns the device makes itself (the first half of a2c/main.py:241-242's insert).  host is the FULL-width field
  * (count = its size, as for sg_rollout_upload), e.g. the page-locked host tensor; its other columns are not read. */
 SG_API int sg_rollout_upload_columns(sg_rollout *r, int field, int n_cols, const float *host, int64_t count);
+/* One step of the collection loop on the device (a2c/main_gail_dyn_ppo.py:209-236): Policy.act / SplitPolicy.act
+ * (a2c/model.py:89-101, a2c/model_split.py:70-82) on the N rows of rollout slot t, written where rollouts.insert
+ * (a2c/storage.py:70-84) puts them: value_preds[t], actions[t] and action_log_probs[t] of the DEVICE rollout; the actions also
+ * to action_host[N,A].  obs_host[N,O] is copied into slot t of OBS first; NULL: slot t is already on the device.  noise[N,A]
+ * (host, standard normal draws) or NULL -> the library generator with `seed`, as in sg_policy_act; deterministic != 0 ->
+ * dist.mode().  Per call: one host->device copy (one more with injected noise), ONE kernel launch -- which writes the actions
+ * into a page-locked block of the context as well, so nothing is copied back -- and one host wait.  Value, action and log-prob
+ * have the bits sg_policy_act gives for the same observations and draws.  No other float of the rollout is written.
+ * Feed-forward policies (SG_POLICY_MLP, SG_POLICY_SPLIT) with the Gaussian head; a recurrent policy, a Categorical / Bernoulli
+ * head, policy and rollout dimensions that differ and t outside [0, T) are errors. */
+SG_API int sg_rollout_act_step(sg_rollout *r, sg_policy *p, int t, const float *obs_host, const float *noise, uint64_t seed,
+                        int deterministic, float *action_host);
 
 /* ---------------------------------------------------------------------- PPO */
 typedef struct {

@@ -12,10 +12,8 @@
 #include <vector>
 
 #include "sg_common.h"
+#include "sg_policy_fwd.hpp"
 #include "sg_rng.hpp"
-
-#define HALF_LOG_2PI 0.91893853320467274178f
-#define SG_ACT_STREAM 0x41435400ull
 
 // --------------------------------------------------------------------------------- forward
 
@@ -29,27 +27,6 @@ struct FwdArgs {
     int hld;
     int wbuf_floats;
 };
-
-// One trunk forward on R = 16*MT rows held in LDS.  W = the trunk's parameter block: its LDS image, or (GW) the block in
-// global memory itself -- the general-shape path for trunks that do not fit a CU's LDS (any hidden size the reference's
-// --hidden-size accepts, a2c/arguments.py:107-109; weights come through L2 one MFMA fragment at a time, sg_gemm.hpp).
-template <int MT, bool GW = false>
-__device__ __forceinline__ void trunk_forward(const SgPolicyDesc& d, const SgTrunk& tr, const float* W,
-                                              const float* X, float* H1, float* H2, float* OUT,
-                                              int ldP) {
-    const int ldO = d.ldO, ldH = tr.ldH, Hp = tr.Hp;   // this trunk's own width (the critic's may differ from the actors')
-    const float* b1 = W + tr.b1;
-    const float* b2 = W + tr.b2;
-    const float* bh = W + tr.bh;
-    sg_layer_nt<MT, GW>(X, ldO, W + tr.w1, ldO, d.Op, Hp,
-                        [&](int r, int c, float v) { H1[r * ldH + c] = sg_tanh(v + b1[c]); });
-    __syncthreads();
-    sg_layer_nt<MT, GW>(H1, ldH, W + tr.w2, ldH, Hp, Hp,
-                        [&](int r, int c, float v) { H2[r * ldH + c] = sg_tanh(v + b2[c]); });
-    __syncthreads();
-    sg_layer_nt<MT, GW>(H2, ldH, W + tr.wh, ldH, Hp, tr.Pp,
-                        [&](int r, int c, float v) { OUT[r * ldP + c] = v + bh[c]; });
-}
 
 template <int MT, bool GW = false>
 __global__ __launch_bounds__(256) void k_policy_forward(FwdArgs a) {
@@ -213,21 +190,6 @@ __global__ void k_discrete_head(HeadArgs a) {
     if (a.ent) a.ent[row] = ent;
 }
 
-// LDS floats needed by the forward kernel / the PPO gradient kernel for a given MT.
-static int max_trunk_size(const SgPolicyDesc& d, int t0, int nt) {
-    int m = 0;
-    for (int t = t0; t < t0 + nt; ++t) m = d.trunk[t].size > m ? d.trunk[t].size : m;
-    return m;
-}
-static int max_ldP(const SgPolicyDesc& d) {
-    int m = 0;
-    for (int t = 0; t < d.n_trunks; ++t) m = d.trunk[t].ldP > m ? d.trunk[t].ldP : m;
-    return m;
-}
-static size_t fwd_lds_bytes(const SgPolicyDesc& d, int MT, bool gw = false) {
-    const int R = 16 * MT;
-    return sizeof(float) * (size_t)((gw ? 0 : max_trunk_size(d, 0, d.n_trunks)) + R * d.ldO + 2 * R * d.ldH + R * max_ldP(d));
-}
 // The LDS-resident kernels need a trunk's whole parameter block beside one 16-row tile; a policy that does not fit takes
 // the global-weight instances (SG_POLICY_GW=1 forces them for any shape: tests).
 bool sg_policy_needs_gw(const sg_ctx* ctx, const SgPolicyDesc& d) {
@@ -243,8 +205,7 @@ static int policy_forward_dev(sg_policy* p, const float* d_obs, const int64_t* d
     a.d = p->desc; a.params = p->d_params; a.obs = d_obs; a.idx = d_idx; a.n = n; a.heads = d_heads; a.hld = hld;
     const bool gw = sg_policy_needs_gw(ctx, p->desc);
     a.wbuf_floats = gw ? 0 : max_trunk_size(p->desc, 0, p->desc.n_trunks);
-    int MT = 4;
-    while (MT > 1 && (fwd_lds_bytes(p->desc, MT, gw) > (size_t)ctx->lds_bytes - 1024 || 16 * (MT / 2) >= n)) MT /= 2;
+    const int MT = fwd_tile_mt(ctx, p->desc, n, gw);
     SG_REQUIRE(fwd_lds_bytes(p->desc, MT, gw) <= (size_t)ctx->lds_bytes,
                "policy forward: one 16-row activation tile (%zu B) does not fit LDS", fwd_lds_bytes(p->desc, MT, gw));
     const int R = 16 * MT;

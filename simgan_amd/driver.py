@@ -20,7 +20,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .utils import RunningMeanStd, to_host_tensor, update_linear_schedule
+from .utils import RunningMeanStd, step_masks, to_host_tensor, update_linear_schedule
 
 _RESULT_SLOTS = 8
 
@@ -125,6 +125,21 @@ class _ResidentRms(RunningMeanStd):
         self._discr.set_rms(self.get_state())
 
 
+def _check_on_device(ro, pol, dup_sym, who):
+    """collect(on_device=True) serves a device-resident rollout and a feed-forward policy with a Gaussian head."""
+    why = None
+    if not ro.device_resident:
+        why = "the rollout is not device-resident (rollouts.device_resident = True): its host tensors are the rollout"
+    elif dup_sym or getattr(ro, "dup_sym", False):
+        why = "the rollout is mirror-augmented (dup_sym): its column upload would overwrite the fields the device writes"
+    elif pol.is_recurrent:
+        why = "the policy is recurrent and the device rollout holds no hidden state"
+    elif getattr(pol, "dist_kind", _lib.DIST_GAUSSIAN) != _lib.DIST_GAUSSIAN:
+        why = "the policy has a Discrete / MultiBinary action space; the one-launch step carries the Gaussian head only"
+    if why is not None:
+        raise ValueError(f"{who}(on_device=True): {why}")
+
+
 class GailDynLearner(object):
     def __init__(self, actor_critic, agent, discr, rollouts, expert, gail_batch_size=128, gail_epoch=5,
                  gamma=0.99, gae_lambda=0.95, use_gae=True, use_proper_time_limits=True,
@@ -157,13 +172,22 @@ class GailDynLearner(object):
             self.discr.set_rms(value.get_state())
 
     # ---------------------------------------------------------------- rollout fill (:209-236)
-    def collect(self, envs, sas_feat_of_infos):
+    def collect(self, envs, sas_feat_of_infos, on_device=False):
+        """on_device=True: every step acts in one launch that fills the policy's half of the rollout slot on the device
+        (RolloutStorage.act_step / insert_env / finish_collect); same draws, same bits, fewer copies."""
         ro, pol = self.rollouts, self.actor_critic
+        if on_device:
+            _check_on_device(ro, pol, False, "GailDynLearner.collect")
+            for step in range(ro.num_steps):
+                obs, reward, done, infos = envs.step(ro.act_step(pol))
+                masks, bad = step_masks(done, infos)
+                ro.insert_env(obs, reward, to_host_tensor(masks), to_host_tensor(bad),
+                              to_host_tensor(np.asarray(sas_feat_of_infos(infos), np.float32)))
+            return ro.finish_collect()
         for step in range(ro.num_steps):
             value, action, logp, hxs = pol.act(ro.obs[step], ro.recurrent_hidden_states[step], ro.masks[step])
             obs, reward, done, infos = envs.step(action)
-            masks = np.array([[0.0] if d else [1.0] for d in done], np.float32)
-            bad = np.array([[0.0] if 'bad_transition' in info.keys() else [1.0] for info in infos], np.float32)
+            masks, bad = step_masks(done, infos)
             ro.insert(obs, hxs, action, logp, value, reward, to_host_tensor(masks), to_host_tensor(bad),
                       to_host_tensor(np.asarray(sas_feat_of_infos(infos), np.float32)))
         if ro.device_resident:
@@ -285,8 +309,17 @@ class PpoLearner(object):
         return actor_critic
 
     # ---------------------------------------------------------------- rollout fill (:207-244)
-    def collect(self, envs, feat_select_func=None):
+    def collect(self, envs, feat_select_func=None, on_device=False):
+        """on_device=True: as GailDynLearner.collect(on_device=True); not for a mirror-augmented (dup_sym) learner."""
         ro, pol = self.rollouts, self.actor_critic
+        if on_device:
+            _check_on_device(ro, pol, self.dup_sym, "PpoLearner.collect")
+            for step in range(ro.num_steps):
+                obs, reward, done, infos = envs.step(ro.act_step(pol))
+                feat = obs if feat_select_func is None else feat_select_func(obs)
+                masks, bad = step_masks(done, infos)
+                ro.insert_env(obs, reward, to_host_tensor(masks), to_host_tensor(bad), feat)
+            return ro.finish_collect()
         n = ro.num_processes
         if self.dup_sym:
             n = ro.num_processes // 2
@@ -301,8 +334,7 @@ class PpoLearner(object):
                 value, action, logp, hxs = pol.act(ro.obs[step], ro.recurrent_hidden_states[step], ro.masks[step])
             obs, reward, done, infos = envs.step(action)
             feat = obs if feat_select_func is None else feat_select_func(obs)
-            masks = np.array([[0.0] if d else [1.0] for d in done], np.float32)
-            bad = np.array([[0.0] if 'bad_transition' in info.keys() else [1.0] for info in infos], np.float32)
+            masks, bad = step_masks(done, infos)
             insert(obs, hxs, action, logp, value, reward, to_host_tensor(masks), to_host_tensor(bad), feat)
         if ro.device_resident:
             ro.sync_to_device()

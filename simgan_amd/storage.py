@@ -47,6 +47,14 @@ _FIELD_ATTR = {
 }
 
 
+def _put(dst, src):
+    """src (tensor / array-like) into the host slot dst, through torch where dst is a tensor (its version counter moves)."""
+    if torch is not None and hasattr(dst, "copy_"):
+        dst.copy_(src if hasattr(src, "dim") else torch.as_tensor(np.asarray(src, np.int64 if dst.dtype == torch.int64 else np.float32)))
+    else:
+        dst[...] = np.asarray(src, dst.dtype)
+
+
 class RolloutStorage(object):
     def __init__(self, num_steps, num_processes, obs_shape, action_space,
                  recurrent_hidden_state_size, feat_len=0, ctx=None):
@@ -223,6 +231,64 @@ class RolloutStorage(object):
         put(self.bad_masks[s + 1], bad_masks)
         self.step = (self.step + 1) % self.num_steps
         self._host_written = True
+
+    # ------------------------------------------------- collection on the device (a2c/main_gail_dyn_ppo.py:209-236)
+    def _on_device_only(self, who):
+        if not self.device_resident:
+            raise ValueError(f"{who}: the rollout is not device-resident (rollouts.device_resident = True): in drop-in mode the host "
+                             "tensors are the rollout and the next device call would overwrite what the step wrote on the device")
+        if self._dup is not None:
+            raise ValueError(f"{who}: the rollout is mirror-augmented (enable_dup_sym): its column upload would overwrite the fields "
+                             "the step writes on the device; collect through insert_dup_sym")
+
+    def act_step(self, policy, deterministic=False, noise=None):
+        """policy.act (a2c/model.py:89-101) on host slot `self.step` of obs, in one launch that also fills the policy's half of
+        insert() (a2c/storage.py:70-84) on the DEVICE: value_preds[step], actions[step], action_log_probs[step].  Returns the
+        [N, A] action as act() returns it and writes it into the host mirror actions[step]; the values and log-probs do not come
+        back (the host mirrors of value_preds and action_log_probs are stale until sync_from_device()).  The draw is the policy's
+        own stream, (policy.seed + policy._act_calls) after incrementing _act_calls, as in policy.act: a run through either path
+        consumes the same draws and gets the same bits.  `noise` ([N, A] standard normal) injects the draw.  bytes_uploaded
+        counts the observation slot.  Device-resident rollouts only; feed-forward policies with a Gaussian head."""
+        self._on_device_only("act_step")
+        s, N = self.step, self.num_processes
+        obs = self._host_np(_lib.F_OBS)[s]
+        nz = None if noise is None else _lib.as_f32(noise).reshape(N, self.act_dim)
+        action = np.empty((N, self.act_dim), np.float32)
+        policy._act_calls += 1
+        _lib.check(self.lib.sg_rollout_act_step(self.h, policy.h, s, _lib.fptr(obs), None if nz is None else _lib.fptr(nz),
+                                                (policy.seed + policy._act_calls) & (2 ** 64 - 1), 1 if deterministic else 0,
+                                                _lib.fptr(action)))
+        self.bytes_uploaded += obs.nbytes
+        _put(self.actions[s], action)
+        return to_host_tensor(action)
+
+    def insert_env(self, obs, rewards, masks, bad_masks, obs_feat=None):
+        """The environment's half of insert() (a2c/storage.py:70-84) after act_step(): host slots obs[s+1], obs_feat[s+1],
+        rewards[s], masks[s+1], bad_masks[s+1]; advances `step`."""
+        s = self.step
+        _put(self.obs[s + 1], obs)
+        if obs_feat is not None:
+            _put(self.obs_feat[s + 1], obs_feat)
+        _put(self.rewards[s], rewards)
+        _put(self.masks[s + 1], masks)
+        _put(self.bad_masks[s + 1], bad_masks)
+        self.step = (self.step + 1) % self.num_steps
+        self._host_written = True   # after_update() rolls the host mirrors over as it does after insert()
+
+    def finish_collect(self):
+        """End of a collection through act_step() / insert_env(): uploads what the device does not have -- obs_feat, rewards,
+        masks, bad_masks, slot T of obs (slots 0..T-1 went up step by step) -- and, so that the device rollout is float for float
+        what sync_to_device() would have left, the host's returns and slot T of value_preds, which no step writes.  Slots
+        0..T-1 of value_preds, actions and action_log_probs never cross the link: the device wrote them itself.  The host mirrors
+        of value_preds and action_log_probs are STALE afterwards (they hold what they held before the collection) until
+        sync_from_device(); actions is current."""
+        self._on_device_only("finish_collect")
+        T = self.num_steps
+        self.sync_to_device([_lib.F_OBS_FEAT, _lib.F_REWARDS, _lib.F_RETURNS, _lib.F_MASKS, _lib.F_BAD_MASKS])
+        for f in (_lib.F_OBS, _lib.F_VALUE_PREDS):
+            a = self._host_np(f)[T]
+            _lib.check(self.lib.sg_rollout_upload_step(self.h, f, T, _lib.fptr(a), a.size))
+            self.bytes_uploaded += a.nbytes
 
     # ------------------------------------------------- mirror-augmented rollouts (a2c/main.py:171-245, --dup-sym)
     def enable_dup_sym(self, mirror_obs, mirror_act):

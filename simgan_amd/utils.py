@@ -35,6 +35,15 @@ def to_host_tensor(a):
     return torch.from_numpy(a) if torch is not None else a
 
 
+def step_masks(done, infos):
+    """(masks, bad_masks) of one environment step as float32 [N, 1] arrays, a2c/main_gail_dyn_ppo.py:228-231 /
+    a2c/main.py:226-229: masks 0 where the environment is done (by truth value, as `if done_` takes it), bad_masks 0 where
+    its info carries 'bad_transition'."""
+    masks = np.fromiter((not d for d in done), np.float32, len(done)).reshape(-1, 1)
+    bad = np.fromiter(('bad_transition' not in info.keys() for info in infos), np.float32, len(infos)).reshape(-1, 1)
+    return masks, bad
+
+
 def update_linear_schedule(optimizer, epoch, total_num_epochs, initial_lr):
     """a2c/utils.py:68-72 -- works on any object exposing param_groups with a mutable 'lr'."""
     lr = initial_lr - (initial_lr * (epoch / float(total_num_epochs)))
