@@ -84,8 +84,8 @@ enum { SG_POLICY_MLP = 0, SG_POLICY_SPLIT = 1, SG_POLICY_GRU = 2 };
  * trunks on the H-wide GRU state, critic_linear and DiagGaussian.  Flat parameter order: base.gru.weight_ih_l0 [3H, O],
  * weight_hh_l0 [3H, H], bias_ih_l0 [3H], bias_hh_l0 [3H], then the MLP kind's order with obs_dim replaced by H.  Such a policy
  * is served by the sg_policy_*_rnn entry points below; sg_policy_act / _get_value / _evaluate / _act_ensemble refuse it (and
- * the _rnn calls refuse a feed-forward policy), as do sg_a2c_create, sg_acktr_create, sg_rollout_compute_returns_policy and
- * sg_rollout_fill_synthetic.  sg_ppo_create takes it: sg_ppo_update then runs PPO through time (sg_ppo_set_hidden_states). */
+ * the _rnn calls refuse a feed-forward policy), as do sg_a2c_create, sg_acktr_create, sg_rollout_compute_returns_policy (on a
+ * rollout without hidden states) and sg_rollout_fill_synthetic.  sg_ppo_create takes it: sg_ppo_update then runs PPO through time (sg_ppo_set_hidden_states). */
 /* Policy(obs_shape, action_space, base_kwargs)            a2c/model.py:38-67   (kind MLP)
  * SplitPolicy(obs_shape, action_space, base_kwargs)       a2c/model_split.py:40-52 (kind SPLIT;
  * requires act_dim == 7*num_feet, a2c/model_split.py:205). Parameters start at zero. */
@@ -178,7 +178,9 @@ SG_API int sg_rollout_after_update(sg_rollout *r);
 /* RolloutStorage.compute_returns a2c/storage.py:103-142 (all four branches); next_value[N] host. */
 SG_API int sg_rollout_compute_returns(sg_rollout *r, const float *next_value, int use_gae, float gamma,
                                float gae_lambda, int use_proper_time_limits);
-/* Same, with next_value = policy.get_value(obs[T]) computed on device (a2c/main_gail_dyn_ppo.py:239-242,299). */
+/* Same, with next_value = policy.get_value(obs[T]) computed on device (a2c/main_gail_dyn_ppo.py:239-242,299).  A recurrent
+ * policy is taken when the rollout holds hidden states of its width (sg_rollout_enable_hidden): next_value =
+ * get_value(obs[T], h[T], masks[T]) from the rollout's own slots, the bits of sg_policy_get_value_rnn; refused otherwise. */
 SG_API int sg_rollout_compute_returns_policy(sg_rollout *r, sg_policy *p, int use_gae, float gamma,
                                       float gae_lambda, int use_proper_time_limits);
 /* Synthetic rollout fill on device for benchmarks: obs, obs_feat ~ N(0,1);
@@ -215,6 +217,25 @@ SG_API int sg_rollout_upload_columns(sg_rollout *r, int field, int n_cols, const
  * head, policy and rollout dimensions that differ and t outside [0, T) are errors. */
 SG_API int sg_rollout_act_step(sg_rollout *r, sg_policy *p, int t, const float *obs_host, const float *noise, uint64_t seed,
                         int deterministic, float *action_host);
+/* rollouts.recurrent_hidden_states (a2c/storage.py:40) on the device, opt-in: a zeroed [T+1, N, hidden_dim] float buffer beside
+ * the SG_F_COUNT fields.  Calling it again with the same hidden_dim does nothing; another width is an error.  Once enabled,
+ * sg_rollout_after_update rolls slot T of the buffer to slot 0 with the fields (a2c/storage.py:96-101), in the same launch. */
+SG_API int sg_rollout_enable_hidden(sg_rollout *r, int hidden_dim);
+/* The whole buffer host <-> device; count must be (T+1)*N*hidden_dim.  Errors before sg_rollout_enable_hidden. */
+SG_API int sg_rollout_upload_hidden(sg_rollout *r, const float *host, int64_t count);
+SG_API int sg_rollout_download_hidden(sg_rollout *r, float *host, int64_t count);
+/* sg_rollout_act_step for a recurrent policy (kind SG_POLICY_GRU): Policy.act with recurrent=True (a2c/model.py:89-101,
+ * 117-201, 255-264) on slot t -- x = GRU(obs[t], h[t] * masks[t]), the trunks and the Gaussian head on x -- and the policy's
+ * half of rollouts.insert (a2c/storage.py:70-84), hidden state included: value_preds[t], actions[t], action_log_probs[t] and
+ * hidden slot t + 1 of the DEVICE rollout; the actions also to action_host[N,A].  obs_host[N,O] and masks_host[N] are copied
+ * into slot t of OBS / MASKS first; NULL: that slot is already on the device.  noise, seed, deterministic as in
+ * sg_rollout_act_step.  ONE kernel launch and one host wait per call; value, action, log-prob and new state have the bits
+ * sg_policy_act_rnn gives for the same inputs and draws.  No other float of the rollout is written.  Errors: a feed-forward
+ * policy, a rollout without hidden states or with another width, policy and rollout dimensions that differ, t outside [0, T),
+ * a mirror-augmented rollout (sg_rollout_set_mirrors), and a shape whose row tile does not fit a CU's LDS (act through
+ * sg_policy_act_rnn then). */
+SG_API int sg_rollout_act_step_rnn(sg_rollout *r, sg_policy *p, int t, const float *obs_host, const float *masks_host,
+                            const float *noise, uint64_t seed, int deterministic, float *action_host);
 
 /* ---------------------------------------------------------------------- PPO */
 typedef struct {
@@ -265,8 +286,11 @@ SG_API int sg_ppo_set_adam(sg_ppo *a, const float *m, const float *v, int64_t n,
  * torch.randperm(num_processes) of every epoch (sg_ppo_last_perms returns the same shape), or NULL.  The sequences start from
  * rollouts.recurrent_hidden_states[0] (a2c/storage.py:216-217) and use masks[:-1]: the rollout's MASKS field must be current,
  * and the states of slot 0, hxs0[N*H], are handed over with this call before EVERY update (the device rollout has no
- * hidden-state field).  One rank only; sg_ppo_set_symmetry refuses a recurrent policy. */
+ * hidden-state field unless sg_rollout_enable_hidden gave it one: sg_ppo_set_hidden_states_rollout then).  One rank only; sg_ppo_set_symmetry refuses a recurrent policy. */
 SG_API int sg_ppo_set_hidden_states(sg_ppo *a, const float *hxs0, int64_t count);
+/* The same hand-over from a rollout that holds its hidden states (sg_rollout_enable_hidden, of the policy's width): slot 0 is
+ * copied device to device on the stream; the host reads no state and does not wait.  Before every update, like the call above. */
+SG_API int sg_ppo_set_hidden_states_rollout(sg_ppo *a, sg_rollout *r);
 /* Mirror-symmetry loss of PPO.update, a2c/algo/ppo.py:110-143 (a2c/main.py:133-146, --loss-sym): every optimizer step adds
  * coef * mean((M_a mu(s) - mu(mirror_obs(s)))^2) over the minibatch's B x A elements, mu = the DiagGaussian mean (fc_mean);
  * M_a mu(s) is a constant of the loss (the reference mirrors it through numpy), so its gradient reaches the actor trunk and

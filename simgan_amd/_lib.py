@@ -91,6 +91,11 @@ PROTOTYPES = {
     "sg_rollout_dup_sym": (C.c_int, [H]),
     "sg_rollout_upload_columns": (C.c_int, [H, C.c_int, C.c_int, c_float_p, C.c_int64]),
     "sg_rollout_act_step": (C.c_int, [H, H, C.c_int, c_float_p, c_float_p, C.c_uint64, C.c_int, c_float_p]),
+    "sg_rollout_enable_hidden": (C.c_int, [H, C.c_int]),
+    "sg_rollout_upload_hidden": (C.c_int, [H, c_float_p, C.c_int64]),
+    "sg_rollout_download_hidden": (C.c_int, [H, c_float_p, C.c_int64]),
+    "sg_rollout_act_step_rnn": (C.c_int, [H, H, C.c_int, c_float_p, c_float_p, c_float_p, C.c_uint64, C.c_int, c_float_p]),
+    "sg_ppo_set_hidden_states_rollout": (C.c_int, [H, H]),
     "sg_ppo_create": (C.c_int, [H, H, C.POINTER(PPOConfig), C.POINTER(H)]),
     "sg_ppo_destroy": (C.c_int, [H]),
     "sg_ppo_set_lr": (C.c_int, [H, C.c_float]),

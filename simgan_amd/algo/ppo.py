@@ -145,7 +145,11 @@ class PPO():
         (include/simgan_hip.h: sg_ppo_update).  fetch_losses=False: queue the update and return None without waiting for
         it (the losses are read later through the results ring, simgan_amd/driver.py)."""
         rollouts._push([_lib.F_OBS, _lib.F_ACTIONS, _lib.F_VALUE_PREDS, _lib.F_RETURNS, _lib.F_LOGP])
-        if self.recurrent:
+        if self.recurrent and getattr(rollouts, "device_hidden", False) and rollouts.device_resident:
+            # the rollout holds its hidden states on the device (enable_device_hidden): slot 0 is handed over there, no host read
+            rollouts._push([_lib.F_MASKS])
+            _lib.check(self.lib.sg_ppo_set_hidden_states_rollout(self.h, rollouts.h))
+        elif self.recurrent:
             # whole environments per minibatch, from the state of slot 0 (a2c/storage.py:194-251): `perms` is [ppo_epoch, N]
             rollouts._push([_lib.F_MASKS])
             hxs0 = rollouts.recurrent_hidden_states[0]

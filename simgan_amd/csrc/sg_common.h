@@ -278,6 +278,9 @@ struct sg_rollout {
     bool mirrors_set = false;
     float* d_mobs = nullptr;             // [O][O] linear obs mirror, or NULL: the caller uploads OBS full-width
     float* d_mact = nullptr;             // [A][A] action mirror
+    // recurrent_hidden_states (a2c/storage.py:40): opt-in (sg_rollout_enable_hidden), beside the SG_F_COUNT fields
+    float* d_hidden = nullptr;           // [T+1][N][hidden_dim], or NULL
+    int hidden_dim = 0;
 };
 
 // A captured launch sequence and what it was captured for (sg_graph_run, below)

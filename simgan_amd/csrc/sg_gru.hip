@@ -131,6 +131,32 @@ static int gru_host_call(sg_policy* p, const char* who, const float* obs, const 
     return 0;
 }
 
+// Policy.get_value (a2c/model.py:103-105) of a recurrent policy on DEVICE inputs (sg_rollout_compute_returns_policy: slot T of a
+// rollout that holds its hidden states): the three launches of sg_policy_get_value_rnn -- the same bits -- with GI, h and the value
+// in the policy's staging block; nothing is copied and nothing waits (unless the block has to grow).
+int sg_gru_value_device(sg_policy* p, const float* d_obs, const float* d_hxs, const float* d_masks, int n, float** d_value) {
+    sg_ctx* ctx = p->ctx;
+    const SgGruDesc& g = p->gru;
+    auto r4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    const size_t f_row = r4((size_t)n), f_gi = r4((size_t)n * 3 * g.Hp), f_h = r4((size_t)n * g.H);
+    const size_t need = sizeof(float) * (f_row + f_gi + f_h);
+    SG_CHECK(hipSetDevice(ctx->device));
+    if (need > p->io_bytes) {
+        SG_CHECK(hipStreamSynchronize(ctx->stream));
+        if (p->d_io) SG_CHECK(sg_dev_free(p->d_io));
+        p->d_io = nullptr; p->io_bytes = 0;
+        SG_CHECK(sg_dev_malloc((void**)&p->d_io, need + need / 2));
+        p->io_bytes = need + need / 2;
+    }
+    float* d_v = p->d_io;
+    float* d_gi = d_v + f_row;
+    float* d_hout = d_gi + f_gi;
+    SG_TRY(gru_forward_dev(p, d_obs, d_hxs, d_masks, 1, n, d_gi, d_hout, nullptr));
+    SG_TRY(sg_policy_forward_device(p, d_hout, n, 1, nullptr, 0, nullptr, d_v, nullptr, nullptr, nullptr));
+    *d_value = d_v;
+    return 0;
+}
+
 extern "C" int sg_policy_act_rnn(sg_policy* p, const float* obs, const float* hxs, const float* masks, int n, const float* noise,
                                  uint64_t seed, int deterministic, float* value, float* action, float* logp, float* hxs_out) {
     SG_REQUIRE(p && obs && hxs && masks && value && action && logp && hxs_out, "sg_policy_act_rnn: NULL argument");

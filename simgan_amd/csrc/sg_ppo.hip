@@ -728,6 +728,34 @@ extern "C" int sg_ppo_set_hidden_states(sg_ppo* a, const float* hxs0, int64_t co
     return 0;
 }
 
+// The same hand-over from a rollout that holds its hidden states on the device (sg_rollout_enable_hidden): slot 0 goes into
+// d_h0 device to device, in stream order; the host neither reads a state nor waits.
+extern "C" int sg_ppo_set_hidden_states_rollout(sg_ppo* a, sg_rollout* r) {
+    SG_REQUIRE(a && r, "sg_ppo_set_hidden_states_rollout: NULL argument");
+    SG_REQUIRE(a->policy->recurrent, "sg_ppo_set_hidden_states_rollout: the policy is feed-forward: it has no hidden state");
+    SG_REQUIRE(a->ctx == r->ctx, "sg_ppo_set_hidden_states_rollout: the agent and the rollout live on different contexts");
+    const int H = a->policy->gru.H;
+    SG_REQUIRE(r->d_hidden, "sg_ppo_set_hidden_states_rollout: the rollout holds no hidden states (sg_rollout_enable_hidden)");
+    SG_REQUIRE(r->hidden_dim == H, "sg_ppo_set_hidden_states_rollout: the rollout's hidden states are %d wide, the policy's %d",
+               r->hidden_dim, H);
+    sg_ctx* ctx = a->ctx;
+    const int64_t count = (int64_t)r->N * H;
+    SG_CHECK(hipSetDevice(ctx->device));
+    if (a->h0_cap < count) {
+        SG_DEVICE_WIDE();
+        SG_CHECK(hipStreamSynchronize(ctx->stream));
+        if (a->d_h0) SG_CHECK(sg_dev_free(a->d_h0));
+        if (a->h_h0) SG_CHECK(sg_host_release(a->h_h0));
+        a->d_h0 = nullptr; a->h_h0 = nullptr; a->h0_cap = 0;
+        SG_CHECK(sg_dev_malloc((void**)&a->d_h0, sizeof(float) * count));
+        SG_CHECK(sg_host_malloc((void**)&a->h_h0, sizeof(float) * count * SG_H0_SLOTS));
+        a->h0_cap = count;
+    }
+    SG_CHECK(hipMemcpyAsync(a->d_h0, r->d_hidden, sizeof(float) * count, hipMemcpyDeviceToDevice, ctx->stream));
+    a->h0_count = count;
+    return 0;
+}
+
 // PPO.update with actor_critic.is_recurrent (a2c/algo/ppo.py:74-90) over RolloutStorage.recurrent_generator's minibatches
 // (a2c/storage.py:194-251): per = N // num_mini_batch whole environments per optimizer step, N // per steps per epoch.
 //   k_adv_stats x3

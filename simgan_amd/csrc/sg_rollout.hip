@@ -13,6 +13,8 @@
 int sg_policy_forward_device(sg_policy* p, const float* d_obs, int n, int mode, const float* d_noise,
                              uint64_t seed, const float* d_action_in, float* d_value, float* d_action,
                              float* d_logp, float* d_ent);
+// sg_gru.hip: get_value of a recurrent policy on device inputs; *d_value -> [n] in the policy's staging, valid in stream order
+int sg_gru_value_device(sg_policy* p, const float* d_obs, const float* d_hxs, const float* d_masks, int n, float** d_value);
 
 extern "C" int sg_rollout_create(sg_ctx* ctx, int T, int N, int obs_dim, int act_dim, int feat_dim,
                                  sg_rollout** out) {
@@ -50,6 +52,7 @@ extern "C" int sg_rollout_destroy(sg_rollout* r) {
     if (r->d_perm) (void)sg_dev_free(r->d_perm);
     if (r->d_mobs) (void)sg_dev_free(r->d_mobs);
     if (r->d_mact) (void)sg_dev_free(r->d_mact);
+    if (r->d_hidden) (void)sg_dev_free(r->d_hidden);
     delete r;
     return 0;
 }
@@ -109,11 +112,55 @@ extern "C" int sg_rollout_download_step(sg_rollout* r, int field, int t, float* 
     return 0;
 }
 
-// slot T -> slot 0 of obs, obs_feat, masks, bad_masks in one launch (four small device-to-device copies
-// through the runtime's copy path cost more than the copy and occasionally stall for milliseconds)
+// ---------------------------------------------------------------- hidden states (a2c/storage.py:40, opt-in)
+// rollouts.recurrent_hidden_states [T+1, N, H] beside the fields: what a recurrent policy's one-launch step
+// (sg_rollout_act_step_rnn) reads at slot t and writes at slot t + 1
+extern "C" int sg_rollout_enable_hidden(sg_rollout* r, int hidden_dim) {
+    SG_DEVICE_WIDE();
+    SG_REQUIRE(r, "sg_rollout_enable_hidden: NULL argument");
+    SG_REQUIRE(hidden_dim > 0, "sg_rollout_enable_hidden: hidden_dim must be positive (got %d)", hidden_dim);
+    if (r->d_hidden) {
+        SG_REQUIRE(r->hidden_dim == hidden_dim, "sg_rollout_enable_hidden: the rollout already holds hidden states of width %d, not %d",
+                   r->hidden_dim, hidden_dim);
+        return 0;
+    }
+    SG_CHECK(hipSetDevice(r->ctx->device));
+    const size_t bytes = sizeof(float) * (size_t)(r->T + 1) * r->N * hidden_dim;
+    float* d = nullptr;
+    SG_CHECK(sg_dev_malloc((void**)&d, bytes));
+    r->d_hidden = d;
+    r->hidden_dim = hidden_dim;
+    SG_CHECK(hipMemsetAsync(d, 0, bytes, r->ctx->stream));
+    SG_CHECK(hipStreamSynchronize(r->ctx->stream));
+    return 0;
+}
+
+static int check_hidden(const sg_rollout* r, const float* host, int64_t count, const char* who) {
+    SG_REQUIRE(r && host, "%s: NULL argument", who);
+    SG_REQUIRE(r->d_hidden, "%s: the rollout holds no hidden states (sg_rollout_enable_hidden)", who);
+    const int64_t want = (int64_t)(r->T + 1) * r->N * r->hidden_dim;
+    SG_REQUIRE(count == want, "%s: the hidden states hold %lld floats, got %lld", who, (long long)want, (long long)count);
+    return 0;
+}
+
+extern "C" int sg_rollout_upload_hidden(sg_rollout* r, const float* host, int64_t count) {
+    SG_TRY(check_hidden(r, host, count, "sg_rollout_upload_hidden"));
+    SG_COPY_SYNC(r->ctx, r->d_hidden, host, sizeof(float) * count, hipMemcpyHostToDevice);
+    return 0;
+}
+
+extern "C" int sg_rollout_download_hidden(sg_rollout* r, float* host, int64_t count) {
+    SG_TRY(check_hidden(r, host, count, "sg_rollout_download_hidden"));
+    SG_COPY_SYNC(r->ctx, host, r->d_hidden, sizeof(float) * count, hipMemcpyDeviceToHost);
+    return 0;
+}
+
+// slot T -> slot 0 of obs, obs_feat, masks, bad_masks -- and of the hidden states when the rollout holds them -- in one launch
+// (four small device-to-device copies through the runtime's copy path cost more than the copy and occasionally stall for
+// milliseconds)
 struct AfterUpdateArgs {
-    float* base[4];
-    int64_t per[4];   // floats per time slot
+    float* base[5];
+    int64_t per[5];   // floats per time slot
     int T;
 };
 __global__ __launch_bounds__(256) void k_after_update(AfterUpdateArgs a) {
@@ -133,7 +180,9 @@ extern "C" int sg_rollout_after_update(sg_rollout* r) {
         a.base[i] = r->d_field[fields[i]];
         a.per[i] = (int64_t)r->N * r->field_width[fields[i]];
     }
-    hipLaunchKernelGGL(k_after_update, dim3(32, 4), dim3(256), 0, r->ctx->stream, a);
+    a.base[4] = r->d_hidden;
+    a.per[4] = (int64_t)r->N * r->hidden_dim;
+    hipLaunchKernelGGL(k_after_update, dim3(32, r->d_hidden ? 5 : 4), dim3(256), 0, r->ctx->stream, a);
     r->feat_version = sg_next_feat_version();
     SG_CHECK(hipGetLastError());
     return 0;
@@ -203,6 +252,18 @@ extern "C" int sg_rollout_compute_returns(sg_rollout* r, const float* next_value
 extern "C" int sg_rollout_compute_returns_policy(sg_rollout* r, sg_policy* p, int use_gae, float gamma,
                                                  float gae_lambda, int use_proper_time_limits) {
     SG_REQUIRE(r && p, "sg_rollout_compute_returns_policy: NULL argument");
+    if (p->recurrent && r->d_hidden && r->hidden_dim == p->gru.H) {
+        // next_value = get_value(obs[T], h[T], masks[T]) (a2c/main_gail_dyn_ppo.py:239-242) from the rollout's own slots: the
+        // launches and the bits of sg_policy_get_value_rnn, the value left in the policy's staging; nothing waits
+        SG_REQUIRE(p->ctx == r->ctx, "sg_rollout_compute_returns_policy: the policy and the rollout live on different contexts");
+        SG_REQUIRE(p->gru.O == r->O, "sg_rollout_compute_returns_policy: obs dim mismatch");
+        const size_t TN = (size_t)r->T * r->N;
+        float* d_nv = nullptr;
+        SG_TRY(sg_gru_value_device(p, r->d_field[SG_F_OBS] + TN * r->O, r->d_hidden + TN * r->hidden_dim, r->d_field[SG_F_MASKS] + TN,
+                                   r->N, &d_nv));
+        SG_TRY(compute_returns_dev(r, d_nv, use_gae, gamma, gae_lambda, use_proper_time_limits));
+        return 0;
+    }
     SG_REQUIRE(!p->recurrent, "sg_rollout_compute_returns_policy: the policy is recurrent and the device rollout holds no hidden state; "
                "pass get_value's result to sg_rollout_compute_returns");
     SG_REQUIRE(p->desc.O == r->O, "sg_rollout_compute_returns_policy: obs dim mismatch");

@@ -132,7 +132,7 @@ def _check_on_device(ro, pol, dup_sym, who):
         why = "the rollout is not device-resident (rollouts.device_resident = True): its host tensors are the rollout"
     elif dup_sym or getattr(ro, "dup_sym", False):
         why = "the rollout is mirror-augmented (dup_sym): its column upload would overwrite the fields the device writes"
-    elif pol.is_recurrent:
+    elif pol.is_recurrent and not getattr(ro, "device_hidden", False):   # (rollouts.enable_device_hidden() lifts it)
         why = "the policy is recurrent and the device rollout holds no hidden state"
     elif getattr(pol, "dist_kind", _lib.DIST_GAUSSIAN) != _lib.DIST_GAUSSIAN:
         why = "the policy has a Discrete / MultiBinary action space; the one-launch step carries the Gaussian head only"
@@ -225,11 +225,13 @@ class GailDynLearner(object):
 
 def _returns_resident(self):
     """GAE on a device-resident rollout.  Feed-forward policy: get_value(obs[T]) and the reverse scan both on the device, nothing
-    waits.  Recurrent policy: the device rollout has no hidden-state field, so the value of slot T comes from get_value on the
-    HOST mirrors (obs[-1], recurrent_hidden_states[-1], masks[-1], which the host-side collector filled through insert()) -- one
-    host wait per update, the only one -- and the scan runs on the device's rewards / values / masks."""
+    waits.  Recurrent policy on a rollout that holds its hidden states (enable_device_hidden): the same, get_value(obs[T], h[T],
+    masks[T]) from the device's own slots.  Recurrent policy otherwise: the device rollout has no hidden-state field, so the value
+    of slot T comes from get_value on the HOST mirrors (obs[-1], recurrent_hidden_states[-1], masks[-1], which the host-side
+    collector filled through insert()) -- one host wait per update, the only one -- and the scan runs on the device's rewards /
+    values / masks."""
     ro, lib = self.rollouts, self.rollouts.lib
-    if self.actor_critic.is_recurrent:
+    if self.actor_critic.is_recurrent and not getattr(ro, "device_hidden", False):
         if getattr(ro, "dup_sym", False):
             # mirror-augmented rollout: the host mirrors hold columns [0, n) only, the device made the rest -- slot T of obs and
             # masks comes back first (this path waits for the device anyway), so that the bootstrap value of a mirrored column

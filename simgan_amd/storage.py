@@ -96,6 +96,7 @@ class RolloutStorage(object):
         self._crcs = {}              # SG_ROLLOUT_VERIFY=1: field -> crc32 of the host content at that moment
         self.bytes_uploaded = 0      # host -> device traffic of this rollout so far (bench.py's `dropin` leg reads it)
         self._dup = None             # enable_dup_sym: {"n", "m_obs" | None, "m_act", "obs_fn" | None}
+        self.device_hidden = False   # enable_device_hidden: the device twin holds recurrent_hidden_states too
 
         h = _lib.H()
         _lib.check(self.lib.sg_rollout_create(self.ctx.h, T, N, O, A, F, C.byref(h)))
@@ -166,8 +167,44 @@ class RolloutStorage(object):
             self._synced[f] = self._stamp(f)
             if _VERIFY:
                 self._crcs[f] = self._crc(f)
+        if fields is None and self.__dict__.get("device_hidden"):
+            hx = self._hidden_np()
+            _lib.check(self.lib.sg_rollout_upload_hidden(self.h, _lib.fptr(hx), hx.size))
+            self.bytes_uploaded += hx.nbytes
+
+    def _hidden_np(self):
+        t = self.recurrent_hidden_states
+        a = t.numpy() if hasattr(t, "numpy") else t
+        if a.dtype != np.float32 or not a.flags["C_CONTIGUOUS"]:
+            raise TypeError("rollouts.recurrent_hidden_states must stay a contiguous float32 host tensor")
+        return a
+
+    def enable_device_hidden(self):
+        """Opt in: the device twin also holds recurrent_hidden_states ([T+1, N, H], uploaded from the host tensor now), so that a
+        recurrent policy can act through act_step() -- one launch per step that reads hidden slot `step` and writes slot
+        `step + 1` on the device -- and PPO.update / the learners' GAE take the states from there.  sync_to_device() /
+        sync_from_device() without a field list move the buffer with the fields; after an on-device collection the host tensor
+        is stale until sync_from_device(), like value_preds.  Device-resident rollouts only, not mirror-augmented ones."""
+        H = int(self.recurrent_hidden_states.shape[-1])
+        if not self.device_resident:
+            raise ValueError("enable_device_hidden: the rollout is not device-resident (rollouts.device_resident = True): in drop-in "
+                             "mode the host tensors are the rollout")
+        if H <= 1:
+            raise ValueError(f"enable_device_hidden: recurrent_hidden_state_size is {H}: the rollout was built for a feed-forward "
+                             "policy, which has no hidden state")
+        if self._dup is not None:
+            raise ValueError("enable_device_hidden: the rollout is mirror-augmented (enable_dup_sym): its mirrored columns have no "
+                             "hidden states of their own on the device")
+        _lib.check(self.lib.sg_rollout_enable_hidden(self.h, H))
+        hx = self._hidden_np()
+        _lib.check(self.lib.sg_rollout_upload_hidden(self.h, _lib.fptr(hx), hx.size))
+        self.bytes_uploaded += hx.nbytes
+        self.device_hidden = True
 
     def sync_from_device(self, fields=None):
+        if fields is None and self.__dict__.get("device_hidden"):
+            hx = self._hidden_np()
+            _lib.check(self.lib.sg_rollout_download_hidden(self.h, _lib.fptr(hx), hx.size))
         for f in (fields if fields is not None else _FIELD_ATTR):
             a = self._host_np(f)
             if a.size and a.dtype == np.int64:   # Discrete actions: the device's float32 class indices back into the int64 host tensor
@@ -248,13 +285,27 @@ class RolloutStorage(object):
         back (the host mirrors of value_preds and action_log_probs are stale until sync_from_device()).  The draw is the policy's
         own stream, (policy.seed + policy._act_calls) after incrementing _act_calls, as in policy.act: a run through either path
         consumes the same draws and gets the same bits.  `noise` ([N, A] standard normal) injects the draw.  bytes_uploaded
-        counts the observation slot.  Device-resident rollouts only; feed-forward policies with a Gaussian head."""
+        counts the observation slot.  Device-resident rollouts only; feed-forward policies with a Gaussian head -- and, once
+        enable_device_hidden() was called, recurrent ones: Policy.act with recurrent=True (a2c/model.py:89-101, 117-201, 255-264) on
+        host slots obs[step] and masks[step] (both uploaded and counted) and DEVICE hidden slot `step`, the new state written to
+        hidden slot step + 1 on the device; it does not come back either."""
         self._on_device_only("act_step")
         s, N = self.step, self.num_processes
         obs = self._host_np(_lib.F_OBS)[s]
         nz = None if noise is None else _lib.as_f32(noise).reshape(N, self.act_dim)
         action = np.empty((N, self.act_dim), np.float32)
         policy._act_calls += 1
+        if getattr(policy, "is_recurrent", False) and self.__dict__.get("device_hidden"):
+            # recurrent policy on a rollout that holds its hidden states (enable_device_hidden): the GRU step runs in the same
+            # launch on hidden slot s and masks[s], and the new state lands in hidden slot s + 1 on the device
+            masks = self._host_np(_lib.F_MASKS)[s]
+            _lib.check(self.lib.sg_rollout_act_step_rnn(self.h, policy.h, s, _lib.fptr(obs), _lib.fptr(masks),
+                                                        None if nz is None else _lib.fptr(nz),
+                                                        (policy.seed + policy._act_calls) & (2 ** 64 - 1), 1 if deterministic else 0,
+                                                        _lib.fptr(action)))
+            self.bytes_uploaded += obs.nbytes + masks.nbytes
+            _put(self.actions[s], action)
+            return to_host_tensor(action)
         _lib.check(self.lib.sg_rollout_act_step(self.h, policy.h, s, _lib.fptr(obs), None if nz is None else _lib.fptr(nz),
                                                 (policy.seed + policy._act_calls) & (2 ** 64 - 1), 1 if deterministic else 0,
                                                 _lib.fptr(action)))
@@ -301,6 +352,9 @@ class RolloutStorage(object):
         if not self.__dict__.get("box_actions", True):
             raise NotImplementedError("enable_dup_sym: a mirror-augmented rollout mirrors actions through a linear map, which a class "
                                       "index or a bit vector (Discrete / MultiBinary action space) does not have; Box action spaces only")
+        if self.__dict__.get("device_hidden"):
+            raise ValueError("enable_dup_sym: the rollout holds its hidden states on the device (enable_device_hidden): the mirrored "
+                             "columns would have none of their own there")
         N = self.num_processes
         if N % 2:
             raise ValueError(f"enable_dup_sym: the rollout has num_processes = {N}, an odd number: a mirror-augmented rollout "
