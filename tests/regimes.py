@@ -37,7 +37,19 @@ SEEDS = {("off_policy", "gru", 47, 12, 64, 1): 2, ("off_policy", "mlp", 20, 12, 
          ("saturated", "mlp", 47, 12, 64, 1, 8.0, 5.0): 7, ("saturated", "mlp", 5, 2, 8, 1, 8.0, 5.0): 6,
          ("saturated", "split", 14, 7, 100, 1, 8.0, 5.0): 2, ("saturated", "split", 64, 28, 100, 4, 8.0, 5.0): 18,
          ("saturated", "gru", 13, 5, 20, 1, 4.0, 3.0): 2, ("saturated", "gru", 13, 5, 20, 1, 8.0, 5.0): 58,
-         ("saturated", "gru", 47, 12, 64, 1, 4.0, 3.0): 6, ("saturated", "gru", 47, 12, 64, 1, 8.0, 5.0): 44}   # every other case: 0
+         ("saturated", "gru", 47, 12, 64, 1, 4.0, 3.0): 6, ("saturated", "gru", 47, 12, 64, 1, 8.0, 5.0): 44,
+         # rollouts of another geometry than T, N = 8, 16 carry it at the end of the key: ... + (T, N)
+         ("off_policy", "gru", 13, 5, 20, 1, 9, 33): 1, ("off_policy", "gru", 47, 12, 64, 1, 27, 48): 5,
+         ("off_policy", "gru", 13, 5, 20, 1, 43, 48): 29, ("off_policy", "gru", 13, 5, 20, 1, 8, 34): 1,
+         ("off_policy", "gru", 13, 5, 100, 1, 8, 17): 1}   # every other case: 0
+
+# The recurrent update past one 16-environment tile (tests/test_gru_tiles_host.py on the CPU, tests/test_gpu_gru_tiles.py on the
+# GPU): (shape, T, N), one minibatch of all N environments.  What each reaches in the launcher is restated and asserted by the
+# host file; the same builder, conditions and seed search as every other off_policy case.
+GRU_TILE_CASES = [(("gru", 11, 3, 32, 1), 8, 17), (("gru", 47, 12, 64, 1), 8, 17), (("gru", 13, 5, 100, 1), 8, 17),
+                  (("gru", 13, 5, 20, 1), 9, 33), (("gru", 13, 5, 20, 1), 27, 48), (("gru", 47, 12, 64, 1), 27, 48),
+                  (("gru", 13, 5, 20, 1), 43, 48)]
+GRU_STEPS_CASE = (("gru", 13, 5, 20, 1), 8, 34)   # two optimizer steps per epoch of 17 environments each (num_mini_batch = 2)
 
 
 def param_shapes(kind, O, A, H, f=1):
@@ -298,17 +310,21 @@ def _check(c):
     assert worst <= limit, f"{c.tag}: float32 evaluations are up to {worst:.2e} from float64 in their worst block (limit {limit:g})"
 
 
+def seed_key(regime, kind, O, A, H, f=1, scale_w=1.0, scale_obs=1.0, T=T, N=N):
+    return (regime, kind, O, A, H, f) + ((scale_w, scale_obs) if regime == "saturated" else ()) + ((T, N) if (T, N) != (8, 16) else ())
+
+
 def build(regime, kind, O, A, H, f=1, T=T, N=N, seed=None, scale_w=1.0, scale_obs=1.0, check=True):
     """-> Case: the shape, `params` (float32, flat), the rollout's float32 arrays (obs [T+1, N, O], actions [T, N, A],
     value_preds / returns / masks [T+1, N, 1], action_log_probs [T, N, 1], hxs0 [N, H] for the GRU), entropy_coef, and `desc`
     (describe()).  regime: "off_policy", "all_clipped" or "saturated" (= off_policy at scale_w, scale_obs)."""
     assert regime in ("off_policy", "all_clipped", "saturated")
-    key = (regime, kind, O, A, H, f) + ((scale_w, scale_obs) if regime == "saturated" else ())
-    seed = SEEDS.get(key, 0) if seed is None else seed
+    seed = SEEDS.get(seed_key(regime, kind, O, A, H, f, scale_w, scale_obs, T, N), 0) if seed is None else seed
     rng = np.random.default_rng([seed, O, A, H, {"mlp": 0, "split": 1, "gru": 2}[kind]])
     c = Case(regime=regime, kind=kind, O=O, A=A, H=H, f=f, T=T, N=N, seed=seed, scale_w=scale_w, scale_obs=scale_obs,
              entropy_coef=0.0 if regime == "all_clipped" else 0.01,
-             tag=f"{regime}{(scale_w, scale_obs) if regime == 'saturated' else ''} {kind} ({O}, {A}, {H}, f={f}) seed {seed}")
+             tag=f"{regime}{(scale_w, scale_obs) if regime == 'saturated' else ''} {kind} ({O}, {A}, {H}, f={f})"
+                 f"{'' if (T, N) == (8, 16) else f' T, N = {T}, {N}'} seed {seed}")
     c["params"] = _init_params(rng, kind, O, A, H, f, scale_w)
     c["obs"] = (scale_obs * rng.standard_normal((T + 1, N, O))).astype(np.float32)
     masks = np.ones((T + 1, N, 1), np.float32)
@@ -342,9 +358,9 @@ def build(regime, kind, O, A, H, f=1, T=T, N=N, seed=None, scale_w=1.0, scale_ob
 
 
 @functools.lru_cache(maxsize=None)
-def case(regime, kind, O, A, H, f=1, scale_w=1.0, scale_obs=1.0):
+def case(regime, kind, O, A, H, f=1, scale_w=1.0, scale_obs=1.0, T=T, N=N):
     """build() at the committed seed, computed once per process and shared (callers must not write into it)"""
-    return build(regime, kind, O, A, H, f, scale_w=scale_w, scale_obs=scale_obs)
+    return build(regime, kind, O, A, H, f, T=T, N=N, scale_w=scale_w, scale_obs=scale_obs)
 
 
 def all_cases():
@@ -433,14 +449,16 @@ if __name__ == "__main__":   # the seed search: prints the SEEDS table
     import os
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    for spec in all_cases():
-        regime, kind, O, A, H, f, sw, so = spec
+    geometries = [spec + (T, N) for spec in all_cases()] + \
+        [("off_policy",) + s + (1.0, 1.0, t, n) for s, t, n in GRU_TILE_CASES + [GRU_STEPS_CASE]]
+    for spec in geometries:
+        regime, kind, O, A, H, f, sw, so, t, n = spec
         for seed in range(400):
             try:
-                c = build(regime, kind, O, A, H, f, seed=seed, scale_w=sw, scale_obs=so)
+                c = build(regime, kind, O, A, H, f, T=t, N=n, seed=seed, scale_w=sw, scale_obs=so)
             except AssertionError:
                 continue
-            key = (regime, kind, O, A, H, f) + ((sw, so) if regime == "saturated" else ())
+            key = seed_key(regime, kind, O, A, H, f, sw, so, t, n)
             d = c.desc
             print(f"    {key}: {seed},   # norm {d['norm']:.3g} / {d['norm_plain']:.3g}, margins {d['margin_ratio']:.1e} {d['margin_value']:.1e} "
                   f"{d['margin_uw']:.1e}, o32 {max(max(d['o32_clipped'].values()), max(d['o32_plain'].values())):.1e}, fwd32 {d['fwd32']:.2f}, saturated {d['saturation']:.2f}, {d['classes']}", flush=True)
