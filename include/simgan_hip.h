@@ -108,6 +108,23 @@ SG_API int sg_policy_create2(sg_ctx *ctx, int kind, int obs_dim, int act_dim, in
 enum { SG_DIST_GAUSSIAN = 0, SG_DIST_CATEGORICAL = 1, SG_DIST_BERNOULLI = 2 };
 SG_API int sg_policy_create3(sg_ctx *ctx, int kind, int obs_dim, int act_dim, int hidden, int num_feet, int critic_hidden,
                              int dist, int n_out, sg_policy **out);
+/* Policy on image observations: the CNN base, a2c/model.py:204-230 (CNNBase, feed-forward), which Policy.__init__ picks for a
+ * 3-D obs_shape (a2c/model.py:40-50).  x / 255.0 -> Conv2d(channels, 32, 8, stride 4) -> Conv2d(32, 64, 4, stride 2) ->
+ * Conv2d(64, 32, 3, stride 1) -> Flatten (channel-major, 1568 values) -> Linear(1568, hidden), ReLU after each; critic_linear =
+ * Linear(hidden, 1) and the distribution's Linear read the same features.  height and width must be 84 (the reference
+ * hard-codes 32 * 7 * 7, a2c/model.py:216).  dist SG_DIST_GAUSSIAN (Box((act_dim,)); n_out ignored) or SG_DIST_CATEGORICAL
+ * (Discrete(n_out); act_dim 1); SG_DIST_BERNOULLI is refused.  An observation row is channels * 84 * 84 floats (NCHW).  Flat
+ * parameter order: base.main.0.weight [32, channels, 8, 8], .bias, base.main.2.weight [64, 32, 4, 4], .bias, base.main.4.weight
+ * [32, 64, 3, 3], .bias, base.main.7.weight [hidden, 1568], .bias, base.critic_linear.weight [1, hidden], .bias, then
+ * dist.linear.weight [n_out, hidden], .bias or dist.fc_mean.weight [act_dim, hidden], .bias, dist.logstd._bias [act_dim].
+ * The handle is taken by sg_policy_act / _get_value / _evaluate / _get_params / _set_params / _num_params, sg_ppo_create
+ * (one rank), sg_ppo_update (feed-forward sampler, injected perms, sg_ppo_last_perms, the results ring), sg_ppo_get_adam /
+ * _set_adam, sg_rollout_compute_returns_policy and sg_rollout_fill_synthetic; it is refused, each with a message naming the
+ * CNN base, by sg_a2c_create, sg_acktr_create, sg_ppo_set_symmetry (coef > 0), sg_policy_act_ensemble, sg_rollout_act_step,
+ * sg_rollout_act_step_rnn and by sg_ppo_create on a context whose communicator has world > 1.  sg_policy_create / create2 /
+ * create3 do not reach it: they keep refusing every kind but their three. */
+SG_API int sg_policy_create_cnn(sg_ctx *ctx, int channels, int height, int width, int hidden, int dist, int act_dim, int n_out,
+                                sg_policy **out);
 SG_API int sg_policy_destroy(sg_policy *p);
 SG_API int sg_policy_num_params(const sg_policy *p, int64_t *n);
 /* nn.Module.load_state_dict / state_dict, flattened. */

@@ -73,6 +73,8 @@ class A2C_ACKTR():
                                           "does, without lr, eps, alpha and max_grad_norm")
         if type(actor_critic).__name__ == "SplitPolicy":
             raise NotImplementedError("A2C_ACKTR: implemented for Policy (MLP) only, not for SplitPolicy")
+        if getattr(actor_critic, "cnn", 0):
+            raise NotImplementedError("A2C_ACKTR: not implemented for the CNN base (image observations), in either mode; PPO is")
         if getattr(actor_critic, "is_recurrent", False):
             raise NotImplementedError("A2C_ACKTR: implemented for feed-forward policies only, not for a recurrent Policy "
                                       "(the reference allows --recurrent-policy with a2c and refuses it with acktr)")

@@ -74,6 +74,12 @@ class PPO():
         if getattr(actor_critic, "dist_kind", 0) and mirror_obs is not None and symmetry_coef > 0:
             raise NotImplementedError("mirror-symmetry loss: it compares action means, which a Categorical / Bernoulli head (Discrete / "
                                       "MultiBinary action space) does not have; symmetry_coef > 0 needs a Box action space")
+        if getattr(actor_critic, "cnn", False) and mirror_obs is not None and symmetry_coef > 0:
+            raise NotImplementedError("mirror-symmetry loss: not implemented for the CNN base (image observations have no mirror map "
+                                      "here); symmetry_coef > 0 needs the MLP base")
+        if getattr(actor_critic, "cnn", False) and getattr(actor_critic.ctx, "world", 1) > 1:
+            raise NotImplementedError("PPO on the CNN base (image observations) runs on one rank: data-parallel PPO on it is not "
+                                      f"implemented (this context's communicator has world {actor_critic.ctx.world})")
         self.ctx = actor_critic.ctx
         self.lib = self.ctx.lib
         cfg = _lib.PPOConfig(float(clip_param), int(ppo_epoch), int(num_mini_batch), float(value_loss_coef),

@@ -41,6 +41,7 @@ _ALLOWED = {
     ("torch.serialization", "_get_layout"), ("torch.storage", "UntypedStorage"),
     ("torch.storage", "TypedStorage"),
     ("torch.nn.modules.linear", "Linear"), ("torch.nn.modules.activation", "Tanh"),
+    ("torch.nn.modules.conv", "Conv2d"), ("torch.nn.modules.activation", "ReLU"),   # CNNBase.main (a2c/model.py:211-215)
     ("torch.nn.modules.container", "Sequential"), ("torch.optim.adam", "Adam"),
     ("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
     ("numpy.core.multiarray", "scalar"), ("numpy._core.multiarray", "scalar"),
@@ -174,6 +175,21 @@ def _dist_class(actor_critic):
 
 
 def _policy_dims(class_name, sd, dist_class=None):
+    if class_name == "Policy" and "base.main.0.weight" in sd:
+        # CNNBase on image observations (a2c/model.py:204-230): main = Conv, ReLU, Conv, ReLU, Conv, ReLU, Flatten, Linear, ReLU
+        C = sd["base.main.0.weight"].shape[1]
+        H = sd["base.main.7.weight"].shape[0]
+        assert sd["base.main.0.weight"].shape == (32, C, 8, 8) and sd["base.main.2.weight"].shape == (64, 32, 4, 4) and \
+            sd["base.main.4.weight"].shape == (32, 64, 3, 3) and sd["base.main.7.weight"].shape == (H, 32 * 7 * 7) and \
+            sd["base.critic_linear.weight"].shape == (1, H), "inconsistent CNN base shapes in the checkpoint"
+        assert "base.gru.weight_ih_l0" not in sd, "a recurrent CNN base is not built"
+        if "dist.linear.weight" in sd:
+            if dist_class != "Categorical":
+                raise ValueError(f"checkpoint policy has the CNN base with a {dist_class} head: Categorical or DiagGaussian expected")
+            K = sd["dist.linear.weight"].shape[0]
+            return dict(kind="cnn_categorical", obs_dim=int(C) * 84 * 84, act_dim=1, hidden=int(H), num_feet=1, dist=1, n_out=int(K), cnn=int(C))
+        A = sd["dist.fc_mean.weight"].shape[0]
+        return dict(kind="cnn", obs_dim=int(C) * 84 * 84, act_dim=int(A), hidden=int(H), num_feet=1, cnn=int(C))
     if class_name == "Policy" and "dist.linear.weight" in sd:
         # Discrete / MultiBinary action space: the two heads have the same parameters, the dist module's class tells them apart
         if dist_class not in _LINEAR_DISTS:
@@ -449,6 +465,12 @@ def reference_module_state(kind, sd):
 RECURRENT_SAVE_MSG = ("a recurrent Policy cannot be written in the reference's object layout (nn.GRU's pickled attributes are private to "
                       "the torch release that wrote them); pickle the policy natively (pickle / torch.save of the object) or save "
                       "policy.state_dict()")
+# nn.Conv2d pickles private attributes too (_reversed_padding_repeated_twice, padding_mode, ...)
+CNN_SAVE_MSG = ("a Policy with the CNN base cannot be written in the reference's object layout (nn.Conv2d's pickled attributes are "
+                "private to the torch release that wrote them); pickle the policy natively (pickle / torch.save of the object) or save "
+                "policy.state_dict()")
+
+
 class _Box(object):
     def __init__(self, n):
         self.shape = (int(n),)
@@ -478,7 +500,10 @@ def load_policy(path, ctx=None):
     from .model import Policy
     from .model_split import SplitPolicy
     ck = read_reference_checkpoint(path)
-    if ck["kind"] in ("mlp_categorical", "mlp_bernoulli"):
+    if ck["kind"] in ("cnn", "cnn_categorical"):
+        space = _Discrete(ck["n_out"]) if ck["kind"] == "cnn_categorical" else _Box(ck["act_dim"])
+        pol = Policy((ck["cnn"], 84, 84), space, base_kwargs={"hidden_size": ck["hidden"]}, ctx=ctx)
+    elif ck["kind"] in ("mlp_categorical", "mlp_bernoulli"):
         space = _Discrete(ck["n_out"]) if ck["kind"] == "mlp_categorical" else _MultiBinary(ck["n_out"])
         pol = Policy((ck["obs_dim"],), space, base_kwargs={"recurrent": False, "hidden_size": ck["hidden"]}, ctx=ctx,
                      critic_hidden=ck.get("critic_hidden"))
@@ -496,6 +521,8 @@ def save_policy(path, policy, ob_rms=None):
     """a2c/main.py:260-269: a file the reference's `torch.load(path)` turns back into `[actor_critic, ob_rms]`."""
     if policy.is_recurrent:
         raise NotImplementedError(RECURRENT_SAVE_MSG)
+    if getattr(policy, "cnn", 0):
+        raise NotImplementedError(CNN_SAVE_MSG)
     kind = {1: "mlp_categorical", 2: "mlp_bernoulli"}.get(getattr(policy, "dist_kind", 0), "mlp")
     save_reference_checkpoint(path, kind if policy.KIND == 0 else "split", policy.state_dict(), ob_rms)
 

@@ -234,6 +234,15 @@ int64_t sg_gru_flat_count(const SgGruDesc& g);
 void sg_gru_pad(const SgGruDesc& g, const float* flat, float* padded);     // padded -> the block's first float, zeroed
 void sg_gru_unpad(const SgGruDesc& g, const float* padded, float* flat);
 
+// CNN base of Policy on [C, 84, 84] image observations (a2c/model.py:204-230; sg_policy_create_cnn, sg_cnn.hip).  Its device
+// parameter vector IS the flat state_dict vector (no tile padding: the implicit-GEMM kernels bound-check their operands), so
+// Adam moments and the gradient share that order too.  Offsets in floats.
+struct SgCnnDesc {
+    int C, Hs, P, A, dist;     // input channels, hidden size, head outputs (n_out or A), action-row width, SG_DIST_*
+    int w1, b1, w2, b2, w3, b3, wf, bf, wc, bc, wd, bd, ls;   // base.main.{0,2,4,7}, base.critic_linear, dist.*, dist.logstd
+    int total;
+};
+
 struct sg_policy {
     sg_ctx* ctx;
     SgPolicyDesc desc;           // recurrent: the heads on h_t, i.e. an MLP policy whose observation is the GRU state (O == H)
@@ -242,7 +251,21 @@ struct sg_policy {
     float* d_params = nullptr;   // padded
     float* d_io = nullptr;       // staging for the host-pointer entry points
     size_t io_bytes = 0;
+    bool cnn = false;            // sg_policy_create_cnn: desc is then a stand-in (kind MLP, O = C*84*84) that carries the dims the
+    SgCnnDesc cnnd;              // shared entry points check and the layout the head kernels read; the network is cnnd's
 };
+
+#define SG_CNN_FWD_ROWS 128   // rows per pass of the CNN base's inference forward (78 KB of activations per row)
+// sg_cnn.hip: the CNN base's launches, enqueued on ctx->stream
+size_t sg_cnn_fwd_floats(const SgCnnDesc& c, int n);     // activation stacks of n rows: A1 | A2 | A3 | F
+size_t sg_cnn_bwd_floats(const SgCnnDesc& c, int n);     // gradient stacks, loss rows and the weight-gradient slabs
+// obs rows (idx NULL: rows 0..n-1) -> act (sg_cnn_fwd_floats(n)) and rows [row0, row0 + n) of heads [2][n_total][hld]
+int sg_cnn_forward_launch(sg_ctx* ctx, const sg_policy* p, const float* d_obs, const int64_t* d_idx, int n, float* act,
+                          float* heads, int hld, int row0, int n_total);
+// one minibatch's loss and gradient from the stacks of sg_cnn_forward_launch: grad[total + 3] flat, loss sums behind it
+int sg_cnn_backward_launch(sg_ctx* ctx, const sg_policy* p, const struct sg_rollout* r, const float* d_obs, const int64_t* d_idx,
+                           int n, const float* act, const float* heads, int hld, float* bwd, float* grad, float inv_B, float clip,
+                           float vcoef, float ecoef, int use_clipped);
 
 size_t sg_policy_padded_count(const sg_policy* p);          // floats of d_params (heads + GRU block)
 bool sg_gru_fits(const sg_ctx* ctx, const SgGruDesc& g);   // sg_gru.hip: the GRU kernels' 16-row tiles fit a CU's LDS

@@ -238,8 +238,19 @@ int sg_policy_forward_device(sg_policy* p, const float* d_obs, int n, int mode, 
     const int hld = sg_policy_heads_ld(p->desc);
     float* scratch = nullptr;
     const size_t heads_bytes = sizeof(float) * (size_t)p->desc.n_trunks * n * hld;
-    SG_TRY(sg_ctx_scratch(ctx, heads_bytes, &scratch));
-    SG_TRY(policy_forward_dev(p, d_obs, nullptr, n, scratch, hld));
+    if (p->cnn) {
+        // the CNN base (sg_cnn.hip) fills the same head stacks, SG_CNN_FWD_ROWS rows at a time so that the activation stacks
+        // behind them stay bounded whatever n is
+        const int chunk = n < SG_CNN_FWD_ROWS ? n : SG_CNN_FWD_ROWS;
+        SG_TRY(sg_ctx_scratch(ctx, heads_bytes + sizeof(float) * sg_cnn_fwd_floats(p->cnnd, chunk), &scratch));
+        float* act = scratch + (size_t)p->desc.n_trunks * n * hld;
+        for (int r0 = 0; r0 < n; r0 += chunk)
+            SG_TRY(sg_cnn_forward_launch(ctx, p, d_obs + (size_t)r0 * p->desc.O, nullptr, n - r0 < chunk ? n - r0 : chunk, act, scratch, hld,
+                                         r0, n));
+    } else {
+        SG_TRY(sg_ctx_scratch(ctx, heads_bytes, &scratch));
+        SG_TRY(policy_forward_dev(p, d_obs, nullptr, n, scratch, hld));
+    }
     HeadArgs h;
     h.d = p->desc; h.params = p->d_params; h.heads = scratch; h.hld = hld; h.n = n; h.mode = mode;
     h.noise = d_noise; h.seed = seed; h.stream = SG_ACT_STREAM + (uint64_t)ctx->rank; h.action_in = d_action_in;
@@ -324,6 +335,7 @@ extern "C" int sg_policy_destroy(sg_policy* p) {
 // flat (state_dict) and padded (device) sizes of the whole policy: a recurrent one carries its GRU's four tensors FIRST in the
 // flat order (base.gru.* precede base.actor.*, a2c/model.py:124-131,240-251) and BEHIND the heads' block on the device
 static int64_t policy_flat_total(const sg_policy* p) {
+    if (p->cnn) return p->cnnd.total;   // the CNN base keeps the flat order on the device
     return sg_policy_flat_count(p->desc) + (p->recurrent ? sg_gru_flat_count(p->gru) : 0);
 }
 size_t sg_policy_padded_count(const sg_policy* p) {
@@ -340,6 +352,11 @@ extern "C" int sg_policy_set_params(sg_policy* p, const float* flat, int64_t n) 
     SG_REQUIRE(p && flat, "sg_policy_set_params: NULL argument");
     SG_REQUIRE(n == policy_flat_total(p), "sg_policy_set_params: expected %lld floats, got %lld",
                (long long)policy_flat_total(p), (long long)n);
+    if (p->cnn) {
+        SG_CHECK(hipStreamSynchronize(p->ctx->stream));
+        SG_COPY_SYNC(p->ctx, p->d_params, flat, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
+        return 0;
+    }
     std::vector<float> padded(sg_policy_padded_count(p), 0.f);
     const int64_t n_gru = p->recurrent ? sg_gru_flat_count(p->gru) : 0;
     if (p->recurrent) sg_gru_pad(p->gru, flat, padded.data() + p->gru.off);
@@ -353,6 +370,11 @@ extern "C" int sg_policy_get_params(sg_policy* p, float* flat, int64_t n) {
     SG_REQUIRE(p && flat, "sg_policy_get_params: NULL argument");
     SG_REQUIRE(n == policy_flat_total(p), "sg_policy_get_params: expected %lld floats, got %lld",
                (long long)policy_flat_total(p), (long long)n);
+    if (p->cnn) {
+        SG_CHECK(hipStreamSynchronize(p->ctx->stream));
+        SG_COPY_SYNC(p->ctx, flat, p->d_params, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
+        return 0;
+    }
     std::vector<float> padded(sg_policy_padded_count(p));
     SG_CHECK(hipStreamSynchronize(p->ctx->stream));
     SG_COPY_SYNC(p->ctx, padded.data(), p->d_params, sizeof(float) * padded.size(), hipMemcpyDeviceToHost);
@@ -539,6 +561,8 @@ extern "C" int sg_policy_act_ensemble(sg_policy* const* policies, int n_policies
     EnsArgs a;
     for (int k = 0; k < n_policies; ++k) {
         SG_REQUIRE(policies[k] && policies[k]->ctx == ctx, "sg_policy_act_ensemble: member %d is NULL or lives on another context", k);
+        SG_REQUIRE(!policies[k]->cnn, "sg_policy_act_ensemble: member %d has the CNN base (image observations); the ensemble launch "
+                   "runs the MLP trunks only", k);
         SG_REQUIRE(!policies[k]->recurrent, "sg_policy_act_ensemble: member %d is a recurrent policy; the ensemble launch carries no hidden "
                    "state (feed-forward policies only)", k);
         const SgPolicyDesc& e = policies[k]->desc;

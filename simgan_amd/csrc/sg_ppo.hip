@@ -200,9 +200,11 @@ extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg
     SG_REQUIRE(!(p->recurrent && ctx->use_comm && ctx->world > 1), "sg_ppo_create: PPO with a recurrent policy runs on one rank: this "
                "context has a communicator of world %d (data-parallel PPO through time is not implemented)", ctx->world);
     SG_REQUIRE(cfg->ppo_epoch > 0 && cfg->num_mini_batch > 0, "sg_ppo_create: ppo_epoch and num_mini_batch must be positive");
+    SG_REQUIRE(!(p->cnn && ctx->use_comm && ctx->world > 1), "sg_ppo_create: PPO on the CNN base (image observations) runs on one rank: "
+               "this context has a communicator of world %d (data-parallel PPO on it is not implemented)", ctx->world);
     // a policy whose trunk does not fit a CU's LDS runs on the global-weight instances; only the 16-row tiles must fit
     const size_t tiles_f = ppo_fwd_lds(p->desc, 1, true), tiles_b = ppo_bwd_tiles_lds(p->desc, 1, 0, 2, false);
-    SG_REQUIRE(tiles_f <= (size_t)ctx->lds_bytes && tiles_b <= (size_t)ctx->lds_bytes,
+    SG_REQUIRE(p->cnn || (tiles_f <= (size_t)ctx->lds_bytes && tiles_b <= (size_t)ctx->lds_bytes),
                "sg_ppo_create: the 16-row activation tiles of this policy do not fit LDS (%zu / %zu > %d bytes)", tiles_f, tiles_b,
                ctx->lds_bytes);
     SG_CHECK(hipSetDevice(ctx->device));
@@ -235,6 +237,7 @@ extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg
 // (a2c/algo/a2c_acktr.py:30-51: RMSprop, square_avg starting at zero).  Policy (MLP) on one rank only.
 extern "C" int sg_a2c_create(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg, sg_ppo** out) {
     SG_REQUIRE(ctx && p && cfg && out, "sg_a2c_create: NULL argument");
+    SG_REQUIRE(!p->cnn, "sg_a2c_create: A2C is not implemented for the CNN base (image observations): PPO is");
     SG_REQUIRE(!p->recurrent, "sg_a2c_create: A2C is implemented for feed-forward policies only, not for a recurrent Policy");
     SG_REQUIRE(p->desc.kind == SG_POLICY_MLP, "sg_a2c_create: A2C is implemented for Policy (MLP) only, not for SplitPolicy");
     SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_a2c_create: A2C runs on one rank: this context has a communicator of "
@@ -260,6 +263,8 @@ extern "C" int sg_a2c_create(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg
 extern "C" int sg_acktr_create(sg_ctx* ctx, sg_policy* p, const sg_acktr_config* cfg, sg_ppo** out) {
     SG_DEVICE_WIDE();   // kfac_setup's clears and copies on ctx->stream, never beside a capture in flight (recursive with sg_ppo_create's)
     SG_REQUIRE(ctx && p && cfg && out, "sg_acktr_create: NULL argument");
+    SG_REQUIRE(!p->cnn, "sg_acktr_create: ACKTR is not implemented for the CNN base (image observations): its convolutions have no "
+               "K-FAC blocks here; PPO is");
     SG_REQUIRE(!p->recurrent, "sg_acktr_create: ACKTR is not defined for a recurrent Policy (the reference refuses it too: "
                "a2c/arguments.py:253-255)");
     SG_REQUIRE(p->desc.kind == SG_POLICY_MLP, "sg_acktr_create: ACKTR is implemented for Policy (MLP) only, not for SplitPolicy");
@@ -334,6 +339,8 @@ extern "C" int sg_ppo_set_symmetry(sg_ppo* a, float coef, const float* m_obs, co
     SG_CHECK(hipStreamSynchronize(ctx->stream));   // a queued update may still read the mirrors
     if (coef == 0.f) { a->sym_coef = 0.f; return 0; }   // a2c/algo/ppo.py:111: plain PPO
     SG_REQUIRE(m_act, "sg_ppo_set_symmetry: symmetry_coef > 0 needs the action mirror m_act");
+    SG_REQUIRE(!a->policy->cnn, "sg_ppo_set_symmetry: the mirror-symmetry loss is not implemented for the CNN base (image "
+               "observations have no linear mirror map here)");
     SG_REQUIRE(d.kind == SG_POLICY_MLP, "sg_ppo_set_symmetry: the mirror-symmetry loss is implemented for Policy (MLP) only, "
                "not for SplitPolicy");
     SG_REQUIRE(d.dist == SG_DIST_GAUSSIAN, "sg_ppo_set_symmetry: the mirror-symmetry loss compares action means: it is defined for "
@@ -400,6 +407,14 @@ extern "C" int sg_ppo_get_adam(sg_ppo* a, float* m, float* v, int64_t n, int64_t
     const SgPolicyDesc& d = a->policy->desc;
     const sg_policy* pol = a->policy;
     const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;   // the GRU's tensors come first in the flat order
+    if (pol->cnn) {   // the CNN base keeps the flat order on the device
+        SG_REQUIRE(n == pol->cnnd.total, "sg_ppo_get_adam: bad length");
+        SG_CHECK(hipStreamSynchronize(a->ctx->stream));
+        SG_COPY_SYNC(a->ctx, m, a->d_m, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
+        SG_COPY_SYNC(a->ctx, v, a->d_v, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
+        *step = a->opt_t;
+        return 0;
+    }
     SG_REQUIRE(n == sg_policy_flat_count(d) + n_gru, "sg_ppo_get_adam: bad length");
     const size_t ptot = sg_policy_padded_count(pol);
     std::vector<float> pm(ptot), pv(ptot);
@@ -423,6 +438,17 @@ extern "C" int sg_ppo_set_adam(sg_ppo* a, const float* m, const float* v, int64_
     const SgPolicyDesc& d = a->policy->desc;
     const sg_policy* pol = a->policy;
     const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;
+    if (pol->cnn) {
+        SG_REQUIRE(n == pol->cnnd.total, "sg_ppo_set_adam: bad length");
+        SG_REQUIRE(step >= 0 && step < (1ll << 30), "sg_ppo_set_adam: step out of range");
+        const int t0c = (int)step;
+        SG_CHECK(hipStreamSynchronize(a->ctx->stream));
+        SG_COPY_SYNC(a->ctx, a->d_m, m, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
+        SG_COPY_SYNC(a->ctx, a->d_v, v, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
+        SG_COPY_SYNC(a->ctx, &reinterpret_cast<SgOptState*>(a->d_state)->t0, &t0c, sizeof t0c, hipMemcpyHostToDevice);
+        a->opt_t = step;
+        return 0;
+    }
     SG_REQUIRE(n == sg_policy_flat_count(d) + n_gru, "sg_ppo_set_adam: bad length");
     const size_t ptot = sg_policy_padded_count(pol);
     std::vector<float> pm(ptot, 0.f), pv(ptot, 0.f);
@@ -949,6 +975,105 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
     return 0;
 }
 
+// PPO.update(rollouts) on the CNN base (a2c/algo/ppo.py:63-160 with a2c/storage.py:144-192's feed-forward sampler; the network:
+// a2c/model.py:204-230): ppo_epoch x num_mini_batch optimizer steps on minibatches of T*N // num_mini_batch rows.
+//   k_adv_stats x3
+//   per step:  the forward of sg_cnn.hip on the step's rows (read in place from the rollout through the permutation: no epoch
+//              copy of the 28 K-float observations) -> k_cnn_head_loss -> head, FC, conv3, conv2, conv1 gradients, each weight
+//              gradient as slabs + k_cnn_reduce -> k_sumsq -> k_ppo_adam over the one flat gradient (one norm, one clip)
+//   then       k_opt_commit
+// All of it behind the permutations is one captured graph, replayed per update; no host wait inside.  The activation and
+// gradient stacks are 41 K floats per minibatch row: minibatches of more than SG_CNN_MAX_MB rows are refused.
+#define SG_CNN_MAX_MB 4096
+static int cnn_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_t n_perms, uint64_t seed, float out3[3]) {
+    sg_ctx* ctx = a->ctx;
+    sg_policy* pol = a->policy;
+    const SgPolicyDesc& d = pol->desc;
+    const SgCnnDesc& c = pol->cnnd;
+    SG_REQUIRE(r->O == d.O && r->A == d.A, "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)", r->O, r->A,
+               d.O, d.A);
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_ppo_update: PPO on the CNN base runs on one rank (world %d)", ctx->world);
+    const int64_t TN = (int64_t)r->T * r->N;
+    const int M = a->cfg.num_mini_batch, E = a->cfg.ppo_epoch;
+    SG_REQUIRE(TN >= M, "PPO requires the number of processes (%d) * number of steps (%d) = %lld to be greater than "
+               "or equal to the number of PPO mini batches (%d).", r->N, r->T, (long long)TN, M);
+    SG_REQUIRE(TN < (1ll << 30), "sg_ppo_update: rollout too large");
+    const int mb = (int)(TN / M);
+    SG_REQUIRE(mb <= SG_CNN_MAX_MB, "sg_ppo_update: a minibatch of %d rows on the CNN base exceeds %d (its activation stacks are "
+               "158 KB per row): raise num_mini_batch", mb, SG_CNN_MAX_MB);
+    if (perms) {
+        SG_REQUIRE(n_perms == (int64_t)E * TN, "sg_ppo_update: perms holds %lld indices, %d epochs x %lld rows need %lld",
+                   (long long)n_perms, E, (long long)TN, (long long)E * TN);
+        for (int64_t i = 0; i < n_perms; ++i)
+            SG_REQUIRE(perms[i] >= 0 && perms[i] < TN, "sg_ppo_update: perms[%lld] = %lld is outside [0, %lld)", (long long)i,
+                       (long long)perms[i], (long long)TN);
+    }
+    SG_CHECK(hipSetDevice(ctx->device));
+    SG_TRY(enqueue_adv_stats(ctx, r, a, false));
+    SG_TRY(ensure_cap(ctx->stream, &a->d_perms, &a->perms_cap, (int64_t)E * TN));
+    a->last_perm_count = (int64_t)E * TN;
+    if (perms) {
+        SG_CHECK(hipMemcpyAsync(a->d_perms, perms, sizeof(int64_t) * (size_t)E * TN, hipMemcpyHostToDevice, ctx->stream));
+        if (!out3) SG_CHECK(hipStreamSynchronize(ctx->stream));
+    } else {
+        for (int e = 0; e < E; ++e) SG_TRY(sg_fill_perm(ctx, a->d_perms + (size_t)e * TN, TN, seed, (uint64_t)e * 2654435761ull));
+    }
+    // scratch: head stacks | activation stacks | gradient stacks and slabs
+    const int hld = d.trunk[0].Pp > 16 ? d.trunk[0].Pp : 16;
+    const size_t heads_f = 2 * (size_t)mb * hld, fwd_f = sg_cnn_fwd_floats(c, mb), bwd_f = sg_cnn_bwd_floats(c, mb);
+    bool grew = false;
+    SG_TRY(ensure_cap(ctx->stream, &a->d_stacks, &a->stacks_cap, heads_f + fwd_f + bwd_f, &grew));
+    if (grew) a->cleared.mode = SG_LAYOUT_INVALID;
+    float* heads = a->d_stacks;
+    float* act = heads + heads_f;
+    float* bwd = act + fwd_f;
+    hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 4);
+    const float inv_B = 1.0f / (float)mb;
+    const int nblk = (c.total + 255) / 256;
+    SgOptState* st = reinterpret_cast<SgOptState*>(a->d_state);
+    const float* obs = r->d_field[SG_F_OBS];
+
+    auto enqueue_steps = [&]() -> int {
+        hipLaunchKernelGGL(k_opt_prepare_first, dim3(1), dim3(1), 0, ctx->stream, st);
+        for (int e = 0; e < E; ++e)
+            for (int k = 0; k < M; ++k) {
+                const int64_t* idx = a->d_perms + (size_t)e * TN + (size_t)k * mb;
+                SG_TRY(sg_cnn_forward_launch(ctx, pol, obs, idx, mb, act, heads, hld, 0, mb));
+                SG_TRY(sg_cnn_backward_launch(ctx, pol, r, obs, idx, mb, act, heads, hld, bwd, a->d_grad, inv_B, a->cfg.clip_param,
+                                              a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.use_clipped_value_loss));
+                hipLaunchKernelGGL(k_sumsq, dim3(nblk), dim3(256), 0, ctx->stream, a->d_grad, c.total, a->d_part);
+                SG_LAUNCH(ctx, SG_PROF_PPO_ADAM, k_ppo_adam, dim3(nblk), dim3(256), 0, pol->d_params, a->d_m, a->d_v, a->d_grad, a->d_part,
+                          nblk, c.total, st, e * M + k + 1, a->cfg.eps, a->cfg.max_grad_norm, inv_B, a->d_loss_acc);
+            }
+        hipLaunchKernelGGL(k_opt_commit, dim3(1), dim3(1), 0, ctx->stream, st, E * M);
+        SG_CHECK(hipGetLastError());
+        return 0;
+    };
+    const bool use_graph = !ctx->profile && !sg_env_is_off("SG_PPO_GRAPH");
+    uint32_t fbits[6];
+    const float fv[6] = {a->cfg.clip_param, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, inv_B};
+    memcpy(fbits, fv, sizeof fbits);
+    const uint64_t key[SG_GRAPH_KEY_WORDS] = {
+            (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_grad, (uint64_t)(uintptr_t)a->d_perms,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
+            (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)pol->d_params,
+            (uint64_t)TN, ((uint64_t)E << 32) | (uint64_t)M, (uint64_t)mb,
+            ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
+            ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)a->cfg.use_clipped_value_loss,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_LOGP],
+            0x434E4Eull + ((uint64_t)r->N << 32),   // 'CNN': the convolutional step sequence
+            (uint64_t)(uintptr_t)r->d_field[SG_F_VALUE_PREDS], (uint64_t)(uintptr_t)r->d_field[SG_F_ADVANTAGES]};
+    SG_TRY(sg_graph_run(ctx, &a->steps_graph, use_graph, key, enqueue_steps));
+    SG_CHECK(hipGetLastError());
+    a->opt_t += (int64_t)E * M;
+    if (!out3) return 0;
+    double acc[3];
+    SG_TRY(sg_ctx_fetch_f64(ctx, a->d_loss_acc, acc, 3));
+    const double nu = (double)E * M;
+    for (int i = 0; i < 3; ++i) out3[i] = (float)(acc[i] / nu);
+    return 0;
+}
+
 extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_t n_perms, uint64_t seed, float out3[3]) {
     SG_REQUIRE(a && r, "sg_ppo_update: NULL argument");
     if (a->a2c) {
@@ -959,6 +1084,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
         return a2c_update(a, r, seed, out3);
     }
     if (a->policy->recurrent) return gru_ppo_update(a, r, perms, n_perms, seed, out3);
+    if (a->policy->cnn) return cnn_ppo_update(a, r, perms, n_perms, seed, out3);
     sg_ctx* ctx = a->ctx;
     const SgPolicyDesc& d = a->policy->desc;
     SG_REQUIRE(r->O == d.O && r->A == d.A, "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)",

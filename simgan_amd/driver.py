@@ -136,6 +136,8 @@ def _check_on_device(ro, pol, dup_sym, who):
         why = "the policy is recurrent and the device rollout holds no hidden state"
     elif getattr(pol, "dist_kind", _lib.DIST_GAUSSIAN) != _lib.DIST_GAUSSIAN:
         why = "the policy has a Discrete / MultiBinary action space; the one-launch step carries the Gaussian head only"
+    elif getattr(pol, "cnn", 0):
+        why = "the policy has the CNN base (image observations); the one-launch step runs the MLP trunks only"
     if why is not None:
         raise ValueError(f"{who}(on_device=True): {why}")
 
@@ -145,6 +147,9 @@ class GailDynLearner(object):
                  gamma=0.99, gae_lambda=0.95, use_gae=True, use_proper_time_limits=True,
                  gail_tar_length=500.0, no_alive_bonus=False, use_linear_lr_decay=False, lr=None,
                  num_updates=None):
+        if getattr(actor_critic, "cnn", 0):
+            raise NotImplementedError("GailDynLearner: the GAIL-dyn loop is built for 1-D observations (the reference's main asserts "
+                                      "them, a2c/main_gail_dyn_ppo.py); a policy with the CNN base (image observations) is not taken")
         self.actor_critic, self.agent, self.discr, self.rollouts = actor_critic, agent, discr, rollouts
         self.loader = expert if hasattr(expert, "batch_size") else ExpertLoader(expert, gail_batch_size)
         self.gail_epoch, self.gamma, self.gae_lambda = gail_epoch, gamma, gae_lambda
@@ -336,6 +341,8 @@ class PpoLearner(object):
                 value, action, logp, hxs = pol.act(ro.obs[step], ro.recurrent_hidden_states[step], ro.masks[step])
             obs, reward, done, infos = envs.step(action)
             feat = obs if feat_select_func is None else feat_select_func(obs)
+            if feat_select_func is None and getattr(ro, "image_shape", None):
+                feat = None   # image observations: the feature slot is not a copy of the observation (it keeps what it holds)
             masks, bad = step_masks(done, infos)
             insert(obs, hxs, action, logp, value, reward, to_host_tensor(masks), to_host_tensor(bad), feat)
         if ro.device_resident:

@@ -1,4 +1,4 @@
-"""Policy -- host mirror of a2c/model.py:37-114 (MLPBase + DiagGaussian on Box actions, Categorical on Discrete, Bernoulli on
+"""Policy -- host mirror of a2c/model.py:37-114 (image observations [C, 84, 84]: CNNBase, a2c/model.py:204-230, with the Categorical or Gaussian head; else MLPBase + DiagGaussian on Box actions, Categorical on Discrete, Bernoulli on
 MultiBinary, a2c/model.py:52-62; feed-forward, or -- Box only -- recurrent with the GRU base of a2c/model.py:117-201).  Parameters live in HBM inside libsimgan_hip.so; this class keeps the
 reference's constructor and method signatures and hands host tensors across the C ABI."""
 import ctypes as C
@@ -15,11 +15,16 @@ from .utils import derive_seed, orthogonal, to_host_tensor
 # `checkpoint.load_policy(path, ctx=ctx)`, which builds the policy on `ctx` directly and never comes through here.
 MATERIALISE_CTX = None
 
+CNN_HW = 84   # the CNN base's image size: the reference hard-codes Linear(32 * 7 * 7, hidden) behind its convolutions (a2c/model.py:216)
+
 
 class _PolicyBase(object):
     KIND = None
 
-    def _create(self, obs_dim, act_dim, hidden, num_feet, ctx, critic_hidden=None, recurrent=False, dist=0, n_out=None):
+    def _create(self, obs_dim, act_dim, hidden, num_feet, ctx, critic_hidden=None, recurrent=False, dist=0, n_out=None, cnn=None):
+        # cnn: None, or the channel count C of [C, 84, 84] image observations -- the CNN base (a2c/model.py:204-230); obs_dim is
+        # then the flat row width C * 84 * 84
+        self.__dict__["cnn"] = int(cnn) if cnn else 0
         # dist_kind: _lib.DIST_GAUSSIAN (Box), DIST_CATEGORICAL (Discrete(n_out): act_dim 1, the class index) or DIST_BERNOULLI
         # (MultiBinary(n_out): act_dim n_out); n_out: the head's outputs
         self.__dict__["_dist_kind"] = int(dist or 0)
@@ -33,7 +38,10 @@ class _PolicyBase(object):
         self.critic_hidden = int(critic_hidden) if critic_hidden else self.hidden_size
         h = _lib.H()
         ch = 0 if self.critic_hidden == self.hidden_size else self.critic_hidden
-        if self.dist_kind:
+        if self.cnn:
+            _lib.check(self.lib.sg_policy_create_cnn(self.ctx.h, self.cnn, CNN_HW, CNN_HW, self.hidden_size, self.dist_kind, self.act_dim,
+                                                     self.n_out, C.byref(h)))
+        elif self.dist_kind:
             _lib.check(self.lib.sg_policy_create3(self.ctx.h, self.KIND, self.obs_dim, self.act_dim, self.hidden_size, self.num_feet, ch,
                                                   self.dist_kind, self.n_out, C.byref(h)))
         else:
@@ -93,7 +101,7 @@ class _PolicyBase(object):
             # the process default otherwise (see the module-level comment)
             self._create(dims["obs_dim"], dims["act_dim"], dims["hidden"], dims["num_feet"], MATERIALISE_CTX,
                          critic_hidden=dims.get("critic_hidden"), recurrent=dims.get("recurrent", False),
-                         dist=dims.get("dist", 0), n_out=dims.get("n_out"))
+                         dist=dims.get("dist", 0), n_out=dims.get("n_out"), cnn=dims.get("cnn"))
             self.seed = derive_seed(0, 0x5EED, per_instance=True)
             self.load_state_dict(sd)
         except BaseException:
@@ -159,7 +167,7 @@ class _PolicyBase(object):
     def __getstate__(self):
         return {"obs_dim": self.obs_dim, "act_dim": self.act_dim, "hidden": self.hidden_size,
                 "num_feet": self.num_feet, "critic_hidden": self.critic_hidden, "recurrent": self._rec(),
-                "dist": self.dist_kind, "n_out": self.n_out, "flat": self.get_flat_params()}
+                "dist": self.dist_kind, "n_out": self.n_out, "cnn": self.__dict__.get("cnn", 0), "flat": self.get_flat_params()}
 
     def __reduce_ex__(self, protocol):
         """A policy built through the reference's import path (`third_party.a2c_ppo_acktr.model[_split]`, i.e. by the
@@ -171,6 +179,9 @@ class _PolicyBase(object):
             if self._rec():
                 from .checkpoint import RECURRENT_SAVE_MSG
                 raise NotImplementedError(RECURRENT_SAVE_MSG)
+            if self.__dict__.get("cnn"):
+                from .checkpoint import CNN_SAVE_MSG
+                raise NotImplementedError(CNN_SAVE_MSG)
             import copyreg
             from .checkpoint import reference_module_state
             kind = {_lib.DIST_CATEGORICAL: "mlp_categorical", _lib.DIST_BERNOULLI: "mlp_bernoulli"}.get(self.dist_kind, "mlp")
@@ -184,7 +195,7 @@ class _PolicyBase(object):
             self.__dict__["_pending"] = st
             return
         self._create(st["obs_dim"], st["act_dim"], st["hidden"], st["num_feet"], None, critic_hidden=st.get("critic_hidden"),
-                     recurrent=st.get("recurrent", False), dist=st.get("dist", 0), n_out=st.get("n_out"))
+                     recurrent=st.get("recurrent", False), dist=st.get("dist", 0), n_out=st.get("n_out"), cnn=st.get("cnn"))
         self.seed = derive_seed(0, 0x5EED, per_instance=True)
         self.set_flat_params(st["flat"])
 
@@ -267,8 +278,17 @@ class Policy(_PolicyBase):
     def __init__(self, obs_shape, action_space, base=None, base_kwargs=None, ctx=None, seed=0, critic_hidden=None):
         if base_kwargs is None:
             base_kwargs = {}
-        if base is not None or len(obs_shape) != 1:
+        if base is not None or len(obs_shape) not in (1, 3):
             raise NotImplementedError("only the MLP base on 1-D observations is built (SURVEY.md section 2, row 3)")
+        cnn = len(obs_shape) == 3   # a2c/model.py:42-46: CNNBase for image observations
+        if cnn and (int(obs_shape[1]) != CNN_HW or int(obs_shape[2]) != CNN_HW):
+            raise ValueError(f"Policy on image observations {tuple(obs_shape)}: the CNN base takes [C, {CNN_HW}, {CNN_HW}] only (the "
+                             "reference hard-codes Linear(32 * 7 * 7, hidden) behind its three convolutions, a2c/model.py:216)")
+        if cnn and int(obs_shape[0]) < 1:
+            raise ValueError(f"Policy on image observations {tuple(obs_shape)}: need at least one channel")
+        if cnn and base_kwargs.get("recurrent", False):
+            raise NotImplementedError("Policy on image observations with base_kwargs={'recurrent': True}: the CNN base is built "
+                                      "feed-forward only (a recurrent CNN base is not)")
         # a2c/model.py:52-62
         space = action_space.__class__.__name__
         if space == "Box":
@@ -282,17 +302,34 @@ class Policy(_PolicyBase):
             dist, act_dim = _lib.DIST_BERNOULLI, n_out
         else:
             raise NotImplementedError(f"action space {space}: Box, Discrete and MultiBinary are built (a2c/model.py:52-62)")
+        if cnn and dist == _lib.DIST_BERNOULLI:
+            raise NotImplementedError("Policy on image observations with a MultiBinary action space: the CNN base is built with the "
+                                      "Categorical (Discrete) and Gaussian (Box) heads only")
         if dist != _lib.DIST_GAUSSIAN and base_kwargs.get("recurrent", False):
             raise NotImplementedError(f"Policy on a {space} action space with base_kwargs={{'recurrent': True}}: the GRU base is built "
                                       "with the Gaussian head (Box actions) only")
-        hidden = base_kwargs.get("hidden_size", 64)
-        self._create(obs_shape[0], act_dim, hidden, 1, ctx, critic_hidden=critic_hidden,
-                     recurrent=base_kwargs.get("recurrent", False), dist=dist, n_out=n_out)
+        hidden = base_kwargs.get("hidden_size", 512 if cnn else 64)   # a2c/model.py:205,234
+        if cnn:
+            if critic_hidden not in (None, hidden):
+                raise NotImplementedError("Policy on image observations: critic_linear reads the shared features (a2c/model.py:220-230); "
+                                          "there is no critic trunk to give a width of its own")
+            self._create(int(obs_shape[0]) * CNN_HW * CNN_HW, act_dim, hidden, 1, ctx, dist=dist, n_out=n_out, cnn=int(obs_shape[0]))
+        else:
+            self._create(obs_shape[0], act_dim, hidden, 1, ctx, critic_hidden=critic_hidden,
+                         recurrent=base_kwargs.get("recurrent", False), dist=dist, n_out=n_out)
         self.seed = derive_seed(seed, 0x5EED, per_instance=True)
         self._init_params(np.random.default_rng(seed))
 
     def param_shapes(self):
         O, A, Hh, Hc = self.obs_dim, self.act_dim, self.hidden_size, self.critic_hidden
+        if getattr(self, "cnn", 0):   # a2c/model.py:211-220: main = Conv, ReLU, Conv, ReLU, Conv, ReLU, Flatten, Linear, ReLU
+            head = ([("dist.linear.weight", (self.n_out, Hh)), ("dist.linear.bias", (self.n_out,))] if self.dist_kind else
+                    [("dist.fc_mean.weight", (A, Hh)), ("dist.fc_mean.bias", (A,)), ("dist.logstd._bias", (A, 1))])
+            return [("base.main.0.weight", (32, self.cnn, 8, 8)), ("base.main.0.bias", (32,)),
+                    ("base.main.2.weight", (64, 32, 4, 4)), ("base.main.2.bias", (64,)),
+                    ("base.main.4.weight", (32, 64, 3, 3)), ("base.main.4.bias", (32,)),
+                    ("base.main.7.weight", (Hh, 32 * 7 * 7)), ("base.main.7.bias", (Hh,)),
+                    ("base.critic_linear.weight", (1, Hh)), ("base.critic_linear.bias", (1,))] + head
         if getattr(self, "dist_kind", 0):   # a2c/distributions.py:74-88,157-168: Categorical / Bernoulli hold one Linear, no log-std
             K = self.n_out
             return [("base.actor.0.weight", (Hh, O)), ("base.actor.0.bias", (Hh,)),
@@ -330,6 +367,10 @@ class Policy(_PolicyBase):
                 sd[name] = orthogonal(rng, *shape, gain=1.0) / 50.0
             elif name.startswith("dist.linear"):
                 sd[name] = orthogonal(rng, *shape, gain=0.01 if self.dist_kind == _lib.DIST_CATEGORICAL else 1.0)
+            elif name.startswith("base.main"):   # a2c/model.py:208-215: orthogonal over [out, in * kh * kw], ReLU gain
+                sd[name] = orthogonal(rng, shape[0], int(np.prod(shape[1:])), gain=np.sqrt(2)).reshape(shape)
+            elif name.startswith("base.critic_linear") and getattr(self, "cnn", 0):   # a2c/model.py:217-220: gain 1
+                sd[name] = orthogonal(rng, *shape, gain=1.0)
             else:
                 sd[name] = orthogonal(rng, *shape, gain=np.sqrt(2))
         self.load_state_dict(sd)
@@ -348,6 +389,10 @@ class Policy(_PolicyBase):
         every warm start).  When the actor is not 64 wide the policy is rebuilt on the device with a critic trunk of its own
         width (sg_policy_create2); actor, mean head and log-std keep their values.  Call it BEFORE constructing PPO on this
         policy, as the reference's main does (:85 then :149): an agent built earlier holds the old device handle."""
+        if getattr(self, "cnn", 0):
+            # the reference's call would hang a fresh MLP critic on the CNNBase that its forward never uses (a2c/model.py:80-87,224-230)
+            raise NotImplementedError("reset_critic on a policy with the CNN base: the reference's call leaves a `critic` module that "
+                                      "CNNBase.forward never reads; there is nothing to reset")
         if int(obs_shape[0]) != self.obs_dim:
             raise ValueError(f"reset_critic: obs_shape {tuple(obs_shape)} != the policy's observation size {self.obs_dim}")
         if self._rec() and self.obs_dim != self.hidden_size:

@@ -59,19 +59,22 @@ class RolloutStorage(object):
     def __init__(self, num_steps, num_processes, obs_shape, action_space,
                  recurrent_hidden_state_size, feat_len=0, ctx=None):
         T, N = int(num_steps), int(num_processes)
-        if len(obs_shape) != 1:
+        if len(obs_shape) not in (1, 3):
             raise NotImplementedError("1-D observations only")
+        # image observations (a2c/storage.py:34: obs [T+1, N, *obs_shape]) for the CNN base: the host tensor keeps the reference's
+        # 5-D shape, the device twin holds each image as one row of C*H*W floats
+        self.image_shape = tuple(int(x) for x in obs_shape) if len(obs_shape) == 3 else None
         # a2c/storage.py:42-48: Discrete -> actions [T, N, 1] int64 (the class index; float32 on the device), else [T, N, shape[0]]
         self.discrete = action_space.__class__.__name__ == 'Discrete'
         self.box_actions = action_space.__class__.__name__ == 'Box'
-        O, A, F = int(obs_shape[0]), 1 if self.discrete else int(action_space.shape[0]), int(feat_len)
+        O, A, F = int(np.prod(obs_shape)), 1 if self.discrete else int(action_space.shape[0]), int(feat_len)
         self.ctx = ctx or _lib.Context.default()   # (first: creating the context is what initialises the HIP runtime, with its settings)
         self.lib = self.ctx.lib
         # the host tensors live in page-locked memory (sg_host_alloc): ordinary CPU tensors to whoever slices them, one DMA
         # per field at the link's speed to sg_rollout_upload / _download
         z = lambda *s: to_host_tensor(_lib.pinned_array(s, 0.0))  # noqa: E731
         o = lambda *s: to_host_tensor(_lib.pinned_array(s, 1.0))  # noqa: E731
-        self.obs = z(T + 1, N, O)
+        self.obs = z(T + 1, N, *(self.image_shape or (O,)))
         self.obs_feat = z(T + 1, N, F)
         self.recurrent_hidden_states = z(T + 1, N, recurrent_hidden_state_size)
         self.rewards = z(T, N, 1)
@@ -186,6 +189,9 @@ class RolloutStorage(object):
         sync_from_device() without a field list move the buffer with the fields; after an on-device collection the host tensor
         is stale until sync_from_device(), like value_preds.  Device-resident rollouts only, not mirror-augmented ones."""
         H = int(self.recurrent_hidden_states.shape[-1])
+        if self.__dict__.get("image_shape"):
+            raise NotImplementedError("enable_device_hidden: the rollout holds image observations, which only the feed-forward CNN base "
+                                      "reads: there is no hidden state to keep on the device")
         if not self.device_resident:
             raise ValueError("enable_device_hidden: the rollout is not device-resident (rollouts.device_resident = True): in drop-in "
                              "mode the host tensors are the rollout")
@@ -271,6 +277,9 @@ class RolloutStorage(object):
 
     # ------------------------------------------------- collection on the device (a2c/main_gail_dyn_ppo.py:209-236)
     def _on_device_only(self, who):
+        if self.__dict__.get("image_shape"):
+            raise NotImplementedError(f"{who}: on-device collection is not built for image observations (the CNN base): act through "
+                                      "policy.act and insert()")
         if not self.device_resident:
             raise ValueError(f"{who}: the rollout is not device-resident (rollouts.device_resident = True): in drop-in mode the host "
                              "tensors are the rollout and the next device call would overwrite what the step wrote on the device")
@@ -316,6 +325,9 @@ class RolloutStorage(object):
     def insert_env(self, obs, rewards, masks, bad_masks, obs_feat=None):
         """The environment's half of insert() (a2c/storage.py:70-84) after act_step(): host slots obs[s+1], obs_feat[s+1],
         rewards[s], masks[s+1], bad_masks[s+1]; advances `step`."""
+        if self.__dict__.get("image_shape"):
+            raise NotImplementedError("insert_env: on-device collection is not built for image observations (the CNN base): act "
+                                      "through policy.act and insert()")
         s = self.step
         _put(self.obs[s + 1], obs)
         if obs_feat is not None:
@@ -349,6 +361,9 @@ class RolloutStorage(object):
         applied on the host row by row in both modes, as PPO applies it for the symmetry loss.  Matrices act on rows:
         mirrored = M @ x.  Fill the rollout through set_initial_obs_dup_sym / insert_dup_sym afterwards."""
         from . import symmetry as _sym
+        if self.__dict__.get("image_shape"):
+            raise NotImplementedError("enable_dup_sym: a mirror-augmented rollout mirrors observations through a linear map or a "
+                                      "per-row callable on 1-D rows; image observations (the CNN base) have neither here")
         if not self.__dict__.get("box_actions", True):
             raise NotImplementedError("enable_dup_sym: a mirror-augmented rollout mirrors actions through a linear map, which a class "
                                       "index or a bit vector (Discrete / MultiBinary action space) does not have; Box action spaces only")
@@ -498,6 +513,9 @@ class RolloutStorage(object):
     def recurrent_generator(self, advantages, num_mini_batch, perm=None):
         """a2c/storage.py:194-251 -- host-side generator: whole environments per minibatch, rows time-major, the hidden
         state of slot 0.  `perm` injects the reference's torch.randperm(num_processes) draw; default: numpy's generator."""
+        if self.__dict__.get("image_shape"):
+            raise NotImplementedError("recurrent_generator: image observations are read by the feed-forward CNN base only (a recurrent "
+                                      "CNN base is not built): use feed_forward_generator")
         return recurrent_batches(self, advantages, num_mini_batch, perm)
 
 
@@ -565,6 +583,8 @@ def feed_forward_batches(ro, advantages, num_mini_batch=None, mini_batch_size=No
     def flat(t, sl):
         a = t.numpy() if hasattr(t, "numpy") else t
         a = a[sl]
+        if a.ndim == 5:   # image observations [T, N, C, H, W] -> obs_batch [-1, C, H, W] (a2c/storage.py:165)
+            return a.reshape(-1, *a.shape[2:])
         return a.reshape(-1, a.shape[-1])
 
     cur, nxt, al = slice(None, -1), slice(1, None), slice(None)
