@@ -253,6 +253,34 @@ SG_API int sg_rollout_download_hidden(sg_rollout *r, float *host, int64_t count)
  * sg_policy_act_rnn then). */
 SG_API int sg_rollout_act_step_rnn(sg_rollout *r, sg_policy *p, int t, const float *obs_host, const float *masks_host,
                             const float *noise, uint64_t seed, int deterministic, float *action_host);
+/* The two policies of a hybrid-sim environment step in ONE launch: the policy that lives inside the environment (row i acts
+ * with members[idx[i]], as in sg_policy_act_ensemble) and the learner (as in sg_rollout_act_step), with what the environment
+ * does between them -- squash the first action, concatenate it behind the state -- kept on the device.
+ *   SG_CHAIN_INNER_FIRST (GAIL-dyn stage, my_pybullet_envs/hopper_env_combined_policy.py:298-325,
+ *     laikago_env_combined_policy.py:420-438): the members act on inner_obs_host[N,O_member]; OBS[t] of the device rollout
+ *     becomes cat(state, squash(a_inner)); the learner acts on that row and fills value_preds[t], actions[t] and
+ *     action_log_probs[t].  state_host[N,Os] with Os = O - A_member; NULL: inner_obs_host is the state (O_member == Os).
+ *     obs_host is not read.  t == T is allowed: the members run, OBS[T] is completed, the learner does not act and action_host
+ *     is not written (it may be NULL then).  inner_action_host[N,A_member] gets the SQUASHED member action (what sits in OBS).
+ *   SG_CHAIN_LEARNER_FIRST (refinement stage, hopper...:195-216, laikago...:240-268): the learner acts on OBS[t] (obs_host[N,O]
+ *     is copied into the slot first; NULL: the slot as it is) and fills the slot's three fields; the members act on
+ *     cat(state, squash(action)), state_host[N,Os] with Os = O_member - A; NULL: OBS[t] is the state (Os == O).
+ *     inner_obs_host is not read.  inner_action_host gets the members' RAW action.
+ * squash != 0: tanhf; 0: the action passes as it is.  action_host[N,A]: the learner's raw action.  inner_raw_host[N,A_member]
+ * (optional): the members' raw action in both orders.  noise / seed / deterministic drive the learner's head and inner_noise /
+ * inner_seed / inner_deterministic the members', each exactly as in its stand-alone call, and each half has that call's bits:
+ * the same weight path, the same row tile class (a half whose own launch would run 16-row tiles runs them inside the chain
+ * too), the same head arithmetic and draw indexing.  Per call: one host->device copy (one more for obs_host), ONE launch, one
+ * host wait.  Errors, each with its own message: NULL arguments; an unknown order; a learner or member with the CNN base, a GRU
+ * or a Categorical / Bernoulli head; members of differing shape or on another context; idx outside [0, n_members); dims that do
+ * not add up; t out of range; halves whose stand-alone launches read their weights differently (one from LDS, one from global
+ * memory); a tile of both policies that does not fit a CU's LDS. */
+enum { SG_CHAIN_INNER_FIRST = 0, SG_CHAIN_LEARNER_FIRST = 1 };
+SG_API int sg_rollout_act_step_chain(sg_rollout *r, sg_policy *learner, int t, int order, sg_policy *const *members, int n_members,
+                              const int32_t *idx, const float *inner_obs_host, const float *state_host, const float *obs_host,
+                              const float *inner_noise, uint64_t inner_seed, int inner_deterministic, const float *noise,
+                              uint64_t seed, int deterministic, int squash, float *action_host, float *inner_action_host,
+                              float *inner_raw_host);
 
 /* ---------------------------------------------------------------------- PPO */
 typedef struct {

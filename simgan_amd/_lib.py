@@ -24,6 +24,7 @@ F_OBS, F_OBS_FEAT, F_ACTIONS, F_REWARDS, F_VALUE_PREDS, F_RETURNS, F_LOGP, F_MAS
     F_ADVANTAGES = range(10)
 POLICY_MLP, POLICY_SPLIT, POLICY_GRU = 0, 1, 2
 DIST_GAUSSIAN, DIST_CATEGORICAL, DIST_BERNOULLI = 0, 1, 2
+CHAIN_INNER_FIRST, CHAIN_LEARNER_FIRST = 0, 1   # sg_rollout_act_step_chain: which policy of the environment step acts first
 PROF_DISC_CHAIN, PROF_DISC_WGRAD, PROF_PPO_FWD, PROF_PPO_BWD, PROF_PPO_REDUCE, PROF_RELABEL, PROF_PPO_ADAM = range(7)
 
 
@@ -96,6 +97,9 @@ PROTOTYPES = {
     "sg_rollout_upload_hidden": (C.c_int, [H, c_float_p, C.c_int64]),
     "sg_rollout_download_hidden": (C.c_int, [H, c_float_p, C.c_int64]),
     "sg_rollout_act_step_rnn": (C.c_int, [H, H, C.c_int, c_float_p, c_float_p, c_float_p, C.c_uint64, C.c_int, c_float_p]),
+    "sg_rollout_act_step_chain": (C.c_int, [H, H, C.c_int, C.c_int, C.POINTER(H), C.c_int, C.POINTER(C.c_int32), c_float_p, c_float_p,
+                                            c_float_p, c_float_p, C.c_uint64, C.c_int, c_float_p, C.c_uint64, C.c_int, C.c_int,
+                                            c_float_p, c_float_p, c_float_p]),
     "sg_ppo_set_hidden_states_rollout": (C.c_int, [H, H]),
     "sg_ppo_create": (C.c_int, [H, H, C.POINTER(PPOConfig), C.POINTER(H)]),
     "sg_ppo_destroy": (C.c_int, [H]),
@@ -169,6 +173,7 @@ TEST_PROTOTYPES = {
     "sg_test_raise_kfac_error": (C.c_int, [H]),
     "sg_test_tear_probe": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_ll_p]),
     "sg_test_raise_handoff_error": (C.c_int, [H, H]),
+    "sg_test_squash": (C.c_int, [c_float_p, c_float_p, C.c_int64]),
 }
 _TEST_LIB = None
 

@@ -542,12 +542,6 @@ __global__ __launch_bounds__(256) void k_policy_act_ensemble(EnsArgs a) {
     }
 }
 
-static size_t ens_lds_bytes(const SgPolicyDesc& d, int MT, bool gw = false) {
-    const int R = 16 * MT;
-    return sizeof(float) * (size_t)((gw ? 0 : max_trunk_size(d, 0, d.n_trunks)) + R * d.ldO + 2 * R * d.ldH + d.n_trunks * R * max_ldP(d)) +
-           sizeof(int) * (size_t)(R + 256 + 4);
-}
-
 extern "C" int sg_policy_act_ensemble(sg_policy* const* policies, int n_policies, const int32_t* idx, const float* obs,
                                       int n, const float* noise, uint64_t seed, int deterministic, float* value,
                                       float* action, float* logp) {
@@ -597,10 +591,9 @@ extern "C" int sg_policy_act_ensemble(sg_policy* const* policies, int n_policies
     a.d = d; a.K = n_policies; a.idx = d_idx; a.obs = d_obs; a.n = n; a.mode = deterministic ? 1 : 0;
     a.noise = (noise && !deterministic) ? d_noise : nullptr; a.seed = seed; a.stream = SG_ACT_STREAM + (uint64_t)ctx->rank;
     a.value = d_value; a.action = d_action; a.logp = d_logp;
-    const bool gw = sg_policy_needs_gw(ctx, d) || ens_lds_bytes(d, 1) > (size_t)ctx->lds_bytes - 1024;
+    const bool gw = ens_needs_gw(ctx, d);
     a.wbuf_floats = gw ? 0 : max_trunk_size(d, 0, d.n_trunks); a.ldPmax = max_ldP(d);
-    int MT = 2;   // 32-row tiles unless the pool is small or LDS is short
-    while (MT > 1 && (ens_lds_bytes(d, MT, gw) > (size_t)ctx->lds_bytes - 1024 || 16 * MT * n_policies > 2 * n)) MT /= 2;
+    const int MT = ens_tile_mt(ctx, d, n, n_policies, gw);
     SG_REQUIRE(ens_lds_bytes(d, MT, gw) <= (size_t)ctx->lds_bytes, "sg_policy_act_ensemble: an activation tile does not fit LDS (%zu B)", ens_lds_bytes(d, MT, gw));
     const int R = 16 * MT;
     const dim3 grid((n + R - 1) / R, n_policies);

@@ -50,3 +50,20 @@ static inline int fwd_tile_mt(const sg_ctx* ctx, const SgPolicyDesc& d, int n, b
     while (MT > 1 && (fwd_lds_bytes(d, MT, gw) > (size_t)ctx->lds_bytes - 1024 || 16 * (MT / 2) >= n)) MT /= 2;
     return MT;
 }
+
+// The ensemble launch (k_policy_act_ensemble, sg_policy.hip): its LDS budget, its weight path and its row tile -- 32-row tiles
+// unless the pool is small or LDS is short.  Shared with the chained act (sg_act_chain.hip), whose member half has to fall on
+// the same weight path and the same side of MT == 1.
+static inline size_t ens_lds_bytes(const SgPolicyDesc& d, int MT, bool gw = false) {
+    const int R = 16 * MT;
+    return sizeof(float) * (size_t)((gw ? 0 : max_trunk_size(d, 0, d.n_trunks)) + R * d.ldO + 2 * R * d.ldH + d.n_trunks * R * max_ldP(d)) +
+           sizeof(int) * (size_t)(R + 256 + 4);
+}
+static inline bool ens_needs_gw(const sg_ctx* ctx, const SgPolicyDesc& d) {
+    return sg_policy_needs_gw(ctx, d) || ens_lds_bytes(d, 1) > (size_t)ctx->lds_bytes - 1024;
+}
+static inline int ens_tile_mt(const sg_ctx* ctx, const SgPolicyDesc& d, int n, int n_policies, bool gw) {
+    int MT = 2;
+    while (MT > 1 && (ens_lds_bytes(d, MT, gw) > (size_t)ctx->lds_bytes - 1024 || 16 * MT * n_policies > 2 * n)) MT /= 2;
+    return MT;
+}

@@ -9,6 +9,7 @@
 
 #include <vector>
 
+#include "sg_act_chain.hpp"
 #include "sg_common.h"
 #include "sg_rng.hpp"
 #include "sg_test_api.h"
@@ -589,6 +590,27 @@ extern "C" int sg_test_rng(sg_ctx* ctx, int kind, int64_t n, uint64_t seed, void
         SG_COPY_SYNC(ctx, out, dev, (size_t)n * 4, hipMemcpyDeviceToHost);
     }
     (void)hipFree(dev);
+    return 0;
+}
+
+// Test hook: the chained act's seam function on the device (tests/test_gpu_act_chain.py).
+__global__ void k_test_squash(const float* in, float* out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = sg_squash(in[i], 1);
+}
+
+extern "C" int sg_test_squash(const float* in, float* out, int64_t n) {
+    SG_REQUIRE(in && out && n > 0, "sg_test_squash: bad argument");
+    float* dev = nullptr;
+    SG_CHECK(hipMalloc((void**)&dev, (size_t)n * 8));
+    int rc = 0;
+    if (hipMemcpy(dev, in, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+    if (!rc) {
+        hipLaunchKernelGGL(k_test_squash, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dev, dev + n, n);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(out, dev + n, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
+    }
+    (void)hipFree(dev);
+    SG_REQUIRE(rc == 0, "sg_test_squash: HIP error");
     return 0;
 }
 

@@ -35,6 +35,8 @@ SG_API int sg_test_kfac_eig(sg_ctx *ctx, int n, const float *A, float *Q, float 
 SG_API int sg_test_acktr_noise(sg_ctx *ctx, int64_t n, uint64_t seed, int64_t update, float *out);
 /* raises an ACKTR object's sticky eigensolver error word, as k_kfac_eig does at its sweep cap */
 SG_API int sg_test_raise_kfac_error(sg_ppo *a);
+/* out[i] = the chained act's squash (sg_act_chain.hpp, squash on) of in[i], computed on the device; host pointers */
+SG_API int sg_test_squash(const float *in, float *out, int64_t n);
 #ifdef __cplusplus
 }
 #endif

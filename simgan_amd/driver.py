@@ -177,10 +177,40 @@ class GailDynLearner(object):
             self.discr.set_rms(value.get_state())
 
     # ---------------------------------------------------------------- rollout fill (:209-236)
-    def collect(self, envs, sas_feat_of_infos, on_device=False):
+    def collect(self, envs, sas_feat_of_infos, on_device=False, inner=None, state=None, inner_obs=None, rng=None):
         """on_device=True: every step acts in one launch that fills the policy's half of the rollout slot on the device
-        (RolloutStorage.act_step / insert_env / finish_collect); same draws, same bits, fewer copies."""
+        (RolloutStorage.act_step / insert_env / finish_collect); same draws, same bits, fewer copies.
+        inner=PolicyEnsemble (on_device=True only): the behaviour policy is taken out of the environments
+        (my_pybullet_envs/hopper_env_combined_policy.py:298-325, laikago_env_combined_policy.py:420-438) and acts in the same
+        launch as the learner (RolloutStorage.act_step_chain, INNER_FIRST).  The pool then hands out states, not observations:
+        envs.step(action, inner_action) -> (state | (state, inner_obs), reward, done, infos), where inner_action is the squashed
+        behaviour action that sat in the observation the learner just acted on; the rollout's obs[s] = cat(state, inner_action) is
+        made on the device.  state / inner_obs: the state after envs.reset(), needed by the FIRST collection only (later ones start
+        on the observation that finish_collect_chain completed); rng draws the members per step (PolicyEnsemble.act's default)."""
         ro, pol = self.rollouts, self.actor_critic
+        if inner is not None:
+            if not on_device:
+                raise ValueError("GailDynLearner.collect(inner=...): the chained step is the on-device collection (on_device=True)")
+            _check_on_device(ro, pol, False, "GailDynLearner.collect")
+            if state is not None or inner_obs is not None:
+                self._chain_state, self._chain_inner_action = (state, inner_obs), None
+            for step in range(ro.num_steps):
+                if ro.chain_slot_complete and self.__dict__.get("_chain_inner_action") is not None:
+                    action, inner_action = ro.act_step(pol), self._chain_inner_action   # (its draw was taken when the slot was made)
+                else:
+                    if self.__dict__.get("_chain_state") is None:
+                        raise ValueError("GailDynLearner.collect(inner=...): the first collection needs state= (and inner_obs= where "
+                                         "the two differ): the environments' state after reset")
+                    action, inner_action, _ = ro.act_step_chain(pol, inner, _lib.CHAIN_INNER_FIRST, state=self._chain_state[0],
+                                                                inner_obs=self._chain_state[1], rng=rng)
+                out, reward, done, infos = envs.step(action, inner_action)
+                self._chain_state = tuple(out) if isinstance(out, (tuple, list)) else (out, None)
+                masks, bad = step_masks(done, infos)
+                ro.insert_env_rest(reward, to_host_tensor(masks), to_host_tensor(bad),
+                                   to_host_tensor(np.asarray(sas_feat_of_infos(infos), np.float32)))
+            self._chain_inner_action, _ = ro.finish_collect_chain(inner, state=self._chain_state[0], inner_obs=self._chain_state[1],
+                                                                  policy=pol, rng=rng)
+            return None
         if on_device:
             _check_on_device(ro, pol, False, "GailDynLearner.collect")
             for step in range(ro.num_steps):
@@ -316,9 +346,30 @@ class PpoLearner(object):
         return actor_critic
 
     # ---------------------------------------------------------------- rollout fill (:207-244)
-    def collect(self, envs, feat_select_func=None, on_device=False):
-        """on_device=True: as GailDynLearner.collect(on_device=True); not for a mirror-augmented (dup_sym) learner."""
+    def collect(self, envs, feat_select_func=None, on_device=False, inner=None, state=None, rng=None):
+        """on_device=True: as GailDynLearner.collect(on_device=True); not for a mirror-augmented (dup_sym) learner.
+        inner=PolicyEnsemble (on_device=True only): the saved dynamics policies are taken out of the environments
+        (my_pybullet_envs/hopper_env_combined_policy.py:195-216, laikago_env_combined_policy.py:240-268) and act in the learner's
+        launch (RolloutStorage.act_step_chain, LEARNER_FIRST) on cat(state, tanh(action)), one member drawn per row and step
+        from rng.  envs.step(action, env_action) -> (obs | (obs, state), reward, done, infos): env_action is the members' raw
+        action, which the environment steps with; where the members' state is not the observation the pool returns it beside
+        the observation, and state= gives the one after envs.reset() for the first step."""
         ro, pol = self.rollouts, self.actor_critic
+        if inner is not None:
+            if not on_device:
+                raise ValueError("PpoLearner.collect(inner=...): the chained step is the on-device collection (on_device=True)")
+            _check_on_device(ro, pol, self.dup_sym, "PpoLearner.collect")
+            if state is not None:
+                self._chain_state = state
+            for step in range(ro.num_steps):
+                action, env_action, _ = ro.act_step_chain(pol, inner, _lib.CHAIN_LEARNER_FIRST, state=self.__dict__.get("_chain_state"),
+                                                          rng=rng)
+                out, reward, done, infos = envs.step(action, env_action)
+                obs, self._chain_state = tuple(out) if isinstance(out, (tuple, list)) else (out, None)
+                feat = obs if feat_select_func is None else feat_select_func(obs)
+                masks, bad = step_masks(done, infos)
+                ro.insert_env(obs, reward, to_host_tensor(masks), to_host_tensor(bad), feat)
+            return ro.finish_collect()
         if on_device:
             _check_on_device(ro, pol, self.dup_sym, "PpoLearner.collect")
             for step in range(ro.num_steps):

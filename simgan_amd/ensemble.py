@@ -5,7 +5,8 @@ The hybrid-sim environments call a batch-1 `actor_critic.act` in every worker ev
 five saved dynamics policies picked at random per step (`np_random.choice`, hopper...:113-140,211-216).  With the
 pool's observations gathered into one [N, O] array per step the same work is ONE device launch
 (`sg_policy_act_ensemble`, csrc/sg_policy.hip): row i runs through the resident weights of policy ind[i].
-Environment stepping itself stays on the host (out of scope)."""
+Environment stepping itself stays on the host (out of scope).  On a device-resident rollout the same members can act in the
+learner's own launch (`RolloutStorage.act_step_chain`, csrc/sg_act_chain.hip), same draws and same bits."""
 import ctypes as C
 import os
 

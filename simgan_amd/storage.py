@@ -353,6 +353,155 @@ class RolloutStorage(object):
             _lib.check(self.lib.sg_rollout_upload_step(self.h, f, T, _lib.fptr(a), a.size))
             self.bytes_uploaded += a.nbytes
 
+    # ------------------------------------------------- chained act: in-environment policy and learner in one launch
+    # (my_pybullet_envs/hopper_env_combined_policy.py:195-216,298-325, laikago_env_combined_policy.py:240-268,420-438)
+    @property
+    def chain_slot_complete(self):
+        """True when the observation of slot `step` is already complete on the device and in the host mirror -- slot 0 after
+        finish_collect_chain() and after_update(), which rolled the completed OBS[T] over.  Such a slot takes plain act_step():
+        the in-environment policy has acted on that state already and its draw must not be taken twice."""
+        return self.__dict__.get("_chain_complete") == self.step
+
+    def _chain_inner(self, who, policy, ensemble, inner_first, inner_obs, state, ind, rng, inner_noise):
+        """The checked inputs of one chained call: (inner_obs | None, state | None, ind, inner noise | None, state width)."""
+        N, K = self.num_processes, len(ensemble)
+        if getattr(policy, "cnn", 0) or getattr(policy, "is_recurrent", False) or getattr(policy, "dist_kind", 0):
+            raise ValueError(f"{who}: the chained step takes a feed-forward learner with the MLP base and a Gaussian head (Policy / "
+                             "SplitPolicy on a Box action space); a CNN base, a GRU or a Discrete / MultiBinary head acts through "
+                             "PolicyEnsemble.act and act_step")
+        if policy.obs_dim != self.obs_dim or policy.act_dim != self.act_dim:
+            raise ValueError(f"{who}: learner/rollout dims differ (obs {policy.obs_dim} vs {self.obs_dim}, action {policy.act_dim} vs "
+                             f"{self.act_dim})")
+        Oi, Ai = ensemble.obs_dim, ensemble.act_dim
+        Os = self.obs_dim - Ai if inner_first else Oi - self.act_dim
+        if Os <= 0:
+            raise ValueError(f"{who}: dims do not add up: " + (f"the learner's observation ({self.obs_dim}) must be state + member action ({Ai})"
+                             if inner_first else f"the members' observation ({Oi}) must be state + learner action ({self.act_dim})"))
+        if inner_first:
+            if inner_obs is None and state is not None:
+                inner_obs, state = state, None          # the state is what the members act on
+            if inner_obs is None:
+                raise ValueError(f"{who}: INNER_FIRST needs inner_obs [N, {Oi}] (or state, where the members act on the state itself)")
+            inner_obs = _lib.as_f32(inner_obs).reshape(-1, Oi)
+            if inner_obs.shape[0] != N:
+                raise ValueError(f"{who}: inner_obs holds {inner_obs.shape[0]} rows, the rollout {N} environments")
+            if state is None and Oi != Os:
+                raise ValueError(f"{who}: dims do not add up: without state the members' observation ({Oi}) is the state, and state + "
+                                 f"member action ({Ai}) must be the learner's observation ({self.obs_dim})")
+        else:
+            if inner_obs is not None:
+                raise ValueError(f"{who}: LEARNER_FIRST builds the members' observation itself (cat(state, squash(action))); inner_obs is "
+                                 "not taken")
+            if state is None and Os != self.obs_dim:
+                raise ValueError(f"{who}: dims do not add up: without state the rollout's observation ({self.obs_dim}) is the state, and "
+                                 f"state + learner action ({self.act_dim}) must be the members' observation ({Oi})")
+        if state is not None:
+            state = _lib.as_f32(state).reshape(-1)
+            if state.size != N * Os:
+                raise ValueError(f"{who}: state holds {state.size} floats, not [N, Os] = [{N}, {Os}]")
+            state = state.reshape(N, Os)
+        if ind is None:
+            ind = (rng or np.random.default_rng()).integers(0, K, size=N)
+        ind = np.ascontiguousarray(ind, np.int32).reshape(-1)
+        if ind.shape != (N,) or ind.min() < 0 or ind.max() >= K:
+            raise ValueError(f"{who}: ind must hold N = {N} member numbers in [0, {K})")
+        inz = None if inner_noise is None else _lib.as_f32(inner_noise).reshape(N, Ai)
+        return inner_obs, state, ind, inz, Os
+
+    def _chain_call(self, policy, ensemble, t, order, ind, inner_obs, state, obs, inz, inner_deterministic, nz, deterministic, squash,
+                    action, inner_action, inner_raw=None):
+        p = lambda a: None if a is None else _lib.fptr(a)  # noqa: E731
+        _lib.check(self.lib.sg_rollout_act_step_chain(
+            self.h, policy.h, t, order, ensemble._handles, len(ensemble), ind.ctypes.data_as(C.POINTER(C.c_int32)),
+            p(inner_obs), p(state), p(obs), p(inz), (ensemble.seed + ensemble._calls) & (2 ** 64 - 1), 1 if inner_deterministic else 0,
+            p(nz), (policy.seed + policy._act_calls) & (2 ** 64 - 1), 1 if deterministic else 0, 1 if squash else 0,
+            p(action), p(inner_action), p(inner_raw)))
+        self.bytes_uploaded += ind.nbytes + sum(a.nbytes for a in (inner_obs, state, obs) if a is not None)
+
+    def act_step_chain(self, policy, ensemble, order, inner_obs=None, state=None, ind=None, rng=None, noise=None, inner_noise=None,
+                       deterministic=False, inner_deterministic=False, squash=True, inner_raw_out=None):
+        """ensemble.act and act_step(policy) on slot `step` as ONE launch, with the environment's seam between them -- tanh on the
+        first action (squash=False: none), concatenated behind the state -- kept on the device.  Returns (action [N, A], the
+        learner's raw action as act_step returns it; inner_action; ind [N], the member each row used, drawn like
+        PolicyEnsemble.act draws it when not given).
+          order = _lib.CHAIN_INNER_FIRST (GAIL-dyn stage): the members act on inner_obs [N, O_member]; obs[step] becomes
+            cat(state, squash(a_inner)) on the device AND in the host mirror; the learner acts on it.  state [N, O - A_member];
+            None: inner_obs is the state.  inner_action is the squashed member action, the one inside obs[step].
+          order = _lib.CHAIN_LEARNER_FIRST (refinement stage): the learner acts on host slot obs[step] (uploaded, as in act_step);
+            the members act on cat(state, squash(action)); state None: obs[step] is the state.  inner_action is the members' raw
+            action, what the environment steps with.
+        policy._act_calls and ensemble._calls advance, and the draws are taken, exactly as by the two separate calls: either
+        path gives the same bits.  The learner's half fills value_preds[step], actions[step], action_log_probs[step] on the
+        device and the host mirror of actions, like act_step.  bytes_uploaded counts ind and the arrays that went up.
+        inner_raw_out (optional, a contiguous float32 [N, A_member] array): receives the members' raw action in either order."""
+        self._on_device_only("act_step_chain")
+        if order not in (_lib.CHAIN_INNER_FIRST, _lib.CHAIN_LEARNER_FIRST):
+            raise ValueError(f"act_step_chain: unknown order {order!r} (_lib.CHAIN_INNER_FIRST / _lib.CHAIN_LEARNER_FIRST)")
+        inner_first = order == _lib.CHAIN_INNER_FIRST
+        s, N = self.step, self.num_processes
+        if inner_first and self.chain_slot_complete:
+            raise ValueError(f"act_step_chain: the observation of slot {s} is already complete (finish_collect_chain made it and "
+                             "after_update rolled it over): the in-environment policy has acted on that state; take act_step()")
+        inner_obs, state, ind, inz, Os = self._chain_inner("act_step_chain", policy, ensemble, inner_first, inner_obs, state, ind, rng,
+                                                           inner_noise)
+        nz = None if noise is None else _lib.as_f32(noise).reshape(N, self.act_dim)
+        if inner_raw_out is not None and (not isinstance(inner_raw_out, np.ndarray) or inner_raw_out.shape != (N, ensemble.act_dim)):
+            raise ValueError(f"act_step_chain: inner_raw_out must be a float32 numpy array of shape [{N}, {ensemble.act_dim}]")
+        obs = None if inner_first else self._host_np(_lib.F_OBS)[s]
+        action = np.empty((N, self.act_dim), np.float32)
+        inner_action = np.empty((N, ensemble.act_dim), np.float32)
+        policy._act_calls += 1
+        ensemble._calls += 1
+        self._chain_call(policy, ensemble, s, order, ind, inner_obs, state, obs, inz, inner_deterministic, nz, deterministic, squash,
+                         action, inner_action, inner_raw_out)
+        self.__dict__["_chain_policy"] = weakref.ref(policy)
+        if inner_first:
+            _put(self.obs[s], np.concatenate([inner_obs if state is None else state, inner_action], axis=1))
+        _put(self.actions[s], action)
+        return to_host_tensor(action), to_host_tensor(inner_action), ind
+
+    def insert_env_rest(self, rewards, masks, bad_masks, obs_feat=None):
+        """The environment's half of insert() (a2c/storage.py:70-84) in an INNER_FIRST collection, where the next observation is
+        not known until the next chained call makes it: host slots obs_feat[s+1], rewards[s], masks[s+1], bad_masks[s+1];
+        advances `step`."""
+        if self.__dict__.get("image_shape"):
+            raise NotImplementedError("insert_env_rest: on-device collection is not built for image observations (the CNN base)")
+        s = self.step
+        if obs_feat is not None:
+            _put(self.obs_feat[s + 1], obs_feat)
+        _put(self.rewards[s], rewards)
+        _put(self.masks[s + 1], masks)
+        _put(self.bad_masks[s + 1], bad_masks)
+        self.step = (self.step + 1) % self.num_steps
+        self._host_written = True
+        self.__dict__["_chain_complete"] = None
+
+    def finish_collect_chain(self, ensemble, inner_obs=None, state=None, policy=None, ind=None, rng=None, inner_noise=None,
+                             inner_deterministic=False, squash=True):
+        """End of an INNER_FIRST collection: the members act on the state the last environment step left (one chained call at
+        t == T, the learner does not act) and obs[T] = cat(state, squash(a_inner)) is completed on the device and in the host
+        mirror; then what finish_collect() does.  Returns (inner_action, ind): the learner keeps the inner action for the next
+        envs.step, since slot 0 of the next collection -- obs[T] rolled over by after_update() -- takes plain act_step().
+        policy: the learner (default: the one the last act_step_chain served)."""
+        self._on_device_only("finish_collect_chain")
+        if policy is None:
+            ref = self.__dict__.get("_chain_policy")
+            policy = ref() if ref is not None else None
+            if policy is None:
+                raise ValueError("finish_collect_chain: no act_step_chain call has served this rollout yet; pass policy=")
+        T, N = self.num_steps, self.num_processes
+        inner_obs, state, ind, inz, Os = self._chain_inner("finish_collect_chain", policy, ensemble, True, inner_obs, state, ind, rng,
+                                                           inner_noise)
+        inner_action = np.empty((N, ensemble.act_dim), np.float32)
+        ensemble._calls += 1
+        self._chain_call(policy, ensemble, T, _lib.CHAIN_INNER_FIRST, ind, inner_obs, state, None, inz, inner_deterministic, None, False,
+                         squash, None, inner_action)
+        _put(self.obs[T], np.concatenate([inner_obs if state is None else state, inner_action], axis=1))
+        self._host_written = True
+        self.finish_collect()
+        self.__dict__["_chain_complete"] = T
+        return to_host_tensor(inner_action), ind
+
     # ------------------------------------------------- mirror-augmented rollouts (a2c/main.py:171-245, --dup-sym)
     def enable_dup_sym(self, mirror_obs, mirror_act):
         """The rollout's N = 2n columns are n environments and their n mirror images: column n + j mirrors column j.
@@ -482,6 +631,8 @@ class RolloutStorage(object):
 
     def after_update(self):
         """a2c/storage.py:96-101"""
+        # a slot T completed by finish_collect_chain() becomes the complete slot 0 of the next collection
+        self.__dict__["_chain_complete"] = 0 if self.__dict__.get("_chain_complete") == self.num_steps else None
         if self.device_resident:   # the device copy is the rollout; the host mirrors are refreshed by sync_from_device()
             _lib.check(self.lib.sg_rollout_after_update(self.h))
             if not self._host_written:
