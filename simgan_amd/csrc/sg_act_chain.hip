@@ -26,7 +26,7 @@
 //   SG_CHAIN_INNER_FIRST    member on inner_obs -> OBS[t] = cat(state, squash(a_inner)), also left in LDS -> learner on it
 //   SG_CHAIN_LEARNER_FIRST  learner on OBS[t] -> cat(state or OBS[t], squash(action)) in LDS -> member on it
 // Each half keeps the bits of its stand-alone launch: the trunk weights staged per trunk in the same LDS region in turn (or
-// read from global memory: GW), the head expressions of k_gauss_head, and the row tile CLASS of that launch -- a half whose
+// read from global memory: GW -- run_trunks), the one head function (gauss_head_row), and the row tile CLASS of that launch -- a half whose
 // launch would run 16-row tiles (fwd_tile_mt: two interleaved accumulators per dot product) runs its trunks 16 rows at a
 // time here too (dual_*), whatever the tile of the chain.
 struct ActChainArgs {
@@ -48,61 +48,6 @@ struct ActChainArgs {
     int wbuf_floats, ldH, out_floats, ldPmax_l, ldPmax_i;
 };
 
-template <int MT, bool GW>
-__device__ __forceinline__ void chain_trunks(const SgPolicyDesc& d, const float* params, bool dual, float* smem, const float* X,
-                                             float* H1, float* H2, float* OUT, int ldPmax) {
-    constexpr int R = 16 * MT;
-    for (int t = 0; t < d.n_trunks; ++t) {
-        const SgTrunk tr = d.trunk[t];
-        __syncthreads();
-        if (!GW) sg_stage(smem, params + tr.off, tr.size / 4);
-        __syncthreads();
-        const float* W = GW ? params + tr.off : smem;
-        float* out = OUT + t * R * ldPmax;
-        if (MT == 1 || !dual) trunk_forward<MT, GW>(d, tr, W, X, H1, H2, out, tr.ldP);
-        else
-            for (int s = 0; s < MT; ++s)
-                trunk_forward<1, GW>(d, tr, W, X + s * 16 * d.ldO, H1 + s * 16 * tr.ldH, H2 + s * 16 * tr.ldH, out + s * 16 * tr.ldP, tr.ldP);
-    }
-    __syncthreads();
-}
-
-// k_gauss_head's arithmetic for local row lr (original row `row`) on the head outputs in LDS; emit(k, act) takes the actions
-template <typename F>
-__device__ __forceinline__ void chain_head(const SgPolicyDesc& d, const float* params, const float* OUT, int R, int ldPmax, int lr,
-                                           int row, int mode, const float* noise, uint64_t seed, uint64_t stream, float* value,
-                                           float* logp_out, F&& emit) {
-    const float* h0 = OUT + lr * d.trunk[0].ldP;
-    const float* h1 = OUT + R * ldPmax + lr * d.trunk[1].ldP;
-    const float* hc = OUT + (d.n_trunks - 1) * R * ldPmax + lr * d.trunk[d.n_trunks - 1].ldP;
-    if (value) value[row] = hc[0];
-    float logp = 0.f;
-    for (int k = 0; k < d.A; ++k) {
-        float mean, ls;
-        if (d.kind == SG_POLICY_MLP) {
-            mean = h0[k];
-            ls = params[d.trunk[0].off + d.trunk[0].ex + k];
-        } else if (k < d.nc) {
-            mean = h0[k];
-            ls = h0[d.nc + k];
-        } else {
-            mean = h1[k - d.nc];
-            ls = h1[d.na + k - d.nc];
-        }
-        const float sigma = expf(ls);
-        float act;
-        if (mode == 1) act = mean;
-        else {
-            const float z = noise ? noise[(size_t)row * d.A + k] : sg_normal(seed, stream, (uint64_t)row * d.A + k);
-            act = z * sigma + mean;
-        }
-        emit(k, act);
-        const float diff = act - mean, var = sigma * sigma;
-        logp += -(diff * diff) / (2.0f * var) - logf(sigma) - HALF_LOG_2PI;
-    }
-    if (logp_out) logp_out[row] = logp;
-}
-
 template <int MT, bool GW = false>
 __global__ __launch_bounds__(256) void k_policy_act_chain(ActChainArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -122,73 +67,60 @@ __global__ __launch_bounds__(256) void k_policy_act_chain(ActChainArgs a) {
     __syncthreads();
     const float* ip = a.iparams[k];
     const int Os = a.Os;
+    auto tile_row = [&](int r) { return rows[r]; };
+    // The heads of a half that has just run its trunks, thread tid on local row tid (original row `row`); emit(j, act) takes the
+    // actions.  The learner's also fills the rollout's value and log-prob.
+    const int row = tid < R ? rows[tid] : -1;
+    auto member_heads = [&](auto&& emit) {
+        if (row < 0) return;
+        gauss_head_row(di, ip, OUT + tid * di.trunk[0].ldP, OUT + R * a.ldPmax_i + tid * di.trunk[1].ldP, row, a.imode, a.inoise, nullptr,
+                       a.iseed, a.stream, emit);
+    };
+    auto learner_heads = [&](auto&& emit) {
+        if (row < 0) return;
+        const float* hc = OUT + (dl.n_trunks - 1) * R * a.ldPmax_l + tid * dl.trunk[dl.n_trunks - 1].ldP;
+        a.value[row] = hc[0];
+        a.logp[row] = gauss_head_row(dl, a.lparams, OUT + tid * dl.trunk[0].ldP, OUT + R * a.ldPmax_l + tid * dl.trunk[1].ldP, row, a.lmode,
+                                     a.lnoise, nullptr, a.lseed, a.stream, emit);
+    };
     if (a.order == SG_CHAIN_INNER_FIRST) {
-        for (int i = tid; i < R * di.Op; i += blockDim.x) {
-            const int r = i / di.Op, c = i - r * di.Op;
-            const int row = rows[r];
-            XI[r * di.ldO + c] = (row >= 0 && c < di.O) ? a.inner_obs[(size_t)row * di.O + c] : 0.f;
-        }
+        stage_rows(XI, R, di.Op, di.ldO, a.inner_obs, di.O, tile_row);
         // the state part of the seam row: into the learner's LDS tile and into OBS[t]; the action part comes from the head
         const float* st = a.state ? a.state : a.inner_obs;
-        for (int i = tid; i < R * dl.Op; i += blockDim.x) {
-            const int r = i / dl.Op, c = i - r * dl.Op;
-            const int row = rows[r];
-            float v = 0.f;
-            if (row >= 0 && c < Os) {
-                v = st[(size_t)row * Os + c];
-                a.obs[(size_t)row * dl.O + c] = v;
-            }
-            XL[r * dl.ldO + c] = v;
-        }
-        chain_trunks<MT, GW>(di, ip, a.dual_i != 0, smem, XI, H1, H2, OUT, a.ldPmax_i);
-        if (tid < R && rows[tid] >= 0) {
-            const int row = rows[tid];
-            chain_head(di, ip, OUT, R, a.ldPmax_i, tid, row, a.imode, a.inoise, a.iseed, a.stream, nullptr, nullptr, [&](int j, float act) {
-                const float sq = sg_squash(act, a.squash);
-                XL[tid * dl.ldO + Os + j] = sq;
-                a.obs[(size_t)row * dl.O + Os + j] = sq;
-                a.inner_action_host[(size_t)row * di.A + j] = sq;
-                if (a.inner_raw_host) a.inner_raw_host[(size_t)row * di.A + j] = act;
-            });
-        }
+        stage_rows(XL, R, dl.Op, dl.ldO, Os, tile_row, [&](int64_t src, int c) {
+            const float v = st[(size_t)src * Os + c];
+            a.obs[(size_t)src * dl.O + c] = v;
+            return v;
+        });
+        run_trunks<MT, GW>(di, ip, a.dual_i != 0, smem, XI, H1, H2, OUT, a.ldPmax_i);
+        member_heads([&](int j, float act) {
+            const float sq = sg_squash(act, a.squash);
+            XL[tid * dl.ldO + Os + j] = sq;
+            a.obs[(size_t)row * dl.O + Os + j] = sq;
+            a.inner_action_host[(size_t)row * di.A + j] = sq;
+            if (a.inner_raw_host) a.inner_raw_host[(size_t)row * di.A + j] = act;
+        });
         if (!a.run_learner) return;
-        chain_trunks<MT, GW>(dl, a.lparams, a.dual_l != 0, smem, XL, H1, H2, OUT, a.ldPmax_l);
-        if (tid < R && rows[tid] >= 0) {
-            const int row = rows[tid];
-            chain_head(dl, a.lparams, OUT, R, a.ldPmax_l, tid, row, a.lmode, a.lnoise, a.lseed, a.stream, a.value, a.logp, [&](int j, float act) {
-                a.action[(size_t)row * dl.A + j] = act;
-                a.action_host[(size_t)row * dl.A + j] = act;
-            });
-        }
+        run_trunks<MT, GW>(dl, a.lparams, a.dual_l != 0, smem, XL, H1, H2, OUT, a.ldPmax_l);
+        learner_heads([&](int j, float act) {
+            a.action[(size_t)row * dl.A + j] = act;
+            a.action_host[(size_t)row * dl.A + j] = act;
+        });
     } else {
-        for (int i = tid; i < R * dl.Op; i += blockDim.x) {
-            const int r = i / dl.Op, c = i - r * dl.Op;
-            const int row = rows[r];
-            XL[r * dl.ldO + c] = (row >= 0 && c < dl.O) ? a.obs[(size_t)row * dl.O + c] : 0.f;
-        }
+        stage_rows(XL, R, dl.Op, dl.ldO, a.obs, dl.O, tile_row);
         const float* st = a.state ? a.state : a.obs;   // (state NULL: Os == dl.O)
-        for (int i = tid; i < R * di.Op; i += blockDim.x) {
-            const int r = i / di.Op, c = i - r * di.Op;
-            const int row = rows[r];
-            XI[r * di.ldO + c] = (row >= 0 && c < Os) ? st[(size_t)row * Os + c] : 0.f;
-        }
-        chain_trunks<MT, GW>(dl, a.lparams, a.dual_l != 0, smem, XL, H1, H2, OUT, a.ldPmax_l);
-        if (tid < R && rows[tid] >= 0) {
-            const int row = rows[tid];
-            chain_head(dl, a.lparams, OUT, R, a.ldPmax_l, tid, row, a.lmode, a.lnoise, a.lseed, a.stream, a.value, a.logp, [&](int j, float act) {
-                a.action[(size_t)row * dl.A + j] = act;
-                a.action_host[(size_t)row * dl.A + j] = act;
-                XI[tid * di.ldO + Os + j] = sg_squash(act, a.squash);
-            });
-        }
-        chain_trunks<MT, GW>(di, ip, a.dual_i != 0, smem, XI, H1, H2, OUT, a.ldPmax_i);
-        if (tid < R && rows[tid] >= 0) {
-            const int row = rows[tid];
-            chain_head(di, ip, OUT, R, a.ldPmax_i, tid, row, a.imode, a.inoise, a.iseed, a.stream, nullptr, nullptr, [&](int j, float act) {
-                a.inner_action_host[(size_t)row * di.A + j] = act;
-                if (a.inner_raw_host) a.inner_raw_host[(size_t)row * di.A + j] = act;
-            });
-        }
+        stage_rows(XI, R, di.Op, di.ldO, st, Os, tile_row);
+        run_trunks<MT, GW>(dl, a.lparams, a.dual_l != 0, smem, XL, H1, H2, OUT, a.ldPmax_l);
+        learner_heads([&](int j, float act) {
+            a.action[(size_t)row * dl.A + j] = act;
+            a.action_host[(size_t)row * dl.A + j] = act;
+            XI[tid * di.ldO + Os + j] = sg_squash(act, a.squash);
+        });
+        run_trunks<MT, GW>(di, ip, a.dual_i != 0, smem, XI, H1, H2, OUT, a.ldPmax_i);
+        member_heads([&](int j, float act) {
+            a.inner_action_host[(size_t)row * di.A + j] = act;
+            if (a.inner_raw_host) a.inner_raw_host[(size_t)row * di.A + j] = act;
+        });
     }
 }
 
@@ -226,24 +158,10 @@ extern "C" int sg_rollout_act_step_chain(sg_rollout* r, sg_policy* learner, int 
     SG_REQUIRE(members[0], "sg_rollout_act_step_chain: member 0 is NULL");
     const SgPolicyDesc& dl = learner->desc;
     const SgPolicyDesc& di = members[0]->desc;
-    ActChainArgs a;
-    for (int k = 0; k < n_members; ++k) {
-        SG_REQUIRE(members[k] && members[k]->ctx == ctx, "sg_rollout_act_step_chain: member %d is NULL or lives on another context", k);
-        SG_REQUIRE(!members[k]->cnn, "sg_rollout_act_step_chain: member %d has the CNN base (image observations); the chained step runs the "
-                   "MLP trunks only", k);
-        SG_REQUIRE(!members[k]->recurrent, "sg_rollout_act_step_chain: member %d is a recurrent policy; the chained step carries no hidden "
-                   "state (feed-forward policies only)", k);
-        const SgPolicyDesc& e = members[k]->desc;
-        SG_REQUIRE(e.dist == SG_DIST_GAUSSIAN, "sg_rollout_act_step_chain: member %d has a Categorical / Bernoulli head; the chained step "
-                   "carries the Gaussian head only (Box action spaces)", k);
-        SG_REQUIRE(e.kind == di.kind && e.O == di.O && e.A == di.A && e.H == di.H && e.Hc == di.Hc && e.num_feet == di.num_feet,
-                   "sg_rollout_act_step_chain: member %d has a different shape", k);
-        a.iparams[k] = members[k]->d_params;
-    }
-    for (int k = n_members; k < SG_ENSEMBLE_MAX; ++k) a.iparams[k] = nullptr;
     const int n = r->N, O = r->O, A = r->A, Oi = di.O, Ai = di.A;
-    for (int i = 0; i < n; ++i)
-        SG_REQUIRE(idx[i] >= 0 && idx[i] < n_members, "sg_rollout_act_step_chain: idx[%d] = %d outside [0, %d)", i, idx[i], n_members);
+    SG_TRY(ens_check_members("sg_rollout_act_step_chain", "the chained step", ctx, members, n_members, idx, n));
+    ActChainArgs a;
+    for (int k = 0; k < SG_ENSEMBLE_MAX; ++k) a.iparams[k] = k < n_members ? members[k]->d_params : nullptr;
     SG_REQUIRE(dl.O == O && dl.A == A, "sg_rollout_act_step_chain: learner/rollout dims differ (obs %d vs %d, action %d vs %d)", dl.O, O,
                dl.A, A);
     int Os;
@@ -294,15 +212,7 @@ extern "C" int sg_rollout_act_step_chain(sg_rollout* r, sg_policy* learner, int 
     SG_CHECK(hipSetDevice(ctx->device));
     void* h_blk = nullptr;
     SG_TRY(sg_ctx_pinned(ctx, 4 * (up_words + out_words), &h_blk));
-    if (4 * up_words > learner->io_bytes) {
-        const size_t need = 4 * up_words;
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (learner->d_io) SG_CHECK(sg_dev_free(learner->d_io));
-        learner->d_io = nullptr;
-        learner->io_bytes = 0;
-        SG_CHECK(sg_dev_malloc((void**)&learner->d_io, need + need / 2));
-        learner->io_bytes = need + need / 2;
-    }
+    SG_TRY(sg_policy_io_reserve(learner, 4 * up_words));
     int* h_tiles = static_cast<int*>(h_blk);
     for (size_t i = 0; i < tile_ints; ++i) h_tiles[i] = -1;
     {
@@ -341,11 +251,9 @@ extern "C" int sg_rollout_act_step_chain(sg_rollout* r, sg_policy* learner, int 
     a.ldPmax_l = max_ldP(dl); a.ldPmax_i = max_ldP(di);
     const dim3 grid(n_tiles);
     const size_t lds = chain_lds_bytes(dl, di, MT, gw);
-    if (gw) {
-        if (MT == 2) hipLaunchKernelGGL((k_policy_act_chain<2, true>), grid, dim3(256), lds, ctx->stream, a);
-        else hipLaunchKernelGGL((k_policy_act_chain<1, true>), grid, dim3(256), lds, ctx->stream, a);
-    } else if (MT == 2) hipLaunchKernelGGL(k_policy_act_chain<2>, grid, dim3(256), lds, ctx->stream, a);
-    else hipLaunchKernelGGL(k_policy_act_chain<1>, grid, dim3(256), lds, ctx->stream, a);
+    sg_dispatch_mt_gw<2>(MT, gw, [&](auto mt, auto g) {
+        hipLaunchKernelGGL((k_policy_act_chain<decltype(mt)::value, decltype(g)::value>), grid, dim3(256), lds, ctx->stream, a);
+    });
     SG_CHECK(hipGetLastError());
     SG_CHECK(hipStreamSynchronize(ctx->stream));
     if (run_learner) memcpy(action_host, h_out, sizeof(float) * f_na);

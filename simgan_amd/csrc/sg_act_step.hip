@@ -14,8 +14,8 @@
 // a2c/model_split.py:70-82) on the N rows of rollout slot t, its results written where rollouts.insert (a2c/storage.py:70-84)
 // puts them -- value_preds[t], actions[t], action_log_probs[t] of the DEVICE rollout -- and the actions once more into
 // page-locked host memory for the environments.  ONE launch: workgroup `tile` runs every trunk on its 16*MT rows (weights staged
-// per trunk, or read from global memory: GW) and then the Gaussian head, one thread per row, in k_gauss_head's arithmetic.
-// The bits are those of sg_policy_act: same row tile class (fwd_tile_mt), same weight path, same head expression, the library's
+// per trunk, or read from global memory: GW -- run_trunks) and then the Gaussian head, one thread per row (gauss_head_row).
+// The bits are those of sg_policy_act: same row tile class (fwd_tile_mt), same weight path, the same head function, the library's
 // draws indexed by row * A + j on stream SG_ACT_STREAM + rank.
 struct ActStepArgs {
     SgPolicyDesc d;
@@ -40,53 +40,51 @@ __global__ __launch_bounds__(256) void k_policy_act_step(ActStepArgs a) {
     float* H1 = X + R * d.ldO;
     float* H2 = H1 + R * d.ldH;
     float* OUT = H2 + R * d.ldH;                       // [n_trunks][R][ldPmax]
-    for (int i = tid; i < R * d.Op; i += blockDim.x) {
-        const int r = i / d.Op, c = i - r * d.Op;
-        const int row = base + r;
-        X[r * d.ldO + c] = (row < a.n && c < d.O) ? a.obs[(size_t)row * d.O + c] : 0.f;
-    }
-    for (int t = 0; t < d.n_trunks; ++t) {
-        const SgTrunk tr = d.trunk[t];
-        __syncthreads();
-        if (!GW) sg_stage(smem, a.params + tr.off, tr.size / 4);
-        __syncthreads();
-        trunk_forward<MT, GW>(d, tr, GW ? a.params + tr.off : smem, X, H1, H2, OUT + t * R * a.ldPmax, tr.ldP);
-    }
-    __syncthreads();
+    stage_rows(X, R, d.Op, d.ldO, a.obs, d.O, [&](int r) { return base + r < a.n ? base + r : -1; });
+    run_trunks<MT, GW>(d, a.params, false, smem, X, H1, H2, OUT, a.ldPmax);
     const int row = base + tid;
     if (tid < R && row < a.n) {
         const float* h0 = OUT + tid * d.trunk[0].ldP;
         const float* h1 = OUT + R * a.ldPmax + tid * d.trunk[1].ldP;
         const float* hc = OUT + (d.n_trunks - 1) * R * a.ldPmax + tid * d.trunk[d.n_trunks - 1].ldP;
         a.value[row] = hc[0];
-        float logp = 0.f;
-        for (int k = 0; k < d.A; ++k) {
-            float mean, ls;
-            if (d.kind == SG_POLICY_MLP) {
-                mean = h0[k];
-                ls = a.params[d.trunk[0].off + d.trunk[0].ex + k];
-            } else if (k < d.nc) {
-                mean = h0[k];
-                ls = h0[d.nc + k];
-            } else {
-                mean = h1[k - d.nc];
-                ls = h1[d.na + k - d.nc];
-            }
-            const float sigma = expf(ls);
-            float act;
-            if (a.mode == 1) act = mean;
-            else {
-                const float z = a.noise ? a.noise[(size_t)row * d.A + k]
-                                        : sg_normal(a.seed, a.stream, (uint64_t)row * d.A + k);
-                act = z * sigma + mean;
-            }
+        a.logp[row] = gauss_head_row(d, a.params, h0, h1, row, a.mode, a.noise, nullptr, a.seed, a.stream, [&](int k, float act) {
             a.action[(size_t)row * d.A + k] = act;
             a.action_host[(size_t)row * d.A + k] = act;
-            const float diff = act - mean, var = sigma * sigma;
-            logp += -(diff * diff) / (2.0f * var) - logf(sigma) - HALF_LOG_2PI;
-        }
-        a.logp[row] = logp;
+        });
     }
+}
+
+// What both steps do before their launch, into the fields that ActStepArgs and ActStepRnnArgs share: the page-locked block
+// the kernel writes the actions to, injected noise uploaded through the policy's staging block, the head's mode and draws,
+// slot t of the rollout's VALUE_PREDS / ACTIONS / LOGP.
+template <typename Args>
+static int act_step_open(sg_rollout* r, sg_policy* p, int t, const float* noise, uint64_t seed, int deterministic, Args* a) {
+    sg_ctx* ctx = r->ctx;
+    const int n = r->N;
+    const size_t f_na = (size_t)n * p->desc.A;
+    SG_CHECK(hipSetDevice(ctx->device));
+    void* h_act = nullptr;
+    SG_TRY(sg_ctx_pinned(ctx, sizeof(float) * f_na, &h_act));
+    const bool inject = noise && !deterministic;
+    if (inject) {
+        SG_TRY(sg_policy_io_reserve(p, sizeof(float) * f_na));
+        SG_CHECK(hipMemcpyAsync(p->d_io, noise, sizeof(float) * f_na, hipMemcpyHostToDevice, ctx->stream));
+    }
+    a->n = n; a->mode = deterministic ? 1 : 0;
+    a->noise = inject ? p->d_io : nullptr; a->seed = seed; a->stream = SG_ACT_STREAM + (uint64_t)ctx->rank;
+    a->value = r->d_field[SG_F_VALUE_PREDS] + (size_t)t * n;
+    a->action = r->d_field[SG_F_ACTIONS] + (size_t)t * f_na;
+    a->logp = r->d_field[SG_F_LOGP] + (size_t)t * n;
+    a->action_host = static_cast<float*>(h_act);
+    return 0;
+}
+// ... and after it: wait for the step and hand the actions to the caller
+static int act_step_close(sg_ctx* ctx, const float* h_act, size_t f_na, float* action_host) {
+    SG_CHECK(hipGetLastError());
+    SG_CHECK(hipStreamSynchronize(ctx->stream));
+    memcpy(action_host, h_act, sizeof(float) * f_na);
+    return 0;
 }
 
 static size_t act_step_lds_bytes(const SgPolicyDesc& d, int MT, bool gw) {
@@ -119,44 +117,19 @@ extern "C" int sg_rollout_act_step(sg_rollout* r, sg_policy* p, int t, const flo
     SG_REQUIRE(act_step_lds_bytes(d, MT, gw) <= (size_t)ctx->lds_bytes && (MT == 1) == (MTf == 1),
                "sg_rollout_act_step: a %d-row tile of this policy with every trunk's head outputs (%zu B) does not fit the %d-byte "
                "LDS; act through sg_policy_act and insert on the host", 16 * MTf, act_step_lds_bytes(d, MTf, gw), ctx->lds_bytes);
-    SG_CHECK(hipSetDevice(ctx->device));
-    void* h_act = nullptr;
-    SG_TRY(sg_ctx_pinned(ctx, sizeof(float) * f_na, &h_act));
-    const bool inject = noise && !deterministic;
-    if (inject && sizeof(float) * f_na > p->io_bytes) {
-        const size_t need = sizeof(float) * f_na;
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (p->d_io) SG_CHECK(sg_dev_free(p->d_io));
-        p->d_io = nullptr;
-        p->io_bytes = 0;
-        SG_CHECK(sg_dev_malloc((void**)&p->d_io, need + need / 2));
-        p->io_bytes = need + need / 2;
-    }
+    ActStepArgs a;
+    SG_TRY(act_step_open(r, p, t, noise, seed, deterministic, &a));
     float* d_obs = r->d_field[SG_F_OBS] + (size_t)t * n * O;
     if (obs_host) SG_CHECK(hipMemcpyAsync(d_obs, obs_host, sizeof(float) * (size_t)n * O, hipMemcpyHostToDevice, ctx->stream));
-    if (inject) SG_CHECK(hipMemcpyAsync(p->d_io, noise, sizeof(float) * f_na, hipMemcpyHostToDevice, ctx->stream));
-    ActStepArgs a;
-    a.d = d; a.params = p->d_params; a.obs = d_obs; a.n = n; a.mode = deterministic ? 1 : 0;
-    a.noise = inject ? p->d_io : nullptr; a.seed = seed; a.stream = SG_ACT_STREAM + (uint64_t)ctx->rank;
-    a.value = r->d_field[SG_F_VALUE_PREDS] + (size_t)t * n;
-    a.action = r->d_field[SG_F_ACTIONS] + (size_t)t * f_na;
-    a.logp = r->d_field[SG_F_LOGP] + (size_t)t * n;
-    a.action_host = static_cast<float*>(h_act);
+    a.d = d; a.params = p->d_params; a.obs = d_obs;
     a.wbuf_floats = gw ? 0 : max_trunk_size(d, 0, d.n_trunks); a.ldPmax = max_ldP(d);
     const int R = 16 * MT;
     const dim3 grid((n + R - 1) / R);
     const size_t lds = act_step_lds_bytes(d, MT, gw);
-    if (gw) {
-        if (MT == 4) hipLaunchKernelGGL((k_policy_act_step<4, true>), grid, dim3(256), lds, ctx->stream, a);
-        else if (MT == 2) hipLaunchKernelGGL((k_policy_act_step<2, true>), grid, dim3(256), lds, ctx->stream, a);
-        else hipLaunchKernelGGL((k_policy_act_step<1, true>), grid, dim3(256), lds, ctx->stream, a);
-    } else if (MT == 4) hipLaunchKernelGGL(k_policy_act_step<4>, grid, dim3(256), lds, ctx->stream, a);
-    else if (MT == 2) hipLaunchKernelGGL(k_policy_act_step<2>, grid, dim3(256), lds, ctx->stream, a);
-    else hipLaunchKernelGGL(k_policy_act_step<1>, grid, dim3(256), lds, ctx->stream, a);
-    SG_CHECK(hipGetLastError());
-    SG_CHECK(hipStreamSynchronize(ctx->stream));
-    memcpy(action_host, h_act, sizeof(float) * f_na);
-    return 0;
+    sg_dispatch_mt_gw<4>(MT, gw, [&](auto mt, auto g) {
+        hipLaunchKernelGGL((k_policy_act_step<decltype(mt)::value, decltype(g)::value>), grid, dim3(256), lds, ctx->stream, a);
+    });
+    return act_step_close(ctx, a.action_host, f_na, action_host);
 }
 
 // ------------------------------------------------------------------------------------------------ recurrent policy
@@ -215,16 +188,9 @@ __global__ __launch_bounds__(256) void k_policy_act_step_rnn(ActStepRnnArgs a) {
     for (int c0 = 0; c0 < MT; c0 += a.mc) {
         const int cbase = base + 16 * c0;              // first environment of the chunk
         __syncthreads();
-        for (int i = tid; i < RC * g.Op; i += blockDim.x) {
-            const int r = i / g.Op, c = i - r * g.Op;
-            const int row = cbase + r;
-            XO[r * g.ldO + c] = (row < a.n && c < g.O) ? a.obs[(size_t)row * g.O + c] : 0.f;
-        }
-        for (int i = tid; i < RC * ldH; i += blockDim.x) {
-            const int r = i / ldH, c = i - r * ldH;
-            const int row = cbase + r;
-            HM[i] = (row < a.n && c < H) ? a.hin[(size_t)row * H + c] * a.masks[row] : 0.f;
-        }
+        auto chunk_row = [&](int r) { return cbase + r < a.n ? cbase + r : -1; };
+        stage_rows(XO, RC, g.Op, g.ldO, a.obs, g.O, chunk_row);
+        stage_rows(HM, RC, ldH, ldH, H, chunk_row, [&](int64_t row, int c) { return a.hin[(size_t)row * H + c] * a.masks[row]; });
         if (!a.gwp) sg_stage(smem, a.gruW + g.wih, (3 * Hp * g.ldO) / 4);
         __syncthreads();
         {
@@ -290,37 +256,17 @@ __global__ __launch_bounds__(256) void k_policy_act_step_rnn(ActStepRnnArgs a) {
     float* H1 = U;
     float* H2 = H1 + R * d.ldH;
     float* OUT = H2 + R * d.ldH;                       // [n_trunks][R][ldPmax]
-    for (int t = 0; t < d.n_trunks; ++t) {
-        const SgTrunk tr = d.trunk[t];
-        __syncthreads();
-        if (!GW) sg_stage(smem, a.params + tr.off, tr.size / 4);
-        __syncthreads();
-        trunk_forward<MT, GW>(d, tr, GW ? a.params + tr.off : smem, XT, H1, H2, OUT + t * R * a.ldPmax, tr.ldP);
-    }
-    __syncthreads();
+    run_trunks<MT, GW>(d, a.params, false, smem, XT, H1, H2, OUT, a.ldPmax);
     const int row = base + tid;
     if (tid < R && row < a.n) {
         const float* h0 = OUT + tid * d.trunk[0].ldP;
         const float* hc = OUT + (d.n_trunks - 1) * R * a.ldPmax + tid * d.trunk[d.n_trunks - 1].ldP;
         a.value[row] = hc[0];
-        float logp = 0.f;
-        for (int k = 0; k < d.A; ++k) {
-            const float mean = h0[k];
-            const float ls = a.params[d.trunk[0].off + d.trunk[0].ex + k];
-            const float sigma = expf(ls);
-            float act;
-            if (a.mode == 1) act = mean;
-            else {
-                const float z = a.noise ? a.noise[(size_t)row * d.A + k]
-                                        : sg_normal(a.seed, a.stream, (uint64_t)row * d.A + k);
-                act = z * sigma + mean;
-            }
+        // (the heads of a recurrent policy are an MLP policy's: no second actor trunk for h1 to point at)
+        a.logp[row] = gauss_head_row(d, a.params, h0, nullptr, row, a.mode, a.noise, nullptr, a.seed, a.stream, [&](int k, float act) {
             a.action[(size_t)row * d.A + k] = act;
             a.action_host[(size_t)row * d.A + k] = act;
-            const float diff = act - mean, var = sigma * sigma;
-            logp += -(diff * diff) / (2.0f * var) - logf(sigma) - HALF_LOG_2PI;
-        }
-        a.logp[row] = logp;
+        });
     }
 }
 
@@ -373,47 +319,21 @@ extern "C" int sg_rollout_act_step_rnn(sg_rollout* r, sg_policy* p, int t, const
                "sg_rollout_act_step_rnn: a %d-row tile of this policy with its GRU step and every trunk's head outputs (%zu B) does not fit "
                "the %d-byte LDS; act through sg_policy_act_rnn and insert on the host", 16 * MTf,
                act_step_rnn_lds_bytes(d, g, MTf, 1, gwp, gws, gw), ctx->lds_bytes);
-    SG_CHECK(hipSetDevice(ctx->device));
-    void* h_act = nullptr;
-    SG_TRY(sg_ctx_pinned(ctx, sizeof(float) * f_na, &h_act));
-    const bool inject = noise && !deterministic;
-    if (inject && sizeof(float) * f_na > p->io_bytes) {
-        const size_t need = sizeof(float) * f_na;
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (p->d_io) SG_CHECK(sg_dev_free(p->d_io));
-        p->d_io = nullptr;
-        p->io_bytes = 0;
-        SG_CHECK(sg_dev_malloc((void**)&p->d_io, need + need / 2));
-        p->io_bytes = need + need / 2;
-    }
+    ActStepRnnArgs a;
+    SG_TRY(act_step_open(r, p, t, noise, seed, deterministic, &a));
     float* d_obs = r->d_field[SG_F_OBS] + (size_t)t * n * O;
     float* d_masks = r->d_field[SG_F_MASKS] + (size_t)t * n;
     if (obs_host) SG_CHECK(hipMemcpyAsync(d_obs, obs_host, sizeof(float) * (size_t)n * O, hipMemcpyHostToDevice, ctx->stream));
     if (masks_host) SG_CHECK(hipMemcpyAsync(d_masks, masks_host, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (inject) SG_CHECK(hipMemcpyAsync(p->d_io, noise, sizeof(float) * f_na, hipMemcpyHostToDevice, ctx->stream));
-    ActStepRnnArgs a;
     a.d = d; a.g = g; a.params = p->d_params; a.gruW = p->d_params + g.off; a.obs = d_obs; a.masks = d_masks;
     a.hin = r->d_hidden + (size_t)t * n * H; a.hout = r->d_hidden + (size_t)(t + 1) * n * H;
-    a.n = n; a.mode = deterministic ? 1 : 0;
-    a.noise = inject ? p->d_io : nullptr; a.seed = seed; a.stream = SG_ACT_STREAM + (uint64_t)ctx->rank;
-    a.value = r->d_field[SG_F_VALUE_PREDS] + (size_t)t * n;
-    a.action = r->d_field[SG_F_ACTIONS] + (size_t)t * f_na;
-    a.logp = r->d_field[SG_F_LOGP] + (size_t)t * n;
-    a.action_host = static_cast<float*>(h_act);
     a.wbuf_floats = (int)act_step_rnn_wbuf(d, g, gwp, gws, gw); a.ldPmax = max_ldP(d);
     a.mc = mc; a.gwp = gwp ? 1 : 0; a.gws = gws ? 1 : 0;
     const int R = 16 * MT;
     const dim3 grid((n + R - 1) / R);
     const size_t lds = act_step_rnn_lds_bytes(d, g, MT, mc, gwp, gws, gw);
-    if (gw) {
-        if (MT == 4) hipLaunchKernelGGL((k_policy_act_step_rnn<4, true>), grid, dim3(256), lds, ctx->stream, a);
-        else if (MT == 2) hipLaunchKernelGGL((k_policy_act_step_rnn<2, true>), grid, dim3(256), lds, ctx->stream, a);
-        else hipLaunchKernelGGL((k_policy_act_step_rnn<1, true>), grid, dim3(256), lds, ctx->stream, a);
-    } else if (MT == 4) hipLaunchKernelGGL(k_policy_act_step_rnn<4>, grid, dim3(256), lds, ctx->stream, a);
-    else if (MT == 2) hipLaunchKernelGGL(k_policy_act_step_rnn<2>, grid, dim3(256), lds, ctx->stream, a);
-    else hipLaunchKernelGGL(k_policy_act_step_rnn<1>, grid, dim3(256), lds, ctx->stream, a);
-    SG_CHECK(hipGetLastError());
-    SG_CHECK(hipStreamSynchronize(ctx->stream));
-    memcpy(action_host, h_act, sizeof(float) * f_na);
-    return 0;
+    sg_dispatch_mt_gw<4>(MT, gw, [&](auto mt, auto w) {
+        hipLaunchKernelGGL((k_policy_act_step_rnn<decltype(mt)::value, decltype(w)::value>), grid, dim3(256), lds, ctx->stream, a);
+    });
+    return act_step_close(ctx, a.action_host, f_na, action_host);
 }

@@ -124,6 +124,8 @@ struct SgDiscDesc {
     int total;
 };
 
+#define HALF_LOG_2PI 0.91893853320467274178f   // the Gaussian log-prob / entropy constant of every head (act, PPO, A2C)
+
 SgPolicyDesc sg_make_policy_desc(int kind, int O, int A, int H, int num_feet, int Hc = 0,   // Hc 0: critic as wide as the actors
                                  int dist = SG_DIST_GAUSSIAN, int n_out = 0);
 int64_t sg_policy_flat_count(const SgPolicyDesc& d);
@@ -268,6 +270,10 @@ int sg_cnn_backward_launch(sg_ctx* ctx, const sg_policy* p, const struct sg_roll
                            float vcoef, float ecoef, int use_clipped);
 
 size_t sg_policy_padded_count(const sg_policy* p);          // floats of d_params (heads + GRU block)
+// sg_policy.hip: the one way p->d_io grows.  Nothing while io_bytes >= bytes; otherwise the stream is drained (queued work may
+// still use the old block), the block released, pointer and size cleared -- a failed allocation leaves an empty buffer, never a
+// released pointer with a size beside it -- and a block half as large again allocated.
+int sg_policy_io_reserve(sg_policy* p, size_t bytes);
 bool sg_gru_fits(const sg_ctx* ctx, const SgGruDesc& g);   // sg_gru.hip: the GRU kernels' 16-row tiles fit a CU's LDS
 
 // Layout of sg_disc::d_state behind the SgOptState at its head, in unsigned words: k_disc_step4's hand-off flags (one

@@ -96,13 +96,7 @@ static int gru_host_call(sg_policy* p, const char* who, const float* obs, const 
     const size_t f_obs = r4(rows * O), f_na = r4(rows * A), f_row = r4(rows), f_h = r4((size_t)n * H);
     const size_t f_gi = r4(rows * 3 * g.Hp), f_hout = r4(rows * H);
     const size_t need = sizeof(float) * (f_obs + 2 * f_na + 4 * f_row + 2 * f_h + f_gi + f_hout);
-    if (need > p->io_bytes) {
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (p->d_io) SG_CHECK(sg_dev_free(p->d_io));
-        p->d_io = nullptr; p->io_bytes = 0;
-        SG_CHECK(sg_dev_malloc((void**)&p->d_io, need + need / 2));
-        p->io_bytes = need + need / 2;
-    }
+    SG_TRY(sg_policy_io_reserve(p, need));
     float* d_obs = p->d_io;
     float* d_in = d_obs + f_obs;
     float* d_action = d_in + f_na;
@@ -141,13 +135,7 @@ int sg_gru_value_device(sg_policy* p, const float* d_obs, const float* d_hxs, co
     const size_t f_row = r4((size_t)n), f_gi = r4((size_t)n * 3 * g.Hp), f_h = r4((size_t)n * g.H);
     const size_t need = sizeof(float) * (f_row + f_gi + f_h);
     SG_CHECK(hipSetDevice(ctx->device));
-    if (need > p->io_bytes) {
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (p->d_io) SG_CHECK(sg_dev_free(p->d_io));
-        p->d_io = nullptr; p->io_bytes = 0;
-        SG_CHECK(sg_dev_malloc((void**)&p->d_io, need + need / 2));
-        p->io_bytes = need + need / 2;
-    }
+    SG_TRY(sg_policy_io_reserve(p, need));
     float* d_v = p->d_io;
     float* d_gi = d_v + f_row;
     float* d_hout = d_gi + f_gi;

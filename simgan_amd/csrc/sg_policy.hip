@@ -44,16 +44,10 @@ __global__ __launch_bounds__(256) void k_policy_forward(FwdArgs a) {
     float* heads = a.heads + (size_t)blockIdx.y * a.n * a.hld;
     for (int base = blockIdx.x * R; base < a.n; base += gridDim.x * R) {
         __syncthreads();
-        for (int i = threadIdx.x; i < R * d.Op; i += blockDim.x) {
-            const int r = i / d.Op, c = i - r * d.Op;
+        stage_rows(X, R, d.Op, d.ldO, a.obs, d.O, [&](int r) -> int64_t {
             const int row = base + r;
-            float v = 0.f;
-            if (row < a.n && c < d.O) {
-                const int64_t src = a.idx ? a.idx[row] : (int64_t)row;
-                v = a.obs[src * d.O + c];
-            }
-            X[r * d.ldO + c] = v;
-        }
+            return row < a.n ? (a.idx ? a.idx[row] : (int64_t)row) : -1;
+        });
         __syncthreads();
         trunk_forward<MT, GW>(d, tr, W, X, H1, H2, OUT, ldP);
         __syncthreads();
@@ -88,33 +82,10 @@ __global__ void k_gauss_head(HeadArgs a) {
     const float* hc = a.heads + (size_t)(d.n_trunks - 1) * hs + (size_t)row * a.hld;
     if (a.value) a.value[row] = hc[0];
     if (!a.logp && !a.action && !a.ent) return;
-    float logp = 0.f, ent = 0.f;
-    for (int k = 0; k < d.A; ++k) {
-        float mean, ls;
-        if (d.kind == SG_POLICY_MLP) {
-            mean = h0[k];
-            ls = a.params[d.trunk[0].off + d.trunk[0].ex + k];
-        } else if (k < d.nc) {
-            mean = h0[k];
-            ls = h0[d.nc + k];
-        } else {
-            mean = h1[k - d.nc];
-            ls = h1[d.na + k - d.nc];
-        }
-        const float sigma = expf(ls);
-        float act;
-        if (a.mode == 2) act = a.action_in[(size_t)row * d.A + k];
-        else if (a.mode == 1) act = mean;
-        else {
-            const float z = a.noise ? a.noise[(size_t)row * d.A + k]
-                                    : sg_normal(a.seed, a.stream, (uint64_t)row * d.A + k);
-            act = z * sigma + mean;
-        }
+    float ent;
+    const float logp = gauss_head_row<true>(d, a.params, h0, h1, row, a.mode, a.noise, a.action_in, a.seed, a.stream, [&](int k, float act) {
         if (a.action) a.action[(size_t)row * d.A + k] = act;
-        const float diff = act - mean, var = sigma * sigma;
-        logp += -(diff * diff) / (2.0f * var) - logf(sigma) - HALF_LOG_2PI;
-        ent += 0.5f + HALF_LOG_2PI + logf(sigma);
-    }
+    }, &ent);
     if (a.logp) a.logp[row] = logp;
     if (a.ent) a.ent[row] = ent;
 }
@@ -213,13 +184,9 @@ static int policy_forward_dev(sg_policy* p, const float* d_obs, const int64_t* d
     if (gx > 4 * ctx->num_cu) gx = 4 * ctx->num_cu;
     dim3 grid(gx, p->desc.n_trunks);
     const size_t lds = fwd_lds_bytes(p->desc, MT, gw);
-    if (gw) {
-        if (MT == 4) hipLaunchKernelGGL((k_policy_forward<4, true>), grid, dim3(256), lds, ctx->stream, a);
-        else if (MT == 2) hipLaunchKernelGGL((k_policy_forward<2, true>), grid, dim3(256), lds, ctx->stream, a);
-        else hipLaunchKernelGGL((k_policy_forward<1, true>), grid, dim3(256), lds, ctx->stream, a);
-    } else if (MT == 4) hipLaunchKernelGGL(k_policy_forward<4>, grid, dim3(256), lds, ctx->stream, a);
-    else if (MT == 2) hipLaunchKernelGGL(k_policy_forward<2>, grid, dim3(256), lds, ctx->stream, a);
-    else hipLaunchKernelGGL(k_policy_forward<1>, grid, dim3(256), lds, ctx->stream, a);
+    sg_dispatch_mt_gw<4>(MT, gw, [&](auto mt, auto g) {
+        hipLaunchKernelGGL((k_policy_forward<decltype(mt)::value, decltype(g)::value>), grid, dim3(256), lds, ctx->stream, a);
+    });
     SG_CHECK(hipGetLastError());
     return 0;
 }
@@ -384,6 +351,18 @@ extern "C" int sg_policy_get_params(sg_policy* p, float* flat, int64_t n) {
     return 0;
 }
 
+int sg_policy_io_reserve(sg_policy* p, size_t need) {
+    if (need <= p->io_bytes) return 0;
+    SG_CHECK(hipStreamSynchronize(p->ctx->stream));
+    if (p->d_io) SG_CHECK(sg_dev_free(p->d_io));
+    p->d_io = nullptr;
+    p->io_bytes = 0;
+    const size_t cap = need + need / 2;
+    SG_CHECK(sg_dev_malloc((void**)&p->d_io, cap));
+    p->io_bytes = cap;
+    return 0;
+}
+
 // host-pointer front end shared by act / get_value / evaluate
 static int policy_host_call(sg_policy* p, const float* obs, int n, int mode, const float* noise, uint64_t seed,
                             const float* action_in, float* value, float* action, float* logp, float* ent_rows) {
@@ -394,12 +373,7 @@ static int policy_host_call(sg_policy* p, const float* obs, int n, int mode, con
     // device staging: obs | noise/action_in | action | value | logp | ent
     const size_t f_obs = (size_t)n * O, f_na = (size_t)n * A;
     const size_t need = sizeof(float) * (f_obs + 2 * f_na + 3 * (size_t)n);
-    if (need > p->io_bytes) {
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (p->d_io) SG_CHECK(sg_dev_free(p->d_io));
-        SG_CHECK(sg_dev_malloc((void**)&p->d_io, need + need / 2));
-        p->io_bytes = need + need / 2;
-    }
+    SG_TRY(sg_policy_io_reserve(p, need));
     float* d_io = p->d_io;
     float* d_obs = d_io;
     float* d_in = d_obs + f_obs;
@@ -501,20 +475,9 @@ __global__ __launch_bounds__(256) void k_policy_act_ensemble(EnsArgs a) {
             if (a.idx[i] == k) { if (rank >= first && rank < first + R) rows[rank - first] = i; ++rank; }
     }
     __syncthreads();
-    for (int i = tid; i < R * d.Op; i += blockDim.x) {
-        const int r = i / d.Op, cc = i - r * d.Op;
-        const int row = rows[r];
-        X[r * d.ldO + cc] = (row >= 0 && cc < d.O) ? a.obs[(size_t)row * d.O + cc] : 0.f;
-    }
+    stage_rows(X, R, d.Op, d.ldO, a.obs, d.O, [&](int r) { return rows[r]; });
     // 2. trunks
-    for (int t = 0; t < d.n_trunks; ++t) {
-        const SgTrunk tr = d.trunk[t];
-        __syncthreads();
-        if (!GW) sg_stage(smem, a.params[k] + tr.off, tr.size / 4);
-        __syncthreads();
-        trunk_forward<MT, GW>(d, tr, GW ? a.params[k] + tr.off : smem, X, H1, H2, OUT + t * R * a.ldPmax, tr.ldP);
-    }
-    __syncthreads();
+    run_trunks<MT, GW>(d, a.params[k], false, smem, X, H1, H2, OUT, a.ldPmax);
     // 3. heads
     if (tid < nrows) {
         const int row = rows[tid];
@@ -522,23 +485,8 @@ __global__ __launch_bounds__(256) void k_policy_act_ensemble(EnsArgs a) {
         const float* h1 = OUT + R * a.ldPmax + tid * d.trunk[1].ldP;
         const float* hc = OUT + (d.n_trunks - 1) * R * a.ldPmax + tid * d.trunk[d.n_trunks - 1].ldP;
         a.value[row] = hc[0];
-        float logp = 0.f;
-        for (int j = 0; j < d.A; ++j) {
-            float mean, ls;
-            if (d.kind == SG_POLICY_MLP) { mean = h0[j]; ls = a.params[k][d.trunk[0].off + d.trunk[0].ex + j]; }
-            else if (j < d.nc) { mean = h0[j]; ls = h0[d.nc + j]; }
-            else { mean = h1[j - d.nc]; ls = h1[d.na + j - d.nc]; }
-            const float sigma = expf(ls);
-            float act = mean;
-            if (a.mode == 0) {
-                const float z = a.noise ? a.noise[(size_t)row * d.A + j] : sg_normal(a.seed, a.stream, (uint64_t)row * d.A + j);
-                act = z * sigma + mean;
-            }
-            a.action[(size_t)row * d.A + j] = act;
-            const float diff = act - mean, var = sigma * sigma;
-            logp += -(diff * diff) / (2.0f * var) - logf(sigma) - HALF_LOG_2PI;
-        }
-        a.logp[row] = logp;
+        a.logp[row] = gauss_head_row(d, a.params[k], h0, h1, row, a.mode, a.noise, nullptr, a.seed, a.stream,
+                                     [&](int j, float act) { a.action[(size_t)row * d.A + j] = act; });
     }
 }
 
@@ -552,33 +500,14 @@ extern "C" int sg_policy_act_ensemble(sg_policy* const* policies, int n_policies
     SG_REQUIRE(p0, "sg_policy_act_ensemble: NULL policy");
     sg_ctx* ctx = p0->ctx;
     const SgPolicyDesc& d = p0->desc;
+    SG_TRY(ens_check_members("sg_policy_act_ensemble", "the ensemble launch", ctx, policies, n_policies, idx, n));
     EnsArgs a;
-    for (int k = 0; k < n_policies; ++k) {
-        SG_REQUIRE(policies[k] && policies[k]->ctx == ctx, "sg_policy_act_ensemble: member %d is NULL or lives on another context", k);
-        SG_REQUIRE(!policies[k]->cnn, "sg_policy_act_ensemble: member %d has the CNN base (image observations); the ensemble launch "
-                   "runs the MLP trunks only", k);
-        SG_REQUIRE(!policies[k]->recurrent, "sg_policy_act_ensemble: member %d is a recurrent policy; the ensemble launch carries no hidden "
-                   "state (feed-forward policies only)", k);
-        const SgPolicyDesc& e = policies[k]->desc;
-        SG_REQUIRE(e.dist == SG_DIST_GAUSSIAN, "sg_policy_act_ensemble: member %d has a Categorical / Bernoulli head; the ensemble "
-                   "launch carries the Gaussian head only (Box action spaces)", k);
-        SG_REQUIRE(e.kind == d.kind && e.O == d.O && e.A == d.A && e.H == d.H && e.Hc == d.Hc && e.num_feet == d.num_feet,
-                   "sg_policy_act_ensemble: member %d has a different shape", k);
-        a.params[k] = policies[k]->d_params;
-    }
-    for (int i = 0; i < n; ++i)
-        SG_REQUIRE(idx[i] >= 0 && idx[i] < n_policies, "sg_policy_act_ensemble: idx[%d] = %d outside [0, %d)", i, idx[i], n_policies);
+    for (int k = 0; k < n_policies; ++k) a.params[k] = policies[k]->d_params;
     SG_CHECK(hipSetDevice(ctx->device));
     const int O = d.O, A = d.A;
     // device staging in the first member's io buffer: obs | noise | action | value | logp | idx
     const size_t f_obs = (size_t)n * O, f_na = (size_t)n * A;
-    const size_t need = sizeof(float) * (f_obs + 2 * f_na + 3 * (size_t)n);
-    if (need > p0->io_bytes) {
-        SG_CHECK(hipStreamSynchronize(ctx->stream));
-        if (p0->d_io) SG_CHECK(sg_dev_free(p0->d_io));
-        SG_CHECK(sg_dev_malloc((void**)&p0->d_io, need + need / 2));
-        p0->io_bytes = need + need / 2;
-    }
+    SG_TRY(sg_policy_io_reserve(p0, sizeof(float) * (f_obs + 2 * f_na + 3 * (size_t)n)));
     float* d_obs = p0->d_io;
     float* d_noise = d_obs + f_obs;
     float* d_action = d_noise + f_na;
@@ -598,11 +527,9 @@ extern "C" int sg_policy_act_ensemble(sg_policy* const* policies, int n_policies
     const int R = 16 * MT;
     const dim3 grid((n + R - 1) / R, n_policies);
     const size_t lds_e = ens_lds_bytes(d, MT, gw);
-    if (gw) {
-        if (MT == 2) hipLaunchKernelGGL((k_policy_act_ensemble<2, true>), grid, dim3(256), lds_e, ctx->stream, a);
-        else hipLaunchKernelGGL((k_policy_act_ensemble<1, true>), grid, dim3(256), lds_e, ctx->stream, a);
-    } else if (MT == 2) hipLaunchKernelGGL(k_policy_act_ensemble<2>, grid, dim3(256), lds_e, ctx->stream, a);
-    else hipLaunchKernelGGL(k_policy_act_ensemble<1>, grid, dim3(256), lds_e, ctx->stream, a);
+    sg_dispatch_mt_gw<2>(MT, gw, [&](auto mt, auto g) {
+        hipLaunchKernelGGL((k_policy_act_ensemble<decltype(mt)::value, decltype(g)::value>), grid, dim3(256), lds_e, ctx->stream, a);
+    });
     SG_CHECK(hipGetLastError());
     SG_CHECK(hipMemcpyAsync(value, d_value, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
     SG_CHECK(hipMemcpyAsync(action, d_action, sizeof(float) * f_na, hipMemcpyDeviceToHost, ctx->stream));

@@ -24,8 +24,6 @@
 #include "sg_common.h"
 #include "sg_thin.hpp"
 
-#define HALF_LOG_2PI 0.91893853320467274178f
-
 struct PpoArgs {
     SgPolicyDesc d;
     const float* params;
