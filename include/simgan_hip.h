@@ -281,6 +281,38 @@ SG_API int sg_rollout_act_step_chain(sg_rollout *r, sg_policy *learner, int t, i
                               const float *inner_noise, uint64_t inner_seed, int inner_deterministic, const float *noise,
                               uint64_t seed, int deterministic, int squash, float *action_host, float *inner_action_host,
                               float *inner_raw_host);
+/* What one looks at after an update, over the T*N rows of the first T slots of the DEVICE rollout and the policy's CURRENT
+ * parameters.  Replaces the host route to numbers the reference's learners do not return (a2c/algo/ppo.py:65-157 and
+ * a2c/algo/a2c_acktr.py:52-102 give value loss, action loss and entropy): Policy.evaluate_actions / SplitPolicy.evaluate_actions
+ * (a2c/model.py:107-114, a2c/model_split.py:84-95) on every row through the host, ratio = exp(action_log_probs -
+ * old_action_log_probs) (a2c/algo/ppo.py:93-94) and the caller's numpy reductions over the downloaded arrays.  With logp_old =
+ * LOGP, vpred = VALUE_PREDS[:-1], ret = RETURNS[:-1], (v_new, logp_new, entropy) = evaluate_actions(OBS[:-1], ACTIONS) and
+ * r = exp(logp_new - logp_old), out10 = SG_DIAG_N doubles:
+ *   [0] rows                    T*N
+ *   [1] approx_kl               mean(logp_old - logp_new)
+ *   [2] approx_kl_k3            mean((r - 1) - log r)
+ *   [3] clip_fraction           share of rows with |r - 1| > clip_param
+ *   [4] entropy                 mean entropy
+ *   [5] ratio_min, [6] ratio_max
+ *   [7] explained_variance_old  1 - Var(ret - vpred) / Var(ret)
+ *   [8] explained_variance_new  1 - Var(ret - v_new) / Var(ret)
+ *   [9] value_mse               mean((ret - v_new)^2)
+ * Both variances are population variances, formed about the mean (a mean far from zero costs no digits); Var(ret) == 0 gives NaN
+ * (or -inf), as numpy's expression does.  Two launches on the context's stream (a recurrent policy: the GRU forward over all N
+ * environments and T steps with MASKS[:-1] first, from hidden slot 0 of a rollout that holds its hidden states
+ * (sg_rollout_enable_hidden), else from hxs0_host[N*H], which is then required); sums in double, no atomics: the same call gives
+ * the same bits.  Nothing of the rollout or the policy is written.  out10 == NULL: the launches are queued and the call returns
+ * without a host wait; sg_rollout_policy_diagnostics_fetch waits for the LAST queued result and reads it, once -- with nothing
+ * pending it is an error.  out10 != NULL is the two calls in one.
+ *   - clip_param = INFINITY is accepted and gives a clip fraction of exactly 0 (A2C / ACKTR have no clip); zero, negative and NaN
+ *     are errors.
+ *   - with a communicator of world > 1 the statistics cover the rank's own columns; no collective is issued.
+ * Policy, SplitPolicy, a Discrete / MultiBinary policy and a recurrent one are taken.  Errors, each with its own message: policy
+ * and rollout on different contexts, dims that differ, a bad clip_param, a recurrent policy with neither hidden source, and a
+ * policy with the CNN base. */
+#define SG_DIAG_N 10
+SG_API int sg_rollout_policy_diagnostics(sg_rollout *r, sg_policy *p, float clip_param, const float *hxs0_host, double *out10);
+SG_API int sg_rollout_policy_diagnostics_fetch(sg_rollout *r, double out10[10]);
 
 /* ---------------------------------------------------------------------- PPO */
 typedef struct {

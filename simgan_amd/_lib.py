@@ -100,6 +100,8 @@ PROTOTYPES = {
     "sg_rollout_act_step_chain": (C.c_int, [H, H, C.c_int, C.c_int, C.POINTER(H), C.c_int, C.POINTER(C.c_int32), c_float_p, c_float_p,
                                             c_float_p, c_float_p, C.c_uint64, C.c_int, c_float_p, C.c_uint64, C.c_int, C.c_int,
                                             c_float_p, c_float_p, c_float_p]),
+    "sg_rollout_policy_diagnostics": (C.c_int, [H, H, C.c_float, c_float_p, c_double_p]),
+    "sg_rollout_policy_diagnostics_fetch": (C.c_int, [H, c_double_p]),
     "sg_ppo_set_hidden_states_rollout": (C.c_int, [H, H]),
     "sg_ppo_create": (C.c_int, [H, H, C.POINTER(PPOConfig), C.POINTER(H)]),
     "sg_ppo_destroy": (C.c_int, [H]),

@@ -9,6 +9,7 @@ import numpy as np
 
 from .. import _lib
 from ..utils import derive_seed
+from . import diagnostics as _diag
 from .ppo import _Group, _ParamGroups
 
 # KFACOptimizer's constructor defaults (a2c/algo/kfac.py:97-107), which a2c/main.py:159-161 keeps
@@ -182,6 +183,15 @@ class A2C_ACKTR():
         if self.acktr:
             self._steps += 1
         return (float(out[0]), float(out[1]), float(out[2])) if fetch_losses else None
+
+    def diagnostics(self, rollouts, fetch=True):
+        """PPO.diagnostics for A2C / ACKTR (both modes): the same ten numbers with clip_param = inf, so clip_fraction is exactly
+        0 -- neither learner clips a ratio; approx_kl is the measured KL to set beside ACKTR's kl_clip.  The rollout's
+        action_log_probs and value_preds (the collection's) are read, which update() itself does not need."""
+        return _diag.run(self, rollouts, float("inf"), fetch)
+
+    def last_diagnostics(self):
+        return _diag.fetch_last(self)
 
     def get_rmsprop(self):
         """-> (square_avg flat in state_dict order, optimizer steps taken)."""

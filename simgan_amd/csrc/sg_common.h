@@ -310,6 +310,13 @@ struct sg_rollout {
     // recurrent_hidden_states (a2c/storage.py:40): opt-in (sg_rollout_enable_hidden), beside the SG_F_COUNT fields
     float* d_hidden = nullptr;           // [T+1][N][hidden_dim], or NULL
     int hidden_dim = 0;
+    // sg_rollout_policy_diagnostics (sg_diag.hip): the workgroups' partial records, the ten results in page-locked host memory
+    // (the reduce kernel writes them there), the event behind the reduce, and whether a result waits to be fetched
+    double* d_diag = nullptr;
+    size_t diag_cap = 0;                 // doubles
+    double* h_diag = nullptr;
+    hipEvent_t diag_ev = nullptr;
+    bool diag_pending = false;
 };
 
 // A captured launch sequence and what it was captured for (sg_graph_run, below)

@@ -53,6 +53,9 @@ extern "C" int sg_rollout_destroy(sg_rollout* r) {
     if (r->d_mobs) (void)sg_dev_free(r->d_mobs);
     if (r->d_mact) (void)sg_dev_free(r->d_mact);
     if (r->d_hidden) (void)sg_dev_free(r->d_hidden);
+    if (r->d_diag) (void)sg_dev_free(r->d_diag);
+    if (r->h_diag) (void)sg_host_release(r->h_diag);
+    if (r->diag_ev) (void)hipEventDestroy(r->diag_ev);
     delete r;
     return 0;
 }

@@ -142,7 +142,24 @@ def _check_on_device(ro, pol, dup_sym, who):
         raise ValueError(f"{who}(on_device=True): {why}")
 
 
-class GailDynLearner(object):
+class _LearnerDiagnostics(object):
+    """update(diagnostics=True): the agent's diagnostics (PPO.diagnostics / A2C_ACKTR.diagnostics) are queued after the agent's
+    update and before rollouts.after_update(), which overwrites obs[0]; the result is fetched on the first read of
+    last_diagnostics, so a queued update keeps having no host wait."""
+    _diag, _diag_pending = None, False
+
+    def _queue_diagnostics(self):
+        self.agent.diagnostics(self.rollouts, fetch=False)
+        self._diag_pending = True
+
+    @property
+    def last_diagnostics(self):
+        if self._diag_pending:
+            self._diag, self._diag_pending = self.agent.last_diagnostics(), False
+        return self._diag
+
+
+class GailDynLearner(_LearnerDiagnostics):
     def __init__(self, actor_critic, agent, discr, rollouts, expert, gail_batch_size=128, gail_epoch=5,
                  gamma=0.99, gae_lambda=0.95, use_gae=True, use_proper_time_limits=True,
                  gail_tar_length=500.0, no_alive_bonus=False, use_linear_lr_decay=False, lr=None,
@@ -229,12 +246,12 @@ class GailDynLearner(object):
             ro.sync_to_device()
 
     # ------------------------------------------------------------- the timed part (:239-304)
-    def update(self):
+    def update(self, diagnostics=False):
         ro, lib = self.rollouts, self.rollouts.lib
         if self.use_linear_lr_decay:            # :203-207
             update_linear_schedule(self.agent.optimizer, self.j, self.num_updates, self.lr)
         if ro.device_resident:
-            return self._update_resident()
+            return self._update_resident(diagnostics)
         if self._rms_on_device:                 # a drop-in update after device-resident ones: bring the state back
             self._ret_rms.set_state(self.discr.scalars()[:3])
             self._rms_on_device = False
@@ -252,6 +269,8 @@ class GailDynLearner(object):
         next_value = self.actor_critic.get_value(ro.obs[-1], ro.recurrent_hidden_states[-1], ro.masks[-1])
         ro.compute_returns(next_value, self.use_gae, self.gamma, self.gae_lambda, self.use_proper_time_limits)
         ppo = self.agent.update(ro)             # :302
+        if diagnostics:
+            self._queue_diagnostics()
         ro.after_update()                       # :304
         self.j += 1
         return {"gail_loss": gail[0], "gail_loss_e": gail[1], "gail_loss_p": gail[2], "value_loss": ppo[0],
@@ -282,7 +301,7 @@ def _returns_resident(self):
                                                      float(self.gae_lambda), 1 if self.use_proper_time_limits else 0))
 
 
-def _gail_update_resident(self):
+def _gail_update_resident(self, diagnostics=False):
     """GailDynLearner.update() on a device-resident rollout: the same call sequence, every call only QUEUES work on the
     library's stream -- discriminator epochs without their loss read-back, the alive-bonus offset from the device's done
     count, ret_rms resident in the library, GAE with get_value(obs[T]) on the device, PPO, after_update -- and the scalars
@@ -296,6 +315,8 @@ def _gail_update_resident(self):
     self.discr.relabel_rewards_auto(ro, self.gamma, self.gail_tar_length, self.no_alive_bonus)     # :258-297
     _returns_resident(self)
     self.agent.update(ro, fetch_losses=False)   # :302
+    if diagnostics:
+        self._queue_diagnostics()
     ro.after_update()                           # :304
     self.j += 1
     return self._ring.publish(self.discr, self.agent, ("gail_loss", "gail_loss_e", "gail_loss_p", "value_loss", "action_loss",
@@ -305,7 +326,7 @@ def _gail_update_resident(self):
 GailDynLearner._update_resident = _gail_update_resident
 
 
-class PpoLearner(object):
+class PpoLearner(_LearnerDiagnostics):
     """a2c/main.py:199-257, the plain-PPO caller (BASELINE.json configs[0] and configs[4]):
 
         [lr decay :201-205] -> [rollout fill :207-244] -> get_value(obs[-1]) :246-249 -> compute_returns :251-252
@@ -400,19 +421,23 @@ class PpoLearner(object):
             ro.sync_to_device()
 
     # ------------------------------------------------------------- the timed part (:201-205, :246-256)
-    def update(self):
+    def update(self, diagnostics=False):
         ro, lib = self.rollouts, self.rollouts.lib
         if self.use_linear_lr_decay:
             update_linear_schedule(self.agent.optimizer, self.j, self.num_updates, self.lr)
         if ro.device_resident:   # nothing below waits for the device: the losses are read from the results ring on demand
             _returns_resident(self)
             self.agent.update(ro, fetch_losses=False)
+            if diagnostics:
+                self._queue_diagnostics()
             ro.after_update()
             self.j += 1
             return self._ring.publish(None, self.agent, ("value_loss", "action_loss", "dist_entropy"))
         next_value = self.actor_critic.get_value(ro.obs[-1], ro.recurrent_hidden_states[-1], ro.masks[-1])
         ro.compute_returns(next_value, self.use_gae, self.gamma, self.gae_lambda, self.use_proper_time_limits)
         value_loss, action_loss, dist_entropy = self.agent.update(ro)
+        if diagnostics:
+            self._queue_diagnostics()
         ro.after_update()
         self.j += 1
         return {"value_loss": value_loss, "action_loss": action_loss, "dist_entropy": dist_entropy}
