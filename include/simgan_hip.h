@@ -518,6 +518,35 @@ SG_API int sg_disc_relabel_rewards(sg_disc *d, sg_rollout *r, float gamma, float
 SG_API int sg_disc_relabel_rewards_auto(sg_disc *d, sg_rollout *r, float gamma, double gail_tar_length, int no_alive_bonus);
 SG_API int sg_disc_set_rms(sg_disc *d, const double rms_state[3]);
 SG_API int sg_disc_get_scalars(sg_disc *d, double out5[5]);
+/* Discriminator diagnostics on the device: what one looks at in the discriminator half of the GAIL-dyn loop, over three row
+ * populations in two queued launches -- policy: the T*N rows of OBS_FEAT[1:] (the rows sg_disc_update_gail_dyn trains on and
+ * the relabel scores); expert: the n_e rows of sg_disc_set_expert; mid: the T*N rows 0.5f * expert[i mod n_e] + 0.5f * policy[i],
+ * the reference's mixup (a2c/algo/gail.py:72-75) at alpha = 0.5, formed on the fly.  Replaces a download of obs_feat,
+ * predict_prob on every row, sg_disc_grad_pen on the mixed rows and numpy.  With d the logit D(x), s = sigmoid(d), g = dD/dx
+ * and |g| its 2-norm per row, out19 = SG_DDIAG_N doubles:
+ *   [0]  policy_rows            T*N                        [1]  expert_rows            n_e
+ *   [2]  policy_accuracy        mean(d_p < 0)              [3]  expert_accuracy        mean(d_e > 0)      (d == 0 is wrong for both)
+ *   [4]  policy_logit_mean                                 [5]  policy_logit_std       population standard deviation
+ *   [6]  expert_logit_mean                                 [7]  expert_logit_std
+ *   [8]  policy_bce             mean softplus(d_p)         [9]  expert_bce             mean softplus(-d_e)
+ *   [10] reward_mean  [11] reward_std  [12] reward_min  [13] reward_max    over the policy rows, of log(s + 1e-7) - log(1 - s + 1e-7)
+ *                               (1e-7 at its float32 value): the raw reward of sg_disc_predict_reward, no offset, before ret_rms
+ *   [14] policy_grad_norm_mean  [15] expert_grad_norm_mean  [16] mid_grad_norm_mean     mean |g| over each population
+ *   [17] mid_grad_pen           10 mean((|g| - 1)^2) over the mid rows
+ *   [18] grad_norm_max          over all three populations
+ * Forward and input gradient in float32 on the matrix cores (the forward is sg_disc_predict_reward's), sums in double, no
+ * atomics, records merged in a fixed order: the same call gives the same bits.  Nothing of the discriminator, the rollout or the
+ * expert matrix is written.  slot is 0 or 1: two results may be pending at once (before and after the discriminator epochs).
+ * out19 == NULL: the launches are queued and the call returns without a host wait; sg_disc_diagnostics_fetch waits for the LAST
+ * result queued into the slot and reads it, once -- with nothing pending in the slot it is an error.  out19 != NULL is the two
+ * calls in one.  The rollout's OBS_FEAT must be current on the device (sg_rollout_upload).
+ * With world > 1 or a sharded discriminator the numbers cover THIS rank's own rollout rows and the expert rows it holds: no
+ * collective is issued.
+ * Errors, each with its own message: NULL argument, slot out of range, discriminator and rollout on different contexts, rollout
+ * feat_len != input_dim, no expert set. */
+#define SG_DDIAG_N 19
+SG_API int sg_disc_diagnostics(sg_disc *d, sg_rollout *r, int slot, double *out19);
+SG_API int sg_disc_diagnostics_fetch(sg_disc *d, int slot, double out19[SG_DDIAG_N]);
 /* sum(1 - masks) over all T+1 slots (a2c/main_gail_dyn_ppo.py:258), for the alive-bonus offset. */
 SG_API int sg_rollout_count_dones(sg_rollout *r, double *dones);
 

@@ -11,6 +11,12 @@ NAMES = ("rows", "approx_kl", "approx_kl_k3", "clip_fraction", "entropy", "ratio
          "explained_variance_new", "value_mse")
 
 
+# include/simgan_hip.h: sg_disc_diagnostics -- Discriminator.diagnostics / GailDynLearner.update(disc_diagnostics=True)
+DISC_NAMES = ("policy_rows", "expert_rows", "policy_accuracy", "expert_accuracy", "policy_logit_mean", "policy_logit_std",
+              "expert_logit_mean", "expert_logit_std", "policy_bce", "expert_bce", "reward_mean", "reward_std", "reward_min", "reward_max",
+              "policy_grad_norm_mean", "expert_grad_norm_mean", "mid_grad_norm_mean", "mid_grad_pen", "grad_norm_max")
+
+
 def _as_dict(out):
     return {k: float(out[i]) for i, k in enumerate(NAMES)}
 
@@ -47,3 +53,20 @@ def fetch_last(agent):
     _lib.check(agent.lib.sg_rollout_policy_diagnostics_fetch(ro.h, out))
     agent._diag_rollouts = None
     return _as_dict(out)
+
+
+def run_disc(disc, rollouts, fetch=True, slot=0):
+    """Discriminator.diagnostics: pushes OBS_FEAT as the other discriminator calls do (a host-resident rollout gives the
+    device-resident one's numbers) and queues the two launches into `slot`.  fetch=True: wait and return the dict of DISC_NAMES;
+    False: return None (fetch_disc reads the slot later)."""
+    rollouts._push([_lib.F_OBS_FEAT])
+    out = (C.c_double * len(DISC_NAMES))()
+    _lib.check(disc.lib.sg_disc_diagnostics(disc.h, rollouts.h, int(slot), out if fetch else None))
+    return {k: float(out[i]) for i, k in enumerate(DISC_NAMES)} if fetch else None
+
+
+def fetch_disc(disc, slot=0):
+    """The pending result of `slot`: waits for it.  An error when none is pending there."""
+    out = (C.c_double * len(DISC_NAMES))()
+    _lib.check(disc.lib.sg_disc_diagnostics_fetch(disc.h, int(slot), out))
+    return {k: float(out[i]) for i, k in enumerate(DISC_NAMES)}

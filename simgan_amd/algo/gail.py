@@ -344,6 +344,21 @@ class Discriminator(object):
         _lib.check(self.lib.sg_disc_predict_prob(self.h, _lib.fptr(x), x.shape[0], _lib.fptr(out)))
         return to_host_tensor(out)
 
+    # ---------------------------------------------------------------------- diagnostics
+    def diagnostics(self, rollouts, fetch=True, slot=0):
+        """Accuracy, logit distribution and BCE on the rollout's rows (obs_feat[1:]) and on the expert rows, the raw reward
+        distribution, and the input-gradient norm on both and on the mixup rows at alpha = 0.5, in two queued launches
+        (include/simgan_hip.h: sg_disc_diagnostics) -> dict in algo.diagnostics.DISC_NAMES order.  Changes no state.  The expert
+        matrix is the one of the last update / set_expert.  fetch=False: None, without a host wait; last_diagnostics(slot)
+        reads the result later.  slot 0 or 1: two results may be pending."""
+        from . import diagnostics as _diag
+        return _diag.run_disc(self, rollouts, fetch, slot)
+
+    def last_diagnostics(self, slot=0):
+        """The pending result of diagnostics(..., fetch=False, slot=slot); an error when none is pending in that slot."""
+        from . import diagnostics as _diag
+        return _diag.fetch_disc(self, slot)
+
     @property
     def returns(self):
         c = self._steps

@@ -136,6 +136,9 @@ struct sg_ctx;
 // their global-weight instances (sg_policy.hip)
 bool sg_policy_needs_gw(const sg_ctx* ctx, const SgPolicyDesc& d);
 SgDiscDesc sg_make_disc_desc(int F, int Hd);
+// true: the discriminator's parameter image does not fit a CU's LDS beside the update step's tiles (or SG_DISC_GW=1): the
+// chain / forward / diagnostics kernels run their global-weight instances (sg_disc.hip)
+bool sg_disc_needs_gw(const sg_ctx* ctx, const SgDiscDesc& dd);
 int64_t sg_disc_flat_count(const SgDiscDesc& d);
 void sg_disc_pad(const SgDiscDesc& d, const float* flat, float* padded);
 void sg_disc_unpad(const SgDiscDesc& d, const float* padded, float* flat);
@@ -380,6 +383,7 @@ struct sg_ppo {
     struct SgKfac* kfac = nullptr;
 };
 
+#define SG_DDIAG_STRIDE 32   // doubles between the two slots' results of sg_disc_diagnostics (SG_DDIAG_N of them used)
 struct sg_disc {
     sg_ctx* ctx;
     SgDiscDesc desc;
@@ -411,6 +415,13 @@ struct sg_disc {
     double* d_loss_acc = nullptr;
     double* d_scal = nullptr;      // device-resident learner scalars: ret_rms {mean, var, count} | sum(1 - masks) | r_sa
     int last_n_d = 0;              // steps of the last epoch (its loss sums in d_loss_acc are divided by this)
+    // sg_disc_diagnostics (sg_disc_diag.hip): the workgroups' partial records, the two slots' results in page-locked host memory
+    // (the reduce kernel writes them there), the event behind each slot's reduce, and whether its result waits to be fetched
+    double* d_ddiag = nullptr;
+    size_t ddiag_cap = 0;                // doubles
+    double* h_ddiag = nullptr;           // [2][SG_DDIAG_STRIDE]
+    hipEvent_t ddiag_ev[2] = {nullptr, nullptr};
+    bool ddiag_pending[2] = {false, false};
     float* d_returns = nullptr;    // Discriminator.returns [n]
     int returns_n = 0;
     bool returns_none = true;

@@ -50,6 +50,7 @@ static bool disc_needs_gw(const sg_ctx* ctx, const SgDiscDesc& dd) {
     if (e && e[0] == '1') return true;
     return disc_chain_lds_bytes(dd) > (size_t)ctx->lds_bytes;
 }
+bool sg_disc_needs_gw(const sg_ctx* ctx, const SgDiscDesc& dd) { return disc_needs_gw(ctx, dd); }
 static void launch_disc_chain(sg_ctx* ctx, const SgDiscDesc& dd, dim3 grid, size_t lds, const DiscArgs& a, bool gw) {
     const int kf = dd.Fp / 16, kh = dd.Hp / 16;
     const dim3 block(SG_DISC_THREADS);
@@ -379,6 +380,9 @@ extern "C" int sg_disc_destroy(sg_disc* d) {
     if (d->d_pperm) (void)sg_dev_free(d->d_pperm);
     if (d->d_loss_acc) (void)sg_dev_free(d->d_loss_acc);
     if (d->d_scal) (void)sg_dev_free(d->d_scal);
+    if (d->d_ddiag) (void)sg_dev_free(d->d_ddiag);
+    if (d->h_ddiag) (void)sg_host_release(d->h_ddiag);
+    for (hipEvent_t ev : d->ddiag_ev) if (ev) (void)hipEventDestroy(ev);
     sg_graph_release(&d->epoch_graph);
     delete d;
     return 0;

@@ -159,7 +159,28 @@ class _LearnerDiagnostics(object):
         return self._diag
 
 
-class GailDynLearner(_LearnerDiagnostics):
+class _DiscDiagnostics(object):
+    """update(disc_diagnostics=True): Discriminator.diagnostics is queued into slot 0 before the first discriminator epoch (the old
+    discriminator on the new rollout) and into slot 1 after the last; both are fetched on the first read of
+    last_disc_diagnostics, so a queued update keeps having no host wait."""
+    _ddiag, _ddiag_pending = None, False
+
+    def _bind_expert(self):
+        self.discr._bind_loader(self.loader)     # the first epoch would do it: the "before" launch needs the expert rows too
+
+    def _queue_disc_diagnostics(self, slot):
+        self.discr.diagnostics(self.rollouts, fetch=False, slot=slot)
+        self._ddiag_pending = slot == 1
+
+    @property
+    def last_disc_diagnostics(self):
+        if self._ddiag_pending:
+            self._ddiag = {"before": self.discr.last_diagnostics(0), "after": self.discr.last_diagnostics(1)}
+            self._ddiag_pending = False
+        return self._ddiag
+
+
+class GailDynLearner(_LearnerDiagnostics, _DiscDiagnostics):
     def __init__(self, actor_critic, agent, discr, rollouts, expert, gail_batch_size=128, gail_epoch=5,
                  gamma=0.99, gae_lambda=0.95, use_gae=True, use_proper_time_limits=True,
                  gail_tar_length=500.0, no_alive_bonus=False, use_linear_lr_decay=False, lr=None,
@@ -246,19 +267,24 @@ class GailDynLearner(_LearnerDiagnostics):
             ro.sync_to_device()
 
     # ------------------------------------------------------------- the timed part (:239-304)
-    def update(self, diagnostics=False):
+    def update(self, diagnostics=False, disc_diagnostics=False):
         ro, lib = self.rollouts, self.rollouts.lib
         if self.use_linear_lr_decay:            # :203-207
             update_linear_schedule(self.agent.optimizer, self.j, self.num_updates, self.lr)
         if ro.device_resident:
-            return self._update_resident(diagnostics)
+            return self._update_resident(diagnostics, disc_diagnostics)
         if self._rms_on_device:                 # a drop-in update after device-resident ones: bring the state back
             self._ret_rms.set_state(self.discr.scalars()[:3])
             self._rms_on_device = False
         gail = None
+        if disc_diagnostics:
+            self._bind_expert()
+            self._queue_disc_diagnostics(0)
         for e in range(self.gail_epoch):        # :255-256 -- the reference keeps the last epoch's losses only
             last = e == self.gail_epoch - 1
             gail = self.discr.update_gail_dyn(self.loader, ro, **({} if last else {"fetch_losses": False}))
+        if disc_diagnostics:
+            self._queue_disc_diagnostics(1)
         # drop-in mode: the host tensors are the rollout; every call below uploads what it reads and returns its result
         ro._push([_lib.F_MASKS])
         dones = C.c_double(0)
@@ -301,7 +327,7 @@ def _returns_resident(self):
                                                      float(self.gae_lambda), 1 if self.use_proper_time_limits else 0))
 
 
-def _gail_update_resident(self, diagnostics=False):
+def _gail_update_resident(self, diagnostics=False, disc_diagnostics=False):
     """GailDynLearner.update() on a device-resident rollout: the same call sequence, every call only QUEUES work on the
     library's stream -- discriminator epochs without their loss read-back, the alive-bonus offset from the device's done
     count, ret_rms resident in the library, GAE with get_value(obs[T]) on the device, PPO, after_update -- and the scalars
@@ -310,8 +336,13 @@ def _gail_update_resident(self, diagnostics=False):
     if not self._rms_on_device:
         self.discr.set_rms(self._ret_rms.get_state())
         self._rms_on_device = True
+    if disc_diagnostics:
+        self._bind_expert()
+        self._queue_disc_diagnostics(0)
     for _ in range(self.gail_epoch):            # :255-256
         self.discr.update_gail_dyn(self.loader, ro, fetch_losses=False)
+    if disc_diagnostics:
+        self._queue_disc_diagnostics(1)
     self.discr.relabel_rewards_auto(ro, self.gamma, self.gail_tar_length, self.no_alive_bonus)     # :258-297
     _returns_resident(self)
     self.agent.update(ro, fetch_losses=False)   # :302
