@@ -306,13 +306,25 @@ SG_API int sg_rollout_act_step_chain(sg_rollout *r, sg_policy *learner, int t, i
  * pending it is an error.  out10 != NULL is the two calls in one.
  *   - clip_param = INFINITY is accepted and gives a clip fraction of exactly 0 (A2C / ACKTR have no clip); zero, negative and NaN
  *     are errors.
- *   - with a communicator of world > 1 the statistics cover the rank's own columns; no collective is issued.
+ *   - with a communicator of world > 1 the statistics cover the rank's own columns; no collective is issued (scope "rank").
  * Policy, SplitPolicy, a Discrete / MultiBinary policy and a recurrent one are taken.  Errors, each with its own message: policy
  * and rollout on different contexts, dims that differ, a bad clip_param, a recurrent policy with neither hidden source, and a
  * policy with the CNN base. */
 #define SG_DIAG_N 10
 SG_API int sg_rollout_policy_diagnostics(sg_rollout *r, sg_policy *p, float clip_param, const float *hxs0_host, double *out10);
 SG_API int sg_rollout_policy_diagnostics_fetch(sg_rollout *r, double out10[10]);
+/* Scope "world": the same ten numbers over the union of all ranks' rows -- what one process computes on the concatenated
+ * rollout, global column = rank * N + n -- and the same bits on every rank.  The rank's workgroup records are folded into one
+ * 16-double record (plain sums, minimum / maximum, three (count, mean, M2) triples), the ranks' records are all-gathered in
+ * float64, and every rank merges them in ascending rank order (Chan's formula for the triples, so the between-rank part of a
+ * variance is kept) and finalises.  Arguments, queued form (out10 == NULL), fetch and errors are sg_rollout_policy_diagnostics's.
+ *   - THIS CALL IS A COLLECTIVE: every rank issues it, at the same point of its stream's sequence of collectives (a rank that
+ *     does not leaves its peers waiting in the all-gather).
+ *   - no communicator, or one of world 1: the rank scope's bits.
+ *   - the ranks' T*N must be equal (the global numbering assumes equal column shards).  If they differ the collective still
+ *     completes, and sg_rollout_policy_diagnostics_fetch -- or this call with out10 != NULL -- returns an error with its own
+ *     message on every rank instead of numbers. */
+SG_API int sg_rollout_policy_diagnostics_world(sg_rollout *r, sg_policy *p, float clip_param, const float *hxs0_host, double *out10);
 
 /* ---------------------------------------------------------------------- PPO */
 typedef struct {
@@ -541,12 +553,24 @@ SG_API int sg_disc_get_scalars(sg_disc *d, double out5[5]);
  * result queued into the slot and reads it, once -- with nothing pending in the slot it is an error.  out19 != NULL is the two
  * calls in one.  The rollout's OBS_FEAT must be current on the device (sg_rollout_upload).
  * With world > 1 or a sharded discriminator the numbers cover THIS rank's own rollout rows and the expert rows it holds: no
- * collective is issued.
+ * collective is issued (scope "rank").
  * Errors, each with its own message: NULL argument, slot out of range, discriminator and rollout on different contexts, rollout
  * feat_len != input_dim, no expert set. */
 #define SG_DDIAG_N 19
 SG_API int sg_disc_diagnostics(sg_disc *d, sg_rollout *r, int slot, double *out19);
 SG_API int sg_disc_diagnostics_fetch(sg_disc *d, int slot, double out19[SG_DDIAG_N]);
+/* Scope "world": the same nineteen numbers over the union of all ranks' rollout rows -- what one process computes on the
+ * concatenated rollout -- and the same bits on every rank, in both discriminator data-parallel modes (sg_ctx_set_disc_dp 0 and
+ * 1).  Per population: the policy and mid parts of the ranks' folded 36-double records are merged in ascending rank order after
+ * a float64 all-gather; every rank holds the whole expert matrix, so the expert part is rank 0's, not a merge, and expert_rows
+ * is n_e.  Mid row (t, n) of rank k is paired with expert[(t * world * N + k * N + n) mod n_e], the pairing of its row number in
+ * the concatenated rollout.  Slots, queued form, fetch and errors are sg_disc_diagnostics's, and world * T*N < 2^31.
+ *   - THIS CALL IS A COLLECTIVE: every rank issues it, at the same point of its stream's sequence of collectives.
+ *   - no communicator, or one of world 1: the rank scope's bits.
+ *   - the ranks' T*N must be equal, and so must their n_e.  If either differs the collective still completes, and
+ *     sg_disc_diagnostics_fetch -- or this call with out19 != NULL -- returns an error with its own message on every rank
+ *     instead of numbers. */
+SG_API int sg_disc_diagnostics_world(sg_disc *d, sg_rollout *r, int slot, double *out19);
 /* sum(1 - masks) over all T+1 slots (a2c/main_gail_dyn_ppo.py:258), for the alive-bonus offset. */
 SG_API int sg_rollout_count_dones(sg_rollout *r, double *dones);
 

@@ -102,6 +102,7 @@ PROTOTYPES = {
                                             c_float_p, c_float_p, c_float_p]),
     "sg_rollout_policy_diagnostics": (C.c_int, [H, H, C.c_float, c_float_p, c_double_p]),
     "sg_rollout_policy_diagnostics_fetch": (C.c_int, [H, c_double_p]),
+    "sg_rollout_policy_diagnostics_world": (C.c_int, [H, H, C.c_float, c_float_p, c_double_p]),
     "sg_ppo_set_hidden_states_rollout": (C.c_int, [H, H]),
     "sg_ppo_create": (C.c_int, [H, H, C.POINTER(PPOConfig), C.POINTER(H)]),
     "sg_ppo_destroy": (C.c_int, [H]),
@@ -146,6 +147,7 @@ PROTOTYPES = {
     "sg_disc_get_scalars": (C.c_int, [H, c_double_p]),
     "sg_disc_diagnostics": (C.c_int, [H, H, C.c_int, c_double_p]),
     "sg_disc_diagnostics_fetch": (C.c_int, [H, C.c_int, c_double_p]),
+    "sg_disc_diagnostics_world": (C.c_int, [H, H, C.c_int, c_double_p]),
     "sg_results_publish": (C.c_int, [H, H, H, C.c_int]),
     "sg_results_fetch": (C.c_int, [H, C.c_int, c_double_p]),
     "sg_ctx_profile": (C.c_int, [H, C.c_int]),

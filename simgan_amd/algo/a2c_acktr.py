@@ -184,11 +184,12 @@ class A2C_ACKTR():
             self._steps += 1
         return (float(out[0]), float(out[1]), float(out[2])) if fetch_losses else None
 
-    def diagnostics(self, rollouts, fetch=True):
+    def diagnostics(self, rollouts, fetch=True, scope="rank"):
         """PPO.diagnostics for A2C / ACKTR (both modes): the same ten numbers with clip_param = inf, so clip_fraction is exactly
         0 -- neither learner clips a ratio; approx_kl is the measured KL to set beside ACKTR's kl_clip.  The rollout's
-        action_log_probs and value_preds (the collection's) are read, which update() itself does not need."""
-        return _diag.run(self, rollouts, float("inf"), fetch)
+        action_log_probs and value_preds (the collection's) are read, which update() itself does not need.  scope: PPO's; A2C and
+        ACKTR run at world 1, where "world" gives the rank scope's bits."""
+        return _diag.run(self, rollouts, float("inf"), fetch, scope)
 
     def last_diagnostics(self):
         return _diag.fetch_last(self)

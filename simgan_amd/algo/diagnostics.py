@@ -17,14 +17,26 @@ DISC_NAMES = ("policy_rows", "expert_rows", "policy_accuracy", "expert_accuracy"
               "policy_grad_norm_mean", "expert_grad_norm_mean", "mid_grad_norm_mean", "mid_grad_pen", "grad_norm_max")
 
 
+SCOPES = ("rank", "world")
+
+
+def check_scope(scope):
+    """"rank": this rank's rows, no collective.  "world": all ranks' rows, the same bits on every rank -- a collective, which every
+    rank issues at the same point of its stream's collectives.  Anything else is a ValueError, before any device call."""
+    if not (isinstance(scope, str) and scope in SCOPES):
+        raise ValueError(f'scope = {scope!r}: "rank" or "world"')
+    return scope
+
+
 def _as_dict(out):
     return {k: float(out[i]) for i, k in enumerate(NAMES)}
 
 
-def run(agent, rollouts, clip_param, fetch=True):
+def run(agent, rollouts, clip_param, fetch=True, scope="rank"):
     """Pushes the fields the launch reads (as update() does: a host-resident rollout works and gives the device-resident one's
     numbers), hands a recurrent policy the hidden states of slot 0 the way PPO.update does, and queues the two launches.
-    fetch=True: wait and return the dict of NAMES; False: return None (fetch_last reads the result later)."""
+    fetch=True: wait and return the dict of NAMES; False: return None (fetch_last reads the result later).  scope: check_scope."""
+    call = {"rank": "sg_rollout_policy_diagnostics", "world": "sg_rollout_policy_diagnostics_world"}[check_scope(scope)]
     pol = agent.actor_critic
     rollouts._push([_lib.F_OBS, _lib.F_ACTIONS, _lib.F_VALUE_PREDS, _lib.F_RETURNS, _lib.F_LOGP])
     hxs0 = None
@@ -38,8 +50,8 @@ def run(agent, rollouts, clip_param, fetch=True):
                                  f"[{rollouts.num_processes}, {pol.recurrent_hidden_state_size}] (build RolloutStorage with "
                                  "actor_critic.recurrent_hidden_state_size)")
     out = (C.c_double * len(NAMES))()
-    _lib.check(agent.lib.sg_rollout_policy_diagnostics(rollouts.h, pol.h, float(clip_param), None if hxs0 is None else _lib.fptr(hxs0),
-                                                       out if fetch else None))
+    _lib.check(getattr(agent.lib, call)(rollouts.h, pol.h, float(clip_param), None if hxs0 is None else _lib.fptr(hxs0),
+                                        out if fetch else None))
     agent._diag_rollouts = None if fetch else rollouts
     return _as_dict(out) if fetch else None
 
@@ -55,13 +67,14 @@ def fetch_last(agent):
     return _as_dict(out)
 
 
-def run_disc(disc, rollouts, fetch=True, slot=0):
+def run_disc(disc, rollouts, fetch=True, slot=0, scope="rank"):
     """Discriminator.diagnostics: pushes OBS_FEAT as the other discriminator calls do (a host-resident rollout gives the
     device-resident one's numbers) and queues the two launches into `slot`.  fetch=True: wait and return the dict of DISC_NAMES;
-    False: return None (fetch_disc reads the slot later)."""
+    False: return None (fetch_disc reads the slot later).  scope: check_scope."""
+    call = {"rank": "sg_disc_diagnostics", "world": "sg_disc_diagnostics_world"}[check_scope(scope)]
     rollouts._push([_lib.F_OBS_FEAT])
     out = (C.c_double * len(DISC_NAMES))()
-    _lib.check(disc.lib.sg_disc_diagnostics(disc.h, rollouts.h, int(slot), out if fetch else None))
+    _lib.check(getattr(disc.lib, call)(disc.h, rollouts.h, int(slot), out if fetch else None))
     return {k: float(out[i]) for i, k in enumerate(DISC_NAMES)} if fetch else None
 
 

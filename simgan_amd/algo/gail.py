@@ -350,9 +350,19 @@ class Discriminator(object):
         distribution, and the input-gradient norm on both and on the mixup rows at alpha = 0.5, in two queued launches
         (include/simgan_hip.h: sg_disc_diagnostics) -> dict in algo.diagnostics.DISC_NAMES order.  Changes no state.  The expert
         matrix is the one of the last update / set_expert.  fetch=False: None, without a host wait; last_diagnostics(slot)
-        reads the result later.  slot 0 or 1: two results may be pending."""
+        reads the result later.  slot 0 or 1: two results may be pending.  With world > 1 these are this rank's rows (the
+        rank scope, no collective); diagnostics_world is the world scope."""
         from . import diagnostics as _diag
         return _diag.run_disc(self, rollouts, fetch, slot)
+
+    def diagnostics_world(self, rollouts, fetch=True, slot=0):
+        """diagnostics in the world scope (include/simgan_hip.h: sg_disc_diagnostics_world; algo.diagnostics.run_disc with
+        scope="world"): the same nineteen numbers over ALL ranks' rollout rows, the same bits on every rank, policy_rows =
+        world * T*N and expert_rows = n_e, in either discriminator data-parallel mode.  A collective: every rank issues it at the
+        same point of its stream's collectives.  Slots and last_diagnostics(slot) are shared with diagnostics; without a
+        communicator, or with one rank, it returns diagnostics' bits."""
+        from . import diagnostics as _diag
+        return _diag.run_disc(self, rollouts, fetch, slot, "world")
 
     def last_diagnostics(self, slot=0):
         """The pending result of diagnostics(..., fetch=False, slot=slot); an error when none is pending in that slot."""

@@ -178,13 +178,15 @@ class PPO():
         self._last_perm_shape = (self.ppo_epoch, rollouts.num_processes if self.recurrent else rollouts.num_steps * rollouts.num_processes)
         return (float(out[0]), float(out[1]), float(out[2])) if fetch_losses else None
 
-    def diagnostics(self, rollouts, fetch=True):
+    def diagnostics(self, rollouts, fetch=True, scope="rank"):
         """What one looks at after an update, over the rollout's T*N rows and the policy's current parameters, computed on the
         device (include/simgan_hip.h: sg_rollout_policy_diagnostics) -> {rows, approx_kl, approx_kl_k3, clip_fraction (at this
         agent's clip_param), entropy, ratio_min, ratio_max, explained_variance_old, explained_variance_new, value_mse}.
         fetch=False: queue it, return None without waiting; last_diagnostics() reads it later.  Call it before
-        rollouts.after_update(), which overwrites obs[0]."""
-        return _diag.run(self, rollouts, self.clip_param, fetch)
+        rollouts.after_update(), which overwrites obs[0].  scope="rank": this rank's rows, no collective.  scope="world"
+        (sg_rollout_policy_diagnostics_world): all ranks' rows, the same bits on every rank, rows = world * T*N -- a collective
+        that every rank issues at the same point; the rank scope's bits without a communicator."""
+        return _diag.run(self, rollouts, self.clip_param, fetch, scope)
 
     def last_diagnostics(self):
         return _diag.fetch_last(self)

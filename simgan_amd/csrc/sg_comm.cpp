@@ -711,3 +711,11 @@ int sg_comm_allgather_f32(sg_ctx* ctx, const float* dev_in, float* dev_out, int6
     SG_NCCL(g_rccl.AllGather(dev_in, dev_out, (size_t)n_per_rank, ncclFloat32, ctx->comm->comm, ctx->stream));
     return 0;
 }
+
+// ncclAllGather places rank r's block at out[r * n_per_rank], the loopback concatenates in rank order: ascending on both.
+int sg_comm_allgather_f64(sg_ctx* ctx, const double* dev_in, double* dev_out, int64_t n_per_rank) {
+    SG_REQUIRE(ctx->comm, "all-gather requested but no communicator (call sg_ctx_comm_init)");
+    if (ctx->comm->lb) return lb_collective(ctx, 1, dev_in, dev_out, (size_t)n_per_rank, 8);
+    SG_NCCL(g_rccl.AllGather(dev_in, dev_out, (size_t)n_per_rank, ncclFloat64, ctx->comm->comm, ctx->stream));
+    return 0;
+}

@@ -522,3 +522,5 @@ int sg_rollout_count_dones_dev(sg_rollout* r, double* d_out);
 int sg_comm_allreduce_f32(sg_ctx* ctx, float* dev, int64_t n);
 int sg_comm_allreduce_f64(sg_ctx* ctx, double* dev, int64_t n);
 int sg_comm_allgather_f32(sg_ctx* ctx, const float* dev_in, float* dev_out, int64_t n_per_rank);
+// n_per_rank doubles of every rank, in ascending rank order on both transports; queued on the context's stream like the others
+int sg_comm_allgather_f64(sg_ctx* ctx, const double* dev_in, double* dev_out, int64_t n_per_rank);

@@ -9,6 +9,10 @@
 // Two launches, queued on the context's stream: k_policy_diag (one partial record per workgroup) and k_policy_diag_reduce; a
 // recurrent policy runs the GRU forward of sg_gru.hip over the rollout first.  Nothing but the record block and the ten results
 // is written.
+// Scope "rank" (sg_rollout_policy_diagnostics): this rank's rows, no collective.  Scope "world"
+// (sg_rollout_policy_diagnostics_world): the statistic over the union of all ranks' rows, the same bits on every rank -- the
+// rank's records folded into one, sg_comm_allgather_f64 of the ranks' folded records, the same fold + finalise over those in
+// ascending rank order.  That call is a collective: every rank issues it at the same point of its stream's collectives.
 #include <math.h>
 #include <string.h>
 
@@ -181,7 +185,14 @@ __device__ __forceinline__ void dg_merge(double* a, const double* b) {
 
 // One workgroup of one wave.  The nrec records are merged in ascending workgroup order, all in double, in two levels: lane i
 // folds the contiguous run [i * per, (i + 1) * per) of them, in order, into its own record, then lane 0 folds the 64 lane
-// records, in order.  The shape of that tree depends on nrec alone.  out[SG_DIAG_N]: include/simgan_hip.h.
+// records, in order.  The shape of that tree depends on nrec alone.  Folding a record into the empty accumulator leaves the
+// record's bits (0 + x, min(inf, x), Chan's update at na = 0), so one record through this fold is that record.
+//   DG_FINAL  the fold, then the ten results: out[SG_DIAG_N] (include/simgan_hip.h), and out[SG_DIAG_N] itself = 0
+//   DG_FOLD   the fold alone: out[DG_REC] is the folded record (plain sums, minimum / maximum, the three triples)
+//   DG_WORLD  DG_FINAL over the ranks' folded records in ascending rank order (nrec = world <= 64: one record per lane);
+//             out[SG_DIAG_N] = 1 if the ranks' row counts differ -- the fetch then refuses the numbers
+enum { DG_FINAL = 0, DG_FOLD, DG_WORLD };
+template <int MODE>
 __global__ __launch_bounds__(64) void k_policy_diag_reduce(const double* rec, int nrec, double* out) {
     __shared__ double part[64][DG_REC + 1];
     const int lane = threadIdx.x;
@@ -207,6 +218,11 @@ __global__ __launch_bounds__(64) void k_policy_diag_reduce(const double* rec, in
         for (int k = 0; k < DG_REC; ++k) b[k] = part[j][k];
         dg_merge(acc, b);
     }
+    if (MODE == DG_FOLD) {
+#pragma unroll
+        for (int k = 0; k < DG_REC; ++k) out[k] = acc[k];
+        return;
+    }
     const double n = acc[DG_CNT];
     const double var_ret = acc[DG_RET_M2] / n;   // population variances; 0 / 0 is NaN, as numpy's 1 - var(e) / var(ret) is
     out[0] = n;
@@ -219,6 +235,11 @@ __global__ __launch_bounds__(64) void k_policy_diag_reduce(const double* rec, in
     out[7] = 1.0 - (acc[DG_EO_M2] / n) / var_ret;
     out[8] = 1.0 - (acc[DG_EN_M2] / n) / var_ret;
     out[9] = acc[DG_SQ] / n;
+    double differ = 0.0;
+    if (MODE == DG_WORLD)
+        for (int i = 1; i < nrec; ++i)
+            if (rec[(size_t)i * DG_REC + DG_CNT] != rec[DG_CNT]) differ = 1.0;
+    out[SG_DIAG_N] = differ;
 }
 
 // LDS of one workgroup: k_policy_act_step's layout (weights of one trunk | X | H1 | H2 | every trunk's head outputs)
@@ -227,22 +248,24 @@ static size_t diag_lds_bytes(const SgPolicyDesc& d, int MT, bool gw) {
     return sizeof(float) * (size_t)((gw ? 0 : max_trunk_size(d, 0, d.n_trunks)) + R * d.ldO + 2 * R * d.ldH + d.n_trunks * R * max_ldP(d));
 }
 
-extern "C" int sg_rollout_policy_diagnostics(sg_rollout* r, sg_policy* p, float clip_param, const float* hxs0_host, double* out10) {
-    SG_REQUIRE(r && p, "sg_rollout_policy_diagnostics: NULL argument");
-    SG_REQUIRE(p->ctx == r->ctx, "sg_rollout_policy_diagnostics: the policy and the rollout live on different contexts");
-    SG_REQUIRE(!p->cnn, "sg_rollout_policy_diagnostics: the policy has the CNN base (image observations); the diagnostics launch runs "
-               "the MLP trunks only: evaluate the rollout through sg_policy_evaluate and reduce on the host");
+// Both scopes.  `who` names the entry point in the messages (the rank scope's are pinned by its tests).
+static int policy_diagnostics(const char* who, bool world_scope, sg_rollout* r, sg_policy* p, float clip_param, const float* hxs0_host,
+                              double* out10) {
+    SG_REQUIRE(r && p, "%s: NULL argument", who);
+    SG_REQUIRE(p->ctx == r->ctx, "%s: the policy and the rollout live on different contexts", who);
+    SG_REQUIRE(!p->cnn, "%s: the policy has the CNN base (image observations); the diagnostics launch runs "
+               "the MLP trunks only: evaluate the rollout through sg_policy_evaluate and reduce on the host", who);
     const int O = p->recurrent ? p->gru.O : p->desc.O;
-    SG_REQUIRE(O == r->O && p->desc.A == r->A, "sg_rollout_policy_diagnostics: policy/rollout dims differ (obs %d vs %d, action %d vs %d)",
+    SG_REQUIRE(O == r->O && p->desc.A == r->A, "%s: policy/rollout dims differ (obs %d vs %d, action %d vs %d)", who,
                O, r->O, p->desc.A, r->A);
-    SG_REQUIRE(clip_param > 0.f, "sg_rollout_policy_diagnostics: clip_param = %g: it must be positive (INFINITY is accepted and gives "
-               "a clip fraction of 0)", (double)clip_param);
+    SG_REQUIRE(clip_param > 0.f, "%s: clip_param = %g: it must be positive (INFINITY is accepted and gives "
+               "a clip fraction of 0)", who, (double)clip_param);
     if (p->recurrent && r->d_hidden)
-        SG_REQUIRE(r->hidden_dim == p->gru.H, "sg_rollout_policy_diagnostics: the rollout's hidden states are %d wide, the policy's %d",
+        SG_REQUIRE(r->hidden_dim == p->gru.H, "%s: the rollout's hidden states are %d wide, the policy's %d", who,
                    r->hidden_dim, p->gru.H);
-    SG_REQUIRE(!p->recurrent || r->d_hidden || hxs0_host, "sg_rollout_policy_diagnostics: the policy is recurrent and the rollout holds "
-               "no hidden states (sg_rollout_enable_hidden): hxs0_host, the N*H states of slot 0, is required");
-    SG_REQUIRE((int64_t)r->T * r->N < (1ll << 30), "sg_rollout_policy_diagnostics: T*N = %lld rows: fewer than 2^30 are taken",
+    SG_REQUIRE(!p->recurrent || r->d_hidden || hxs0_host, "%s: the policy is recurrent and the rollout holds "
+               "no hidden states (sg_rollout_enable_hidden): hxs0_host, the N*H states of slot 0, is required", who);
+    SG_REQUIRE((int64_t)r->T * r->N < (1ll << 30), "%s: T*N = %lld rows: fewer than 2^30 are taken", who,
                (long long)r->T * r->N);
     sg_ctx* ctx = r->ctx;
     const SgPolicyDesc& d = p->desc;
@@ -253,15 +276,18 @@ extern "C" int sg_rollout_policy_diagnostics(sg_rollout* r, sg_policy* p, float 
     const bool gw = sg_policy_needs_gw(ctx, d) || diag_lds_bytes(d, 1, false) > room;
     int MT = fwd_tile_mt(ctx, d, n, gw);
     while (MT > 1 && diag_lds_bytes(d, MT, gw) > room) MT /= 2;
-    SG_REQUIRE(diag_lds_bytes(d, MT, gw) <= room, "sg_rollout_policy_diagnostics: a 16-row tile of this policy with every trunk's head "
-               "outputs (%zu B) does not fit the %d-byte LDS", diag_lds_bytes(d, MT, gw), ctx->lds_bytes);
+    SG_REQUIRE(diag_lds_bytes(d, MT, gw) <= room, "%s: a 16-row tile of this policy with every trunk's head "
+               "outputs (%zu B) does not fit the %d-byte LDS", who, diag_lds_bytes(d, MT, gw), ctx->lds_bytes);
     SG_CHECK(hipSetDevice(ctx->device));
     const int R = 16 * MT, gx = (n + R - 1) / R;
     if (!r->h_diag) {
         SG_CHECK(sg_host_malloc((void**)&r->h_diag, sizeof(double) * 16));
         SG_CHECK(hipEventCreateWithFlags(&r->diag_ev, hipEventDisableTiming));
     }
-    SG_TRY(ensure_cap(ctx->stream, &r->d_diag, &r->diag_cap, (size_t)gx * DG_REC));
+    // world scope: behind the workgroups' records, this rank's folded record and the world's gathered ones
+    const bool gather = world_scope && ctx->comm;
+    const int world = gather ? ctx->world : 1;
+    SG_TRY(ensure_cap(ctx->stream, &r->d_diag, &r->diag_cap, (size_t)gx * DG_REC + (world_scope ? (size_t)(1 + world) * DG_REC : 0)));
     DiagArgs a;
     a.x = r->d_field[SG_F_OBS];
     if (p->recurrent) {
@@ -290,7 +316,16 @@ extern "C" int sg_rollout_policy_diagnostics(sg_rollout* r, sg_policy* p, float 
         hipLaunchKernelGGL((k_policy_diag<decltype(mt)::value, decltype(g)::value>), dim3(gx), dim3(256), lds, ctx->stream, a);
     });
     SG_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_policy_diag_reduce, dim3(1), dim3(64), 0, ctx->stream, r->d_diag, gx, r->h_diag);
+    if (!world_scope) {
+        hipLaunchKernelGGL(k_policy_diag_reduce<DG_FINAL>, dim3(1), dim3(64), 0, ctx->stream, r->d_diag, gx, r->h_diag);
+    } else {
+        double* mine = r->d_diag + (size_t)gx * DG_REC;
+        double* all = mine + DG_REC;
+        hipLaunchKernelGGL(k_policy_diag_reduce<DG_FOLD>, dim3(1), dim3(64), 0, ctx->stream, r->d_diag, gx, mine);
+        SG_CHECK(hipGetLastError());
+        if (gather) SG_TRY(sg_comm_allgather_f64(ctx, mine, all, DG_REC));
+        hipLaunchKernelGGL(k_policy_diag_reduce<DG_WORLD>, dim3(1), dim3(64), 0, ctx->stream, gather ? all : mine, world, r->h_diag);
+    }
     SG_CHECK(hipGetLastError());
     SG_CHECK(hipEventRecord(r->diag_ev, ctx->stream));
     r->diag_pending = true;
@@ -298,12 +333,26 @@ extern "C" int sg_rollout_policy_diagnostics(sg_rollout* r, sg_policy* p, float 
     return 0;
 }
 
+extern "C" int sg_rollout_policy_diagnostics(sg_rollout* r, sg_policy* p, float clip_param, const float* hxs0_host, double* out10) {
+    return policy_diagnostics("sg_rollout_policy_diagnostics", false, r, p, clip_param, hxs0_host, out10);
+}
+
+// The world scope: k_policy_diag, the fold alone, the all-gather of the ranks' 16-double records, fold + finalise over them.
+// A COLLECTIVE: every rank issues it at the same point of its stream's sequence of collectives.  No communicator: the rank
+// scope's bits (the folded record through the second fold is itself).
+extern "C" int sg_rollout_policy_diagnostics_world(sg_rollout* r, sg_policy* p, float clip_param, const float* hxs0_host, double* out10) {
+    return policy_diagnostics("sg_rollout_policy_diagnostics_world", true, r, p, clip_param, hxs0_host, out10);
+}
+
 extern "C" int sg_rollout_policy_diagnostics_fetch(sg_rollout* r, double out10[10]) {
     SG_REQUIRE(r && out10, "sg_rollout_policy_diagnostics_fetch: NULL argument");
     SG_REQUIRE(r->diag_pending, "sg_rollout_policy_diagnostics_fetch: no diagnostics are pending on this rollout (queue them with "
                "sg_rollout_policy_diagnostics(..., out10 = NULL) first; a result is fetched once)");
     SG_CHECK(hipEventSynchronize(r->diag_ev));
-    memcpy(out10, r->h_diag, sizeof(double) * SG_DIAG_N);
     r->diag_pending = false;
+    SG_REQUIRE(r->h_diag[SG_DIAG_N] == 0.0, "sg_rollout_policy_diagnostics_fetch: the ranks of the world scope hold different numbers of "
+               "rows (this rank: T*N = %lld): the global numbering takes equal column shards, no numbers are returned",
+               (long long)r->T * r->N);
+    memcpy(out10, r->h_diag, sizeof(double) * SG_DIAG_N);
     return 0;
 }

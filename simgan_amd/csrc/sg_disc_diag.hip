@@ -10,6 +10,11 @@
 //   and the numpy reductions a caller would run on the downloaded arrays.
 // Two launches, queued on the context's stream: k_disc_diag (one partial record per workgroup) and k_disc_diag_reduce.  Nothing
 // but the record block and the SG_DDIAG_N results of the slot is written.
+// Scope "rank" (sg_disc_diagnostics): this rank's rows, no collective.  Scope "world" (sg_disc_diagnostics_world): the statistic
+// over the union of all ranks' rows, the same bits on every rank -- the rank's records folded into one, sg_comm_allgather_f64 of
+// the ranks' folded records, the same fold + finalise over those in ascending rank order; the expert part is rank 0's and mid
+// row (t, n) of rank k pairs with expert row (t * world * N + k * N + n) mod n_e, as one launch on the concatenated rollout
+// would.  That call is a collective: every rank issues it at the same point of its stream's collectives.
 #include <math.h>
 #include <string.h>
 
@@ -38,6 +43,7 @@ struct DiscDiagArgs {
     const float* expert;     // [n_e, F]
     int n_p, n_e;
     int tiles_p, tiles_e;    // 32-row tiles of the policy (and mid) rows, of the expert rows
+    int cols, cols_g, col0;  // the mid pairing: this rank's columns N, the world's, this rank's first (rank scope: N, N, 0)
     double* rec;             // [gridDim.x][DD_REC]
 };
 
@@ -86,8 +92,9 @@ static size_t disc_diag_lds_bytes(const SgDiscDesc& d, bool gw) {
 }
 
 // Row tiles as in k_disc_forward: 32 rows, 256 threads, a capped grid with trips over the remaining tiles.  The tiles are
-// numbered policy | expert | mid; a tile lies in one population.  mid row i is 0.5f * expert[i mod n_e] + 0.5f * policy[i]
-// (a2c/algo/gail.py:72-75 at alpha = 0.5), formed while the tile is staged.  Per tile:
+// numbered policy | expert | mid; a tile lies in one population.  mid row i is 0.5f * expert[g mod n_e] + 0.5f * policy[i]
+// (a2c/algo/gail.py:72-75 at alpha = 0.5), formed while the tile is staged; g is row i = t * cols + n in the world's numbering,
+// t * cols_g + col0 + n (< 2^31: the launcher), which is i itself at cols_g = cols, col0 = 0.  Per tile:
 //   H1 = tanh(X W1^T + b1), H2 = tanh(H1 W2^T + b2), d = H2 . w3 + b3                            (k_disc_forward's forward)
 //   D2 = w3 (1 - H2^2) (over H2), D1 = (D2 W2) (1 - H1^2) (over H1), G = D1 W1 (over X), |g| = ||G||_2 per row
 // every contraction an LDS-tile fp32 MFMA GEMM.  Then one lane of wave 0 per row forms the row's terms -- the reward by
@@ -132,8 +139,11 @@ __global__ __launch_bounds__(256) void k_disc_diag(DiscDiagArgs a) {
                     const bool in = i < R * Fp && c < F;
                     v[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, in ? (r * F + c) * 4 : 0x7ffffff0, 0, 0));
                     e[u] = 0.f;
-                    if (pop == DD_MID)
-                        e[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(re, in ? (((base + r) % a.n_e) * F + c) * 4 : 0x7ffffff0, 0, 0));
+                    if (pop == DD_MID) {
+                        const unsigned t = (unsigned)(base + r) / (unsigned)a.cols;
+                        const unsigned g = t * (unsigned)a.cols_g + (unsigned)a.col0 + ((unsigned)(base + r) - t * (unsigned)a.cols);
+                        e[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(re, in ? (int)((g % (unsigned)a.n_e) * F + c) * 4 : 0x7ffffff0, 0, 0));
+                    }
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -211,16 +221,26 @@ __global__ __launch_bounds__(256) void k_disc_diag(DiscDiagArgs a) {
 
 // One workgroup of one wave.  Population by population, the nrec records' parts are merged in ascending workgroup order, all in
 // double, in two levels: lane i folds the contiguous run [i * per, (i + 1) * per) of them, in order, into its own part, then
-// lane 0 folds the 64 lane parts, in order.  The shape of that tree depends on nrec alone.  out[SG_DDIAG_N]: include/simgan_hip.h.
+// lane 0 folds the 64 lane parts, in order.  The shape of that tree depends on nrec alone.  A part folded into the empty
+// accumulator keeps its bits, so one record through this fold is that record.
+//   DD_FINAL  the fold, then the results: out[SG_DDIAG_N] (include/simgan_hip.h), and out[SG_DDIAG_N] itself = 0
+//   DD_FOLD   the fold alone: out[DD_REC] is the folded record
+//   DD_WORLD  DD_FINAL over the ranks' folded records in ascending rank order -- the policy and mid parts; every rank holds the
+//             whole expert matrix (sg_disc_set_expert; the update slices the batch by rank, not the matrix), so the world's expert
+//             population is one rank's: rank 0's part is taken, none merged.  out[SG_DDIAG_N] = 1 if the ranks' policy row
+//             counts differ, + 2 if their expert row counts do -- the fetch then refuses the numbers
+enum { DD_FINAL = 0, DD_FOLD, DD_WORLD };
+template <int MODE>
 __global__ __launch_bounds__(64) void k_disc_diag_reduce(const double* rec, int nrec, double* out) {
     __shared__ double part[64][DD_POP + 1];
     const int lane = threadIdx.x;
     const int per = (nrec + 63) / 64;
     double g_max = -INFINITY;
     for (int pop = 0; pop < 3; ++pop) {
+        const int npop = MODE == DD_WORLD && pop == DD_EXPERT ? 1 : nrec;
         double acc[DD_POP];
         dd_clear(acc);
-        for (int i = lane * per; i < nrec && i < (lane + 1) * per; ++i) {
+        for (int i = lane * per; i < npop && i < (lane + 1) * per; ++i) {
             double b[DD_POP];
 #pragma unroll
             for (int k = 0; k < DD_POP; ++k) b[k] = rec[(size_t)i * DD_REC + pop * DD_POP + k];
@@ -236,6 +256,11 @@ __global__ __launch_bounds__(64) void k_disc_diag_reduce(const double* rec, int 
 #pragma unroll
             for (int k = 0; k < DD_POP; ++k) b[k] = part[j][k];
             dd_merge(acc, b);
+        }
+        if (MODE == DD_FOLD) {
+#pragma unroll
+            for (int k = 0; k < DD_POP; ++k) out[pop * DD_POP + k] = acc[k];
+            continue;
         }
         const double n = acc[DD_CNT];
         g_max = fmax(g_max, acc[DD_G_MAX]);
@@ -261,26 +286,43 @@ __global__ __launch_bounds__(64) void k_disc_diag_reduce(const double* rec, int 
             out[16] = acc[DD_G_SUM] / n;
             out[17] = 10.0 * (acc[DD_PEN] / n);  // lambda = 10, a2c/algo/gail.py:67
             out[18] = g_max;
+            double differ = 0.0;
+            if (MODE == DD_WORLD) {
+                bool rows = false, experts = false;
+                for (int i = 1; i < nrec; ++i) {
+                    rows |= rec[(size_t)i * DD_REC + DD_POLICY * DD_POP + DD_CNT] != rec[DD_POLICY * DD_POP + DD_CNT];
+                    experts |= rec[(size_t)i * DD_REC + DD_EXPERT * DD_POP + DD_CNT] != rec[DD_EXPERT * DD_POP + DD_CNT];
+                }
+                differ = (rows ? 1.0 : 0.0) + (experts ? 2.0 : 0.0);
+            }
+            out[SG_DDIAG_N] = differ;
         }
     }
 }
 
-extern "C" int sg_disc_diagnostics(sg_disc* d, sg_rollout* r, int slot, double* out19) {
-    SG_REQUIRE(d && r, "sg_disc_diagnostics: NULL argument");
-    SG_REQUIRE(slot == 0 || slot == 1, "sg_disc_diagnostics: slot %d is out of range (two results may be pending: slot 0 or 1)", slot);
-    SG_REQUIRE(d->ctx == r->ctx, "sg_disc_diagnostics: the discriminator and the rollout live on different contexts");
-    SG_REQUIRE(r->F == d->desc.F, "sg_disc_diagnostics: rollout feat_len %d != discriminator input_dim %d", r->F, d->desc.F);
-    SG_REQUIRE(d->d_expert && d->n_expert > 0, "sg_disc_diagnostics: no expert data (call sg_disc_set_expert first)");
-    SG_REQUIRE((int64_t)r->T * r->N < (1ll << 30), "sg_disc_diagnostics: T*N = %lld rows: fewer than 2^30 are taken", (long long)r->T * r->N);
-    SG_REQUIRE(d->n_expert * d->desc.F < (1ll << 29), "sg_disc_diagnostics: an expert matrix of %lld x %d floats: fewer than 2^29 are taken",
+// Both scopes.  `who` names the entry point in the messages (the rank scope's are pinned by its tests).
+static int disc_diagnostics(const char* who, bool world_scope, sg_disc* d, sg_rollout* r, int slot, double* out19) {
+    SG_REQUIRE(d && r, "%s: NULL argument", who);
+    SG_REQUIRE(slot == 0 || slot == 1, "%s: slot %d is out of range (two results may be pending: slot 0 or 1)", who, slot);
+    SG_REQUIRE(d->ctx == r->ctx, "%s: the discriminator and the rollout live on different contexts", who);
+    SG_REQUIRE(r->F == d->desc.F, "%s: rollout feat_len %d != discriminator input_dim %d", who, r->F, d->desc.F);
+    SG_REQUIRE(d->d_expert && d->n_expert > 0, "%s: no expert data (call sg_disc_set_expert first)", who);
+    SG_REQUIRE((int64_t)r->T * r->N < (1ll << 30), "%s: T*N = %lld rows: fewer than 2^30 are taken", who, (long long)r->T * r->N);
+    SG_REQUIRE(d->n_expert * d->desc.F < (1ll << 29), "%s: an expert matrix of %lld x %d floats: fewer than 2^29 are taken", who,
                (long long)d->n_expert, d->desc.F);
     sg_ctx* ctx = d->ctx;
     const SgDiscDesc& dd = d->desc;
+    // world scope: the ranks' records are gathered when there is a communicator, and a mid row pairs with the expert row of its
+    // number in the world's rollout
+    const bool gather = world_scope && ctx->comm;
+    const int world = gather ? ctx->world : 1, rank = gather ? ctx->rank : 0;
+    SG_REQUIRE((int64_t)world * r->T * r->N < (1ll << 31), "%s: %d ranks of T*N = %lld rows: fewer than 2^31 rows in the world are taken",
+               who, world, (long long)r->T * r->N);
     // the weight path of the forward launch (SG_DISC_GW=1 forces global weights), or the image does not fit beside this tile
     const bool gw = sg_disc_needs_gw(ctx, dd) || disc_diag_lds_bytes(dd, false) > (size_t)ctx->lds_bytes;
     const size_t lds = disc_diag_lds_bytes(dd, gw);
-    SG_REQUIRE(lds <= (size_t)ctx->lds_bytes, "sg_disc_diagnostics: the activation tiles of a (%d x %d) discriminator need %zu bytes of LDS, "
-               "the CU has %d", dd.F, dd.Hd, lds, ctx->lds_bytes);
+    SG_REQUIRE(lds <= (size_t)ctx->lds_bytes, "%s: the activation tiles of a (%d x %d) discriminator need %zu bytes of LDS, "
+               "the CU has %d", who, dd.F, dd.Hd, lds, ctx->lds_bytes);
     SG_CHECK(hipSetDevice(ctx->device));
     if (!d->h_ddiag) {
         SG_CHECK(sg_host_malloc((void**)&d->h_ddiag, sizeof(double) * 2 * SG_DDIAG_STRIDE));
@@ -292,20 +334,44 @@ extern "C" int sg_disc_diagnostics(sg_disc* d, sg_rollout* r, int slot, double* 
     a.expert = d->d_expert;
     a.n_p = r->T * r->N; a.n_e = (int)d->n_expert;
     a.tiles_p = (a.n_p + 31) / 32; a.tiles_e = (a.n_e + 31) / 32;
+    a.cols = r->N; a.cols_g = world * r->N; a.col0 = rank * r->N;
     int grid = 2 * a.tiles_p + a.tiles_e;
     if (grid > 2 * ctx->num_cu) grid = 2 * ctx->num_cu;
-    // (sized for the capped grid once: a result pending in the other slot never sees the block move)
-    SG_TRY(ensure_cap(ctx->stream, &d->d_ddiag, &d->ddiag_cap, (size_t)2 * ctx->num_cu * DD_REC));
+    // (sized for the capped grid once, with the world scope's folded record and the ranks' gathered ones behind it: a result
+    // pending in the other slot never sees the block move)
+    const size_t grid_doubles = (size_t)2 * ctx->num_cu * DD_REC;
+    SG_TRY(ensure_cap(ctx->stream, &d->d_ddiag, &d->ddiag_cap, grid_doubles + (size_t)(1 + ctx->world) * DD_REC));
     a.rec = d->d_ddiag;
     if (gw) hipLaunchKernelGGL(k_disc_diag<true>, dim3(grid), dim3(256), lds, ctx->stream, a);
     else hipLaunchKernelGGL(k_disc_diag<false>, dim3(grid), dim3(256), lds, ctx->stream, a);
     SG_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_disc_diag_reduce, dim3(1), dim3(64), 0, ctx->stream, d->d_ddiag, grid, d->h_ddiag + slot * SG_DDIAG_STRIDE);
+    double* out = d->h_ddiag + slot * SG_DDIAG_STRIDE;
+    if (!world_scope) {
+        hipLaunchKernelGGL(k_disc_diag_reduce<DD_FINAL>, dim3(1), dim3(64), 0, ctx->stream, d->d_ddiag, grid, out);
+    } else {
+        double* mine = d->d_ddiag + grid_doubles;
+        double* all = mine + DD_REC;
+        hipLaunchKernelGGL(k_disc_diag_reduce<DD_FOLD>, dim3(1), dim3(64), 0, ctx->stream, d->d_ddiag, grid, mine);
+        SG_CHECK(hipGetLastError());
+        if (gather) SG_TRY(sg_comm_allgather_f64(ctx, mine, all, DD_REC));
+        hipLaunchKernelGGL(k_disc_diag_reduce<DD_WORLD>, dim3(1), dim3(64), 0, ctx->stream, gather ? all : mine, world, out);
+    }
     SG_CHECK(hipGetLastError());
     SG_CHECK(hipEventRecord(d->ddiag_ev[slot], ctx->stream));
     d->ddiag_pending[slot] = true;
     if (out19) return sg_disc_diagnostics_fetch(d, slot, out19);
     return 0;
+}
+
+extern "C" int sg_disc_diagnostics(sg_disc* d, sg_rollout* r, int slot, double* out19) {
+    return disc_diagnostics("sg_disc_diagnostics", false, d, r, slot, out19);
+}
+
+// The world scope: k_disc_diag with the world's mid pairing, the fold alone, the all-gather of the ranks' 36-double records,
+// fold + finalise over them.  A COLLECTIVE: every rank issues it at the same point of its stream's sequence of collectives, in
+// either discriminator data-parallel mode.  No communicator: the rank scope's bits.
+extern "C" int sg_disc_diagnostics_world(sg_disc* d, sg_rollout* r, int slot, double* out19) {
+    return disc_diagnostics("sg_disc_diagnostics_world", true, d, r, slot, out19);
 }
 
 extern "C" int sg_disc_diagnostics_fetch(sg_disc* d, int slot, double out19[SG_DDIAG_N]) {
@@ -314,7 +380,14 @@ extern "C" int sg_disc_diagnostics_fetch(sg_disc* d, int slot, double out19[SG_D
     SG_REQUIRE(d->ddiag_pending[slot], "sg_disc_diagnostics_fetch: no diagnostics are pending in slot %d of this discriminator (queue them "
                "with sg_disc_diagnostics(..., out19 = NULL) first; a result is fetched once)", slot);
     SG_CHECK(hipEventSynchronize(d->ddiag_ev[slot]));
-    memcpy(out19, d->h_ddiag + slot * SG_DDIAG_STRIDE, sizeof(double) * SG_DDIAG_N);
     d->ddiag_pending[slot] = false;
+    const double differ = d->h_ddiag[slot * SG_DDIAG_STRIDE + SG_DDIAG_N];
+    SG_REQUIRE(differ != 1.0 && differ != 3.0, "sg_disc_diagnostics_fetch: the ranks of the world scope hold different numbers of rows "
+               "(%lld in all): the global numbering takes equal column shards, no numbers are returned",
+               (long long)d->h_ddiag[slot * SG_DDIAG_STRIDE]);
+    SG_REQUIRE(differ == 0.0, "sg_disc_diagnostics_fetch: the ranks of the world scope hold expert matrices of different numbers of rows "
+               "(rank 0: %lld): every rank holds the whole expert matrix, no numbers are returned",
+               (long long)d->h_ddiag[slot * SG_DDIAG_STRIDE + 1]);
+    memcpy(out19, d->h_ddiag + slot * SG_DDIAG_STRIDE, sizeof(double) * SG_DDIAG_N);
     return 0;
 }

@@ -142,14 +142,26 @@ def _check_on_device(ro, pol, dup_sym, who):
         raise ValueError(f"{who}(on_device=True): {why}")
 
 
+def _diag_scope(flag, name):
+    """update(diagnostics=..., disc_diagnostics=...): False | True | "world" -> None | "rank" | "world" """
+    if flag is False or flag is None:
+        return None
+    if flag is True:
+        return "rank"
+    if isinstance(flag, str) and flag == "world":
+        return "world"
+    raise ValueError(f'{name} = {flag!r}: False, True (this rank\'s rows) or "world" (all ranks\' rows: a collective)')
+
+
 class _LearnerDiagnostics(object):
     """update(diagnostics=True): the agent's diagnostics (PPO.diagnostics / A2C_ACKTR.diagnostics) are queued after the agent's
     update and before rollouts.after_update(), which overwrites obs[0]; the result is fetched on the first read of
-    last_diagnostics, so a queued update keeps having no host wait."""
+    last_diagnostics, so a queued update keeps having no host wait.  diagnostics="world": the same in the world scope -- over all
+    ranks' rows, the same on every rank; a collective, so every rank's update asks for it."""
     _diag, _diag_pending = None, False
 
-    def _queue_diagnostics(self):
-        self.agent.diagnostics(self.rollouts, fetch=False)
+    def _queue_diagnostics(self, scope="rank"):
+        self.agent.diagnostics(self.rollouts, fetch=False, scope=scope)
         self._diag_pending = True
 
     @property
@@ -162,14 +174,15 @@ class _LearnerDiagnostics(object):
 class _DiscDiagnostics(object):
     """update(disc_diagnostics=True): Discriminator.diagnostics is queued into slot 0 before the first discriminator epoch (the old
     discriminator on the new rollout) and into slot 1 after the last; both are fetched on the first read of
-    last_disc_diagnostics, so a queued update keeps having no host wait."""
+    last_disc_diagnostics, so a queued update keeps having no host wait.  disc_diagnostics="world": both in the world scope."""
     _ddiag, _ddiag_pending = None, False
 
     def _bind_expert(self):
         self.discr._bind_loader(self.loader)     # the first epoch would do it: the "before" launch needs the expert rows too
 
-    def _queue_disc_diagnostics(self, slot):
-        self.discr.diagnostics(self.rollouts, fetch=False, slot=slot)
+    def _queue_disc_diagnostics(self, slot, scope="rank"):
+        call = self.discr.diagnostics_world if scope == "world" else self.discr.diagnostics
+        call(self.rollouts, fetch=False, slot=slot)
         self._ddiag_pending = slot == 1
 
     @property
@@ -269,6 +282,7 @@ class GailDynLearner(_LearnerDiagnostics, _DiscDiagnostics):
     # ------------------------------------------------------------- the timed part (:239-304)
     def update(self, diagnostics=False, disc_diagnostics=False):
         ro, lib = self.rollouts, self.rollouts.lib
+        diagnostics, disc_diagnostics = _diag_scope(diagnostics, "diagnostics"), _diag_scope(disc_diagnostics, "disc_diagnostics")
         if self.use_linear_lr_decay:            # :203-207
             update_linear_schedule(self.agent.optimizer, self.j, self.num_updates, self.lr)
         if ro.device_resident:
@@ -279,12 +293,12 @@ class GailDynLearner(_LearnerDiagnostics, _DiscDiagnostics):
         gail = None
         if disc_diagnostics:
             self._bind_expert()
-            self._queue_disc_diagnostics(0)
+            self._queue_disc_diagnostics(0, disc_diagnostics)
         for e in range(self.gail_epoch):        # :255-256 -- the reference keeps the last epoch's losses only
             last = e == self.gail_epoch - 1
             gail = self.discr.update_gail_dyn(self.loader, ro, **({} if last else {"fetch_losses": False}))
         if disc_diagnostics:
-            self._queue_disc_diagnostics(1)
+            self._queue_disc_diagnostics(1, disc_diagnostics)
         # drop-in mode: the host tensors are the rollout; every call below uploads what it reads and returns its result
         ro._push([_lib.F_MASKS])
         dones = C.c_double(0)
@@ -296,7 +310,7 @@ class GailDynLearner(_LearnerDiagnostics, _DiscDiagnostics):
         ro.compute_returns(next_value, self.use_gae, self.gamma, self.gae_lambda, self.use_proper_time_limits)
         ppo = self.agent.update(ro)             # :302
         if diagnostics:
-            self._queue_diagnostics()
+            self._queue_diagnostics(diagnostics)
         ro.after_update()                       # :304
         self.j += 1
         return {"gail_loss": gail[0], "gail_loss_e": gail[1], "gail_loss_p": gail[2], "value_loss": ppo[0],
@@ -338,16 +352,16 @@ def _gail_update_resident(self, diagnostics=False, disc_diagnostics=False):
         self._rms_on_device = True
     if disc_diagnostics:
         self._bind_expert()
-        self._queue_disc_diagnostics(0)
+        self._queue_disc_diagnostics(0, disc_diagnostics)
     for _ in range(self.gail_epoch):            # :255-256
         self.discr.update_gail_dyn(self.loader, ro, fetch_losses=False)
     if disc_diagnostics:
-        self._queue_disc_diagnostics(1)
+        self._queue_disc_diagnostics(1, disc_diagnostics)
     self.discr.relabel_rewards_auto(ro, self.gamma, self.gail_tar_length, self.no_alive_bonus)     # :258-297
     _returns_resident(self)
     self.agent.update(ro, fetch_losses=False)   # :302
     if diagnostics:
-        self._queue_diagnostics()
+        self._queue_diagnostics(diagnostics)
     ro.after_update()                           # :304
     self.j += 1
     return self._ring.publish(self.discr, self.agent, ("gail_loss", "gail_loss_e", "gail_loss_p", "value_loss", "action_loss",
@@ -454,13 +468,14 @@ class PpoLearner(_LearnerDiagnostics):
     # ------------------------------------------------------------- the timed part (:201-205, :246-256)
     def update(self, diagnostics=False):
         ro, lib = self.rollouts, self.rollouts.lib
+        diagnostics = _diag_scope(diagnostics, "diagnostics")
         if self.use_linear_lr_decay:
             update_linear_schedule(self.agent.optimizer, self.j, self.num_updates, self.lr)
         if ro.device_resident:   # nothing below waits for the device: the losses are read from the results ring on demand
             _returns_resident(self)
             self.agent.update(ro, fetch_losses=False)
             if diagnostics:
-                self._queue_diagnostics()
+                self._queue_diagnostics(diagnostics)
             ro.after_update()
             self.j += 1
             return self._ring.publish(None, self.agent, ("value_loss", "action_loss", "dist_entropy"))
@@ -468,7 +483,7 @@ class PpoLearner(_LearnerDiagnostics):
         ro.compute_returns(next_value, self.use_gae, self.gamma, self.gae_lambda, self.use_proper_time_limits)
         value_loss, action_loss, dist_entropy = self.agent.update(ro)
         if diagnostics:
-            self._queue_diagnostics()
+            self._queue_diagnostics(diagnostics)
         ro.after_update()
         self.j += 1
         return {"value_loss": value_loss, "action_loss": action_loss, "dist_entropy": dist_entropy}
