@@ -411,6 +411,18 @@ typedef struct {
  * adv = returns[:-1] - values, out3 = {mean(adv^2), -mean(adv.detach() * logp), mean(entropy)}, loss = out3[0] * vcoef +
  * out3[1] - out3[2] * ecoef, clip_grad_norm_(max_grad_norm), one RMSprop step. */
 SG_API int sg_a2c_create(sg_ctx *ctx, sg_policy *p, const sg_a2c_config *cfg, sg_ppo **out);
+/* The same learner on a recurrent policy (kind SG_POLICY_GRU; --algo a2c --recurrent-policy): A2C through time.  Opt-in by entry
+ * point: sg_a2c_create keeps refusing a recurrent policy.  Refused here, each with its own message: a feed-forward policy, a head
+ * other than the Gaussian one, and a context with a communicator of world > 1.
+ * One update (a2c/algo/a2c_acktr.py:55-102 with a2c/model.py:117-201): evaluate_actions on the rollout's T*N rows in their own
+ * order t*N + n, the GRU stepped with h <- h * masks[t] from the hidden states of slot 0, which the caller hands over before
+ * EVERY update with sg_ppo_set_hidden_states or sg_ppo_set_hidden_states_rollout (as for PPO through time); the losses and out3
+ * as above, all means over T*N rows; back-propagation through the heads and through time (no gradient for h_0 or the
+ * observations); clip_grad_norm_ over ALL parameters, the GRU's included; one RMSprop step over all of them.  The environments
+ * go through the scans in groups of at most 65,536 rows (whole multiples of 16 environments; SG_A2C_GROUP_ENVS=<multiple of 16>
+ * forces a smaller group: test knob), so the scratch does not grow with N.  sg_a2c_get_rmsprop / sg_a2c_set_rmsprop cover the
+ * GRU's tensors, which come first in state_dict order. */
+SG_API int sg_a2c_create_rnn(sg_ctx *ctx, sg_policy *p, const sg_a2c_config *cfg, sg_ppo **out);
 /* RMSprop state for checkpoint/parity: square_avg flat [n] in state_dict order; *step = optimizer steps taken. */
 SG_API int sg_a2c_get_rmsprop(sg_ppo *a, float *square_avg, int64_t n, int64_t *step);
 SG_API int sg_a2c_set_rmsprop(sg_ppo *a, const float *square_avg, int64_t n, int64_t step);

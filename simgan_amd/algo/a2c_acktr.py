@@ -64,7 +64,8 @@ class A2C_ACKTR():
                  alpha=None,
                  max_grad_norm=None,
                  acktr=False,
-                 seed=0):
+                 seed=0,
+                 recurrent=False):
         if acktr:
             given = [k for k, v in (("lr", lr), ("eps", eps), ("alpha", alpha), ("max_grad_norm", max_grad_norm)) if v is not None]
             if given:
@@ -76,9 +77,14 @@ class A2C_ACKTR():
             raise NotImplementedError("A2C_ACKTR: implemented for Policy (MLP) only, not for SplitPolicy")
         if getattr(actor_critic, "cnn", 0):
             raise NotImplementedError("A2C_ACKTR: not implemented for the CNN base (image observations), in either mode; PPO is")
-        if getattr(actor_critic, "is_recurrent", False):
+        is_rec = bool(getattr(actor_critic, "is_recurrent", False))
+        if is_rec and (acktr or not recurrent):
             raise NotImplementedError("A2C_ACKTR: implemented for feed-forward policies only, not for a recurrent Policy "
-                                      "(the reference allows --recurrent-policy with a2c and refuses it with acktr)")
+                                      "(the reference allows --recurrent-policy with a2c and refuses it with acktr); "
+                                      "A2C through time is opt-in: A2C_ACKTR(..., acktr=False, recurrent=True)")
+        if recurrent and not is_rec:
+            raise ValueError("A2C_ACKTR(recurrent=True) takes a recurrent Policy (base_kwargs={'recurrent': True}); this policy is "
+                             "feed-forward: leave the keyword out")
         if acktr and getattr(actor_critic, "dist_kind", 0):
             raise NotImplementedError("A2C_ACKTR(acktr=True): K-FAC's Fisher sampling is built for the Gaussian head (Box action spaces) "
                                       "only, not for a Discrete / MultiBinary policy; acktr=False (A2C) runs")
@@ -91,6 +97,7 @@ class A2C_ACKTR():
                              "a2c/main.py:123-131 passes --lr, --eps, --alpha, --max-grad-norm)")
         self.actor_critic = actor_critic
         self.acktr = acktr
+        self.recurrent = is_rec
         self.value_loss_coef = value_loss_coef
         self.entropy_coef = entropy_coef
         self.max_grad_norm = max_grad_norm
@@ -100,7 +107,8 @@ class A2C_ACKTR():
         self.lib = self.ctx.lib
         cfg = _lib.A2CConfig(float(value_loss_coef), float(entropy_coef), float(lr), float(eps), float(alpha), float(max_grad_norm))
         h = _lib.H()
-        _lib.check(self.lib.sg_a2c_create(self.ctx.h, actor_critic.h, C.byref(cfg), C.byref(h)))
+        create = self.lib.sg_a2c_create_rnn if is_rec else self.lib.sg_a2c_create
+        _lib.check(create(self.ctx.h, actor_critic.h, C.byref(cfg), C.byref(h)))
         self.h = h
         if hasattr(actor_critic, "_register_handle_user"):
             actor_critic._register_handle_user(self)
@@ -109,6 +117,7 @@ class A2C_ACKTR():
     def _init_acktr(self, actor_critic, value_loss_coef, entropy_coef, seed):
         self.actor_critic = actor_critic
         self.acktr = True
+        self.recurrent = False
         self.value_loss_coef = value_loss_coef
         self.entropy_coef = entropy_coef
         self.max_grad_norm = None
@@ -170,6 +179,8 @@ class A2C_ACKTR():
         return None without waiting for it (the losses are read later through the results ring, simgan_amd/driver.py).
         value_noise (ACKTR only): the update's torch.randn(values.size()) [T, N, 1] instead of the library's own draws."""
         rollouts._push([_lib.F_OBS, _lib.F_ACTIONS, _lib.F_RETURNS])
+        if self.recurrent:
+            self._hand_over_hidden(rollouts)
         seed = 0
         if self.acktr:
             if value_noise is not None:
@@ -183,6 +194,21 @@ class A2C_ACKTR():
         if self.acktr:
             self._steps += 1
         return (float(out[0]), float(out[1]), float(out[2])) if fetch_losses else None
+
+    def _hand_over_hidden(self, rollouts):
+        """recurrent_hidden_states[0] for the next update, as PPO.update hands it over: device to device from a rollout that
+        holds its hidden states there (enable_device_hidden), from the host tensor otherwise."""
+        rollouts._push([_lib.F_MASKS])
+        if getattr(rollouts, "device_hidden", False) and rollouts.device_resident:
+            _lib.check(self.lib.sg_ppo_set_hidden_states_rollout(self.h, rollouts.h))
+            return
+        hxs0 = rollouts.recurrent_hidden_states[0]
+        hxs0 = np.ascontiguousarray(hxs0.numpy() if hasattr(hxs0, "numpy") else hxs0, np.float32)
+        if hxs0.shape != (rollouts.num_processes, self.actor_critic.recurrent_hidden_state_size):
+            raise ValueError(f"rollouts.recurrent_hidden_states[0] is {hxs0.shape}; the policy's state is "
+                             f"[{rollouts.num_processes}, {self.actor_critic.recurrent_hidden_state_size}] (build RolloutStorage with "
+                             "actor_critic.recurrent_hidden_state_size)")
+        _lib.check(self.lib.sg_ppo_set_hidden_states(self.h, _lib.fptr(hxs0), hxs0.size))
 
     def diagnostics(self, rollouts, fetch=True, scope="rank"):
         """PPO.diagnostics for A2C / ACKTR (both modes): the same ten numbers with clip_param = inf, so clip_fraction is exactly

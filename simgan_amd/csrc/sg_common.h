@@ -333,7 +333,7 @@ struct SgGraphCache {
 // The scratch layout an sg_ppo's buffers were last cleared for: padding columns / rows that the kernels never write must
 // read as zero, which holds for as long as the layout is the same.  Compared whole.  SG_LAYOUT_INVALID: clear before the next
 // update whatever its layout (after a reallocation, after sg_ppo_set_adam).
-enum { SG_LAYOUT_INVALID = 0, SG_LAYOUT_PPO, SG_LAYOUT_A2C, SG_LAYOUT_GRU };
+enum { SG_LAYOUT_INVALID = 0, SG_LAYOUT_PPO, SG_LAYOUT_A2C, SG_LAYOUT_GRU, SG_LAYOUT_A2C_GRU };
 struct SgScratchLayout {
     int64_t mode = SG_LAYOUT_INVALID;
     int64_t dims[8] = {0};
@@ -379,6 +379,7 @@ struct sg_ppo {
     // A2C (sg_a2c_create): one RMSprop step over the whole rollout per update; d_v holds square_avg, opt_t counts the steps
     bool a2c = false;
     float alpha = 0.f;
+    bool a2c_rnn = false;          // sg_a2c_create_rnn: A2C through time on a recurrent Policy (the update's recurrent branch)
     // ACKTR (sg_acktr_create): A2C's gradient (a2c is set too), then the K-FAC step (sg_ppo.hip); d_m holds SGD's momentum buffer
     struct SgKfac* kfac = nullptr;
 };

@@ -11,6 +11,8 @@
 //                      gradients [dr, dz, dn] (input side) and [dr, dz, dn r] (hidden side); carried = (dh z + dGH W_hh) masks[t]
 //   k_gru_wgrad        dW_ih = dGI^T X, dW_hh = dGH^T Hm, db = column sums: GEMMs over all T*per rows AFTER the scan, split
 //                      over row ranges into partial blocks;  k_gru_reduce adds the partials in a fixed order
+//   k_a2c_gru_gather   A2C through time: a group of environments in the rollout's own order, time-major;  k_gru_reduce_acc adds the
+//                      groups' GRU gradients in group order and finishes them after the last
 // No floating-point atomics anywhere: every sum has one order, two runs give the same bits.
 #pragma once
 #include "sg_common.h"
@@ -290,6 +292,59 @@ __global__ __launch_bounds__(256) void k_gru_reduce(const float* partial, int KS
     __syncthreads();
     if (threadIdx.x == 0) part[part_off + blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
     if (blockIdx.x == 0 && threadIdx.x < 8) grad[total + gtotal + threadIdx.x] = tail;
+}
+
+// The accumulate variant (A2C through time: the environments go through the scans in groups).  Group k's partial sums are added
+// to gacc, the sums of the groups before it (acc == 0: the first group starts them), in group order -- one order, the same bits
+// every run.  Only the last group (last != 0) touches grad and part: the finished GRU gradient goes behind the heads', the loss
+// sums move behind it and the blocks' sums of squares are taken over the finished gradient, as k_gru_reduce does for its one group.
+template <int DUMMY = 0>
+__global__ __launch_bounds__(256) void k_gru_reduce_acc(const float* partial, int KS, int gtotal, float* gacc, int acc, int last,
+                                                        float* grad, int total, float* part, int part_off) {
+    __shared__ float ws[4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    float s = 0.f;
+    if (i < gtotal) {
+        if (acc) s = gacc[i];
+        for (int k = 0; k < KS; ++k) s += partial[(size_t)k * gtotal + i];
+    }
+    if (!last) {
+        if (i < gtotal) gacc[i] = s;
+        return;
+    }
+    float tail = 0.f;
+    if (blockIdx.x == 0 && threadIdx.x < 8) tail = grad[total + threadIdx.x];
+    __syncthreads();
+    if (i < gtotal) grad[total + i] = s;
+    float sq = sg_wave_sum(s * s);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    if (threadIdx.x == 0) part[part_off + blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+    if (blockIdx.x == 0 && threadIdx.x < 8) grad[total + gtotal + threadIdx.x] = tail;
+}
+
+// ------------------------------------------------------------- group gather of A2C through time (a2c/algo/a2c_acktr.py:56-63)
+// Group row rr = t * n + j  <-  rollout row t * N + e0 + j: the group's n environments in the rollout's own order, time-major.
+// Padded observations, actions, the return (the one per-row scalar A2C reads), masks[:-1], and the hidden state of slot 0.
+struct A2cGruGatherArgs {
+    const float *obs, *actions, *ret, *masks, *h0;
+    int T, N, e0, n, O, ldO, A, H, sc_stride;
+    float *X, *ACT, *SC, *MK, *H0;
+};
+
+template <int DUMMY = 0>
+__global__ __launch_bounds__(64) void k_a2c_gru_gather(A2cGruGatherArgs a) {
+    const int rr = blockIdx.x;   // one workgroup per group row
+    const int t = rr / a.n, j = rr - t * a.n;
+    const size_t src = (size_t)t * a.N + a.e0 + j;
+    for (int c = threadIdx.x; c < a.ldO; c += blockDim.x) a.X[(size_t)rr * a.ldO + c] = c < a.O ? a.obs[src * a.O + c] : 0.f;
+    for (int c = threadIdx.x; c < a.A; c += blockDim.x) a.ACT[(size_t)rr * a.A + c] = a.actions[src * a.A + c];
+    if (threadIdx.x == 0) {
+        a.SC[3 * (size_t)a.sc_stride + rr] = a.ret[src];
+        a.MK[rr] = a.masks[src];
+    }
+    if (t == 0)
+        for (int c = threadIdx.x; c < a.H; c += blockDim.x) a.H0[(size_t)j * a.H + c] = a.h0[(size_t)(a.e0 + j) * a.H + c];
 }
 
 // ------------------------------------------------------------------------- epoch gather (a2c/storage.py:194-251)

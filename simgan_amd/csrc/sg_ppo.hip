@@ -21,6 +21,10 @@
 //   per chunk of <= SG_A2C_CHUNK_ROWS rows:  k_ppo_fwd -> k_a2c_bwd -> k_a2c_reduce (adds to the gradient)
 //   then         k_a2c_rmsprop                      clip + RMSprop, the update's one optimizer step
 //
+// A2C through time (sg_a2c_create_rnn: the same learner on a recurrent Policy; a2c_gru_update), per group of environments:
+//   k_a2c_gru_gather -> k_gru_inproj -> k_gru_scan_fwd<TRAIN>;  per chunk:  k_ppo_fwd -> k_a2c_bwd_dx -> k_a2c_reduce;
+//   k_gru_scan_bwd -> k_gru_wgrad -> k_gru_reduce_acc;  then one k_a2c_rmsprop over heads + GRU
+//
 // ACKTR (sg_acktr_create: A2C's gradient with the K-FAC step of a2c/algo/kfac.py, sg_kfac.hpp), one update:
 //   k_a2c_gather
 //   per chunk:  k_ppo_fwd -> k_a2c_bwd -> k_a2c_reduce -> k_acktr_fisher -> k_kfac_stats (adds to the factor sums)
@@ -157,6 +161,7 @@ struct PpoInstance {
 #define SG_K_FWD_SYM(mt, o, h, gw) k_ppo_fwd_sym<mt, o, h, gw>
 #define SG_K_BWD_SYM(mt, o, h, gw) k_ppo_bwd_sym<mt, o, h, gw>
 #define SG_K_A2C_BWD(mt, o, h, gw) k_a2c_bwd<mt, o, h, gw>
+#define SG_K_A2C_BWD_DX(mt, o, h, gw) k_a2c_bwd_dx<mt, gw>
 #define SG_K_BWD_FUSED_CAT(mt, o, h, gw) k_ppo_bwd_dist<mt, gw, SG_DIST_CATEGORICAL>
 #define SG_K_BWD_FUSED_BER(mt, o, h, gw) k_ppo_bwd_dist<mt, gw, SG_DIST_BERNOULLI>
 #define SG_K_A2C_BWD_CAT(mt, o, h, gw) k_a2c_bwd_dist<mt, gw, SG_DIST_CATEGORICAL>
@@ -171,6 +176,7 @@ SG_PPO_FAMILY(ppo_bwd_fused_dx_family, SG_K_BWD_FUSED_DX, SG_NONE, SG_MT_21, SG_
 SG_PPO_FAMILY(ppo_fwd_sym_family, SG_K_FWD_SYM, SG_SYM_SHAPES, SG_MT_21, SG_MT_21);               // mirror-symmetry loss: grid (row groups, 3)
 SG_PPO_FAMILY(ppo_bwd_sym_family, SG_K_BWD_SYM, SG_SYM_SHAPES, SG_MT_21, SG_MT_21);
 SG_PPO_FAMILY(a2c_bwd_family, SG_K_A2C_BWD, SG_A2C_SHAPES, SG_MT_21, SG_MT_21);
+SG_PPO_FAMILY(a2c_bwd_dx_family, SG_K_A2C_BWD_DX, SG_NONE, SG_MT_21, SG_MT_21);               // A2C through time: + d loss / d h_t
 // Policy on a Discrete / MultiBinary action space: PPO in the fused form, A2C in the two-launch form; run-time shapes
 SG_PPO_FAMILY(ppo_bwd_fused_cat_family, SG_K_BWD_FUSED_CAT, SG_NONE, SG_MT_21, SG_MT_21);
 SG_PPO_FAMILY(ppo_bwd_fused_ber_family, SG_K_BWD_FUSED_BER, SG_NONE, SG_MT_21, SG_MT_21);
@@ -253,6 +259,34 @@ extern "C" int sg_a2c_create(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg
     sg_ppo* a = nullptr;
     SG_TRY(sg_ppo_create(ctx, p, &pc, &a));
     a->a2c = true;
+    a->alpha = cfg->alpha;
+    *out = a;
+    return 0;
+}
+
+// The same learner on a recurrent Policy (a2c/main.py:123-131 with --recurrent-policy): evaluate_actions steps the GRU through
+// the rollout from the state of slot 0 (a2c/algo/a2c_acktr.py:56-63, a2c/model.py:117-201); clip and RMSprop cover the GRU's
+// tensors too.  An entry point of its own: sg_a2c_create keeps refusing a recurrent policy.
+extern "C" int sg_a2c_create_rnn(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg, sg_ppo** out) {
+    SG_REQUIRE(ctx && p && cfg && out, "sg_a2c_create_rnn: NULL argument");
+    SG_REQUIRE(p->recurrent, "sg_a2c_create_rnn: A2C through time takes a recurrent Policy (kind SG_POLICY_GRU); this policy is "
+               "feed-forward (sg_a2c_create)");
+    SG_REQUIRE(!p->cnn && p->desc.kind == SG_POLICY_MLP && p->desc.dist == SG_DIST_GAUSSIAN,
+               "sg_a2c_create_rnn: A2C through time is implemented for the Gaussian head (Box action spaces) only");
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_a2c_create_rnn: A2C with a recurrent policy runs on one rank: this context has a "
+               "communicator of world %d (data-parallel A2C through time is not implemented)", ctx->world);
+    SG_REQUIRE(cfg->alpha >= 0.f && cfg->alpha <= 1.f && cfg->eps >= 0.f && cfg->max_grad_norm > 0.f,
+               "sg_a2c_create_rnn: alpha must lie in [0, 1], eps >= 0 and max_grad_norm > 0 (got %g, %g, %g)", (double)cfg->alpha,
+               (double)cfg->eps, (double)cfg->max_grad_norm);
+    sg_ppo_config pc;
+    memset(&pc, 0, sizeof pc);
+    pc.ppo_epoch = 1; pc.num_mini_batch = 1;
+    pc.value_loss_coef = cfg->value_loss_coef; pc.entropy_coef = cfg->entropy_coef;
+    pc.lr = cfg->lr; pc.eps = cfg->eps; pc.max_grad_norm = cfg->max_grad_norm;
+    sg_ppo* a = nullptr;
+    SG_TRY(sg_ppo_create(ctx, p, &pc, &a));
+    a->a2c = true;
+    a->a2c_rnn = true;
     a->alpha = cfg->alpha;
     *out = a;
     return 0;
@@ -478,12 +512,16 @@ extern "C" int sg_a2c_get_rmsprop(sg_ppo* a, float* square_avg, int64_t n, int64
     SG_REQUIRE(!a->kfac, "sg_a2c_get_rmsprop: an ACKTR handle has K-FAC state, not RMSprop's (sg_acktr_get_state)");
     SG_REQUIRE(a->a2c, "sg_a2c_get_rmsprop: not an A2C handle (sg_ppo_get_adam)");
     const SgPolicyDesc& d = a->policy->desc;
-    SG_REQUIRE(n == sg_policy_flat_count(d), "sg_a2c_get_rmsprop: bad length");
-    std::vector<float> pv(d.total);
+    const sg_policy* pol = a->policy;
+    const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;   // the GRU's tensors come first in the flat order
+    SG_REQUIRE(n == sg_policy_flat_count(d) + n_gru, "sg_a2c_get_rmsprop: bad length");
+    const size_t ptot = sg_policy_padded_count(pol);
+    std::vector<float> pv(ptot);
     SG_CHECK(hipSetDevice(a->ctx->device));
     SG_CHECK(hipStreamSynchronize(a->ctx->stream));
-    SG_COPY_SYNC(a->ctx, pv.data(), a->d_v, sizeof(float) * d.total, hipMemcpyDeviceToHost);
-    sg_policy_unpad(d, pv.data(), square_avg);
+    SG_COPY_SYNC(a->ctx, pv.data(), a->d_v, sizeof(float) * ptot, hipMemcpyDeviceToHost);
+    if (pol->recurrent) sg_gru_unpad(pol->gru, pv.data() + pol->gru.off, square_avg);
+    sg_policy_unpad(d, pv.data(), square_avg + n_gru);
     *step = a->opt_t;
     return 0;
 }
@@ -493,13 +531,17 @@ extern "C" int sg_a2c_set_rmsprop(sg_ppo* a, const float* square_avg, int64_t n,
     SG_REQUIRE(!a->kfac, "sg_a2c_set_rmsprop: an ACKTR handle has K-FAC state, not RMSprop's (sg_acktr_get_state)");
     SG_REQUIRE(a->a2c, "sg_a2c_set_rmsprop: not an A2C handle (sg_ppo_set_adam)");
     const SgPolicyDesc& d = a->policy->desc;
-    SG_REQUIRE(n == sg_policy_flat_count(d), "sg_a2c_set_rmsprop: bad length");
+    const sg_policy* pol = a->policy;
+    const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;
+    SG_REQUIRE(n == sg_policy_flat_count(d) + n_gru, "sg_a2c_set_rmsprop: bad length");
     SG_REQUIRE(step >= 0, "sg_a2c_set_rmsprop: step out of range");
-    std::vector<float> pv(d.total, 0.f);
-    sg_policy_pad(d, square_avg, pv.data());
+    const size_t ptot = sg_policy_padded_count(pol);
+    std::vector<float> pv(ptot, 0.f);
+    if (pol->recurrent) sg_gru_pad(pol->gru, square_avg, pv.data() + pol->gru.off);
+    sg_policy_pad(d, square_avg + n_gru, pv.data());
     SG_CHECK(hipSetDevice(a->ctx->device));
     SG_CHECK(hipStreamSynchronize(a->ctx->stream));
-    SG_COPY_SYNC(a->ctx, a->d_v, pv.data(), sizeof(float) * d.total, hipMemcpyHostToDevice);
+    SG_COPY_SYNC(a->ctx, a->d_v, pv.data(), sizeof(float) * ptot, hipMemcpyHostToDevice);
     a->opt_t = step;
     return 0;
 }
@@ -1074,10 +1116,199 @@ static int cnn_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
     return 0;
 }
 
+// ------------------------------------------------------------------- A2C through time (recurrent policy)
+// Rows one environment group may hold: the scan scratch is rows x (13 Hp + 5 ldH + ldO) floats (GI, dGI, dGH: 9 Hp; the saved
+// gates: 4 Hp; the masked state, the heads' input and the two d loss / d h: 4 ldH beside ACT and SC; the observation copy: ldO),
+// 4.6 KB per row at H = 64, obs 47.  65,536 rows (303 MB there) make the north-star rollout (128 x 512) ONE group: fewer
+// environments per scan do not shorten its T-long chain, they only run it again.
+#define SG_A2C_RNN_GROUP_ROWS 65536
+// environments per group: the most that fit the row cap, in whole scan tiles of 16; SG_A2C_GROUP_ENVS (a multiple of 16: test
+// knob) forces a smaller group
+static int a2c_gru_group_envs(int T, int N) {
+    int ng = std::max(16, (SG_A2C_RNN_GROUP_ROWS / T) & ~15);
+    if (const char* e = getenv("SG_A2C_GROUP_ENVS")) {
+        const int v = atoi(e);
+        if (v >= 16 && v % 16 == 0) ng = v;
+    }
+    return std::min(ng, N);
+}
+
+// A2C_ACKTR.update(rollouts), acktr=False, with actor_critic.is_recurrent (a2c/algo/a2c_acktr.py:52-102 over a2c/model.py:117-201):
+// evaluate_actions steps the GRU through all T steps of all N environments from the state of slot 0 (h <- h * masks[t]), the
+// heads see the states; one loss over the T*N rows, one clip over ALL parameters, one RMSprop step.  Per environment group:
+//   k_a2c_gru_gather -> k_gru_inproj -> k_gru_scan_fwd<TRAIN>
+//   per chunk of <= SG_A2C_CHUNK_ROWS rows:  k_ppo_fwd -> k_a2c_bwd_dx -> k_a2c_reduce (adds to the heads' gradient)
+//   k_gru_scan_bwd -> k_gru_wgrad -> k_gru_reduce_acc (adds to the GRU's gradient; the last group finishes it)
+// then k_a2c_rmsprop over heads + GRU.  One captured graph from the first gather on; no host wait inside.
+static int a2c_gru_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
+    sg_ctx* ctx = a->ctx;
+    sg_policy* pol = a->policy;
+    const SgPolicyDesc& d = pol->desc;
+    const SgGruDesc& g = pol->gru;
+    SG_REQUIRE(r->O == g.O && r->A == d.A, "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)", r->O, r->A,
+               g.O, d.A);
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_ppo_update: A2C with a recurrent policy runs on one rank (world %d)", ctx->world);
+    const int T = r->T, N = r->N;
+    SG_REQUIRE((int64_t)a->h0_count == (int64_t)N * g.H, "sg_ppo_update: a recurrent policy takes the hidden states of rollout slot 0 "
+               "from the host: sg_ppo_set_hidden_states must hand over %lld floats before every update (pending: %lld)",
+               (long long)N * g.H, (long long)a->h0_count);
+    a->h0_count = 0;
+    const int64_t TN = (int64_t)T * N;
+    SG_REQUIRE(TN > 0 && TN < (1ll << 30), "sg_ppo_update: %lld rollout rows", (long long)TN);
+    SG_CHECK(hipSetDevice(ctx->device));
+
+    // geometry.  Groups of ng environments (the last one may be smaller); a full group has Bg rows, time-major.  Heads: the
+    // two-launch A2C form on chunks of the group's rows.  Scans: one workgroup per 16 environments of the group.
+    const int ng = a2c_gru_group_envs(T, N);
+    const int n_groups = (N + ng - 1) / ng;
+    SG_REQUIRE((int64_t)T * ng < (1ll << 26), "sg_ppo_update: %d steps x %d environments do not fit one scan group", T, ng);
+    const int Bg = T * ng;
+    const int chunk = std::min(Bg, SG_A2C_CHUNK_ROWS);
+    auto bwd_lds = [&](int mt, bool gwv) { return ppo_bwd_tiles_lds(d, mt, gwv ? 0 : max_bwd_floats(d), 2, false); };
+    auto fits = [&](int mt, bool gwv) { return ppo_fwd_lds(d, mt, gwv) <= (size_t)ctx->lds_bytes && bwd_lds(mt, gwv) <= (size_t)ctx->lds_bytes; };
+    const bool gw = sg_policy_needs_gw(ctx, d) || !fits(1, false);
+    SG_REQUIRE(fits(1, gw), "sg_ppo_update: the 16-row tiles of the A2C step do not fit LDS");
+    const int MT = ppo_row_tiles(ctx, d, chunk, d.n_trunks, true, 2, 2, [&](int mt) { return fits(mt, gw); });
+    const int R = 16 * MT, G = (chunk + R - 1) / R, mbp = G * R;
+    const int ldP = stack_ldP(d);
+    const int slab_stride = (d.total + 8 + 63) & ~63;
+    const int Bgp = Bg + 64;             // slack rows: the last row tile reads (and writes d loss / d h) up to R - 1 rows past the group
+    const int rows_p = (Bg + 15) & ~15;
+    const int Hp = g.Hp, G3 = 3 * Hp;
+    auto ks_of = [](int rp) { return std::max(1, std::min(16, (rp / 16) / 8)); };   // row ranges of k_gru_wgrad, as in the PPO step
+    const int KS = ks_of(rows_p);
+    const int gblocks = (g.total + 255) / 256;
+    const int nblk_r = (d.total + 8 + SG_PPO_REDUCE_PARAMS - 1) / SG_PPO_REDUCE_PARAMS;
+    const int tot_all = d.total + g.total;
+    const int nblk = (tot_all + 8 + 255) / 256;
+
+    // scratch: slabs; d_stacks = heads' input rows | ACT | SC | the chunk's activation stacks; d_gru = everything of the GRU
+    const size_t slab_f = (size_t)G * slab_stride;
+    const size_t hx_f = (size_t)Bgp * d.ldO;
+    auto r4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    const size_t act_f = r4((size_t)Bgp * d.A);   // (the activation stacks behind ACT and SC stay 16-byte aligned)
+    const size_t ep_f = hx_f + act_f + 4 * (size_t)Bgp;
+    const size_t stack_f = ep_f + (size_t)d.n_trunks * mbp * (2 * (size_t)d.ldH + ldP);
+    const size_t o_x = 0, o_mk = o_x + r4((size_t)Bgp * g.ldO), o_h0 = o_mk + r4((size_t)Bgp), o_gi = o_h0 + r4((size_t)ng * g.H);
+    const size_t o_sr = o_gi + (size_t)rows_p * G3, o_sz = o_sr + (size_t)rows_p * Hp, o_sn = o_sz + (size_t)rows_p * Hp;
+    const size_t o_shn = o_sn + (size_t)rows_p * Hp, o_hm = o_shn + (size_t)rows_p * Hp, o_dgi = o_hm + (size_t)rows_p * g.ldH;
+    const size_t o_dgh = o_dgi + (size_t)rows_p * G3, o_dxa = o_dgh + (size_t)rows_p * G3, o_dxc = o_dxa + (size_t)Bgp * d.ldO;
+    const size_t o_part = o_dxc + (size_t)Bgp * d.ldO, o_acc = o_part + (size_t)KS * g.total, gru_f = o_acc + r4((size_t)g.total);
+    bool grew = false;
+    SG_TRY(ensure_cap(ctx->stream, &a->d_slabs, &a->slabs_cap, slab_f, &grew));
+    SG_TRY(ensure_cap(ctx->stream, &a->d_stacks, &a->stacks_cap, stack_f, &grew));
+    SG_TRY(ensure_cap(ctx->stream, &a->d_gru, &a->gru_cap, gru_f, &grew));
+    if (grew) a->cleared.mode = SG_LAYOUT_INVALID;
+    SG_TRY(clear_for_layout(a, {SG_LAYOUT_A2C_GRU, {G, slab_stride, mbp, Bgp, MT, KS, ng, ((int64_t)g.total << 32) | (int64_t)rows_p}},
+                            slab_f, stack_f, gru_f));
+    hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 4);
+
+    float* hX = a->d_stacks;
+    float* epACT = hX + hx_f;
+    float* epSC = epACT + act_f;
+    float* stk = a->d_stacks + ep_f;
+    float* gb = a->d_gru;
+
+    A2cGruGatherArgs ga;
+    ga.obs = r->d_field[SG_F_OBS]; ga.actions = r->d_field[SG_F_ACTIONS]; ga.ret = r->d_field[SG_F_RETURNS];
+    ga.masks = r->d_field[SG_F_MASKS]; ga.h0 = a->d_h0;
+    ga.T = T; ga.N = N; ga.e0 = 0; ga.n = ng; ga.O = g.O; ga.ldO = g.ldO; ga.A = d.A; ga.H = g.H; ga.sc_stride = Bgp;
+    ga.X = gb + o_x; ga.ACT = epACT; ga.SC = epSC; ga.MK = gb + o_mk; ga.H0 = gb + o_h0;
+
+    PpoArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.d = d; pa.params = pol->d_params;
+    pa.sc_stride = Bgp; pa.mbp = mbp; pa.inv_B = 1.0f / (float)TN;   // 1 / (T N) of the whole rollout, whatever the group or chunk
+    pa.vcoef = a->cfg.value_loss_coef; pa.ecoef = a->cfg.entropy_coef;
+    pa.slabs = a->d_slabs; pa.slab_stride = slab_stride; pa.ldP = ldP;
+    pa.st = reinterpret_cast<SgOptState*>(a->d_state); pa.G = G; pa.k1 = 1;
+    for (int t = 0; t < d.n_trunks; ++t) {
+        pa.H1[t] = stk; stk += (size_t)mbp * d.ldH;
+        pa.H2[t] = stk; stk += (size_t)mbp * d.ldH;
+        pa.OUT[t] = stk; stk += (size_t)mbp * ldP;
+    }
+    const int wb_f = gw ? 0 : max_trunk_floats(d), wb_b = gw ? 0 : max_bwd_floats(d);
+    const size_t lds_f = ppo_fwd_lds(d, MT, gw), lds_b = bwd_lds(MT, gw);
+    const double oma = 1.0 - (double)a->alpha;
+
+    GruScanArgs tr;
+    tr.sr = gb + o_sr; tr.sz = gb + o_sz; tr.sn = gb + o_sn; tr.shn = gb + o_shn; tr.hm = gb + o_hm;
+    GruBwdArgs ba;
+    ba.g = g; ba.W = pol->d_params + g.off; ba.dxa = gb + o_dxa; ba.dxc = gb + o_dxc; ba.dx_ld = d.ldO;
+    ba.sr = tr.sr; ba.sz = tr.sz; ba.sn = tr.sn; ba.shn = tr.shn; ba.hm = tr.hm; ba.T = T; ba.n = ng;
+    ba.masks = gb + o_mk; ba.dgi = gb + o_dgi; ba.dgh = gb + o_dgh;
+    GruWgradArgs wa;
+    wa.g = g; wa.dgi = ba.dgi; wa.dgh = ba.dgh; wa.hm = tr.hm; wa.x = gb + o_x; wa.rows_p = rows_p; wa.KS = KS; wa.partial = gb + o_part;
+    const bool gw_scan = sg_gru_force_gw() || sg_gru_scan_lds(g, false) > (size_t)ctx->lds_bytes - 1024 ||
+                         sg_gru_bwd_lds(g, false) > (size_t)ctx->lds_bytes - 1024;
+    const int n_tiles = (G3 / 16) * (g.Op / 16 + Hp / 16) + 2 * (G3 / 16);
+
+    auto enqueue_step = [&]() -> int {
+        for (int k = 0; k < n_groups; ++k) {
+            const int e0 = k * ng, n = std::min(ng, N - e0), rows = T * n, rows_pk = (rows + 15) & ~15;
+            ga.e0 = e0; ga.n = n;
+            hipLaunchKernelGGL(k_a2c_gru_gather<0>, dim3((unsigned)rows), dim3(64), 0, ctx->stream, ga);
+            SG_TRY(sg_gru_forward_launch(ctx, g, pol->d_params + g.off, gb + o_x, g.ldO, gb + o_h0, gb + o_mk, T, n, gb + o_gi, hX, d.ldO,
+                                         nullptr, &tr));
+            for (int rb = 0, c = 0; rb < rows; rb += chunk, ++c) {
+                const int cnt = std::min(chunk, rows - rb), Gc = (cnt + R - 1) / R;
+                pa.mb = cnt;
+                pa.X = hX + (size_t)rb * d.ldO; pa.ACT = epACT + (size_t)rb * d.A; pa.SC = epSC + rb;
+                pa.DX[0] = gb + o_dxa + (size_t)rb * d.ldO; pa.DX[1] = gb + o_dxc + (size_t)rb * d.ldO;
+                pa.wbuf_floats = wb_f;
+                SG_TRY(ppo_launch(ctx, ppo_fwd_family, "k_ppo_fwd", SG_PROF_PPO_FWD, MT, d, dim3(Gc, d.n_trunks), lds_f, pa, gw));
+                pa.wbuf_floats = wb_b;
+                SG_TRY(ppo_launch(ctx, a2c_bwd_dx_family, "k_a2c_bwd (with d loss / d h)", SG_PROF_PPO_BWD, MT, d, dim3(Gc, d.n_trunks),
+                                  lds_b, pa, gw));
+                SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_a2c_reduce, dim3(nblk_r), dim3(256), 0, a->d_slabs, Gc, slab_stride, d.total, a->d_grad,
+                          a->d_part, (k > 0 || c > 0) ? 1 : 0);
+            }
+            if (rows_pk > rows && n < ng) {   // a smaller last group: its padding rows hold a full group's gate gradients
+                SG_CHECK(hipMemsetAsync(gb + o_dgi + (size_t)rows * G3, 0, sizeof(float) * (size_t)(rows_pk - rows) * G3, ctx->stream));
+                SG_CHECK(hipMemsetAsync(gb + o_dgh + (size_t)rows * G3, 0, sizeof(float) * (size_t)(rows_pk - rows) * G3, ctx->stream));
+            }
+            ba.n = n;
+            if (gw_scan) hipLaunchKernelGGL(k_gru_scan_bwd<true>, dim3((n + 15) / 16), dim3(256), sg_gru_bwd_lds(g, true), ctx->stream, ba);
+            else hipLaunchKernelGGL(k_gru_scan_bwd<false>, dim3((n + 15) / 16), dim3(256), sg_gru_bwd_lds(g, false), ctx->stream, ba);
+            wa.rows_p = rows_pk; wa.KS = ks_of(rows_pk);
+            hipLaunchKernelGGL(k_gru_wgrad<0>, dim3(n_tiles, wa.KS), dim3(64), 0, ctx->stream, wa);
+            hipLaunchKernelGGL(k_gru_reduce_acc<0>, dim3(gblocks), dim3(256), 0, ctx->stream, wa.partial, wa.KS, g.total, gb + o_acc,
+                               k > 0 ? 1 : 0, k + 1 == n_groups ? 1 : 0, a->d_grad, d.total, a->d_part, nblk_r);
+        }
+        SG_LAUNCH(ctx, SG_PROF_PPO_ADAM, k_a2c_rmsprop, dim3(nblk), dim3(256), 0, pol->d_params, a->d_v, a->d_grad, a->d_part,
+                  nblk_r + gblocks, tot_all, pa.st, a->alpha, (float)oma, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B, a->d_loss_acc);
+        SG_CHECK(hipGetLastError());
+        return 0;
+    };
+    const bool use_graph = !ctx->profile && !sg_env_is_off("SG_PPO_GRAPH");
+    uint32_t fbits[6];
+    const float fv[6] = {a->alpha, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, pa.inv_B};
+    memcpy(fbits, fv, sizeof fbits);
+    const uint64_t key[SG_GRAPH_KEY_WORDS] = {
+            (uint64_t)(uintptr_t)a->d_slabs, (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_gru,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
+            (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)pol->d_params,
+            (uint64_t)TN, ((uint64_t)T << 32) | (uint64_t)N, ((uint64_t)MT << 32) | (uint64_t)G,
+            ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
+            ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)(uintptr_t)r->d_field[SG_F_MASKS],
+            (uint64_t)(uintptr_t)a->d_h0,
+            0x413247ull + (gw ? 8 : 0) + (gw_scan ? 16 : 0) + ((uint64_t)ng << 32),   // 'A2G': A2C through time, the group size
+            ((uint64_t)chunk << 32) | (uint64_t)rows_p, (uint64_t)KS};
+    SG_TRY(sg_graph_run(ctx, &a->steps_graph, use_graph, key, enqueue_step));
+    SG_CHECK(hipGetLastError());
+    a->opt_t += 1;
+    if (!out3) return 0;   // queued: the losses come through the results ring (step count 1)
+    double acc[3];
+    SG_TRY(sg_ctx_fetch_f64(ctx, a->d_loss_acc, acc, 3));
+    for (int i = 0; i < 3; ++i) out3[i] = (float)acc[i];
+    return 0;
+}
+
 extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_t n_perms, uint64_t seed, float out3[3]) {
     SG_REQUIRE(a && r, "sg_ppo_update: NULL argument");
     if (a->a2c) {
         SG_REQUIRE(!perms, "sg_ppo_update: an A2C update takes the rollout in its own order: perms must be NULL");
+        if (a->a2c_rnn) return a2c_gru_update(a, r, out3);
         SG_REQUIRE(r->O == a->policy->desc.O && r->A == a->policy->desc.A,
                    "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)", r->O, r->A,
                    a->policy->desc.O, a->policy->desc.A);

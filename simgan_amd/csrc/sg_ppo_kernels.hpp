@@ -271,7 +271,8 @@ template <int MT, int KO, int KH, bool FUSED, bool GW = false, bool PAIR = false
 __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, const int bx) {
     static_assert(DIST == SG_DIST_GAUSSIAN || (!PAIR && !SYM && !DX), "Categorical / Bernoulli heads: plain Policy only");
     static_assert(!(SYM && (FUSED || PAIR)), "the symmetric step runs the two-launch form");
-    static_assert(!DX || ((FUSED || GW) && !PAIR && !SYM && !A2C), "d loss / d X needs w1 at hand: the fused or the global-weight form");
+    static_assert(!DX || ((FUSED || GW || A2C) && !PAIR && !SYM), "d loss / d X needs w1 at hand: the fused or the global-weight form, "
+                  "or A2C's two-launch form, which reads w1 from global memory");
     static_assert(!(A2C && (FUSED || PAIR || SYM)), "the A2C step runs the two-launch form");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // (No spare workgroup for Adam's bias corrections any more: with G x trunks = 256 row-group blocks, two extra blocks
@@ -697,6 +698,10 @@ __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, c
         SG_LDS_SYNC();
     }
     if (DX) {   // H1 holds d loss / d (layer-1 pre-activation): dX = that times W1, this trunk's share of d loss / d h_t
+        // (A2C's two-launch form has staged the block from w2 on only: there w1 is read through L2, as the global-weight instances
+        // read every weight -- each element feeds MT <= 2 row tiles, so an LDS copy would be read no more often than it is written)
+        const float* const Wimg_ = W;
+        const float* W = (FUSED || GW) ? Wimg_ : a.params + tr.off;
         float* gdx = a.DX[t] + (size_t)row0 * ldO;
         sg_layer_nn_u<MT>(H1, ldH, W + tr.w1, ldO, Hp, Op, [&](int r, int c, float v) { gdx[r * ldO + c] = v; });
     }
@@ -726,6 +731,12 @@ __global__ __launch_bounds__(512) void k_ppo_bwd_sym(PpoArgs a) {
 template <int MT, int KO, int KH, bool GW = false>
 __global__ __launch_bounds__(512) void k_a2c_bwd(PpoArgs a) {
     sg_ppo_bwd_body<MT, KO, KH, false, GW, false, false, true>(a, blockIdx.y, blockIdx.x);
+}
+// ... on the heads of a recurrent Policy (the rows are GRU states): + d loss / d h_t of both trunks into a.DX (run-time shapes).
+// A kernel of its own, so that the feed-forward instances keep their names and their code.
+template <int MT, bool GW>
+__global__ __launch_bounds__(512) void k_a2c_bwd_dx(PpoArgs a) {
+    sg_ppo_bwd_body<MT, 0, 0, false, GW, false, false, true, true>(a, blockIdx.y, blockIdx.x);
 }
 // ... with a Categorical / Bernoulli head (run-time shapes)
 template <int MT, bool GW, int DIST>
