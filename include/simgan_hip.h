@@ -84,8 +84,8 @@ enum { SG_POLICY_MLP = 0, SG_POLICY_SPLIT = 1, SG_POLICY_GRU = 2 };
  * trunks on the H-wide GRU state, critic_linear and DiagGaussian.  Flat parameter order: base.gru.weight_ih_l0 [3H, O],
  * weight_hh_l0 [3H, H], bias_ih_l0 [3H], bias_hh_l0 [3H], then the MLP kind's order with obs_dim replaced by H.  Such a policy
  * is served by the sg_policy_*_rnn entry points below; sg_policy_act / _get_value / _evaluate / _act_ensemble refuse it (and
- * the _rnn calls refuse a feed-forward policy), as do sg_a2c_create, sg_acktr_create, sg_rollout_compute_returns_policy (on a
- * rollout without hidden states) and sg_rollout_fill_synthetic.  sg_ppo_create takes it: sg_ppo_update then runs PPO through time (sg_ppo_set_hidden_states). */
+ * the _rnn calls refuse a feed-forward policy), as do sg_a2c_create, sg_a2c_create_cnn, sg_acktr_create,
+ * sg_rollout_compute_returns_policy (on a rollout without hidden states) and sg_rollout_fill_synthetic.  sg_ppo_create takes it: sg_ppo_update then runs PPO through time (sg_ppo_set_hidden_states). */
 /* Policy(obs_shape, action_space, base_kwargs)            a2c/model.py:38-67   (kind MLP)
  * SplitPolicy(obs_shape, action_space, base_kwargs)       a2c/model_split.py:40-52 (kind SPLIT;
  * requires act_dim == 7*num_feet, a2c/model_split.py:205). Parameters start at zero. */
@@ -103,8 +103,8 @@ SG_API int sg_policy_create2(sg_ctx *ctx, int kind, int obs_dim, int act_dim, in
  * == n_out, an action row holds n_out 0/1 floats.  Neither has a log-std: the flat order ends with dist.linear.weight
  * [n_out, hidden], dist.linear.bias [n_out].  kind must be SG_POLICY_MLP.  `noise` of sg_policy_act is then UNIFORM draws in
  * [0, 1): one per row (categorical: inverse CDF over ascending class index) or one per bit (Bernoulli: bit = u < p).
- * sg_ppo_create (any world) and sg_a2c_create take such a policy; sg_acktr_create, sg_ppo_set_symmetry (coef > 0) and
- * sg_policy_act_ensemble refuse it. */
+ * sg_ppo_create (any world) and sg_a2c_create take such a policy (sg_a2c_create_cnn: the Categorical head on the CNN base);
+ * sg_acktr_create, sg_ppo_set_symmetry (coef > 0) and sg_policy_act_ensemble refuse it. */
 enum { SG_DIST_GAUSSIAN = 0, SG_DIST_CATEGORICAL = 1, SG_DIST_BERNOULLI = 2 };
 SG_API int sg_policy_create3(sg_ctx *ctx, int kind, int obs_dim, int act_dim, int hidden, int num_feet, int critic_hidden,
                              int dist, int n_out, sg_policy **out);
@@ -119,8 +119,9 @@ SG_API int sg_policy_create3(sg_ctx *ctx, int kind, int obs_dim, int act_dim, in
  * dist.linear.weight [n_out, hidden], .bias or dist.fc_mean.weight [act_dim, hidden], .bias, dist.logstd._bias [act_dim].
  * The handle is taken by sg_policy_act / _get_value / _evaluate / _get_params / _set_params / _num_params, sg_ppo_create
  * (one rank), sg_ppo_update (feed-forward sampler, injected perms, sg_ppo_last_perms, the results ring), sg_ppo_get_adam /
- * _set_adam, sg_rollout_compute_returns_policy and sg_rollout_fill_synthetic; it is refused, each with a message naming the
- * CNN base, by sg_a2c_create, sg_acktr_create, sg_ppo_set_symmetry (coef > 0), sg_policy_act_ensemble, sg_rollout_act_step,
+ * _set_adam, sg_a2c_create_cnn (one rank; sg_a2c_get_rmsprop / _set_rmsprop), sg_rollout_compute_returns_policy and
+ * sg_rollout_fill_synthetic; it is refused, each with a message naming the CNN base, by sg_a2c_create (A2C on it is opt-in by
+ * entry point), sg_acktr_create, sg_ppo_set_symmetry (coef > 0), sg_policy_act_ensemble, sg_rollout_act_step,
  * sg_rollout_act_step_rnn and by sg_ppo_create on a context whose communicator has world > 1.  sg_policy_create / create2 /
  * create3 do not reach it: they keep refusing every kind but their three. */
 SG_API int sg_policy_create_cnn(sg_ctx *ctx, int channels, int height, int width, int hidden, int dist, int act_dim, int n_out,
@@ -423,6 +424,16 @@ SG_API int sg_a2c_create(sg_ctx *ctx, sg_policy *p, const sg_a2c_config *cfg, sg
  * forces a smaller group: test knob), so the scratch does not grow with N.  sg_a2c_get_rmsprop / sg_a2c_set_rmsprop cover the
  * GRU's tensors, which come first in state_dict order. */
 SG_API int sg_a2c_create_rnn(sg_ctx *ctx, sg_policy *p, const sg_a2c_config *cfg, sg_ppo **out);
+/* The same learner on the CNN base (sg_policy_create_cnn; --algo a2c on image observations, the reference's default pairing):
+ * a2c/algo/a2c_acktr.py:52-102 over a2c/model.py:204-230.  Opt-in by entry point: sg_a2c_create keeps refusing a CNN policy.
+ * Refused here, each with its own message: a policy without the CNN base, and a context with a communicator of world > 1.
+ * One update: evaluate_actions on the rollout's T*N rows in their own order, the losses and out3 as above, all means over T*N
+ * rows; clip_grad_norm_ over all parameters, one RMSprop step (the learning rate of sg_ppo_set_lr).  The rows go through the
+ * network in chunks of at most 4096 (SG_A2C_CNN_CHUNK_ROWS=<n >= 1> forces a smaller chunk: test and tuning knob), each
+ * chunk's gradient added to that of the chunks before it in a fixed order, so the scratch (167 KB per chunk row) does not grow
+ * with T*N, no rollout size is refused below 2^30 rows, and two runs are bit-identical.  sg_a2c_get_rmsprop / sg_a2c_set_rmsprop
+ * take square_avg in the CNN's flat order (sg_policy_create_cnn). */
+SG_API int sg_a2c_create_cnn(sg_ctx *ctx, sg_policy *p, const sg_a2c_config *cfg, sg_ppo **out);
 /* RMSprop state for checkpoint/parity: square_avg flat [n] in state_dict order; *step = optimizer steps taken. */
 SG_API int sg_a2c_get_rmsprop(sg_ppo *a, float *square_avg, int64_t n, int64_t *step);
 SG_API int sg_a2c_set_rmsprop(sg_ppo *a, const float *square_avg, int64_t n, int64_t step);

@@ -2,7 +2,8 @@
 acktr=True (--algo acktr, a2c/main.py:159-161, with KFACOptimizer of a2c/algo/kfac.py).
 update() runs entirely on the GPU: evaluate_actions over the whole rollout, the A2C loss and its gradient, then either
 global-norm clipping and one RMSprop step, or the K-FAC statistics, preconditioning and KL-bounded momentum-SGD step.  The
-device object is an sg_ppo in A2C or ACKTR mode (include/simgan_hip.h: sg_a2c_create, sg_acktr_create)."""
+device object is an sg_ppo in A2C or ACKTR mode (include/simgan_hip.h: sg_a2c_create, sg_a2c_create_rnn, sg_a2c_create_cnn,
+sg_acktr_create).  A2C through time (recurrent=True) and A2C on the CNN base (cnn=True) are opt-in by keyword."""
 import ctypes as C
 
 import numpy as np
@@ -65,7 +66,8 @@ class A2C_ACKTR():
                  max_grad_norm=None,
                  acktr=False,
                  seed=0,
-                 recurrent=False):
+                 recurrent=False,
+                 cnn=False):
         if acktr:
             given = [k for k, v in (("lr", lr), ("eps", eps), ("alpha", alpha), ("max_grad_norm", max_grad_norm)) if v is not None]
             if given:
@@ -75,8 +77,19 @@ class A2C_ACKTR():
                                           "does, without lr, eps, alpha and max_grad_norm")
         if type(actor_critic).__name__ == "SplitPolicy":
             raise NotImplementedError("A2C_ACKTR: implemented for Policy (MLP) only, not for SplitPolicy")
-        if getattr(actor_critic, "cnn", 0):
-            raise NotImplementedError("A2C_ACKTR: not implemented for the CNN base (image observations), in either mode; PPO is")
+        is_cnn = bool(getattr(actor_critic, "cnn", 0))
+        if cnn and acktr:
+            raise NotImplementedError("A2C_ACKTR(acktr=True, cnn=True): ACKTR is not implemented for the CNN base (image "
+                                      "observations): K-FAC has no convolution statistics here; acktr=False (A2C) runs")
+        if is_cnn and not cnn:
+            raise NotImplementedError("A2C_ACKTR: not implemented for the CNN base (image observations), in either mode; PPO is "
+                                      "(A2C on the CNN base is opt-in: A2C_ACKTR(..., acktr=False, cnn=True); ACKTR on it is not built)")
+        if cnn and not is_cnn:
+            raise ValueError("A2C_ACKTR(cnn=True) takes a Policy with the CNN base (a [C, 84, 84] obs_shape); this policy has "
+                             "none: leave the keyword out")
+        if cnn and getattr(getattr(actor_critic, "ctx", None), "world", 1) > 1:
+            raise NotImplementedError("A2C_ACKTR(cnn=True): A2C on the CNN base (image observations) runs on one rank "
+                                      f"(this context's world is {actor_critic.ctx.world}): data-parallel A2C is not implemented")
         is_rec = bool(getattr(actor_critic, "is_recurrent", False))
         if is_rec and (acktr or not recurrent):
             raise NotImplementedError("A2C_ACKTR: implemented for feed-forward policies only, not for a recurrent Policy "
@@ -98,6 +111,7 @@ class A2C_ACKTR():
         self.actor_critic = actor_critic
         self.acktr = acktr
         self.recurrent = is_rec
+        self.cnn = is_cnn
         self.value_loss_coef = value_loss_coef
         self.entropy_coef = entropy_coef
         self.max_grad_norm = max_grad_norm
@@ -107,7 +121,7 @@ class A2C_ACKTR():
         self.lib = self.ctx.lib
         cfg = _lib.A2CConfig(float(value_loss_coef), float(entropy_coef), float(lr), float(eps), float(alpha), float(max_grad_norm))
         h = _lib.H()
-        create = self.lib.sg_a2c_create_rnn if is_rec else self.lib.sg_a2c_create
+        create = self.lib.sg_a2c_create_cnn if is_cnn else self.lib.sg_a2c_create_rnn if is_rec else self.lib.sg_a2c_create
         _lib.check(create(self.ctx.h, actor_critic.h, C.byref(cfg), C.byref(h)))
         self.h = h
         if hasattr(actor_critic, "_register_handle_user"):
@@ -118,6 +132,7 @@ class A2C_ACKTR():
         self.actor_critic = actor_critic
         self.acktr = True
         self.recurrent = False
+        self.cnn = False
         self.value_loss_coef = value_loss_coef
         self.entropy_coef = entropy_coef
         self.max_grad_norm = None
@@ -215,6 +230,9 @@ class A2C_ACKTR():
         0 -- neither learner clips a ratio; approx_kl is the measured KL to set beside ACKTR's kl_clip.  The rollout's
         action_log_probs and value_preds (the collection's) are read, which update() itself does not need.  scope: PPO's; A2C and
         ACKTR run at world 1, where "world" gives the rank scope's bits."""
+        if getattr(self, "cnn", False):
+            raise NotImplementedError("A2C_ACKTR.diagnostics: the diagnostics kernels do not cover the CNN base (image "
+                                      "observations); update() returns the three losses")
         return _diag.run(self, rollouts, float("inf"), fetch, scope)
 
     def last_diagnostics(self):

@@ -1,6 +1,8 @@
 // sg_cnn.hip -- the CNN base of Policy on [C, 84, 84] image observations: creation, layout and the launch sequences of its
 // forward and backward passes (kernels: sg_cnn_kernels.hpp).  The entry points a policy handle goes through (sg_policy_act /
 // _get_value / _evaluate, sg_rollout_compute_returns_policy: sg_policy.hip; sg_ppo_update: sg_ppo.hip) call in here.
+// The backward has two forms: PPO's (one minibatch through a permutation, the gradient written) and A2C's (one row chunk of the
+// rollout in place, k_cnn_head_loss_a2c, the gradient written by the first chunk and added to by every later one).
 //
 // Replaces (reference, a2c/ = third_party/a2c_ppo_acktr/):
 //   CNNBase.__init__ / forward        a2c/model.py:204-230   (feed-forward: Conv 8/4 - Conv 4/2 - Conv 3/1 - Flatten - Linear, ReLU
@@ -123,7 +125,7 @@ int sg_cnn_forward_launch(sg_ctx* ctx, const sg_policy* p, const float* d_obs, c
 
 template <typename KernelT>
 static void cnn_wgrad_layer(sg_ctx* ctx, KernelT kernel, const float* dz, const float* in, const int64_t* idx, int n, int ohw, int Ci, int Co,
-                            int kk, int div255, float* slabs, float* gw, float* gb) {
+                            int kk, int div255, float* slabs, float* gw, float* gb, int acc) {
     const int64_t rows = (int64_t)n * ohw;
     const int S = cnn_wgrad_slabs(rows);
     CnnWgradArgs w;
@@ -131,12 +133,12 @@ static void cnn_wgrad_layer(sg_ctx* ctx, KernelT kernel, const float* dz, const 
     w.rows_per_slab = (int)((((rows + S - 1) / S) + 3) & ~(int64_t)3);
     const int K = Ci * kk, N = K + 1;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((N + 127) / 128), (unsigned)((Co + 15) / 16), (unsigned)S), dim3(256), 0, ctx->stream, w);
-    hipLaunchKernelGGL(k_cnn_reduce, dim3((unsigned)(((int64_t)Co * N + 255) / 256)), dim3(256), 0, ctx->stream, slabs, S, Co, K, gw, gb);
+    hipLaunchKernelGGL(k_cnn_reduce, dim3((unsigned)(((int64_t)Co * N + 255) / 256)), dim3(256), 0, ctx->stream, slabs, S, Co, K, gw, gb, acc);
 }
 
 int sg_cnn_backward_launch(sg_ctx* ctx, const sg_policy* p, const sg_rollout* r, const float* d_obs, const int64_t* d_idx, int n,
                            const float* act, const float* heads, int hld, float* bwd, float* grad, float inv_B, float clip,
-                           float vcoef, float ecoef, int use_clipped) {
+                           float vcoef, float ecoef, int use_clipped, int a2c, int acc, int64_t row0) {
     const SgCnnDesc& c = p->cnnd;
     const float* W = p->d_params;
     const float* A1 = act;
@@ -154,21 +156,22 @@ int sg_cnn_backward_launch(sg_ctx* ctx, const sg_policy* p, const sg_rollout* r,
     slabs += (4 - ((slabs - bwd) & 3)) & 3;
 
     CnnLossArgs l;
-    l.d = c; l.params = W; l.heads = heads; l.hld = hld; l.n = n; l.idx = d_idx;
+    l.d = c; l.params = W; l.heads = heads; l.hld = hld; l.n = n; l.idx = d_idx; l.row0 = row0;
     l.actions = r->d_field[SG_F_ACTIONS]; l.old_logp = r->d_field[SG_F_LOGP]; l.adv = r->d_field[SG_F_ADVANTAGES];
     l.vpred = r->d_field[SG_F_VALUE_PREDS]; l.ret = r->d_field[SG_F_RETURNS];
     l.inv_B = inv_B; l.clip = clip; l.vcoef = vcoef; l.ecoef = ecoef; l.use_clipped = use_clipped;
     l.dout = dout; l.dls = dls; l.rowl = rowl;
-    hipLaunchKernelGGL(k_cnn_head_loss, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, l);
+    if (a2c) hipLaunchKernelGGL(k_cnn_head_loss_a2c, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, l);
+    else hipLaunchKernelGGL(k_cnn_head_loss, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, l);
 
     CnnHeadBwdArgs hb;
-    hb.d = c; hb.params = W; hb.feat = F; hb.dout = dout; hb.dls = dls; hb.rowl = rowl; hb.n = n; hb.dzf = dZf; hb.grad = grad;
+    hb.d = c; hb.params = W; hb.feat = F; hb.dout = dout; hb.dls = dls; hb.rowl = rowl; hb.n = n; hb.acc = acc; hb.dzf = dZf; hb.grad = grad;
     hipLaunchKernelGGL(k_cnn_head_dfeat, dim3((unsigned)(((int64_t)n * c.Hs + 255) / 256)), dim3(256), 0, ctx->stream, hb);
     const int n_head = (c.P + 1) * (c.Hs + 1) + c.A;
     hipLaunchKernelGGL(k_cnn_head_wgrad, dim3((unsigned)((n_head + 255) / 256)), dim3(256), 0, ctx->stream, hb);
 
     // FC: weight gradient on A3, data gradient dZf x Wf (a 1x1 "convolution" with the weight read transposed), conv3's mask
-    cnn_wgrad_layer(ctx, k_cnn_wgrad<7, 7, 1, 1>, dZf, A3, nullptr, n, 1, 32, c.Hs, 49, 0, slabs, grad + c.wf, grad + c.bf);
+    cnn_wgrad_layer(ctx, k_cnn_wgrad<7, 7, 1, 1>, dZf, A3, nullptr, n, 1, 32, c.Hs, 49, 0, slabs, grad + c.wf, grad + c.bf, acc);
     CnnConvArgs a;
     memset(&a, 0, sizeof a);
     a.n_img = n;
@@ -178,18 +181,18 @@ int sg_cnn_backward_launch(sg_ctx* ctx, const sg_policy* p, const sg_rollout* r,
     const int64_t n3 = (int64_t)n * SG_CNN_A3;
     hipLaunchKernelGGL(k_cnn_relu_mask, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, ctx->stream, dZ3, A3, n3);
     // conv3
-    cnn_wgrad_layer(ctx, k_cnn_wgrad<3, 3, 1, 7>, dZ3, A2, nullptr, n, 49, 64, 32, 9, 0, slabs, grad + c.w3, grad + c.b3);
+    cnn_wgrad_layer(ctx, k_cnn_wgrad<3, 3, 1, 7>, dZ3, A2, nullptr, n, 49, 64, 32, 9, 0, slabs, grad + c.w3, grad + c.b3, acc);
     a.wt = 0;
     a.in = dZ3; a.w = W + c.w3; a.mask = A2; a.out = dZ2;
     a.Ci = 64; a.Co = 32; a.IH = a.IW = 9; a.OH = a.OW = 7;
     hipLaunchKernelGGL((k_cnn_conv_bwd_data<3, 3, 1>), cnn_grid((int64_t)n * 81, 64), dim3(256), 0, ctx->stream, a);
     // conv2
-    cnn_wgrad_layer(ctx, k_cnn_wgrad<4, 4, 2, 9>, dZ2, A1, nullptr, n, 81, 32, 64, 16, 0, slabs, grad + c.w2, grad + c.b2);
+    cnn_wgrad_layer(ctx, k_cnn_wgrad<4, 4, 2, 9>, dZ2, A1, nullptr, n, 81, 32, 64, 16, 0, slabs, grad + c.w2, grad + c.b2, acc);
     a.in = dZ2; a.w = W + c.w2; a.mask = A1; a.out = dZ1;
     a.Ci = 32; a.Co = 64; a.IH = a.IW = 20; a.OH = a.OW = 9;
     hipLaunchKernelGGL((k_cnn_conv_bwd_data<4, 4, 2>), cnn_grid((int64_t)n * 400, 32), dim3(256), 0, ctx->stream, a);
     // conv1 (no data gradient: the observation is a leaf)
-    cnn_wgrad_layer(ctx, k_cnn_wgrad<8, 8, 4, 20>, dZ1, d_obs, d_idx, n, 400, c.C, 32, 64, 1, slabs, grad + c.w1, grad + c.b1);
+    cnn_wgrad_layer(ctx, k_cnn_wgrad<8, 8, 4, 20>, dZ1, d_obs, d_idx, n, 400, c.C, 32, 64, 1, slabs, grad + c.w1, grad + c.b1, acc);
     SG_CHECK(hipGetLastError());
     return 0;
 }

@@ -191,16 +191,17 @@ __global__ __launch_bounds__(256) void k_cnn_wgrad(CnnWgradArgs a) {
     }
 }
 
-// slabs [S][Co][K + 1] -> the flat gradient's weight [Co][K] and bias [Co], slab 0 first
-__global__ __launch_bounds__(256) void k_cnn_reduce(const float* slabs, int n_slabs, int Co, int K, float* gw, float* gb) {
+// slabs [S][Co][K + 1] -> the flat gradient's weight [Co][K] and bias [Co], slab 0 first.  acc: the running value starts from
+// what the flat gradient already holds (a later row chunk of one A2C update) instead of from 0
+__global__ __launch_bounds__(256) void k_cnn_reduce(const float* slabs, int n_slabs, int Co, int K, float* gw, float* gb, int acc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int N = K + 1;
     if (i >= Co * N) return;
-    float g = 0.f;
-    for (int s = 0; s < n_slabs; ++s) g += slabs[(size_t)s * Co * N + i];
     const int co = i / N, k = i - co * N;
-    if (k < K) gw[(size_t)co * K + k] = g;
-    else gb[co] = g;
+    float* dst = k < K ? gw + (size_t)co * K + k : gb + co;
+    float g = acc ? *dst : 0.f;
+    for (int s = 0; s < n_slabs; ++s) g += slabs[(size_t)s * Co * N + i];
+    *dst = g;
 }
 
 // ------------------------------------------------------------------------------------------------ heads
@@ -232,22 +233,80 @@ __global__ __launch_bounds__(256) void k_cnn_head_fwd(CnnHeadArgs a) {
     else a.heads[r * a.hld + (j - 1)] = s;
 }
 
-// PPO's per-row loss and its gradient at the head outputs (a2c/algo/ppo.py:92-106), one thread per minibatch row: the
-// arithmetic of k_ppo_bwd / k_ppo_bwd_dist's loss blocks (the clipped surrogate through sg_ppo_row_weight's lines, the clipped
-// or plain value loss, the entropy bonus), reading the row's action and scalars in place from the rollout through idx.
+// The per-row losses and their gradients at the head outputs, one thread per row.  PPO (k_cnn_head_loss, a2c/algo/ppo.py:92-106):
+// the arithmetic of k_ppo_bwd / k_ppo_bwd_dist's loss blocks (the clipped surrogate through sg_ppo_row_weight's lines, the clipped
+// or plain value loss, the entropy bonus), reading the row's action and scalars in place from the rollout through idx.  A2C
+// (k_cnn_head_loss_a2c, a2c/algo/a2c_acktr.py:65-72): adv = R - v, value loss adv^2, action loss -adv.detach() logp, on the
+// chunk's rows [row0, row0 + n) of the rollout in its own order.  Both share the distribution arithmetic below.
 struct CnnLossArgs {
     SgCnnDesc d;
     const float* params;
     const float* heads;   // [2][n][hld]
     int hld, n;
-    const int64_t* idx;   // [n] rollout rows of this minibatch
-    const float *actions, *old_logp, *adv, *vpred, *ret;   // rollout fields
-    float inv_B, clip, vcoef, ecoef;
+    const int64_t* idx;   // PPO: [n] rollout rows of this minibatch
+    int64_t row0;         // A2C: the chunk's first rollout row
+    const float *actions, *old_logp, *adv, *vpred, *ret;   // rollout fields (A2C reads actions and ret only)
+    float inv_B, clip, vcoef, ecoef;   // A2C: inv_B = 1 / (T N) of the whole rollout in every chunk
     int use_clipped;
     float* dout;          // [n][1 + P]: d loss / d value, then d loss / d logits (or means)
     float* dls;           // [n][A] per-row d loss / d log-std (Gaussian)
     float* rowl;          // [3][n]: value loss, action loss, entropy of each row
 };
+
+// log-prob of the row's action and the entropy of its distribution at the head outputs z: Categorical with the row maximum
+// subtracted and the log-normaliser from the OTHER classes' mass (log1p), Gaussian with the float32 constants of
+// a2c/distributions.py's FixedNormal.  m, l1p and act are what sg_cnn_dist_grad needs again.
+struct CnnDistRow {
+    float logp, ent, m, l1p;
+    int act;
+};
+__device__ __forceinline__ CnnDistRow sg_cnn_dist_row(const SgCnnDesc& d, const float* params, const float* z, const float* actions,
+                                                      int64_t src) {
+    CnnDistRow s;
+    s.logp = 0.f; s.ent = 0.f; s.m = 0.f; s.l1p = 0.f; s.act = 0;
+    if (d.dist == SG_DIST_CATEGORICAL) {
+        const int K = d.P;
+        s.m = z[0];
+        int am = 0;
+        for (int k = 1; k < K; ++k)
+            if (z[k] > s.m) { s.m = z[k]; am = k; }
+        float S = 0.f;
+        for (int k = 0; k < K; ++k)
+            if (k != am) S += expf(z[k] - s.m);
+        s.l1p = log1pf(S);
+        for (int k = 0; k < K; ++k) { const float lp = (z[k] - s.m) - s.l1p; s.ent -= expf(lp) * lp; }
+        s.act = (int)actions[src];
+        s.act = s.act < 0 ? 0 : (s.act > K - 1 ? K - 1 : s.act);
+        s.logp = (z[s.act] - s.m) - s.l1p;
+    } else {
+        for (int k = 0; k < d.A; ++k) {
+            const float ls = params[d.ls + k];
+            const float sigma = expf(ls), diff = actions[src * d.A + k] - z[k], lsig = logf(sigma);
+            s.logp += -(diff * diff) / (2.f * sigma * sigma) - lsig - 0.91893853320467274178f;
+            s.ent += 0.5f + 0.91893853320467274178f + lsig;
+        }
+    }
+    return s;
+}
+
+// d loss / d logits (or means, and the row's d loss / d log-std) from dlogp = d loss / d logp and dent = ecoef inv_B, the
+// entropy bonus's weight
+__device__ __forceinline__ void sg_cnn_dist_grad(const SgCnnDesc& d, const float* params, const float* z, const float* actions,
+                                                 int64_t src, const CnnDistRow& s, float dlogp, float dent, float* dout, float* dls) {
+    if (d.dist == SG_DIST_CATEGORICAL) {
+        for (int k = 0; k < d.P; ++k) {
+            const float lp = (z[k] - s.m) - s.l1p, p = expf(lp);
+            dout[1 + k] = dlogp * ((k == s.act ? 1.f : 0.f) - p) + dent * p * (lp + s.ent);
+        }
+    } else {
+        for (int k = 0; k < d.A; ++k) {
+            const float ls = params[d.ls + k];
+            const float sigma = expf(ls), var = sigma * sigma, diff = actions[src * d.A + k] - z[k];
+            dout[1 + k] = dlogp * diff / var;
+            dls[k] = dlogp * (diff * diff / var - 1.f) - dent;
+        }
+    }
+}
 
 __global__ __launch_bounds__(256) void k_cnn_head_loss(CnnLossArgs a) {
     const int row = blockIdx.x * blockDim.x + threadIdx.x;
@@ -275,34 +334,10 @@ __global__ __launch_bounds__(256) void k_cnn_head_loss(CnnLossArgs a) {
         dout[0] = dv * a.vcoef;
         a.rowl[row] = lv;
     }
-    float logp = 0.f, ent = 0.f;
-    float m = 0.f, l1p = 0.f;
-    int act = 0;
-    if (d.dist == SG_DIST_CATEGORICAL) {
-        const int K = d.P;
-        m = z[0];
-        int am = 0;
-        for (int k = 1; k < K; ++k)
-            if (z[k] > m) { m = z[k]; am = k; }
-        float S = 0.f;
-        for (int k = 0; k < K; ++k)
-            if (k != am) S += expf(z[k] - m);
-        l1p = log1pf(S);
-        for (int k = 0; k < K; ++k) { const float lp = (z[k] - m) - l1p; ent -= expf(lp) * lp; }
-        act = (int)a.actions[src];
-        act = act < 0 ? 0 : (act > K - 1 ? K - 1 : act);
-        logp = (z[act] - m) - l1p;
-    } else {
-        for (int k = 0; k < d.A; ++k) {
-            const float ls = a.params[d.ls + k];
-            const float sigma = expf(ls), diff = a.actions[src * d.A + k] - z[k], lsig = logf(sigma);
-            logp += -(diff * diff) / (2.f * sigma * sigma) - lsig - 0.91893853320467274178f;
-            ent += 0.5f + 0.91893853320467274178f + lsig;
-        }
-    }
+    const CnnDistRow s = sg_cnn_dist_row(d, a.params, z, a.actions, src);
     // the clipped surrogate (a2c/algo/ppo.py:92-97)
     const float adv = a.adv[src];
-    const float ratio = expf(logp - a.old_logp[src]);
+    const float ratio = expf(s.logp - a.old_logp[src]);
     const float surr1 = ratio * adv;
     const float surr2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * adv;
     const float w1 = surr1 < surr2 ? 1.f : (surr1 > surr2 ? 0.f : 0.5f);  // torch.min tie -> 1/2, 1/2
@@ -310,20 +345,28 @@ __global__ __launch_bounds__(256) void k_cnn_head_loss(CnnLossArgs a) {
     const float dlogp = -a.inv_B * (w1 * adv + (1.f - w1) * adv * inr) * ratio;
     const float dent = a.ecoef * a.inv_B;
     a.rowl[a.n + row] = -fminf(surr1, surr2);
-    a.rowl[2 * a.n + row] = ent;
-    if (d.dist == SG_DIST_CATEGORICAL) {
-        for (int k = 0; k < d.P; ++k) {
-            const float lp = (z[k] - m) - l1p, p = expf(lp);
-            dout[1 + k] = dlogp * ((k == act ? 1.f : 0.f) - p) + dent * p * (lp + ent);
-        }
-    } else {
-        for (int k = 0; k < d.A; ++k) {
-            const float ls = a.params[d.ls + k];
-            const float sigma = expf(ls), var = sigma * sigma, diff = a.actions[src * d.A + k] - z[k];
-            dout[1 + k] = dlogp * diff / var;
-            a.dls[(size_t)row * d.A + k] = dlogp * (diff * diff / var - 1.f) - dent;
-        }
-    }
+    a.rowl[2 * a.n + row] = s.ent;
+    sg_cnn_dist_grad(d, a.params, z, a.actions, src, s, dlogp, dent, dout, a.dls + (size_t)row * d.A);
+}
+
+// A2C: loss = vcoef mean(adv^2) - mean(adv.detach() logp) - ecoef mean(ent) over ALL T N rows, of which this launch holds n
+__global__ __launch_bounds__(256) void k_cnn_head_loss_a2c(CnnLossArgs a) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= a.n) return;
+    const SgCnnDesc& d = a.d;
+    const int64_t src = a.row0 + row;
+    const float* z = a.heads + (size_t)row * a.hld;
+    const float v = a.heads[((size_t)a.n + row) * a.hld];
+    float* dout = a.dout + (size_t)row * (d.P + 1);
+    const float Rt = a.ret[src];
+    const float adv = Rt - v;
+    dout[0] = a.vcoef * 2.f * (v - Rt) * a.inv_B;
+    a.rowl[row] = adv * adv;
+    const CnnDistRow s = sg_cnn_dist_row(d, a.params, z, a.actions, src);
+    a.rowl[a.n + row] = -(adv * s.logp);
+    a.rowl[2 * a.n + row] = s.ent;
+    // d/dlogp of -adv logp inv_B with adv detached; the value head's gradient is dout[0] alone
+    sg_cnn_dist_grad(d, a.params, z, a.actions, src, s, -adv * a.inv_B, a.ecoef * a.inv_B, dout, a.dls + (size_t)row * d.A);
 }
 
 struct CnnHeadBwdArgs {
@@ -334,6 +377,7 @@ struct CnnHeadBwdArgs {
     const float* dls;     // [n][A]
     const float* rowl;    // [3][n]
     int n;
+    int acc;              // k_cnn_head_wgrad: add to what grad holds (a later row chunk of one A2C update) instead of starting from 0
     float* dzf;           // [n][Hs]: gradient at the FC layer's pre-activation
     float* grad;          // the flat gradient (+ 3 loss sums behind it)
 };
@@ -351,7 +395,8 @@ __global__ __launch_bounds__(256) void k_cnn_head_dfeat(CnnHeadBwdArgs a) {
 }
 
 // gradients of critic_linear, the distribution's Linear and the log-std: one thread per parameter, rows in ascending order;
-// block 0 also leaves the three loss sums behind the gradient (k_ppo_adam's convention)
+// block 0 also leaves the three loss sums behind the gradient (k_ppo_adam's convention).  acc: every element, the loss sums
+// too, starts from what grad already holds
 __global__ __launch_bounds__(256) void k_cnn_head_wgrad(CnnHeadBwdArgs a) {
     const SgCnnDesc& d = a.d;
     const int P1 = d.P + 1, Hs = d.Hs;
@@ -359,17 +404,19 @@ __global__ __launch_bounds__(256) void k_cnn_head_wgrad(CnnHeadBwdArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_w) {
         const int j = i / Hs, h = i - j * Hs;
-        float g = 0.f;
+        float* dst = a.grad + (j == 0 ? d.wc : d.wd + (j - 1) * Hs) + h;
+        float g = a.acc ? *dst : 0.f;
         for (int r = 0; r < a.n; ++r) g += a.dout[(size_t)r * P1 + j] * a.feat[(size_t)r * Hs + h];
-        a.grad[(j == 0 ? d.wc : d.wd + (j - 1) * Hs) + h] = g;
+        *dst = g;
     } else if (i < n_w + n_b) {
         const int j = i - n_w;
-        float g = 0.f;
+        float* dst = a.grad + (j == 0 ? d.bc : d.bd + (j - 1));
+        float g = a.acc ? *dst : 0.f;
         for (int r = 0; r < a.n; ++r) g += a.dout[(size_t)r * P1 + j];
-        a.grad[j == 0 ? d.bc : d.bd + (j - 1)] = g;
+        *dst = g;
     } else if (i < n_w + n_b + n_ls) {
         const int k = i - n_w - n_b;
-        float g = 0.f;
+        float g = a.acc ? a.grad[d.ls + k] : 0.f;
         for (int r = 0; r < a.n; ++r) g += a.dls[(size_t)r * d.A + k];
         a.grad[d.ls + k] = g;
     }
@@ -384,7 +431,7 @@ __global__ __launch_bounds__(256) void k_cnn_head_wgrad(CnnHeadBwdArgs a) {
                 if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
                 __syncthreads();
             }
-            if (threadIdx.x == 0) a.grad[d.total + l] = red[0];
+            if (threadIdx.x == 0) a.grad[d.total + l] = a.acc ? a.grad[d.total + l] + red[0] : red[0];
             __syncthreads();
         }
     }

@@ -267,10 +267,12 @@ size_t sg_cnn_bwd_floats(const SgCnnDesc& c, int n);     // gradient stacks, los
 // obs rows (idx NULL: rows 0..n-1) -> act (sg_cnn_fwd_floats(n)) and rows [row0, row0 + n) of heads [2][n_total][hld]
 int sg_cnn_forward_launch(sg_ctx* ctx, const sg_policy* p, const float* d_obs, const int64_t* d_idx, int n, float* act,
                           float* heads, int hld, int row0, int n_total);
-// one minibatch's loss and gradient from the stacks of sg_cnn_forward_launch: grad[total + 3] flat, loss sums behind it
+// one minibatch's loss and gradient from the stacks of sg_cnn_forward_launch: grad[total + 3] flat, loss sums behind it.
+// a2c: the A2C loss (k_cnn_head_loss_a2c) on rollout rows [row0, row0 + n), d_obs pointing at the first of them and d_idx NULL;
+// acc: add to what grad holds (the row chunks of one A2C update after the first)
 int sg_cnn_backward_launch(sg_ctx* ctx, const sg_policy* p, const struct sg_rollout* r, const float* d_obs, const int64_t* d_idx,
                            int n, const float* act, const float* heads, int hld, float* bwd, float* grad, float inv_B, float clip,
-                           float vcoef, float ecoef, int use_clipped);
+                           float vcoef, float ecoef, int use_clipped, int a2c, int acc, int64_t row0);
 
 size_t sg_policy_padded_count(const sg_policy* p);          // floats of d_params (heads + GRU block)
 // sg_policy.hip: the one way p->d_io grows.  Nothing while io_bytes >= bytes; otherwise the stream is drained (queued work may
@@ -380,6 +382,7 @@ struct sg_ppo {
     bool a2c = false;
     float alpha = 0.f;
     bool a2c_rnn = false;          // sg_a2c_create_rnn: A2C through time on a recurrent Policy (the update's recurrent branch)
+    bool a2c_cnn = false;          // sg_a2c_create_cnn: A2C on the CNN base, the whole rollout in row chunks (a2c_cnn_update)
     // ACKTR (sg_acktr_create): A2C's gradient (a2c is set too), then the K-FAC step (sg_ppo.hip); d_m holds SGD's momentum buffer
     struct SgKfac* kfac = nullptr;
 };

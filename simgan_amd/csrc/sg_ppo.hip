@@ -25,6 +25,10 @@
 //   k_a2c_gru_gather -> k_gru_inproj -> k_gru_scan_fwd<TRAIN>;  per chunk:  k_ppo_fwd -> k_a2c_bwd_dx -> k_a2c_reduce;
 //   k_gru_scan_bwd -> k_gru_wgrad -> k_gru_reduce_acc;  then one k_a2c_rmsprop over heads + GRU
 //
+// A2C on the CNN base (sg_a2c_create_cnn; a2c_cnn_update), per chunk of <= SG_A2C_CNN_CHUNK_ROWS rows:
+//   the forward of sg_cnn.hip -> k_cnn_head_loss_a2c -> head, FC, conv3, conv2, conv1 gradients (adding from the second chunk on);
+//   then k_sumsq -> k_a2c_rmsprop
+//
 // ACKTR (sg_acktr_create: A2C's gradient with the K-FAC step of a2c/algo/kfac.py, sg_kfac.hpp), one update:
 //   k_a2c_gather
 //   per chunk:  k_ppo_fwd -> k_a2c_bwd -> k_a2c_reduce -> k_acktr_fisher -> k_kfac_stats (adds to the factor sums)
@@ -243,7 +247,8 @@ extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg
 // (a2c/algo/a2c_acktr.py:30-51: RMSprop, square_avg starting at zero).  Policy (MLP) on one rank only.
 extern "C" int sg_a2c_create(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg, sg_ppo** out) {
     SG_REQUIRE(ctx && p && cfg && out, "sg_a2c_create: NULL argument");
-    SG_REQUIRE(!p->cnn, "sg_a2c_create: A2C is not implemented for the CNN base (image observations): PPO is");
+    SG_REQUIRE(!p->cnn, "sg_a2c_create: A2C is not implemented for the CNN base (image observations): PPO is (A2C on it has an "
+               "entry point of its own, sg_a2c_create_cnn)");
     SG_REQUIRE(!p->recurrent, "sg_a2c_create: A2C is implemented for feed-forward policies only, not for a recurrent Policy");
     SG_REQUIRE(p->desc.kind == SG_POLICY_MLP, "sg_a2c_create: A2C is implemented for Policy (MLP) only, not for SplitPolicy");
     SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_a2c_create: A2C runs on one rank: this context has a communicator of "
@@ -287,6 +292,32 @@ extern "C" int sg_a2c_create_rnn(sg_ctx* ctx, sg_policy* p, const sg_a2c_config*
     SG_TRY(sg_ppo_create(ctx, p, &pc, &a));
     a->a2c = true;
     a->a2c_rnn = true;
+    a->alpha = cfg->alpha;
+    *out = a;
+    return 0;
+}
+
+// The same learner on the CNN base (a2c/algo/a2c_acktr.py:52-102 over a2c/model.py:204-230, the reference's default pairing):
+// the update takes the whole rollout in row chunks whose gradients accumulate (a2c_cnn_update).  An entry point of its own:
+// sg_a2c_create keeps refusing a CNN policy.
+extern "C" int sg_a2c_create_cnn(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg, sg_ppo** out) {
+    SG_REQUIRE(ctx && p && cfg && out, "sg_a2c_create_cnn: NULL argument");
+    SG_REQUIRE(p->cnn, "sg_a2c_create_cnn: A2C on image observations takes a policy with the CNN base (sg_policy_create_cnn); this "
+               "policy has none (sg_a2c_create%s)", p->recurrent ? "_rnn" : "");
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_a2c_create_cnn: A2C on the CNN base (image observations) runs on one rank: this "
+               "context has a communicator of world %d (data-parallel A2C is not implemented)", ctx->world);
+    SG_REQUIRE(cfg->alpha >= 0.f && cfg->alpha <= 1.f && cfg->eps >= 0.f && cfg->max_grad_norm > 0.f,
+               "sg_a2c_create_cnn: alpha must lie in [0, 1], eps >= 0 and max_grad_norm > 0 (got %g, %g, %g)", (double)cfg->alpha,
+               (double)cfg->eps, (double)cfg->max_grad_norm);
+    sg_ppo_config pc;
+    memset(&pc, 0, sizeof pc);
+    pc.ppo_epoch = 1; pc.num_mini_batch = 1;
+    pc.value_loss_coef = cfg->value_loss_coef; pc.entropy_coef = cfg->entropy_coef;
+    pc.lr = cfg->lr; pc.eps = cfg->eps; pc.max_grad_norm = cfg->max_grad_norm;
+    sg_ppo* a = nullptr;
+    SG_TRY(sg_ppo_create(ctx, p, &pc, &a));
+    a->a2c = true;
+    a->a2c_cnn = true;
     a->alpha = cfg->alpha;
     *out = a;
     return 0;
@@ -514,6 +545,14 @@ extern "C" int sg_a2c_get_rmsprop(sg_ppo* a, float* square_avg, int64_t n, int64
     const SgPolicyDesc& d = a->policy->desc;
     const sg_policy* pol = a->policy;
     const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;   // the GRU's tensors come first in the flat order
+    if (pol->cnn) {   // the CNN base keeps the flat order on the device
+        SG_REQUIRE(n == pol->cnnd.total, "sg_a2c_get_rmsprop: bad length");
+        SG_CHECK(hipSetDevice(a->ctx->device));
+        SG_CHECK(hipStreamSynchronize(a->ctx->stream));
+        SG_COPY_SYNC(a->ctx, square_avg, a->d_v, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
+        *step = a->opt_t;
+        return 0;
+    }
     SG_REQUIRE(n == sg_policy_flat_count(d) + n_gru, "sg_a2c_get_rmsprop: bad length");
     const size_t ptot = sg_policy_padded_count(pol);
     std::vector<float> pv(ptot);
@@ -533,6 +572,15 @@ extern "C" int sg_a2c_set_rmsprop(sg_ppo* a, const float* square_avg, int64_t n,
     const SgPolicyDesc& d = a->policy->desc;
     const sg_policy* pol = a->policy;
     const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;
+    if (pol->cnn) {
+        SG_REQUIRE(n == pol->cnnd.total, "sg_a2c_set_rmsprop: bad length");
+        SG_REQUIRE(step >= 0, "sg_a2c_set_rmsprop: step out of range");
+        SG_CHECK(hipSetDevice(a->ctx->device));
+        SG_CHECK(hipStreamSynchronize(a->ctx->stream));
+        SG_COPY_SYNC(a->ctx, a->d_v, square_avg, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
+        a->opt_t = step;
+        return 0;
+    }
     SG_REQUIRE(n == sg_policy_flat_count(d) + n_gru, "sg_a2c_set_rmsprop: bad length");
     SG_REQUIRE(step >= 0, "sg_a2c_set_rmsprop: step out of range");
     const size_t ptot = sg_policy_padded_count(pol);
@@ -1082,7 +1130,7 @@ static int cnn_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
                 const int64_t* idx = a->d_perms + (size_t)e * TN + (size_t)k * mb;
                 SG_TRY(sg_cnn_forward_launch(ctx, pol, obs, idx, mb, act, heads, hld, 0, mb));
                 SG_TRY(sg_cnn_backward_launch(ctx, pol, r, obs, idx, mb, act, heads, hld, bwd, a->d_grad, inv_B, a->cfg.clip_param,
-                                              a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.use_clipped_value_loss));
+                                              a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.use_clipped_value_loss, 0, 0, 0));
                 hipLaunchKernelGGL(k_sumsq, dim3(nblk), dim3(256), 0, ctx->stream, a->d_grad, c.total, a->d_part);
                 SG_LAUNCH(ctx, SG_PROF_PPO_ADAM, k_ppo_adam, dim3(nblk), dim3(256), 0, pol->d_params, a->d_m, a->d_v, a->d_grad, a->d_part,
                           nblk, c.total, st, e * M + k + 1, a->cfg.eps, a->cfg.max_grad_norm, inv_B, a->d_loss_acc);
@@ -1113,6 +1161,97 @@ static int cnn_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
     SG_TRY(sg_ctx_fetch_f64(ctx, a->d_loss_acc, acc, 3));
     const double nu = (double)E * M;
     for (int i = 0; i < 3; ++i) out3[i] = (float)(acc[i] / nu);
+    return 0;
+}
+
+// ------------------------------------------------------------------- A2C on the CNN base
+// Rows of one chunk: its activation and gradient stacks are 167 KB per row, 684 MB at 4096 -- the fastest of 256 ... 4096 measured
+// at 8192 rows (66.6, 58.7, 58.2, 56.3, 56.0 ms) that stays under 1 GB, and PPO's minibatch cap.  A rollout of
+// fewer rows is one chunk of its own size.  SG_A2C_CNN_CHUNK_ROWS (any n >= 1: test and tuning knob, after SG_A2C_GROUP_ENVS)
+// forces a smaller chunk.
+#define SG_A2C_CNN_CHUNK_ROWS 4096
+static int a2c_cnn_chunk_rows(int64_t TN) {
+    int chunk = SG_A2C_CNN_CHUNK_ROWS;
+    if (const char* e = getenv("SG_A2C_CNN_CHUNK_ROWS")) {
+        const long v = atol(e);
+        if (v >= 1) chunk = (int)std::min<long>(v, SG_CNN_MAX_MB);
+    }
+    return (int)std::min<int64_t>(chunk, TN);
+}
+
+// A2C_ACKTR.update(rollouts), acktr=False, on the CNN base (a2c/algo/a2c_acktr.py:52-102 over a2c/model.py:204-230): ONE loss
+// over all T*N rows, one clip, one RMSprop step.  The rows go through the network in chunks, in rollout order:
+//   per chunk:  the forward of sg_cnn.hip on the chunk's frames (read in place from the rollout: no epoch copy)
+//               -> k_cnn_head_loss_a2c (inv_B = 1 / (T N) whatever the chunk) -> head, FC, conv3, conv2, conv1 gradients, each
+//               weight gradient as slabs + k_cnn_reduce; from the second chunk on every reduce ADDS to the flat gradient
+//               (acc = 1: the running value starts from what the gradient holds), so nothing is cleared and the summation
+//               order of every element is fixed by T*N and the chunk size
+//   then        k_sumsq -> k_a2c_rmsprop (the learning rate from the device scalars: sg_ppo_set_lr)
+// One captured graph, replayed per update; no host wait inside.  The scratch is sized by the chunk, not by T*N.
+static int a2c_cnn_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
+    sg_ctx* ctx = a->ctx;
+    sg_policy* pol = a->policy;
+    const SgPolicyDesc& d = pol->desc;
+    const SgCnnDesc& c = pol->cnnd;
+    SG_REQUIRE(r->O == d.O && r->A == d.A, "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)", r->O, r->A,
+               d.O, d.A);
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_ppo_update: A2C on the CNN base runs on one rank (world %d)", ctx->world);
+    const int64_t TN = (int64_t)r->T * r->N;
+    SG_REQUIRE(TN > 0 && TN < (1ll << 30), "sg_ppo_update: %lld rollout rows", (long long)TN);
+    SG_CHECK(hipSetDevice(ctx->device));
+    const int chunk = a2c_cnn_chunk_rows(TN);
+    const int n_chunks = (int)((TN + chunk - 1) / chunk);
+    // scratch of one full chunk: head stacks | activation stacks | gradient stacks and slabs
+    const int hld = d.trunk[0].Pp > 16 ? d.trunk[0].Pp : 16;
+    const size_t heads_f = 2 * (size_t)chunk * hld, fwd_f = sg_cnn_fwd_floats(c, chunk), bwd_f = sg_cnn_bwd_floats(c, chunk);
+    bool grew = false;
+    SG_TRY(ensure_cap(ctx->stream, &a->d_stacks, &a->stacks_cap, heads_f + fwd_f + bwd_f, &grew));
+    if (grew) a->cleared.mode = SG_LAYOUT_INVALID;
+    float* heads = a->d_stacks;
+    float* act = heads + heads_f;
+    float* bwd = act + fwd_f;
+    hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 4);
+    const float inv_B = 1.0f / (float)TN;
+    const int nblk = (c.total + 255) / 256;
+    const double oma = 1.0 - (double)a->alpha;   // torch: value = 1 - alpha in Python doubles
+    SgOptState* st = reinterpret_cast<SgOptState*>(a->d_state);
+    const float* obs = r->d_field[SG_F_OBS];
+
+    auto enqueue_step = [&]() -> int {
+        for (int k = 0; k < n_chunks; ++k) {
+            const int64_t rb = (int64_t)k * chunk;
+            const int cnt = (int)std::min<int64_t>(chunk, TN - rb);
+            const float* frames = obs + (size_t)rb * d.O;
+            SG_TRY(sg_cnn_forward_launch(ctx, pol, frames, nullptr, cnt, act, heads, hld, 0, cnt));
+            SG_TRY(sg_cnn_backward_launch(ctx, pol, r, frames, nullptr, cnt, act, heads, hld, bwd, a->d_grad, inv_B, 0.f,
+                                          a->cfg.value_loss_coef, a->cfg.entropy_coef, 0, 1, k > 0 ? 1 : 0, rb));
+        }
+        hipLaunchKernelGGL(k_sumsq, dim3(nblk), dim3(256), 0, ctx->stream, a->d_grad, c.total, a->d_part);
+        SG_LAUNCH(ctx, SG_PROF_PPO_ADAM, k_a2c_rmsprop, dim3(nblk), dim3(256), 0, pol->d_params, a->d_v, a->d_grad, a->d_part, nblk,
+                  c.total, st, a->alpha, (float)oma, a->cfg.eps, a->cfg.max_grad_norm, inv_B, a->d_loss_acc);
+        SG_CHECK(hipGetLastError());
+        return 0;
+    };
+    const bool use_graph = !ctx->profile && !sg_env_is_off("SG_PPO_GRAPH");
+    uint32_t fbits[6];
+    const float fv[6] = {a->alpha, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, inv_B};
+    memcpy(fbits, fv, sizeof fbits);
+    const uint64_t key[SG_GRAPH_KEY_WORDS] = {
+            (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_grad, 0,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
+            (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)pol->d_params,
+            (uint64_t)TN, ((uint64_t)n_chunks << 32) | (uint64_t)chunk, 0,
+            ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
+            ((uint64_t)fbits[4] << 32) | fbits[5], 0, 0,
+            0x413243434Eull,   // 'A2CCN': A2C on the CNN base, the chunked step sequence
+            0, 0};
+    SG_TRY(sg_graph_run(ctx, &a->steps_graph, use_graph, key, enqueue_step));
+    SG_CHECK(hipGetLastError());
+    a->opt_t += 1;
+    if (!out3) return 0;   // queued: the losses come through the results ring (step count 1)
+    double acc[3];
+    SG_TRY(sg_ctx_fetch_f64(ctx, a->d_loss_acc, acc, 3));
+    for (int i = 0; i < 3; ++i) out3[i] = (float)acc[i];
     return 0;
 }
 
@@ -1309,6 +1448,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
     if (a->a2c) {
         SG_REQUIRE(!perms, "sg_ppo_update: an A2C update takes the rollout in its own order: perms must be NULL");
         if (a->a2c_rnn) return a2c_gru_update(a, r, out3);
+        if (a->a2c_cnn) return a2c_cnn_update(a, r, out3);
         SG_REQUIRE(r->O == a->policy->desc.O && r->A == a->policy->desc.A,
                    "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)", r->O, r->A,
                    a->policy->desc.O, a->policy->desc.A);
