@@ -108,6 +108,15 @@ SG_API int sg_policy_create2(sg_ctx *ctx, int kind, int obs_dim, int act_dim, in
 enum { SG_DIST_GAUSSIAN = 0, SG_DIST_CATEGORICAL = 1, SG_DIST_BERNOULLI = 2 };
 SG_API int sg_policy_create3(sg_ctx *ctx, int kind, int obs_dim, int act_dim, int hidden, int num_feet, int critic_hidden,
                              int dist, int n_out, sg_policy **out);
+/* The recurrent Policy on a Discrete / MultiBinary action space (a2c/model.py:40-62 with base_kwargs={'recurrent': True}): kind
+ * SG_POLICY_GRU with dist SG_DIST_CATEGORICAL (an action row is 1 class index) or SG_DIST_BERNOULLI (n_out bits); sg_policy_create3
+ * keeps refusing the pair.  The heads are sg_policy_create3's on the hidden-wide GRU state; flat order: base.gru.weight_ih_l0,
+ * .weight_hh_l0, .bias_ih_l0, .bias_hh_l0, the trunks, base.critic_linear, dist.linear.weight [n_out, hidden], dist.linear.bias.
+ * sg_policy_act_rnn / _get_value_rnn / _evaluate_rnn take it (`noise`: uniform draws, one per row or per bit), as do sg_ppo_create
+ * and sg_a2c_create_rnn (one rank each) and sg_rollout_policy_diagnostics; sg_acktr_create, sg_ppo_set_symmetry (coef > 0),
+ * sg_policy_act_ensemble, sg_rollout_act_step_rnn and sg_rollout_act_step_chain refuse it (those act kernels carry the Gaussian
+ * head: act through sg_policy_act_rnn). */
+SG_API int sg_policy_create_rnn_dist(sg_ctx *ctx, int obs_dim, int hidden, int critic_hidden, int dist, int n_out, sg_policy **out);
 /* Policy on image observations: the CNN base, a2c/model.py:204-230 (CNNBase, feed-forward), which Policy.__init__ picks for a
  * 3-D obs_shape (a2c/model.py:40-50).  x / 255.0 -> Conv2d(channels, 32, 8, stride 4) -> Conv2d(32, 64, 4, stride 2) ->
  * Conv2d(64, 32, 3, stride 1) -> Flatten (channel-major, 1568 values) -> Linear(1568, hidden), ReLU after each; critic_linear =

@@ -91,6 +91,10 @@ class A2C_ACKTR():
             raise NotImplementedError("A2C_ACKTR(cnn=True): A2C on the CNN base (image observations) runs on one rank "
                                       f"(this context's world is {actor_critic.ctx.world}): data-parallel A2C is not implemented")
         is_rec = bool(getattr(actor_critic, "is_recurrent", False))
+        if is_rec and acktr and getattr(actor_critic, "dist_kind", 0):
+            raise NotImplementedError("A2C_ACKTR(acktr=True): ACKTR is not built for a recurrent Policy on a Discrete / MultiBinary action "
+                                      "space (the reference refuses --recurrent-policy with acktr, and K-FAC's Fisher sampling is "
+                                      "built for the Gaussian head); acktr=False, recurrent=True (A2C through time) runs")
         if is_rec and (acktr or not recurrent):
             raise NotImplementedError("A2C_ACKTR: implemented for feed-forward policies only, not for a recurrent Policy "
                                       "(the reference allows --recurrent-policy with a2c and refuses it with acktr); "

@@ -67,6 +67,9 @@ class PPO():
         self.is_cuda = True   # the rollout the update reads lives in HBM whatever the host tensors are
 
         self.recurrent = bool(getattr(actor_critic, "is_recurrent", False))   # a2c/algo/ppo.py:74-76: recurrent_generator
+        if self.recurrent and getattr(actor_critic, "dist_kind", 0) and mirror_obs is not None and symmetry_coef > 0:
+            raise NotImplementedError("mirror-symmetry loss: not for a recurrent Policy on a Discrete / MultiBinary action space (it "
+                                      "compares action means of a feed-forward policy); symmetry_coef > 0 needs the MLP base and Box")
         if self.recurrent and mirror_obs is not None and symmetry_coef > 0:
             raise NotImplementedError("mirror-symmetry loss: implemented for feed-forward policies only, not for a recurrent Policy")
         if self.recurrent and getattr(actor_critic.ctx, "world", 1) > 1:

@@ -197,10 +197,15 @@ def _policy_dims(class_name, sd, dist_class=None):
         H, O = sd["base.actor.0.weight"].shape
         K = sd["dist.linear.weight"].shape[0]
         Hc = sd["base.critic.0.weight"].shape[0]
-        assert "base.gru.weight_ih_l0" not in sd, "a recurrent policy with a Categorical / Bernoulli head is not built"
+        kind, dist = _LINEAR_DISTS[dist_class]
+        if "base.gru.weight_ih_l0" in sd:            # recurrent=True: the trunks read the H-wide GRU state, as for the Gaussian head below
+            G3, O_in = sd["base.gru.weight_ih_l0"].shape
+            assert G3 == 3 * H and O == H and sd["base.gru.weight_hh_l0"].shape == (3 * H, H) and \
+                sd["base.critic.0.weight"].shape == (Hc, H), "inconsistent GRU / trunk shapes in the checkpoint"
+            return dict(kind=kind, obs_dim=int(O_in), act_dim=1 if dist == 1 else int(K), hidden=int(H), num_feet=1, critic_hidden=int(Hc),
+                        dist=dist, n_out=int(K), recurrent=True)
         assert sd["base.critic.0.weight"].shape == (Hc, O) and sd["base.critic.2.weight"].shape == (Hc, Hc) and \
             sd["base.critic_linear.weight"].shape == (1, Hc), "inconsistent critic shapes in the checkpoint"
-        kind, dist = _LINEAR_DISTS[dist_class]
         return dict(kind=kind, obs_dim=int(O), act_dim=1 if dist == 1 else int(K), hidden=int(H), num_feet=1, critic_hidden=int(Hc),
                     dist=dist, n_out=int(K))
     if class_name == "Policy":
@@ -505,8 +510,8 @@ def load_policy(path, ctx=None):
         pol = Policy((ck["cnn"], 84, 84), space, base_kwargs={"hidden_size": ck["hidden"]}, ctx=ctx)
     elif ck["kind"] in ("mlp_categorical", "mlp_bernoulli"):
         space = _Discrete(ck["n_out"]) if ck["kind"] == "mlp_categorical" else _MultiBinary(ck["n_out"])
-        pol = Policy((ck["obs_dim"],), space, base_kwargs={"recurrent": False, "hidden_size": ck["hidden"]}, ctx=ctx,
-                     critic_hidden=ck.get("critic_hidden"))
+        pol = Policy((ck["obs_dim"],), space, base_kwargs={"recurrent": bool(ck.get("recurrent")), "hidden_size": ck["hidden"]}, ctx=ctx,
+                     critic_hidden=ck.get("critic_hidden"), recurrent_heads=True)
     elif ck["kind"] == "mlp":
         pol = Policy((ck["obs_dim"],), _Box(ck["act_dim"]), base_kwargs={"recurrent": bool(ck.get("recurrent")), "hidden_size": ck["hidden"]}, ctx=ctx,
                      critic_hidden=ck.get("critic_hidden"))

@@ -291,6 +291,9 @@ extern "C" int sg_rollout_act_step_rnn(sg_rollout* r, sg_policy* p, int t, const
                "served by the one-launch steps: act through sg_policy_act and upload the step");
     SG_REQUIRE(p->recurrent, "sg_rollout_act_step_rnn: the policy is feed-forward (kind %d); act through sg_rollout_act_step",
                p->desc.kind);
+    SG_REQUIRE(p->desc.dist == SG_DIST_GAUSSIAN, "sg_rollout_act_step_rnn: the recurrent policy has a %s head; the one-launch recurrent "
+               "step carries the Gaussian head only (Box action spaces): act through sg_policy_act_rnn and insert on the host",
+               p->desc.dist == SG_DIST_CATEGORICAL ? "Categorical" : "Bernoulli");
     SG_REQUIRE(r->d_hidden, "sg_rollout_act_step_rnn: the rollout holds no hidden states; call sg_rollout_enable_hidden first");
     SG_REQUIRE(r->hidden_dim == p->gru.H, "sg_rollout_act_step_rnn: the rollout's hidden states are %d wide, the policy's %d",
                r->hidden_dim, p->gru.H);

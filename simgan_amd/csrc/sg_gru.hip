@@ -6,7 +6,8 @@
 //   Policy.act / get_value / evaluate_actions a2c/model.py:89-114   (returning the new rnn_hxs)
 //
 // Two kernels (sg_gru_kernels.hpp: k_gru_inproj, k_gru_scan_fwd), then the feed-forward heads of sg_policy.hip on x = h_t
-// (an MLP policy whose observation is the GRU state).  PPO through time is in sg_ppo.hip.
+// (an MLP policy whose observation is the GRU state; with a Categorical / Bernoulli head -- sg_policy_create_rnn_dist -- the heads'
+// launch is k_discrete_head, `noise` uniform draws and an action row a class index or n bits).  PPO through time is in sg_ppo.hip.
 // The reference cuts the sequence where any mask is 0 and multiplies h by masks[t] at the head of each piece (a2c/model.py:
 // 150-193); for 0/1 masks that is h_{t-1} <- h_{t-1} * masks[t] at every step, which is what the scan does.
 #include <math.h>

@@ -240,8 +240,9 @@ extern "C" int sg_policy_create2(sg_ctx* ctx, int kind, int obs_dim, int act_dim
     return sg_policy_create3(ctx, kind, obs_dim, act_dim, hidden, num_feet, critic_hidden, SG_DIST_GAUSSIAN, 0, out);
 }
 
-extern "C" int sg_policy_create3(sg_ctx* ctx, int kind, int obs_dim, int act_dim, int hidden, int num_feet, int critic_hidden,
-                                 int dist, int n_out, sg_policy** out) {
+// rnn_heads: a Categorical / Bernoulli head on kind SG_POLICY_GRU is admitted (sg_policy_create_rnn_dist)
+static int policy_create(sg_ctx* ctx, int kind, int obs_dim, int act_dim, int hidden, int num_feet, int critic_hidden, int dist, int n_out,
+                         bool rnn_heads, sg_policy** out) {
     SG_DEVICE_WIDE();
     SG_REQUIRE(ctx && out, "sg_policy_create: NULL argument");
     SG_REQUIRE(critic_hidden >= 0, "sg_policy_create2: bad critic_hidden");
@@ -250,8 +251,8 @@ extern "C" int sg_policy_create3(sg_ctx* ctx, int kind, int obs_dim, int act_dim
     SG_REQUIRE(dist == SG_DIST_GAUSSIAN || dist == SG_DIST_CATEGORICAL || dist == SG_DIST_BERNOULLI,
                "sg_policy_create3: unknown dist %d", dist);
     if (dist != SG_DIST_GAUSSIAN) {
-        SG_REQUIRE(kind == SG_POLICY_MLP, "sg_policy_create3: a Categorical / Bernoulli head is built on the feed-forward Policy "
-                   "(kind SG_POLICY_MLP) only, not on kind %d", kind);
+        SG_REQUIRE(kind == SG_POLICY_MLP || (rnn_heads && kind == SG_POLICY_GRU), "sg_policy_create3: a Categorical / Bernoulli head is "
+                   "built on the feed-forward Policy (kind SG_POLICY_MLP) only, not on kind %d", kind);
         SG_REQUIRE(n_out > 0 && n_out < (1 << 24), "sg_policy_create3: n_out = %d: need 0 < n_out < 2^24 (a class index travels as a "
                    "float)", n_out);
         SG_REQUIRE(act_dim == (dist == SG_DIST_CATEGORICAL ? 1 : n_out), "sg_policy_create3: act_dim (%d) must be %s", act_dim,
@@ -267,7 +268,8 @@ extern "C" int sg_policy_create3(sg_ctx* ctx, int kind, int obs_dim, int act_dim
     if (kind == SG_POLICY_GRU) {
         // a2c/model.py:233-253 with recurrent=True: the trunks' first layers take the GRU state (H inputs), not the observation
         p->recurrent = true;
-        p->desc = sg_make_policy_desc(SG_POLICY_MLP, hidden, act_dim, hidden, 1, critic_hidden);
+        // (the heads block is the feed-forward layout with obs_dim = H, whatever the head: a Categorical / Bernoulli one has no log-std)
+        p->desc = sg_make_policy_desc(SG_POLICY_MLP, hidden, act_dim, hidden, 1, critic_hidden, dist, n_out);
         p->gru = sg_make_gru_desc(obs_dim, hidden, p->desc.total);
         if (!sg_gru_fits(ctx, p->gru)) {
             delete p;
@@ -287,6 +289,21 @@ extern "C" int sg_policy_create3(sg_ctx* ctx, int kind, int obs_dim, int act_dim
     SG_CHECK(hipMemsetAsync(p->d_params, 0, sizeof(float) * sg_policy_padded_count(p), ctx->stream));
     *out = p;
     return 0;
+}
+
+extern "C" int sg_policy_create3(sg_ctx* ctx, int kind, int obs_dim, int act_dim, int hidden, int num_feet, int critic_hidden,
+                                 int dist, int n_out, sg_policy** out) {
+    return policy_create(ctx, kind, obs_dim, act_dim, hidden, num_feet, critic_hidden, dist, n_out, false, out);
+}
+
+// Policy(obs_shape, Discrete(K) | MultiBinary(n), base_kwargs={'recurrent': True}) (a2c/model.py:40-62): kind SG_POLICY_GRU with a
+// Categorical / Bernoulli head.  The heads block is sg_policy_create3's MLP layout on the H-wide GRU state (no log-std, the
+// n_out-wide head, an action row of 1 class index or n_out bits), the GRU block sits behind it; in the flat order the four GRU
+// tensors come first and dist.linear.{weight, bias} last.  An entry point of its own: sg_policy_create3 keeps refusing the pair.
+extern "C" int sg_policy_create_rnn_dist(sg_ctx* ctx, int obs_dim, int hidden, int critic_hidden, int dist, int n_out, sg_policy** out) {
+    SG_REQUIRE(dist == SG_DIST_CATEGORICAL || dist == SG_DIST_BERNOULLI, "sg_policy_create_rnn_dist: dist %d: SG_DIST_CATEGORICAL or "
+               "SG_DIST_BERNOULLI (the Gaussian head on the GRU base is sg_policy_create2 with kind SG_POLICY_GRU)", dist);
+    return policy_create(ctx, SG_POLICY_GRU, obs_dim, dist == SG_DIST_CATEGORICAL ? 1 : n_out, hidden, 1, critic_hidden, dist, n_out, true, out);
 }
 
 extern "C" int sg_policy_destroy(sg_policy* p) {

@@ -25,6 +25,10 @@
 //   k_a2c_gru_gather -> k_gru_inproj -> k_gru_scan_fwd<TRAIN>;  per chunk:  k_ppo_fwd -> k_a2c_bwd_dx -> k_a2c_reduce;
 //   k_gru_scan_bwd -> k_gru_wgrad -> k_gru_reduce_acc;  then one k_a2c_rmsprop over heads + GRU
 //
+// A recurrent Policy with a Categorical / Bernoulli head (sg_policy_create_rnn_dist) runs both sequences through time
+// with the head kernels k_ppo_bwd_dist_dx / k_a2c_bwd_dist_dx: the Categorical / Bernoulli loss block followed by the d loss / d h_t
+// epilogue of both trunks.
+//
 // A2C on the CNN base (sg_a2c_create_cnn; a2c_cnn_update), per chunk of <= SG_A2C_CNN_CHUNK_ROWS rows:
 //   the forward of sg_cnn.hip -> k_cnn_head_loss_a2c -> head, FC, conv3, conv2, conv1 gradients (adding from the second chunk on);
 //   then k_sumsq -> k_a2c_rmsprop
@@ -170,6 +174,10 @@ struct PpoInstance {
 #define SG_K_BWD_FUSED_BER(mt, o, h, gw) k_ppo_bwd_dist<mt, gw, SG_DIST_BERNOULLI>
 #define SG_K_A2C_BWD_CAT(mt, o, h, gw) k_a2c_bwd_dist<mt, gw, SG_DIST_CATEGORICAL>
 #define SG_K_A2C_BWD_BER(mt, o, h, gw) k_a2c_bwd_dist<mt, gw, SG_DIST_BERNOULLI>
+#define SG_K_BWD_FUSED_CAT_DX(mt, o, h, gw) k_ppo_bwd_dist_dx<mt, gw, SG_DIST_CATEGORICAL>
+#define SG_K_BWD_FUSED_BER_DX(mt, o, h, gw) k_ppo_bwd_dist_dx<mt, gw, SG_DIST_BERNOULLI>
+#define SG_K_A2C_BWD_CAT_DX(mt, o, h, gw) k_a2c_bwd_dist_dx<mt, gw, SG_DIST_CATEGORICAL>
+#define SG_K_A2C_BWD_BER_DX(mt, o, h, gw) k_a2c_bwd_dist_dx<mt, gw, SG_DIST_BERNOULLI>
 SG_PPO_FAMILY(ppo_fwd_family, SG_K_FWD, SG_PPO_SHAPES, SG_MT_421, SG_MT_21);
 SG_PPO_FAMILY(ppo_fwd_critic_family, SG_K_FWD_CRITIC, SG_SPLIT_SHAPES, SG_MT_21, SG_NONE);   // SplitPolicy, critic in the forward launch
 SG_PPO_FAMILY(ppo_pair_family, SG_K_PAIR, SG_SPLIT_SHAPES, SG_MT_21, SG_NONE);               // SplitPolicy, one launch per step
@@ -186,6 +194,11 @@ SG_PPO_FAMILY(ppo_bwd_fused_cat_family, SG_K_BWD_FUSED_CAT, SG_NONE, SG_MT_21, S
 SG_PPO_FAMILY(ppo_bwd_fused_ber_family, SG_K_BWD_FUSED_BER, SG_NONE, SG_MT_21, SG_MT_21);
 SG_PPO_FAMILY(a2c_bwd_cat_family, SG_K_A2C_BWD_CAT, SG_NONE, SG_MT_21, SG_MT_21);
 SG_PPO_FAMILY(a2c_bwd_ber_family, SG_K_A2C_BWD_BER, SG_NONE, SG_MT_21, SG_MT_21);
+// ... as the heads of a recurrent Policy (sg_policy_create_rnn_dist): + d loss / d h_t
+SG_PPO_FAMILY(ppo_bwd_fused_cat_dx_family, SG_K_BWD_FUSED_CAT_DX, SG_NONE, SG_MT_21, SG_MT_21);
+SG_PPO_FAMILY(ppo_bwd_fused_ber_dx_family, SG_K_BWD_FUSED_BER_DX, SG_NONE, SG_MT_21, SG_MT_21);
+SG_PPO_FAMILY(a2c_bwd_cat_dx_family, SG_K_A2C_BWD_CAT_DX, SG_NONE, SG_MT_21, SG_MT_21);
+SG_PPO_FAMILY(a2c_bwd_ber_dx_family, SG_K_A2C_BWD_BER_DX, SG_NONE, SG_MT_21, SG_MT_21);
 
 // Launches the family's instance for (MT, the policy's shape, gw): with gw a global-weight instance, else the one specialised
 // for the shape, else the run-time-shape one.  (The specialised instances fold ONE hidden width into the code: a policy whose
@@ -276,8 +289,8 @@ extern "C" int sg_a2c_create_rnn(sg_ctx* ctx, sg_policy* p, const sg_a2c_config*
     SG_REQUIRE(ctx && p && cfg && out, "sg_a2c_create_rnn: NULL argument");
     SG_REQUIRE(p->recurrent, "sg_a2c_create_rnn: A2C through time takes a recurrent Policy (kind SG_POLICY_GRU); this policy is "
                "feed-forward (sg_a2c_create)");
-    SG_REQUIRE(!p->cnn && p->desc.kind == SG_POLICY_MLP && p->desc.dist == SG_DIST_GAUSSIAN,
-               "sg_a2c_create_rnn: A2C through time is implemented for the Gaussian head (Box action spaces) only");
+    SG_REQUIRE(!p->cnn && p->desc.kind == SG_POLICY_MLP,
+               "sg_a2c_create_rnn: A2C through time is implemented for the GRU base of Policy only, not for the CNN base");
     SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_a2c_create_rnn: A2C with a recurrent policy runs on one rank: this context has a "
                "communicator of world %d (data-parallel A2C through time is not implemented)", ctx->world);
     SG_REQUIRE(cfg->alpha >= 0.f && cfg->alpha <= 1.f && cfg->eps >= 0.f && cfg->max_grad_norm > 0.f,
@@ -876,7 +889,8 @@ extern "C" int sg_ppo_set_hidden_states_rollout(sg_ppo* a, sg_rollout* r) {
 // (a2c/storage.py:194-251): per = N // num_mini_batch whole environments per optimizer step, N // per steps per epoch.
 //   k_adv_stats x3
 //   per epoch:  k_gru_epoch_gather            environment-permuted, time-major copy of the rollout
-//   per step:   k_gru_inproj -> k_gru_scan_fwd<TRAIN> (h_t = the heads' input rows) -> k_ppo_bwd<fused, DX> -> k_ppo_reduce
+//   per step:   k_gru_inproj -> k_gru_scan_fwd<TRAIN> (h_t = the heads' input rows) -> k_ppo_bwd<fused, DX> (a Categorical /
+//               Bernoulli head: k_ppo_bwd_dist_dx) -> k_ppo_reduce
 //               -> k_gru_scan_bwd -> k_gru_wgrad -> k_gru_reduce -> k_ppo_adam over heads + GRU (one norm, one clip)
 //   then        k_opt_commit
 // All of it from the first gather on is one captured graph, replayed per update; no host wait inside.
@@ -932,11 +946,16 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
     // geometry.  Heads: the fused forward + backward on 16- or 32-row groups of the step's T*per rows.  Scans: one workgroup per
     // 16 environments of the minibatch.
     const int mb = T * per;
-    const bool gw = sg_policy_needs_gw(ctx, d) || ppo_fwd_lds(d, 1, false) > (size_t)ctx->lds_bytes;
+    // (a Categorical / Bernoulli head: the actor trunk carries an n_out-wide head beside w1, so the whole fused tile set decides,
+    // not the forward's alone -- what does not fit a CU's LDS takes the global-weight instances)
+    const bool dist_heads = d.dist != SG_DIST_GAUSSIAN;
+    const bool gw = sg_policy_needs_gw(ctx, d) || ppo_fwd_lds(d, 1, false) > (size_t)ctx->lds_bytes ||
+                    (dist_heads && ppo_bwd_tiles_lds(d, 1, max_trunk_floats(d), 2, false) > (size_t)ctx->lds_bytes);
     const int ldP = stack_ldP(d);
     auto bwd_lds = [&](int mt) { return ppo_bwd_tiles_lds(d, mt, gw ? 0 : max_trunk_floats(d), 2, false); };   // the fused form
-    // (neither SG_PPO_ROWS nor the 24 MB slab rule here; 32-row groups fall back to 16-row ones only)
-    const int MT = ppo_row_tiles(ctx, d, mb, d.n_trunks, false, 0, 2, [&](int mt) { return bwd_lds(mt) <= (size_t)ctx->lds_bytes; });
+    // (neither SG_PPO_ROWS nor the 24 MB slab rule here; 32-row groups fall back to 16-row ones only.  The Categorical / Bernoulli
+    // heads read SG_PPO_ROWS = 16 / 32, as their feed-forward step does.)
+    const int MT = ppo_row_tiles(ctx, d, mb, d.n_trunks, false, dist_heads ? 2 : 0, 2, [&](int mt) { return bwd_lds(mt) <= (size_t)ctx->lds_bytes; });
     SG_REQUIRE(bwd_lds(MT) <= (size_t)ctx->lds_bytes, "sg_ppo_update: the heads' 16-row tiles do not fit LDS (%zu bytes)", bwd_lds(MT));
     const int R = 16 * MT, G = (mb + R - 1) / R, mbp = G * R;
     const int slab_stride = (d.total + 8 + 63) & ~63;
@@ -1021,8 +1040,15 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
                                              gb + o_gi, hX, d.ldO, nullptr, &tr));
                 pa.ACT = epACT + rb * d.A; pa.SC = epSC + rb;
                 pa.k1 = e * S + k + 1;
-                SG_TRY(ppo_launch(ctx, ppo_bwd_fused_dx_family, "k_ppo_bwd (fused, with d loss / d h)", SG_PROF_PPO_BWD, MT, d, dim3(G, 2),
-                                  lds_b, pa, gw));
+                if (d.dist == SG_DIST_CATEGORICAL)
+                    SG_TRY(ppo_launch(ctx, ppo_bwd_fused_cat_dx_family, "k_ppo_bwd_dist_dx (Categorical)", SG_PROF_PPO_BWD, MT, d, dim3(G, 2),
+                                      lds_b, pa, gw));
+                else if (d.dist == SG_DIST_BERNOULLI)
+                    SG_TRY(ppo_launch(ctx, ppo_bwd_fused_ber_dx_family, "k_ppo_bwd_dist_dx (Bernoulli)", SG_PROF_PPO_BWD, MT, d, dim3(G, 2),
+                                      lds_b, pa, gw));
+                else
+                    SG_TRY(ppo_launch(ctx, ppo_bwd_fused_dx_family, "k_ppo_bwd (fused, with d loss / d h)", SG_PROF_PPO_BWD, MT, d, dim3(G, 2),
+                                      lds_b, pa, gw));
                 SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_ppo_reduce, dim3(nblk_r), dim3(256), 0, a->d_slabs, G, slab_stride, d.total, a->d_grad,
                           a->d_part);
                 ba.masks = mk;
@@ -1052,7 +1078,8 @@ static int gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
             ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
             ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)a->cfg.use_clipped_value_loss,
             (uint64_t)(uintptr_t)r->d_field[SG_F_LOGP],
-            0x475255ull + (gw ? 8 : 0) + (gw_scan ? 16 : 0) + ((uint64_t)N << 32),   // 'GRU': the recurrent step sequence
+            // 'GRU': the recurrent step sequence; the head's distribution (0 for the Gaussian: its key is what it was)
+            0x475255ull + (gw ? 8 : 0) + (gw_scan ? 16 : 0) + ((uint64_t)d.dist << 24) + ((uint64_t)N << 32),
             (uint64_t)(uintptr_t)a->d_gru, (uint64_t)(uintptr_t)a->d_h0 ^ ((uint64_t)(uintptr_t)r->d_field[SG_F_MASKS] << 1)};
     SG_TRY(sg_graph_run(ctx, &a->steps_graph, use_graph, key, enqueue_steps));
     SG_CHECK(hipGetLastError());
@@ -1276,7 +1303,8 @@ static int a2c_gru_group_envs(int T, int N) {
 // evaluate_actions steps the GRU through all T steps of all N environments from the state of slot 0 (h <- h * masks[t]), the
 // heads see the states; one loss over the T*N rows, one clip over ALL parameters, one RMSprop step.  Per environment group:
 //   k_a2c_gru_gather -> k_gru_inproj -> k_gru_scan_fwd<TRAIN>
-//   per chunk of <= SG_A2C_CHUNK_ROWS rows:  k_ppo_fwd -> k_a2c_bwd_dx -> k_a2c_reduce (adds to the heads' gradient)
+//   per chunk of <= SG_A2C_CHUNK_ROWS rows:  k_ppo_fwd -> k_a2c_bwd_dx (a Categorical / Bernoulli head: k_a2c_bwd_dist_dx)
+//                                            -> k_a2c_reduce (adds to the heads' gradient)
 //   k_gru_scan_bwd -> k_gru_wgrad -> k_gru_reduce_acc (adds to the GRU's gradient; the last group finishes it)
 // then k_a2c_rmsprop over heads + GRU.  One captured graph from the first gather on; no host wait inside.
 static int a2c_gru_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
@@ -1397,8 +1425,15 @@ static int a2c_gru_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
                 pa.wbuf_floats = wb_f;
                 SG_TRY(ppo_launch(ctx, ppo_fwd_family, "k_ppo_fwd", SG_PROF_PPO_FWD, MT, d, dim3(Gc, d.n_trunks), lds_f, pa, gw));
                 pa.wbuf_floats = wb_b;
-                SG_TRY(ppo_launch(ctx, a2c_bwd_dx_family, "k_a2c_bwd (with d loss / d h)", SG_PROF_PPO_BWD, MT, d, dim3(Gc, d.n_trunks),
-                                  lds_b, pa, gw));
+                if (d.dist == SG_DIST_CATEGORICAL)
+                    SG_TRY(ppo_launch(ctx, a2c_bwd_cat_dx_family, "k_a2c_bwd_dist_dx (Categorical)", SG_PROF_PPO_BWD, MT, d, dim3(Gc, d.n_trunks),
+                                      lds_b, pa, gw));
+                else if (d.dist == SG_DIST_BERNOULLI)
+                    SG_TRY(ppo_launch(ctx, a2c_bwd_ber_dx_family, "k_a2c_bwd_dist_dx (Bernoulli)", SG_PROF_PPO_BWD, MT, d, dim3(Gc, d.n_trunks),
+                                      lds_b, pa, gw));
+                else
+                    SG_TRY(ppo_launch(ctx, a2c_bwd_dx_family, "k_a2c_bwd (with d loss / d h)", SG_PROF_PPO_BWD, MT, d, dim3(Gc, d.n_trunks),
+                                      lds_b, pa, gw));
                 SG_LAUNCH(ctx, SG_PROF_PPO_REDUCE, k_a2c_reduce, dim3(nblk_r), dim3(256), 0, a->d_slabs, Gc, slab_stride, d.total, a->d_grad,
                           a->d_part, (k > 0 || c > 0) ? 1 : 0);
             }
@@ -1431,7 +1466,8 @@ static int a2c_gru_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
             ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
             ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)(uintptr_t)r->d_field[SG_F_MASKS],
             (uint64_t)(uintptr_t)a->d_h0,
-            0x413247ull + (gw ? 8 : 0) + (gw_scan ? 16 : 0) + ((uint64_t)ng << 32),   // 'A2G': A2C through time, the group size
+            // 'A2G': A2C through time, the head's distribution (0 for the Gaussian), the group size
+            0x413247ull + (gw ? 8 : 0) + (gw_scan ? 16 : 0) + ((uint64_t)d.dist << 24) + ((uint64_t)ng << 32),
             ((uint64_t)chunk << 32) | (uint64_t)rows_p, (uint64_t)KS};
     SG_TRY(sg_graph_run(ctx, &a->steps_graph, use_graph, key, enqueue_step));
     SG_CHECK(hipGetLastError());

@@ -265,11 +265,14 @@ __device__ __forceinline__ void sg_ppo_row_weight(const PpoArgs& a, const float*
 // read it in place of old_logp).  No ratio, no clip, no clipped value loss; the entropy term is PPO's.
 // DIST (SG_DIST_*): the action distribution the actor column's loss block evaluates.  The default keeps the Gaussian code;
 // the Categorical / Bernoulli instances (Policy on Discrete / MultiBinary action spaces, kind MLP) exist in the fused and the
-// A2C forms.
+// A2C forms, each also with DX (the heads of a recurrent Policy: the loss block leaves d loss / d logits with exact zeros in the
+// padding columns of the [R][ldP] tile, the head GEMM and then the W1 product of the DX epilogue read them; the critic column
+// writes its d loss / d h tile as well, the reverse scan adds actor + critic).
 template <int MT, int KO, int KH, bool FUSED, bool GW = false, bool PAIR = false, bool SYM = false, bool A2C = false, bool DX = false,
           int DIST = SG_DIST_GAUSSIAN>
 __device__ __forceinline__ void sg_ppo_bwd_body(const PpoArgs& a, const int t, const int bx) {
-    static_assert(DIST == SG_DIST_GAUSSIAN || (!PAIR && !SYM && !DX), "Categorical / Bernoulli heads: plain Policy only");
+    static_assert(DIST == SG_DIST_GAUSSIAN || (!PAIR && !SYM), "Categorical / Bernoulli heads: Policy only (feed-forward, or with DX the "
+                  "heads of a recurrent one)");
     static_assert(!(SYM && (FUSED || PAIR)), "the symmetric step runs the two-launch form");
     static_assert(!DX || ((FUSED || GW || A2C) && !PAIR && !SYM), "d loss / d X needs w1 at hand: the fused or the global-weight form, "
                   "or A2C's two-launch form, which reads w1 from global memory");
@@ -721,6 +724,11 @@ template <int MT, bool GW, int DIST>
 __global__ __launch_bounds__(512) void k_ppo_bwd_dist(PpoArgs a) {
     sg_ppo_bwd_body<MT, 0, 0, true, GW, false, false, false, false, DIST>(a, blockIdx.y, blockIdx.x);
 }
+// ... on the heads of a recurrent Policy (the rows are GRU states): + d loss / d h_t of both trunks into a.DX
+template <int MT, bool GW, int DIST>
+__global__ __launch_bounds__(512) void k_ppo_bwd_dist_dx(PpoArgs a) {
+    sg_ppo_bwd_body<MT, 0, 0, true, GW, false, false, false, true, DIST>(a, blockIdx.y, blockIdx.x);
+}
 // Policy with the mirror-symmetry loss: grid (row groups, 3), after k_ppo_fwd_sym
 template <int MT, int KO, int KH, bool GW = false>
 __global__ __launch_bounds__(512) void k_ppo_bwd_sym(PpoArgs a) {
@@ -742,6 +750,11 @@ __global__ __launch_bounds__(512) void k_a2c_bwd_dx(PpoArgs a) {
 template <int MT, bool GW, int DIST>
 __global__ __launch_bounds__(512) void k_a2c_bwd_dist(PpoArgs a) {
     sg_ppo_bwd_body<MT, 0, 0, false, GW, false, false, true, false, DIST>(a, blockIdx.y, blockIdx.x);
+}
+// ... with a Categorical / Bernoulli head on a recurrent Policy: + d loss / d h_t of both trunks into a.DX
+template <int MT, bool GW, int DIST>
+__global__ __launch_bounds__(512) void k_a2c_bwd_dist_dx(PpoArgs a) {
+    sg_ppo_bwd_body<MT, 0, 0, false, GW, false, false, true, true, DIST>(a, blockIdx.y, blockIdx.x);
 }
 
 // SplitPolicy, ONE launch per step when its 3 G workgroups fit the chip together: every trunk's fused forward + loss + backward,

@@ -132,6 +132,9 @@ def _check_on_device(ro, pol, dup_sym, who):
         why = "the rollout is not device-resident (rollouts.device_resident = True): its host tensors are the rollout"
     elif dup_sym or getattr(ro, "dup_sym", False):
         why = "the rollout is mirror-augmented (dup_sym): its column upload would overwrite the fields the device writes"
+    elif pol.is_recurrent and getattr(pol, "dist_kind", _lib.DIST_GAUSSIAN) != _lib.DIST_GAUSSIAN:
+        why = ("the policy is recurrent with a Discrete / MultiBinary action space; the one-launch recurrent step carries the Gaussian "
+               "head only: acting goes through Policy.act")
     elif pol.is_recurrent and not getattr(ro, "device_hidden", False):   # (rollouts.enable_device_hidden() lifts it)
         why = "the policy is recurrent and the device rollout holds no hidden state"
     elif getattr(pol, "dist_kind", _lib.DIST_GAUSSIAN) != _lib.DIST_GAUSSIAN:

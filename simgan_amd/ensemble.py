@@ -23,6 +23,10 @@ class PolicyEnsemble(object):
         if any(getattr(p, "cnn", 0) for p in self.policies):
             raise NotImplementedError("PolicyEnsemble: members with the MLP base only (the one-launch act does not run the CNN base of "
                                       "image observations)")
+        if any(getattr(p, "is_recurrent", False) and getattr(p, "dist_kind", 0) for p in self.policies):
+            raise NotImplementedError("PolicyEnsemble: a recurrent member on a Discrete / MultiBinary action space is not served (the "
+                                      "one-launch act carries neither a hidden state nor a Categorical / Bernoulli head): it acts "
+                                      "through Policy.act")
         if any(getattr(p, "is_recurrent", False) for p in self.policies):
             raise NotImplementedError("PolicyEnsemble: feed-forward members only (the one-launch act carries no hidden state)")
         if any(getattr(p, "dist_kind", 0) for p in self.policies):

@@ -1,5 +1,6 @@
 """Policy -- host mirror of a2c/model.py:37-114 (image observations [C, 84, 84]: CNNBase, a2c/model.py:204-230, with the Categorical or Gaussian head; else MLPBase + DiagGaussian on Box actions, Categorical on Discrete, Bernoulli on
-MultiBinary, a2c/model.py:52-62; feed-forward, or -- Box only -- recurrent with the GRU base of a2c/model.py:117-201).  Parameters live in HBM inside libsimgan_hip.so; this class keeps the
+MultiBinary, a2c/model.py:52-62; feed-forward, or recurrent with the GRU base of a2c/model.py:117-201 -- on Discrete / MultiBinary
+with recurrent_heads=True or SG_RECURRENT_HEADS=1).  Parameters live in HBM inside libsimgan_hip.so; this class keeps the
 reference's constructor and method signatures and hands host tensors across the C ABI."""
 import ctypes as C
 
@@ -41,6 +42,8 @@ class _PolicyBase(object):
         if self.cnn:
             _lib.check(self.lib.sg_policy_create_cnn(self.ctx.h, self.cnn, CNN_HW, CNN_HW, self.hidden_size, self.dist_kind, self.act_dim,
                                                      self.n_out, C.byref(h)))
+        elif self.dist_kind and self._rec():   # the GRU base with a Categorical / Bernoulli head: an entry point of its own
+            _lib.check(self.lib.sg_policy_create_rnn_dist(self.ctx.h, self.obs_dim, self.hidden_size, ch, self.dist_kind, self.n_out, C.byref(h)))
         elif self.dist_kind:
             _lib.check(self.lib.sg_policy_create3(self.ctx.h, self.KIND, self.obs_dim, self.act_dim, self.hidden_size, self.num_feet, ch,
                                                   self.dist_kind, self.n_out, C.byref(h)))
@@ -228,6 +231,8 @@ class _PolicyBase(object):
                                                   None if nz is None else _lib.fptr(nz), (self.seed + self._act_calls) & (2 ** 64 - 1),
                                                   1 if deterministic else 0, _lib.fptr(value), _lib.fptr(action), _lib.fptr(logp),
                                                   _lib.fptr(hxs_out)))
+            if self.dist_kind == _lib.DIST_CATEGORICAL:   # the class index crossed the ABI as a float
+                action = action.astype(np.int64)
             return to_host_tensor(value), to_host_tensor(action), to_host_tensor(logp), to_host_tensor(hxs_out)
         _lib.check(self.lib.sg_policy_act(self.h, _lib.fptr(obs), n,
                                           None if nz is None else _lib.fptr(nz), (self.seed + self._act_calls) & (2 ** 64 - 1),
@@ -275,7 +280,13 @@ class _PolicyBase(object):
 class Policy(_PolicyBase):
     KIND = _lib.POLICY_MLP
 
-    def __init__(self, obs_shape, action_space, base=None, base_kwargs=None, ctx=None, seed=0, critic_hidden=None):
+    def __init__(self, obs_shape, action_space, base=None, base_kwargs=None, ctx=None, seed=0, critic_hidden=None, recurrent_heads=None):
+        # recurrent_heads: the GRU base with a Categorical / Bernoulli head (Discrete / MultiBinary with base_kwargs['recurrent']) is
+        # opt-in: True here, or SG_RECURRENT_HEADS=1 in the environment when the policy is constructed (for an unchanged reference
+        # main); with neither the pair is refused as before
+        if recurrent_heads is None:
+            import os
+            recurrent_heads = os.environ.get("SG_RECURRENT_HEADS", "") == "1"
         if base_kwargs is None:
             base_kwargs = {}
         if base is not None or len(obs_shape) not in (1, 3):
@@ -305,7 +316,7 @@ class Policy(_PolicyBase):
         if cnn and dist == _lib.DIST_BERNOULLI:
             raise NotImplementedError("Policy on image observations with a MultiBinary action space: the CNN base is built with the "
                                       "Categorical (Discrete) and Gaussian (Box) heads only")
-        if dist != _lib.DIST_GAUSSIAN and base_kwargs.get("recurrent", False):
+        if dist != _lib.DIST_GAUSSIAN and base_kwargs.get("recurrent", False) and not recurrent_heads:
             raise NotImplementedError(f"Policy on a {space} action space with base_kwargs={{'recurrent': True}}: the GRU base is built "
                                       "with the Gaussian head (Box actions) only")
         hidden = base_kwargs.get("hidden_size", 512 if cnn else 64)   # a2c/model.py:205,234
@@ -330,19 +341,19 @@ class Policy(_PolicyBase):
                     ("base.main.4.weight", (32, 64, 3, 3)), ("base.main.4.bias", (32,)),
                     ("base.main.7.weight", (Hh, 32 * 7 * 7)), ("base.main.7.bias", (Hh,)),
                     ("base.critic_linear.weight", (1, Hh)), ("base.critic_linear.bias", (1,))] + head
-        if getattr(self, "dist_kind", 0):   # a2c/distributions.py:74-88,157-168: Categorical / Bernoulli hold one Linear, no log-std
-            K = self.n_out
-            return [("base.actor.0.weight", (Hh, O)), ("base.actor.0.bias", (Hh,)),
-                    ("base.actor.2.weight", (Hh, Hh)), ("base.actor.2.bias", (Hh,)),
-                    ("base.critic.0.weight", (Hc, O)), ("base.critic.0.bias", (Hc,)),
-                    ("base.critic.2.weight", (Hc, Hc)), ("base.critic.2.bias", (Hc,)),
-                    ("base.critic_linear.weight", (1, Hc)), ("base.critic_linear.bias", (1,)),
-                    ("dist.linear.weight", (K, Hh)), ("dist.linear.bias", (K,))]
         gru = []
         if self._rec():   # a2c/model.py:124-131: nn.GRU's four tensors come first and the trunks read its H-wide state
             gru = [("base.gru.weight_ih_l0", (3 * Hh, O)), ("base.gru.weight_hh_l0", (3 * Hh, Hh)),
                    ("base.gru.bias_ih_l0", (3 * Hh,)), ("base.gru.bias_hh_l0", (3 * Hh,))]
             O = Hh
+        if getattr(self, "dist_kind", 0):   # a2c/distributions.py:74-88,157-168: Categorical / Bernoulli hold one Linear, no log-std
+            K = self.n_out
+            return gru + [("base.actor.0.weight", (Hh, O)), ("base.actor.0.bias", (Hh,)),
+                          ("base.actor.2.weight", (Hh, Hh)), ("base.actor.2.bias", (Hh,)),
+                          ("base.critic.0.weight", (Hc, O)), ("base.critic.0.bias", (Hc,)),
+                          ("base.critic.2.weight", (Hc, Hc)), ("base.critic.2.bias", (Hc,)),
+                          ("base.critic_linear.weight", (1, Hc)), ("base.critic_linear.bias", (1,)),
+                          ("dist.linear.weight", (K, Hh)), ("dist.linear.bias", (K,))]
         return gru + [("base.actor.0.weight", (Hh, O)), ("base.actor.0.bias", (Hh,)),
                       ("base.actor.2.weight", (Hh, Hh)), ("base.actor.2.bias", (Hh,)),
                       ("base.critic.0.weight", (Hc, O)), ("base.critic.0.bias", (Hc,)),

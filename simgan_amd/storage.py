@@ -299,6 +299,9 @@ class RolloutStorage(object):
         host slots obs[step] and masks[step] (both uploaded and counted) and DEVICE hidden slot `step`, the new state written to
         hidden slot step + 1 on the device; it does not come back either."""
         self._on_device_only("act_step")
+        if getattr(policy, "is_recurrent", False) and getattr(policy, "dist_kind", 0):
+            raise NotImplementedError("act_step: a recurrent policy on a Discrete / MultiBinary action space acts through Policy.act and "
+                                      "insert(): the one-launch recurrent step carries the Gaussian head only")
         s, N = self.step, self.num_processes
         obs = self._host_np(_lib.F_OBS)[s]
         nz = None if noise is None else _lib.as_f32(noise).reshape(N, self.act_dim)
