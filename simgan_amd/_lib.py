@@ -177,6 +177,8 @@ TEST_PROTOTYPES = {
     "sg_test_graph_state": (C.c_int, [H, H, c_int_p]),
     "sg_test_disc_gathers": (C.c_int, [H, c_ll_p]),
     "sg_test_rng": (C.c_int, [H, C.c_int, C.c_int64, C.c_uint64, C.c_void_p]),
+    "sg_test_rng_at": (C.c_int, [H, C.c_int, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "sg_test_rng_host": (C.c_int, [C.c_int, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "sg_test_kfac_eig": (C.c_int, [H, C.c_int, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_int)]),
     "sg_test_acktr_noise": (C.c_int, [H, C.c_int64, C.c_uint64, C.c_int64, c_float_p]),
     "sg_test_raise_kfac_error": (C.c_int, [H]),

@@ -593,6 +593,46 @@ extern "C" int sg_test_rng(sg_ctx* ctx, int kind, int64_t n, uint64_t seed, void
     return 0;
 }
 
+// Test hook: the generators at ANY (seed, stream, first counter), so that tests can stand where the product's consumers stand
+// (tests/test_gpu_rng.py).  kind 1 / 2: sg_uniform / sg_normal at (seed, stream, ctr0 + i) -> float out[n];  kind 0: sg_perm_at
+// under sg_key(seed, 0x5045524D, stream), the key sg_fill_perm forms from its (seed, stream_id) -> int64 out[n] (ctr0 unused).
+__global__ void k_test_rng_at(float* out, int64_t n, uint64_t seed, uint64_t stream, uint64_t ctr0, int kind) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = kind == 1 ? sg_uniform(seed, stream, ctr0 + (uint64_t)i) : sg_normal(seed, stream, ctr0 + (uint64_t)i);
+}
+
+extern "C" int sg_test_rng_at(sg_ctx* ctx, int kind, int64_t n, uint64_t seed, uint64_t stream, uint64_t ctr0, void* out) {
+    SG_REQUIRE(ctx && out && n > 0 && n <= 0x7FFFFFFFll && kind >= 0 && kind <= 2, "sg_test_rng_at: bad argument");
+    SG_CHECK(hipSetDevice(ctx->device));
+    void* dev = nullptr;
+    SG_CHECK(hipMalloc(&dev, (size_t)n * 8));
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (kind == 0)
+        hipLaunchKernelGGL(k_test_fill_perm, grid, block, 0, ctx->stream, (int64_t*)dev, n, sg_perm_half_bits((uint64_t)n),
+                           sg_key(seed, 0x5045524Dull, stream));
+    else
+        hipLaunchKernelGGL(k_test_rng_at, grid, block, 0, ctx->stream, (float*)dev, n, seed, stream, ctr0, kind);
+    int rc = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess &&
+             hipMemcpy(out, dev, (size_t)n * (kind == 0 ? 8 : 4), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+    (void)hipFree(dev);
+    SG_REQUIRE(rc == 0, "sg_test_rng_at: HIP error");
+    return 0;
+}
+
+// The same through the header's own __host__ functions: no device call, so it runs where there is no GPU
+// (tests/test_rng_host.py).  kinds 0 and 1 only: sg_normal is device code.
+extern "C" int sg_test_rng_host(int kind, int64_t n, uint64_t seed, uint64_t stream, uint64_t ctr0, void* out) {
+    SG_REQUIRE(out && n > 0 && n <= 0x7FFFFFFFll && (kind == 0 || kind == 1), "sg_test_rng_host: bad argument");
+    if (kind == 0) {
+        const int hb = sg_perm_half_bits((uint64_t)n);
+        const uint64_t key = sg_key(seed, 0x5045524Dull, stream);
+        for (int64_t i = 0; i < n; ++i) static_cast<int64_t*>(out)[i] = sg_perm_at(i, n, hb, key);
+    } else {
+        for (int64_t i = 0; i < n; ++i) static_cast<float*>(out)[i] = sg_uniform(seed, stream, ctr0 + (uint64_t)i);
+    }
+    return 0;
+}
+
 // Test hook: the chained act's seam function on the device (tests/test_gpu_act_chain.py).
 __global__ void k_test_squash(const float* in, float* out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
