@@ -50,18 +50,19 @@ def rows_of(c):
     return (c.obs[:-1].reshape(B, c.C, HW, HW), np.asarray(c.actions).reshape(B, -1), np.asarray(c.returns)[:-1].reshape(B))
 
 
-def a2c_loss(p, obs, actions, returns, dist, vcoef=VCOEF, ecoef=ECOEF, fault=None):
+def a2c_loss(p, obs, actions, returns, dist, vcoef=VCOEF, ecoef=ECOEF, fault=None, dtype=cr.F64):
     """a2c/algo/a2c_acktr.py:55-72 on the given rows -> (total, (value_loss, action_loss, dist_entropy))"""
-    values, logp, entropy = cr.evaluate(p, ar.t64(obs), actions, dist)
-    adv = ar.t64(returns).reshape(-1) - values
+    values, logp, entropy = cr.evaluate(p, ar.t64(obs).to(dtype), actions, dist)
+    adv = ar.t64(returns).to(dtype).reshape(-1) - values
     value_loss = adv.pow(2).mean()
     action_loss = -((adv if fault == "adv_attached" else adv.detach()) * logp).mean()
     v_term = 0.5 * value_loss + 0.5 * value_loss.detach() if fault == "value_no_2" else value_loss
     return v_term * vcoef + action_loss - entropy * ecoef, (value_loss, action_loss, entropy)
 
 
-def a2c_grad(shapes, params, obs, actions, returns, dist, vcoef=VCOEF, ecoef=ECOEF, fault=None, chunk=None):
-    """-> (flat gradient of the loss over ALL the given rows, losses[3]).  The chunked faults take `chunk` rows at a time."""
+def a2c_grad(shapes, params, obs, actions, returns, dist, vcoef=VCOEF, ecoef=ECOEF, fault=None, chunk=None, dtype=cr.F64):
+    """-> (flat gradient of the loss over ALL the given rows, losses[3]).  The chunked faults take `chunk` rows at a time.  dtype
+    torch.float32: the same expressions in torch's float32 CPU arithmetic (the admission rule of tests/cnn_regimes.py)."""
     if fault in ("inv_chunk", "drop_last_chunk"):
         n = obs.shape[0]
         g = np.zeros(cr.num_params(shapes))
@@ -70,8 +71,8 @@ def a2c_grad(shapes, params, obs, actions, returns, dist, vcoef=VCOEF, ecoef=ECO
             gk, _ = a2c_grad(shapes, params, obs[b:e], actions[b:e], returns[b:e], dist, vcoef, ecoef)
             g += gk * ((e - b) / n if fault == "drop_last_chunk" else (e - b) / chunk)
         return g, a2c_grad(shapes, params, obs, actions, returns, dist, vcoef, ecoef)[1]
-    p = cr.leaves(params, shapes)
-    total, parts = a2c_loss(p, obs, actions, returns, dist, vcoef, ecoef, fault)
+    p = cr.leaves(params, shapes, dtype, grad=True)
+    total, parts = a2c_loss(p, obs, actions, returns, dist, vcoef, ecoef, fault, dtype)
     return ar.flat_grad(total, p), np.array([float(t.detach()) for t in parts])
 
 

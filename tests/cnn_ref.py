@@ -63,29 +63,33 @@ def block_distances(got, ref, shapes, atol=ATOL):
     return out
 
 
-def leaves(flat, shapes, dtype=F64):
+def leaves(flat, shapes, dtype=F64, grad=None):
+    """grad None: float64 leaves take a gradient, others do not (tests/cnn_regimes.py's float32 admission asks for one)"""
     flat = np.asarray(flat, np.float64).reshape(-1)
     out, off = {}, 0
     for name, shape in shapes:
         n = int(np.prod(shape))
-        out[name] = torch.as_tensor(np.ascontiguousarray(flat[off:off + n].reshape(shape)), dtype=dtype).requires_grad_(dtype == F64)
+        out[name] = torch.as_tensor(np.ascontiguousarray(flat[off:off + n].reshape(shape)), dtype=dtype).requires_grad_(dtype == F64 if grad is None else grad)
         off += n
     assert off == flat.size, (off, flat.size)
     return out
 
 
 # ------------------------------------------------------------------------------------------------------------ forward
-def trunk(p, x, fault=None):
+def trunk(p, x, fault=None, tap=None):
     """CNNBase.main on x [n, C, 84, 84] (a2c/model.py:211-215, 225) -> (features [n, Hs], the four pre-activations).  `fault`
-    injects one defect, for the test of the test: "no_div255", "flatten_yxc" (ppo_grad has three more)."""
+    injects one defect, for the test of the test: "no_div255", "flatten_yxc" (ppo_grad has three more).  `tap(name, tensor) ->
+    tensor` sees every pre-activation ("z1", "z2", "z3", "zf") and every activation ("a1", "a2", "a3", "feat") and may replace it:
+    tests/cnn_regimes.py builds its injected defects from it (a tap that returns what it is given changes nothing)."""
+    tap = tap or (lambda name, t: t)
     x = x if fault == "no_div255" else x / 255.0
-    z1 = F.conv2d(x, p["base.main.0.weight"], p["base.main.0.bias"], stride=4)
-    z2 = F.conv2d(F.relu(z1), p["base.main.2.weight"], p["base.main.2.bias"], stride=2)
-    z3 = F.conv2d(F.relu(z2), p["base.main.4.weight"], p["base.main.4.bias"], stride=1)
-    a3 = F.relu(z3)
+    z1 = tap("z1", F.conv2d(x, p["base.main.0.weight"], p["base.main.0.bias"], stride=4))
+    z2 = tap("z2", F.conv2d(tap("a1", F.relu(z1)), p["base.main.2.weight"], p["base.main.2.bias"], stride=2))
+    z3 = tap("z3", F.conv2d(tap("a2", F.relu(z2)), p["base.main.4.weight"], p["base.main.4.bias"], stride=1))
+    a3 = tap("a3", F.relu(z3))
     flat = a3.permute(0, 2, 3, 1).reshape(a3.shape[0], -1) if fault == "flatten_yxc" else a3.reshape(a3.shape[0], -1)
-    zf = F.linear(flat, p["base.main.7.weight"], p["base.main.7.bias"])
-    return F.relu(zf), (z1, z2, z3, zf)
+    zf = tap("zf", F.linear(flat, p["base.main.7.weight"], p["base.main.7.bias"]))
+    return tap("feat", F.relu(zf)), (z1, z2, z3, zf)
 
 
 def heads(p, feat, dist):
@@ -97,9 +101,9 @@ def heads(p, feat, dist):
     return value, mean, torch.zeros_like(mean) + p["dist.logstd._bias"].t().view(1, -1)
 
 
-def evaluate(p, x, actions, dist, fault=None):
+def evaluate(p, x, actions, dist, fault=None, tap=None):
     """Policy.evaluate_actions (a2c/model.py:107-114) -> (values [n], logp [n], entropy.mean())"""
-    feat, _ = trunk(p, x, fault)
+    feat, _ = trunk(p, x, fault, tap)
     h = heads(p, feat, dist)
     if dist == "categorical":
         ls = F.log_softmax(h[1], dim=-1)                       # FixedCategorical.log_probs / entropy, a2c/distributions.py:33-48
@@ -155,13 +159,16 @@ def act64(shapes, params, obs, dist, noise=None):
 
 
 # ------------------------------------------------------------------------------------------------------------ PPO
-def ppo_grad(shapes, params, obs, actions, old_logp, value_preds, returns, adv, dist, use_clipped=True, ecoef=ECOEF, fault=None):
+def ppo_grad(shapes, params, obs, actions, old_logp, value_preds, returns, adv, dist, use_clipped=True, ecoef=ECOEF, fault=None,
+             dtype=F64, tap=None):
     """One optimizer step's loss and gradient on the given rows: obs [n, C, 84, 84], the rest [n]; adv = the rows' normalised
-    advantages (normalised over the WHOLE rollout, a2c/algo/ppo.py:66-68) -> (flat gradient, losses[3])"""
-    p = leaves(params, shapes)
-    values, logp, entropy = evaluate(p, ar.t64(obs), actions, dist, fault)
-    total, parts = ar.ppo_loss(values, logp, entropy, ar.t64(old_logp).reshape(-1), ar.t64(adv).reshape(-1), ar.t64(value_preds).reshape(-1),
-                               ar.t64(returns).reshape(-1), CLIP, VCOEF, ecoef, use_clipped)
+    advantages (normalised over the WHOLE rollout, a2c/algo/ppo.py:66-68) -> (flat gradient, losses[3]).  dtype torch.float32:
+    the same expressions evaluated by torch's float32 CPU kernels (the admission rule of tests/cnn_regimes.py)."""
+    t = lambda a: ar.t64(a).to(dtype)  # noqa: E731
+    p = leaves(params, shapes, dtype, grad=True)
+    values, logp, entropy = evaluate(p, t(obs), actions, dist, fault, tap)
+    total, parts = ar.ppo_loss(values, logp, entropy, t(old_logp).reshape(-1), t(adv).reshape(-1), t(value_preds).reshape(-1),
+                               t(returns).reshape(-1), CLIP, VCOEF, ecoef, use_clipped)
     g = ar.flat_grad(total, p)
     if fault == "wgrad_khkw":      # conv1's weight gradient with kh and kw swapped
         n = int(np.prod(shapes[0][1]))
@@ -291,15 +298,22 @@ def build(C, Hs, dist, P, T, N, regime="off_policy", seed=None):
     seed = SEEDS[key] if seed is None else seed
     rng = np.random.default_rng([seed, C, Hs, P, T, N])
     shapes = param_shapes(C, Hs, dist, P)
-    B = T * N
     c = Case(C=C, Hs=Hs, dist=dist, P=P, T=T, N=N, regime=regime, seed=seed, shapes=shapes, tag=f"{regime} C={C} Hs={Hs} {dist}({P}) {T}x{N} seed {seed}")
     c["params"] = init_params(rng, shapes)
     c["obs"] = rng.integers(0, 256, (T + 1, N, C, HW, HW)).astype(np.float32)
+    return complete(c, rng)
+
+
+def complete(c, rng, actions=None):
+    """the rest of a case from its params and obs: actions (drawn here unless given: Categorical class indices [T * N]), value
+    predictions, returns and old log-probs of the case's regime, the normalised advantages"""
+    C, dist, P, T, N, regime, shapes = c.C, c.dist, c.P, c.T, c.N, c.regime, c.shapes
+    B = T * N
     rows = c.obs[:-1].reshape(B, C, HW, HW)
     out = forward64(shapes, c.params, rows, dist)
     v = out[0]
     if dist == "categorical":
-        act = rng.integers(0, P, B)
+        act = rng.integers(0, P, B) if actions is None else np.asarray(actions).reshape(B)
         c["actions"] = act.reshape(T, N, 1).astype(np.int64)
         lp = log_softmax64(out[1] )[np.arange(B), act]
     else:

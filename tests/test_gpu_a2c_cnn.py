@@ -94,16 +94,22 @@ def _record(label, rec):
 
 
 def _hold_gradient(sg, key, label):
-    c = ref.case(key)
-    want, want_losses = ref.case_grad(c)
-    agent, p, losses = _run(sg, c, max_grad_norm=ref.NO_CLIP, eps=ref.EPS_RECOVER)
+    return hold_case(sg, ref.case(key), label)
+
+
+def hold_case(sg, c, label, want=None, record=None, **over):
+    """the recovered one-step gradient of a case against float64 autograd (`want`: its gradient and losses, where the caller has
+    them already) per block, the losses with assert_close -> the recovered gradient.  tests/test_gpu_cnn_regimes.py's cases come
+    through here too, with their own record."""
+    want, want_losses = ref.case_grad(c, **({"ecoef": over["entropy_coef"]} if "entropy_coef" in over else {})) if want is None else want
+    agent, p, losses = _run(sg, c, max_grad_norm=ref.NO_CLIP, eps=ref.EPS_RECOVER, **over)
     sq, step = agent.get_rmsprop()
     assert step == 1
     got = ref.recovered_gradient(c.params, p.get_flat_params(), sq)
     d = cr.block_distances(got, want, c.shapes)
     lr_ = float(np.max(np.abs(np.asarray(losses[0]) - want_losses) / (cr.ATOL + RTOL * np.abs(want_losses))))
     print(f"{label}: worst block {max(d, key=d.get)} {max(d.values()) / RTOL:.3f} x RTOL, losses {lr_:.3f} of tol")
-    _record(label, {"worst": max(d.values()) / RTOL, "blocks": {k: x / RTOL for k, x in d.items()}, "losses": lr_})
+    (record or _record)(label, {"worst": max(d.values()) / RTOL, "blocks": {k: x / RTOL for k, x in d.items()}, "losses": lr_})
     assert_close(losses[0], want_losses, what=f"{label} losses")
     bad = {k: x for k, x in d.items() if not x <= RTOL}
     assert not bad, f"{label}: blocks past {RTOL:g}: {bad}"

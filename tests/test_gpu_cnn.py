@@ -216,9 +216,9 @@ def test_forward_past_one_pass_of_rows_matches_float64(sg):
 
 
 # ------------------------------------------------------------------------------------------------- 2 one-step gradient
-def one_step(sg, c, max_grad_norm, use_clipped, perms=None, E=1, M=1, lr=LR):
+def one_step(sg, c, max_grad_norm, use_clipped, perms=None, E=1, M=1, lr=LR, ecoef=cr.ECOEF):
     p = make_policy(sg, c.C, c.Hs, c.dist, c.P, c.params)
-    agent = sg.algo.PPO(p, cr.CLIP, E, M, cr.VCOEF, cr.ECOEF, lr=lr, eps=EPS, max_grad_norm=max_grad_norm, use_clipped_value_loss=use_clipped)
+    agent = sg.algo.PPO(p, cr.CLIP, E, M, cr.VCOEF, ecoef, lr=lr, eps=EPS, max_grad_norm=max_grad_norm, use_clipped_value_loss=use_clipped)
     B = c.T * c.N
     perms = np.arange(B, dtype=np.int64)[None] if perms is None else perms
     losses = agent.update(rollout_of(sg, c), perms=perms)
