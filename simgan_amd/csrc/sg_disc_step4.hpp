@@ -11,14 +11,25 @@
 //     and moments and the Adam scalars are in registers, and they sit in a poll loop when the chain ends;
 //   * the chain blocks publish their rows of the operand stacks with write-through (`sc1`) stores, drain them, and raise one
 //     flag word each (the Adam step number: monotonic, never reset inside an epoch or across replays of the epoch's graph);
-//     the other side polls the 12G words with coalesced L1-bypassing loads from one wave and then reads its two operand
-//     slabs with `sc1` loads (MI355X: write-through stores + sc1 loads are the cross-XCD-coherent pair);
+//     the other side polls the words with coalesced L1-bypassing loads -- in a tile workgroup wave 7 the 8G BCE flags and
+//     wave 6 the 4G mixup flags, each telling the other waves through an LDS word of its own -- and then reads its two
+//     operand slabs with `sc1` loads (MI355X: write-through stores + sc1 loads are the cross-XCD-coherent pair);
 //   * the dependence is ONE-WAY -- no chain block ever waits for anything -- so whatever the dispatcher does (blocks are
 //     dispatched in index order, the chain blocks first) the launch cannot deadlock on residency; the spin is bounded by the
 //     wall clock all the same and a time-out is reported through an error word the host reads at its next synchronisation;
 //   * the second edge (new weights -> the next step's chain blocks) stays a launch boundary, which is also what keeps every
 //     L2 coherent for the plain loads of the next launch.
-// Arithmetic, summation order and stores are those of the two-launch step: results are bit-identical (tests/test_gpu_parity.py).
+// Arithmetic, summation order and stores are those of the two-launch step: results are bit-identical at every batch size
+// (tests/test_gpu_parity.py, tests/test_gpu_step4_detect.py).
+//
+// Anatomy of the hand-off in a tile workgroup (north-star shape, ns after the first chain block starts, medians of the stamp
+// build; before -> now): the last mixup flag is stored at 4410 -> 4360; the mixup operands are requested at ~5840 (behind a
+// barrier, the BCE half's loads and one poll queued behind them) -> 5540 (wave 6 sees the flags at 5330, the other waves its
+// LDS word); all operands contracted at 6500 -> 5970.  Polls in flight on the mixup flags (SG_STEP4_POLLS = k), device
+// clock per step incl. the epoch's row copy, three alternations on one box: before 8.67-8.80 us; k = 1: 8.51-8.54;
+// k = 2: 8.55-8.58; k = 3: 8.60-8.62.  The polling wave of its own and the LDS words are the gain; every further poll in
+// flight costs ~0.04 us (91 workgroups x 32 lines x k reads per round trip queue in front of the chain's write-through stores,
+// as round 4's four polls on all 96 lines did), so k = 1 ships.
 //
 // Round 5 tried the hand-off WITHOUT flags (every operand word poisoned one launch ahead and validated by its reader, no drain, no
 // flag: `SG_STEP4_POISON`): measured negative (profiles/r05_step4_poison_handoff_negative.txt) and removed from the library in
@@ -66,6 +77,46 @@ __device__ __forceinline__ bool sg_step4_wait(const unsigned* flags, int lo, int
         if ((it & 31) == 31 && wall_clock64() > deadline) return false;
         __builtin_amdgcn_s_sleep(1);
     }
+}
+
+// The same wait on n <= 64 flags from [0, n) with SG_STEP4_POLLS polls in flight, one flag per lane.  The polls are asm loads
+// and the waits are spelt out: the compiler's wait-count pass knows nothing of them (and would drain a pipe it knew of).  The
+// prologue spaces the polls a k-th of a round trip apart; from then on a poll is re-issued when the oldest has been examined,
+// which keeps the spacing.  On return up to k - 1 polls are still in flight: their registers stay in `pp`, which the caller
+// hands to sg_step4_polls_retire() behind its next full `vmcnt` wait, so that nothing else is allocated to them before.
+// `quit` is an LDS word whose value 2 ends the wait (the other polling wave gave up).
+#define SG_STEP4_POLLS 1                     // 1, 2 or 3: measured 8.52 / 8.57 / 8.61 us per step
+#define SG_STEP4_POLL_START_TICKS 340        // no mixup poll before 3.4 us after the tile workgroup's start
+struct SgStep4Polls { unsigned r[SG_STEP4_POLLS] = {}; };
+__device__ __forceinline__ unsigned sg_step4_poll(const unsigned* p) {
+    unsigned r;
+    asm volatile("global_load_dword %0, %1, off sc1" : "=v"(r) : "v"(p) : "memory");
+    return r;
+}
+__device__ __forceinline__ bool sg_step4_wait_piped(SgStep4Polls& pp, const unsigned* flags, int n, unsigned want, int lane, const int* quit) {
+    constexpr int K = SG_STEP4_POLLS;
+    static_assert(K >= 1 && K <= 3, "SG_STEP4_POLLS: 1, 2 or 3");
+    const unsigned* p = flags + (lane < n ? lane : n - 1) * SG_STEP4_FLAG_STRIDE;   // spare lanes repeat the last flag
+    const long long deadline = wall_clock64() + SG_STEP4_TIMEOUT_TICKS;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        pp.r[i] = sg_step4_poll(p);
+        if (i + 1 < K) __builtin_amdgcn_s_sleep(28 / K);   // 64 clocks each: ~0.75 us / k
+    }
+    for (int it = 0;; ++it) {
+#pragma unroll
+        for (int i = 0; i < K; ++i) {   // oldest first
+            asm volatile("s_waitcnt vmcnt(%1)" : "+v"(pp.r[i]) : "n"(K - 1) : "memory");
+            if (__all(pp.r[i] == want)) return true;
+            __builtin_amdgcn_s_sleep(1);
+            pp.r[i] = sg_step4_poll(p);
+        }
+        if ((it & 31) == 31 && (wall_clock64() > deadline || __hip_atomic_load(quit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 2)) return false;
+    }
+}
+__device__ __forceinline__ void sg_step4_polls_retire(SgStep4Polls& pp) {
+#pragma unroll
+    for (int i = 0; i < SG_STEP4_POLLS; ++i) asm volatile("" : "+v"(pp.r[i]) : : "memory");
 }
 
 template <int KF, int KH>
@@ -134,7 +185,7 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
             p0 = c_params[idx]; m0 = c_m[idx]; v0 = c_v[idx];
             sc = *reinterpret_cast<const float4*>(c_st->step_size2);
         }
-        if (tid < 256 || wave == 7) t0 = c_st->t0;
+        if (tid < 256 || wave >= 6) t0 = c_st->t0;
         const SgStacks stk = sg_disc_stacks(c_ops, Kt, Hp, Fp, ldF);
         const float* L = (w2 ? stk.L2 : stk.L1) + (size_t)tm * Kt * 16;
         const float* Rr = (w2 ? stk.R2 : stk.R1t) + (size_t)tn * Kt * 16;
@@ -143,54 +194,109 @@ __global__ __launch_bounds__(512) void k_disc_step4(float* c_params, float* c_m,
         const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Rr), 0, Kt * 64, 0x00020000);
         int img0 = 0, img1 = 0;
         sg_disc_img_pos(d, w2, tm * 16 + ((tid & 255) >> 4), tn * 16 + (tid & 15), img0, img1);
-        if (tid == 0) *sh_ok = 1;
-        __syncthreads();
         // The stacked rows [0, 32G) come from the BCE workgroups (chain blocks [4G, 12G)), which finish ~0.7 us before the mixup
-        // workgroups ([0, 4G): seven dependent GEMMs against three): their half of the two slabs is requested and contracted
-        // while the mixup half is still being computed.  Waves take 16-row chunks round-robin, two chunks (16 loads per
-        // lane) per batch; at batch 128 this is the chunk order of k_disc_wgrad, so the sums are bit-identical to it.
+        // workgroups ([0, 4G): seven dependent GEMMs against three).  Wave 7 waits for the BCE flags, wave 6 for the mixup flags
+        // (with SG_STEP4_POLLS polls in flight, see sg_step4_wait_piped); each tells the others through an LDS word of its own
+        // -- 0 pending, 1 up, 2 gave up -- written once and spun on with LDS reads, so no wave stands at a barrier while the
+        // flag it needs is already up.  A wave requests its first BCE batch when the BCE word is up and its first mixup batch
+        // when the mixup word is up, into fragment registers of their own and before the BCE batch is consumed.  Waves take
+        // 16-row chunks round-robin, two chunks (16 loads per lane) per batch, BCE chunks before mixup chunks: a wave's chunks
+        // and their order are those of k_disc_wgrad, so the sums are bit-identical to it.
+        const int half_chunks = n_chunks >> 1;
+        // byte offsets of one batch of a wave's share of chunks [.., c_hi): chunks c0 and c0 + 8
+        auto batch_offs = [&](int c0, int c_hi, int (&o)[2][4]) {
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int c = c0 + cc * nw;
+                    const int r = c < c_hi ? 16 * c + 4 * s + lq : Kt;   // past this half: the buffer's range check returns zero
+                    o[cc][s] = (r * 16 + li) * 4;
+                }
+        };
+        // the first batch of either half: its offsets are worked out here, ahead of the waits (the empty asm keeps the compiler
+        // from sinking the sixteen address computations to their use, between a word coming up and the requests)
+        // chunk c goes to wave c mod 8 in both halves, as in k_disc_wgrad: the mixup half starts at this wave's first chunk at or
+        // past half_chunks (half_chunks + wave whenever G is a multiple of 4; before, the mixup half was dealt from half_chunks
+        // on, which at other G gave a wave other chunks than k_disc_wgrad gives it and the sums another rounding)
+        const int mix0 = half_chunks + ((wave - half_chunks) & (nw - 1));
+        int oa[2][4], ob[2][4];
+        batch_offs(wave, half_chunks, oa);
+        batch_offs(mix0, n_chunks, ob);
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(oa[cc][s]), "+v"(ob[cc][s]));
+        int* sh_bce = sh_ok + 1;
+        int* sh_mix = sh_ok + 2;
+        if (tid == 0) { *sh_bce = 0; *sh_mix = 0; }
+        const long long poll_from = wall_clock64() + SG_STEP4_POLL_START_TICKS;
+        __syncthreads();
         const unsigned want = (unsigned)(t0 + c_k1);
+        auto word_set = [&](int* w, bool up) {
+            if (lane == 0) __hip_atomic_store(w, up ? 1 : 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        };
+        auto word_up = [&](int* w) -> bool {   // bounded by the polling wave, which always writes its word
+            int s;
+            while ((s = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0) __builtin_amdgcn_s_sleep(1);
+            asm volatile("" ::: "memory");     // the operand loads stay behind the word
+            return s == 1;
+        };
         // (a time-out is sticky: once the error word is up, the waiting workgroups of every later launch give up at once instead
         // of spinning out their own three seconds -- the update ends in its normal time, with NaN losses and the error reported)
-        if (wave == 7 && (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 || !sg_step4_wait(flags, 4 * c_G, n_chain, want, lane)) && lane == 0) *sh_ok = 0;
-        __syncthreads();
-        if (!*sh_ok) { if (tid == 0) { atomicOr(err, 1u); a.loss_acc[0] = __builtin_nanf(""); } return; }   // the host sees NaN losses, then the error word
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f}, alt = acc;
-        const int half_chunks = n_chunks >> 1;
-        // contract chunks [c_lo, c_hi): this wave's share, two chunks per batch; `between` runs once, after the first batch's
-        // loads have been issued and before they are consumed (the polling wave looks for the mixup flags there)
-        auto contract = [&](int c_lo, int c_hi, auto&& between) {
-            bool first = true;
-            for (int c0 = c_lo + wave; c0 < c_hi || first; c0 += 2 * nw) {
-                float x[2][4], y[2][4];
-#pragma unroll
-                for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        const int c = c0 + cc * nw;
-                        const int r = c < c_hi ? 16 * c + 4 * s + lq : Kt;   // past this half: the buffer's range check returns zero
-                        x[cc][s] = sg_ld_sc1(rL, (r * 16 + li) * 4);
-                        y[cc][s] = sg_ld_sc1(rR, (r * 16 + li) * 4);
-                    }
-                if (first) { between(); first = false; }
-#pragma unroll
-                for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        if (s & 1) alt = sg_mfma(x[cc][s], y[cc][s], alt);
-                        else acc = sg_mfma(x[cc][s], y[cc][s], acc);
-                    }
+        SgStep4Polls pp;
+        if (wave == 7) {
+            word_set(sh_bce, __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 && sg_step4_wait(flags, 4 * c_G, n_chain, want, lane));
+        } else if (wave == 6) {
+            bool up = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
+            if (up) {
+                while (wall_clock64() < poll_from) __builtin_amdgcn_s_sleep(2);   // the mixup chain cannot be done sooner
+                // the pipe holds one flag per lane; a larger batch (4G > 64) keeps the plain loop over all its flags
+                up = 4 * c_G <= 64 ? sg_step4_wait_piped(pp, flags, 4 * c_G, want, lane, sh_bce) : sg_step4_wait(flags, 0, 4 * c_G, want, lane);
             }
+            word_set(sh_mix, up);
+        }
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f}, alt = acc;
+        auto load_offs = [&](const int (&o)[2][4], float (&x)[2][4], float (&y)[2][4]) {
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    x[cc][s] = sg_ld_sc1(rL, o[cc][s]);
+                    y[cc][s] = sg_ld_sc1(rR, o[cc][s]);
+                }
         };
-        contract(0, half_chunks, [&]() {
-            if (wave == 7 && !sg_step4_wait(flags, 0, 4 * c_G, want, lane) && lane == 0) *sh_ok = 0;
-        });
-        __syncthreads();
-        if (!*sh_ok) { if (tid == 0) { atomicOr(err, 1u); a.loss_acc[0] = __builtin_nanf(""); } return; }   // the host sees NaN losses, then the error word
-        contract(half_chunks, n_chunks, []() {});
+        auto load_batch = [&](int c0, int c_hi, float (&x)[2][4], float (&y)[2][4]) {
+            int o[2][4];
+            batch_offs(c0, c_hi, o);
+            load_offs(o, x, y);
+        };
+        auto mma_batch = [&](const float (&x)[2][4], const float (&y)[2][4]) {
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    if (s & 1) alt = sg_mfma(x[cc][s], y[cc][s], alt);
+                    else acc = sg_mfma(x[cc][s], y[cc][s], acc);
+                }
+        };
+        float xa[2][4], ya[2][4], xb[2][4], yb[2][4];
+        bool up = word_up(sh_bce);
+        if (up) {
+            load_offs(oa, xa, ya);
+            up = word_up(sh_mix);
+        }
+        if (!up) { if (tid == 0) { atomicOr(err, 1u); a.loss_acc[0] = __builtin_nanf(""); } return; }   // the host sees NaN losses, then the error word
+        load_offs(ob, xb, yb);
+        __builtin_amdgcn_sched_barrier(0);   // the mixup requests go out before the first wait for a BCE operand
+        mma_batch(xa, ya);
+        for (int c0 = wave + 2 * nw; c0 < half_chunks; c0 += 2 * nw) { load_batch(c0, half_chunks, xa, ya); mma_batch(xa, ya); }
+        mma_batch(xb, yb);
+        for (int c0 = mix0 + 2 * nw; c0 < n_chunks; c0 += 2 * nw) { load_batch(c0, n_chunks, xb, yb); mma_batch(xb, yb); }
         acc += alt;
 #pragma unroll
         for (int r = 0; r < 4; ++r) red[wave][(4 * lq + r) * 16 + li] = acc[r];
+        sg_step4_polls_retire(pp);   // the sums above needed operands requested after the last poll: every poll has landed
         __syncthreads();
         if (tid < 256) {
             float g = 0.f;

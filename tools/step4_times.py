@@ -66,7 +66,10 @@ if len(vt):
     print(f"vector blocks ({len(vt)}): start {rng(vt[:, 0])}, partials in {rng(vt[:, 1])}, reduce barrier {rng(vt[:, 2])}, stores acknowledged {rng(vt[:, 3])}")
 if len(gt):
     print(f"row-copy blocks ({len(gt)}): start {rng(gt[:, 0])}, stores acknowledged {rng(gt[:, 1])}")
-print(f"tile blocks ({len(tt)}), wave 0: ready {rng(tt[:, 0])}, BCE half contracted and mixup flags seen {rng(tt[:, 1])}, "
+print(f"tile blocks ({len(tt)}), wave 0: ready {rng(tt[:, 0])}, BCE word seen and BCE operands requested {rng(tt[:, 1])}, "
       f"all contracted {rng(tt[:, 2])}, past the reduce barrier {rng(tt[:, 3])}")
+print(f"tile blocks, mixup hand-off: mixup word up (wave 6) {rng(tt[:, 4])}, mixup operands requested (wave 0) {rng(tt[:, 5])}")
+print(f"last mixup flag stored -> median mixup word up: {int(np.median(tt[:, 4])) - mix[:, 3].max()} ns, "
+      f"-> median mixup operands requested: {int(np.median(tt[:, 5])) - mix[:, 3].max()} ns")
 print(f"last chain body done -> median tile wave 0 has its operands contracted: {int(np.median(tt[:, 2])) - c[:, 1].max()} ns")
 fn(disc.h, 0, None, 0)
