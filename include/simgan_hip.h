@@ -135,6 +135,23 @@ SG_API int sg_policy_create_rnn_dist(sg_ctx *ctx, int obs_dim, int hidden, int c
  * create3 do not reach it: they keep refusing every kind but their three. */
 SG_API int sg_policy_create_cnn(sg_ctx *ctx, int channels, int height, int width, int hidden, int dist, int act_dim, int n_out,
                                 sg_policy **out);
+/* The same base with recurrent=True (a2c/model.py:117-230, --recurrent-policy on image observations): the three convolutions and
+ * the FC layer, then nn.GRU(hidden, hidden) on the features, then critic_linear and the Categorical / Gaussian head on the GRU
+ * state.  sg_policy_create_cnn's checks and heads; it also refuses, with its own message, a `hidden` whose 16-row GRU tiles
+ * (input projection, the two scans, the input gradient) do not fit a CU's LDS even with the weights read from global memory
+ * (hidden = 512, the reference's default, fits).  Flat (state_dict) order: base.gru.weight_ih_l0 [3 hidden, hidden], weight_hh_l0,
+ * bias_ih_l0, bias_hh_l0 (NNBase.__init__ creates the GRU before `main`), then sg_policy_create_cnn's order; on the device the
+ * CNN's flat block comes first and the GRU's tile-padded block behind it (padding stays zero in weights, gradient and moments).
+ * Served by sg_policy_act_rnn / _get_value_rnn / _evaluate_rnn (obs rows are the C * 7056-float images; hxs [n][hidden], masks
+ * [T * n]; a one-step call and the same step inside a sequence give the same bits), sg_policy_get_params / _set_params,
+ * sg_ppo_create (one rank) with sg_ppo_set_hidden_states (slot 0) before every sg_ppo_update -- PPO through time over minibatches
+ * of N // num_mini_batch whole environments read time-major in place from the image rollout, injected perms [ppo_epoch][N],
+ * minibatches above 4096 rows refused -- and sg_ppo_get_adam / _set_adam.  Everything else that can reach the handle refuses it
+ * with a message naming the recurrent CNN base: sg_a2c_create / _create_rnn / _create_cnn, sg_acktr_create, the diagnostics entry
+ * points, sg_rollout_act_step / _act_step_rnn / _act_step_chain, sg_rollout_compute_returns_policy, sg_policy_act_ensemble,
+ * sg_ppo_set_symmetry (coef > 0), sg_ppo_create on a communicator of world > 1; sg_rollout_enable_hidden refuses an image rollout. */
+SG_API int sg_policy_create_cnn_rnn(sg_ctx *ctx, int channels, int height, int width, int hidden, int dist, int act_dim, int n_out,
+                                    sg_policy **out);
 SG_API int sg_policy_destroy(sg_policy *p);
 SG_API int sg_policy_num_params(const sg_policy *p, int64_t *n);
 /* nn.Module.load_state_dict / state_dict, flattened. */

@@ -65,6 +65,7 @@ PROTOTYPES = {
     "sg_policy_create3": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(H)]),
     "sg_policy_create_rnn_dist": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(H)]),
     "sg_policy_create_cnn": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(H)]),
+    "sg_policy_create_cnn_rnn": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(H)]),
     "sg_policy_destroy": (C.c_int, [H]),
     "sg_policy_num_params": (C.c_int, [H, c_i64_p]),
     "sg_policy_set_params": (C.c_int, [H, c_float_p, C.c_int64]),

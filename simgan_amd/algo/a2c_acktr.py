@@ -78,6 +78,9 @@ class A2C_ACKTR():
         if type(actor_critic).__name__ == "SplitPolicy":
             raise NotImplementedError("A2C_ACKTR: implemented for Policy (MLP) only, not for SplitPolicy")
         is_cnn = bool(getattr(actor_critic, "cnn", 0))
+        if is_cnn and getattr(actor_critic, "is_recurrent", False):
+            raise NotImplementedError("A2C_ACKTR: not implemented for the recurrent CNN base (image observations with "
+                                      "base_kwargs={'recurrent': True}), in any mode -- acktr, cnn=True or recurrent=True; PPO is")
         if cnn and acktr:
             raise NotImplementedError("A2C_ACKTR(acktr=True, cnn=True): ACKTR is not implemented for the CNN base (image "
                                       "observations): K-FAC has no convolution statistics here; acktr=False (A2C) runs")

@@ -38,6 +38,9 @@ def run(agent, rollouts, clip_param, fetch=True, scope="rank"):
     fetch=True: wait and return the dict of NAMES; False: return None (fetch_last reads the result later).  scope: check_scope."""
     call = {"rank": "sg_rollout_policy_diagnostics", "world": "sg_rollout_policy_diagnostics_world"}[check_scope(scope)]
     pol = agent.actor_critic
+    if getattr(pol, "cnn", 0) and getattr(pol, "is_recurrent", False):
+        raise NotImplementedError("diagnostics: not built for the recurrent CNN base (the launch runs the MLP trunks only); evaluate the "
+                                  "rollout through Policy.evaluate_actions and reduce on the host")
     rollouts._push([_lib.F_OBS, _lib.F_ACTIONS, _lib.F_VALUE_PREDS, _lib.F_RETURNS, _lib.F_LOGP])
     hxs0 = None
     if getattr(pol, "is_recurrent", False):

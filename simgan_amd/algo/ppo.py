@@ -67,6 +67,13 @@ class PPO():
         self.is_cuda = True   # the rollout the update reads lives in HBM whatever the host tensors are
 
         self.recurrent = bool(getattr(actor_critic, "is_recurrent", False))   # a2c/algo/ppo.py:74-76: recurrent_generator
+        if self.recurrent and getattr(actor_critic, "cnn", 0):   # the recurrent CNN base (CNN + GRU): plain PPO through time on one rank
+            if mirror_obs is not None and symmetry_coef > 0:
+                raise NotImplementedError("mirror-symmetry loss: not implemented for the recurrent CNN base (image observations have no "
+                                          "mirror map here and the mirrored rows no hidden state); symmetry_coef > 0 needs the MLP base")
+            if getattr(actor_critic.ctx, "world", 1) > 1:
+                raise NotImplementedError("PPO on the recurrent CNN base runs on one rank: data-parallel PPO through time on image "
+                                          f"observations is not implemented (this context's communicator has world {actor_critic.ctx.world})")
         if self.recurrent and getattr(actor_critic, "dist_kind", 0) and mirror_obs is not None and symmetry_coef > 0:
             raise NotImplementedError("mirror-symmetry loss: not for a recurrent Policy on a Discrete / MultiBinary action space (it "
                                       "compares action means of a feed-forward policy); symmetry_coef > 0 needs the MLP base and Box")

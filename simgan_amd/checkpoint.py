@@ -182,14 +182,18 @@ def _policy_dims(class_name, sd, dist_class=None):
         assert sd["base.main.0.weight"].shape == (32, C, 8, 8) and sd["base.main.2.weight"].shape == (64, 32, 4, 4) and \
             sd["base.main.4.weight"].shape == (32, 64, 3, 3) and sd["base.main.7.weight"].shape == (H, 32 * 7 * 7) and \
             sd["base.critic_linear.weight"].shape == (1, H), "inconsistent CNN base shapes in the checkpoint"
-        assert "base.gru.weight_ih_l0" not in sd, "a recurrent CNN base is not built"
+        rec = {}
+        if "base.gru.weight_ih_l0" in sd:   # recurrent=True (a2c/model.py:124-131): nn.GRU(H, H) between the FC layer and the heads
+            assert sd["base.gru.weight_ih_l0"].shape == (3 * H, H) and sd["base.gru.weight_hh_l0"].shape == (3 * H, H), \
+                "inconsistent GRU shapes on the CNN base in the checkpoint"
+            rec = dict(recurrent=True)
         if "dist.linear.weight" in sd:
             if dist_class != "Categorical":
                 raise ValueError(f"checkpoint policy has the CNN base with a {dist_class} head: Categorical or DiagGaussian expected")
             K = sd["dist.linear.weight"].shape[0]
-            return dict(kind="cnn_categorical", obs_dim=int(C) * 84 * 84, act_dim=1, hidden=int(H), num_feet=1, dist=1, n_out=int(K), cnn=int(C))
+            return dict(kind="cnn_categorical", obs_dim=int(C) * 84 * 84, act_dim=1, hidden=int(H), num_feet=1, dist=1, n_out=int(K), cnn=int(C), **rec)
         A = sd["dist.fc_mean.weight"].shape[0]
-        return dict(kind="cnn", obs_dim=int(C) * 84 * 84, act_dim=int(A), hidden=int(H), num_feet=1, cnn=int(C))
+        return dict(kind="cnn", obs_dim=int(C) * 84 * 84, act_dim=int(A), hidden=int(H), num_feet=1, cnn=int(C), **rec)
     if class_name == "Policy" and "dist.linear.weight" in sd:
         # Discrete / MultiBinary action space: the two heads have the same parameters, the dist module's class tells them apart
         if dist_class not in _LINEAR_DISTS:
@@ -507,7 +511,8 @@ def load_policy(path, ctx=None):
     ck = read_reference_checkpoint(path)
     if ck["kind"] in ("cnn", "cnn_categorical"):
         space = _Discrete(ck["n_out"]) if ck["kind"] == "cnn_categorical" else _Box(ck["act_dim"])
-        pol = Policy((ck["cnn"], 84, 84), space, base_kwargs={"hidden_size": ck["hidden"]}, ctx=ctx)
+        pol = Policy((ck["cnn"], 84, 84), space, base_kwargs={"recurrent": bool(ck.get("recurrent")), "hidden_size": ck["hidden"]}, ctx=ctx,
+                     recurrent_cnn=True)
     elif ck["kind"] in ("mlp_categorical", "mlp_bernoulli"):
         space = _Discrete(ck["n_out"]) if ck["kind"] == "mlp_categorical" else _MultiBinary(ck["n_out"])
         pol = Policy((ck["obs_dim"],), space, base_kwargs={"recurrent": bool(ck.get("recurrent")), "hidden_size": ck["hidden"]}, ctx=ctx,
@@ -524,10 +529,10 @@ def load_policy(path, ctx=None):
 
 def save_policy(path, policy, ob_rms=None):
     """a2c/main.py:260-269: a file the reference's `torch.load(path)` turns back into `[actor_critic, ob_rms]`."""
+    if getattr(policy, "cnn", 0):   # (the recurrent CNN base too)
+        raise NotImplementedError(CNN_SAVE_MSG)
     if policy.is_recurrent:
         raise NotImplementedError(RECURRENT_SAVE_MSG)
-    if getattr(policy, "cnn", 0):
-        raise NotImplementedError(CNN_SAVE_MSG)
     kind = {1: "mlp_categorical", 2: "mlp_bernoulli"}.get(getattr(policy, "dist_kind", 0), "mlp")
     save_reference_checkpoint(path, kind if policy.KIND == 0 else "split", policy.state_dict(), ob_rms)
 

@@ -148,6 +148,8 @@ extern "C" int sg_rollout_act_step_chain(sg_rollout* r, sg_policy* learner, int 
     SG_REQUIRE(inner_action_host, "sg_rollout_act_step_chain: NULL inner_action_host (the in-environment policy's action has nowhere to go)");
     SG_REQUIRE(n_members > 0 && n_members <= SG_ENSEMBLE_MAX, "sg_rollout_act_step_chain: 1..%d members, got %d", SG_ENSEMBLE_MAX, n_members);
     SG_REQUIRE(learner->ctx == r->ctx, "sg_rollout_act_step_chain: the learner and the rollout live on different contexts");
+    SG_REQUIRE(!sg_policy_cnn_rnn(learner), "sg_rollout_act_step_chain: the learner has the recurrent CNN base (sg_policy_create_cnn_rnn); "
+               "the chained step runs the MLP trunks only and carries no hidden state");
     SG_REQUIRE(!learner->cnn, "sg_rollout_act_step_chain: the learner has the CNN base (image observations); the chained step runs the MLP "
                "trunks only");
     SG_REQUIRE(!learner->recurrent, "sg_rollout_act_step_chain: the learner is recurrent (kind SG_POLICY_GRU); the chained step carries no "

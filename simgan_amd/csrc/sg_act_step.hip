@@ -96,6 +96,8 @@ extern "C" int sg_rollout_act_step(sg_rollout* r, sg_policy* p, int t, const flo
                                    int deterministic, float* action_host) {
     SG_REQUIRE(r && p && action_host, "sg_rollout_act_step: NULL argument");
     SG_REQUIRE(p->ctx == r->ctx, "sg_rollout_act_step: the policy and the rollout live on different contexts");
+    SG_REQUIRE(!sg_policy_cnn_rnn(p), "sg_rollout_act_step: the policy has the recurrent CNN base (sg_policy_create_cnn_rnn); the "
+               "one-launch step runs the MLP trunks only: act through sg_policy_act_rnn and upload the step");
     SG_REQUIRE(!p->cnn, "sg_rollout_act_step: the policy has the CNN base (image observations); the one-launch step runs the MLP "
                "trunks only: act through sg_policy_act and upload the step");
     SG_REQUIRE(!p->recurrent, "sg_rollout_act_step: the policy is recurrent (kind SG_POLICY_GRU) and the device rollout holds no hidden "
@@ -287,6 +289,9 @@ extern "C" int sg_rollout_act_step_rnn(sg_rollout* r, sg_policy* p, int t, const
                                        const float* noise, uint64_t seed, int deterministic, float* action_host) {
     SG_REQUIRE(r && p && action_host, "sg_rollout_act_step_rnn: NULL argument");
     SG_REQUIRE(p->ctx == r->ctx, "sg_rollout_act_step_rnn: the policy and the rollout live on different contexts");
+    SG_REQUIRE(!sg_policy_cnn_rnn(p), "sg_rollout_act_step_rnn: the policy has the recurrent CNN base (sg_policy_create_cnn_rnn), "
+               "which the one-launch steps do not serve (an image rollout holds no hidden states on the device): act through "
+               "sg_policy_act_rnn and upload the step");
     SG_REQUIRE(!p->cnn, "sg_rollout_act_step_rnn: the policy has the CNN base (image observations), which is feed-forward and not "
                "served by the one-launch steps: act through sg_policy_act and upload the step");
     SG_REQUIRE(p->recurrent, "sg_rollout_act_step_rnn: the policy is feed-forward (kind %d); act through sg_rollout_act_step",

@@ -12,6 +12,7 @@
 
 #include "sg_common.h"
 #include "sg_cnn_kernels.hpp"
+#include "sg_gru_kernels.hpp"
 
 // per-row floats of the three feature maps
 #define SG_CNN_A1 (32 * 20 * 20)
@@ -55,28 +56,47 @@ size_t sg_cnn_bwd_floats(const SgCnnDesc& c, int n) {
     return (size_t)n * (SG_CNN_A1 + SG_CNN_A2 + SG_CNN_A3 + c.Hs + (c.P + 1) + c.A + 3) + cnn_slab_floats(c, n) + 16;
 }
 
-/* CNNBase on image observations, a2c/model.py:204-230 (chosen by Policy.__init__, a2c/model.py:40-50, for a 3-D obs_shape). */
-extern "C" int sg_policy_create_cnn(sg_ctx* ctx, int channels, int height, int width, int hidden, int dist, int act_dim, int n_out,
-                                    sg_policy** out) {
+// rnn: sg_policy_create_cnn_rnn, the same base with nn.GRU(hidden, hidden) between the FC layer and the heads
+static int cnn_create(const char* who, sg_ctx* ctx, int channels, int height, int width, int hidden, int dist, int act_dim, int n_out,
+                      bool rnn, sg_policy** out) {
     SG_DEVICE_WIDE();
-    SG_REQUIRE(ctx && out, "sg_policy_create_cnn: NULL argument");
-    SG_REQUIRE(height == SG_CNN_HW && width == SG_CNN_HW, "sg_policy_create_cnn: the CNN base takes %d x %d images only (got %d x %d): "
-               "the reference hard-codes Linear(32 * 7 * 7, hidden) behind its three convolutions (a2c/model.py:216)", SG_CNN_HW,
+    SG_REQUIRE(ctx && out, "%s: NULL argument", who);
+    SG_REQUIRE(height == SG_CNN_HW && width == SG_CNN_HW, "%s: the CNN base takes %d x %d images only (got %d x %d): "
+               "the reference hard-codes Linear(32 * 7 * 7, hidden) behind its three convolutions (a2c/model.py:216)", who, SG_CNN_HW,
                SG_CNN_HW, height, width);
-    SG_REQUIRE(channels > 0 && channels <= 4096 && hidden > 0 && hidden <= 65536, "sg_policy_create_cnn: bad dims (channels %d, hidden %d)",
+    SG_REQUIRE(channels > 0 && channels <= 4096 && hidden > 0 && hidden <= 65536, "%s: bad dims (channels %d, hidden %d)", who,
                channels, hidden);
-    SG_REQUIRE(dist == SG_DIST_GAUSSIAN || dist == SG_DIST_CATEGORICAL, "sg_policy_create_cnn: the CNN base is built with the Gaussian "
-               "(Box) and Categorical (Discrete) heads; dist %d (%s) is not", dist, dist == SG_DIST_BERNOULLI ? "Bernoulli / MultiBinary" : "unknown");
-    SG_REQUIRE(act_dim > 0 && act_dim <= 4096, "sg_policy_create_cnn: bad act_dim %d", act_dim);
+    SG_REQUIRE(dist == SG_DIST_GAUSSIAN || dist == SG_DIST_CATEGORICAL, "%s: the CNN base is built with the Gaussian "
+               "(Box) and Categorical (Discrete) heads; dist %d (%s) is not", who, dist, dist == SG_DIST_BERNOULLI ? "Bernoulli / MultiBinary" : "unknown");
+    SG_REQUIRE(act_dim > 0 && act_dim <= 4096, "%s: bad act_dim %d", who, act_dim);
     if (dist == SG_DIST_CATEGORICAL) {
-        SG_REQUIRE(n_out > 0 && n_out <= 4096, "sg_policy_create_cnn: n_out = %d: need 0 < n_out <= 4096", n_out);
-        SG_REQUIRE(act_dim == 1, "sg_policy_create_cnn: act_dim (%d) must be 1 for a Categorical head (an action row is one class index)", act_dim);
+        SG_REQUIRE(n_out > 0 && n_out <= 4096, "%s: n_out = %d: need 0 < n_out <= 4096", who, n_out);
+        SG_REQUIRE(act_dim == 1, "%s: act_dim (%d) must be 1 for a Categorical head (an action row is one class index)", who, act_dim);
+    }
+    const SgCnnDesc cd = make_cnn_desc(channels, hidden, dist, act_dim, n_out);
+    // the GRU block starts on a 16-byte boundary behind the flat block (its images are staged with 128-bit loads)
+    SgGruDesc gd;
+    memset(&gd, 0, sizeof gd);
+    if (rnn) {
+        // before the descriptor is built (its offsets are ints): the reverse scan's two tiles hold at least 16 x 4 Hp floats
+        // (sg_gru_bwd_lds), so a width whose 256 bytes per hidden unit exceed the LDS can never fit
+        SG_REQUIRE((int64_t)256 * hidden <= (int64_t)ctx->lds_bytes, "%s: hidden %d: the GRU's 16-row tiles (at least %lld bytes for the "
+                   "reverse scan's) do not fit the %d-byte LDS of a CU even with the weights read from global memory", who, hidden,
+                   (long long)256 * hidden, ctx->lds_bytes);
+        gd = sg_make_gru_desc(hidden, hidden, (cd.total + 3) & ~3);
+        // the 16-row tiles of the global-weight instances are what has to fit: input projection, both scans, k_gru_dx
+        const size_t need[4] = {sg_gru_proj_lds(gd, 1, true), sg_gru_scan_lds(gd, true), sg_gru_bwd_lds(gd, true), sg_gru_dx_lds(gd, true)};
+        size_t worst = 0;
+        for (size_t v : need) worst = v > worst ? v : worst;
+        SG_REQUIRE(sg_cnn_gru_fits(ctx, gd), "%s: hidden %d: the GRU's 16-row tiles (%zu bytes for the largest: projection %zu, scan %zu, "
+                   "reverse scan %zu, input gradient %zu) do not fit the %d-byte LDS of a CU even with the weights read from global "
+                   "memory", who, hidden, worst, need[0], need[1], need[2], need[3], ctx->lds_bytes);
     }
     SG_CHECK(hipSetDevice(ctx->device));
     sg_policy* p = new sg_policy();
     p->ctx = ctx;
     p->cnn = true;
-    p->cnnd = make_cnn_desc(channels, hidden, dist, act_dim, n_out);
+    p->cnnd = cd;
     // the stand-in the shared code reads: row widths, the head kernels' layout (trunk 0: P outputs, trunk 1: the value) and the
     // log-std's place in the parameter vector
     SgPolicyDesc& d = p->desc;
@@ -85,22 +105,40 @@ extern "C" int sg_policy_create_cnn(sg_ctx* ctx, int channels, int height, int w
     d.n_trunks = 2; d.dist = dist; d.n_out = p->cnnd.P; d.total = p->cnnd.total;
     d.trunk[0].P = p->cnnd.P; d.trunk[0].Pp = SG_PAD16(p->cnnd.P); d.trunk[0].ex = p->cnnd.ls; d.trunk[0].EX = dist == SG_DIST_GAUSSIAN ? act_dim : 0;
     d.trunk[1].P = 1; d.trunk[1].Pp = 16;
-    SG_CHECK(sg_dev_malloc((void**)&p->d_params, sizeof(float) * (size_t)d.total));
-    SG_CHECK(hipMemsetAsync(p->d_params, 0, sizeof(float) * (size_t)d.total, ctx->stream));
+    if (rnn) {
+        p->recurrent = true;
+        p->gru = gd;
+    }
+    const size_t total = sg_policy_padded_count(p);
+    SG_CHECK(sg_dev_malloc((void**)&p->d_params, sizeof(float) * total));
+    SG_CHECK(hipMemsetAsync(p->d_params, 0, sizeof(float) * total, ctx->stream));
     *out = p;
     return 0;
 }
 
+/* CNNBase on image observations, a2c/model.py:204-230 (chosen by Policy.__init__, a2c/model.py:40-50, for a 3-D obs_shape). */
+extern "C" int sg_policy_create_cnn(sg_ctx* ctx, int channels, int height, int width, int hidden, int dist, int act_dim, int n_out,
+                                    sg_policy** out) {
+    return cnn_create("sg_policy_create_cnn", ctx, channels, height, width, hidden, dist, act_dim, n_out, false, out);
+}
+
+/* CNNBase(recurrent=True), a2c/model.py:117-230: the same trunk, nn.GRU(hidden, hidden) on its features (NNBase.__init__ creates it
+   before `main`, so its four tensors come first in the flat order), critic_linear and the distribution's Linear on the GRU state.
+   An entry point of its own: sg_policy_create_cnn is unchanged. */
+extern "C" int sg_policy_create_cnn_rnn(sg_ctx* ctx, int channels, int height, int width, int hidden, int dist, int act_dim, int n_out,
+                                        sg_policy** out) {
+    return cnn_create("sg_policy_create_cnn_rnn", ctx, channels, height, width, hidden, dist, act_dim, n_out, true, out);
+}
+
 static dim3 cnn_grid(int64_t rows, int cols) { return dim3((unsigned)((rows + 63) / 64), (unsigned)((cols + 31) / 32)); }
 
-int sg_cnn_forward_launch(sg_ctx* ctx, const sg_policy* p, const float* d_obs, const int64_t* d_idx, int n, float* act,
-                          float* heads, int hld, int row0, int n_total) {
+int sg_cnn_trunk_forward_launch(sg_ctx* ctx, const sg_policy* p, const float* d_obs, const int64_t* d_idx, int n, float* act, float* F_out) {
     const SgCnnDesc& c = p->cnnd;
     const float* W = p->d_params;
     float* A1 = act;
     float* A2 = A1 + (size_t)n * SG_CNN_A1;
     float* A3 = A2 + (size_t)n * SG_CNN_A2;
-    float* F = A3 + (size_t)n * SG_CNN_A3;
+    float* F = F_out ? F_out : A3 + (size_t)n * SG_CNN_A3;
     CnnConvArgs a;
     memset(&a, 0, sizeof a);
     a.n_img = n;
@@ -116,11 +154,23 @@ int sg_cnn_forward_launch(sg_ctx* ctx, const sg_policy* p, const float* d_obs, c
     a.in = A3; a.w = W + c.wf; a.bias = W + c.bf; a.out = F;
     a.Ci = 32; a.Co = c.Hs; a.IH = a.IW = 7; a.OH = a.OW = 1;
     hipLaunchKernelGGL((k_cnn_conv_fwd<7, 7, 1>), cnn_grid(n, c.Hs), dim3(256), 0, ctx->stream, a);
+    SG_CHECK(hipGetLastError());
+    return 0;
+}
+
+int sg_cnn_head_forward_launch(sg_ctx* ctx, const sg_policy* p, const float* feat, int n, float* heads, int hld, int row0, int n_total) {
+    const SgCnnDesc& c = p->cnnd;
     CnnHeadArgs h;
-    h.d = c; h.params = W; h.feat = F; h.n = n; h.row0 = row0; h.n_total = n_total; h.heads = heads; h.hld = hld;
+    h.d = c; h.params = p->d_params; h.feat = feat; h.n = n; h.row0 = row0; h.n_total = n_total; h.heads = heads; h.hld = hld;
     hipLaunchKernelGGL(k_cnn_head_fwd, dim3((unsigned)(((int64_t)n * (c.P + 1) + 255) / 256)), dim3(256), 0, ctx->stream, h);
     SG_CHECK(hipGetLastError());
     return 0;
+}
+
+int sg_cnn_forward_launch(sg_ctx* ctx, const sg_policy* p, const float* d_obs, const int64_t* d_idx, int n, float* act,
+                          float* heads, int hld, int row0, int n_total) {
+    SG_TRY(sg_cnn_trunk_forward_launch(ctx, p, d_obs, d_idx, n, act, nullptr));
+    return sg_cnn_head_forward_launch(ctx, p, act + (size_t)n * (SG_CNN_A1 + SG_CNN_A2 + SG_CNN_A3), n, heads, hld, row0, n_total);
 }
 
 template <typename KernelT>
@@ -141,19 +191,11 @@ int sg_cnn_backward_launch(sg_ctx* ctx, const sg_policy* p, const sg_rollout* r,
                            float vcoef, float ecoef, int use_clipped, int a2c, int acc, int64_t row0) {
     const SgCnnDesc& c = p->cnnd;
     const float* W = p->d_params;
-    const float* A1 = act;
-    const float* A2 = A1 + (size_t)n * SG_CNN_A1;
-    const float* A3 = A2 + (size_t)n * SG_CNN_A2;
-    const float* F = A3 + (size_t)n * SG_CNN_A3;
-    float* dZ1 = bwd;
-    float* dZ2 = dZ1 + (size_t)n * SG_CNN_A1;
-    float* dZ3 = dZ2 + (size_t)n * SG_CNN_A2;
-    float* dZf = dZ3 + (size_t)n * SG_CNN_A3;
+    const float* F = act + (size_t)n * (SG_CNN_A1 + SG_CNN_A2 + SG_CNN_A3);
+    float* dZf = bwd + (size_t)n * (SG_CNN_A1 + SG_CNN_A2 + SG_CNN_A3);
     float* dout = dZf + (size_t)n * c.Hs;
     float* dls = dout + (size_t)n * (c.P + 1);
     float* rowl = dls + (size_t)n * c.A;
-    float* slabs = rowl + 3 * (size_t)n;
-    slabs += (4 - ((slabs - bwd) & 3)) & 3;
 
     CnnLossArgs l;
     l.d = c; l.params = W; l.heads = heads; l.hld = hld; l.n = n; l.idx = d_idx; l.row0 = row0;
@@ -169,6 +211,22 @@ int sg_cnn_backward_launch(sg_ctx* ctx, const sg_policy* p, const sg_rollout* r,
     hipLaunchKernelGGL(k_cnn_head_dfeat, dim3((unsigned)(((int64_t)n * c.Hs + 255) / 256)), dim3(256), 0, ctx->stream, hb);
     const int n_head = (c.P + 1) * (c.Hs + 1) + c.A;
     hipLaunchKernelGGL(k_cnn_head_wgrad, dim3((unsigned)((n_head + 255) / 256)), dim3(256), 0, ctx->stream, hb);
+    return sg_cnn_trunk_backward_launch(ctx, p, d_obs, d_idx, n, act, bwd, grad, acc);
+}
+
+int sg_cnn_trunk_backward_launch(sg_ctx* ctx, const sg_policy* p, const float* d_obs, const int64_t* d_idx, int n, const float* act,
+                                 float* bwd, float* grad, int acc) {
+    const SgCnnDesc& c = p->cnnd;
+    const float* W = p->d_params;
+    const float* A1 = act;
+    const float* A2 = A1 + (size_t)n * SG_CNN_A1;
+    const float* A3 = A2 + (size_t)n * SG_CNN_A2;
+    float* dZ1 = bwd;
+    float* dZ2 = dZ1 + (size_t)n * SG_CNN_A1;
+    float* dZ3 = dZ2 + (size_t)n * SG_CNN_A2;
+    float* dZf = dZ3 + (size_t)n * SG_CNN_A3;
+    float* slabs = dZf + (size_t)n * (c.Hs + (c.P + 1) + c.A + 3);
+    slabs += (4 - ((slabs - bwd) & 3)) & 3;
 
     // FC: weight gradient on A3, data gradient dZf x Wf (a 1x1 "convolution" with the weight read transposed), conv3's mask
     cnn_wgrad_layer(ctx, k_cnn_wgrad<7, 7, 1, 1>, dZf, A3, nullptr, n, 1, 32, c.Hs, 49, 0, slabs, grad + c.wf, grad + c.bf, acc);
@@ -193,6 +251,71 @@ int sg_cnn_backward_launch(sg_ctx* ctx, const sg_policy* p, const sg_rollout* r,
     hipLaunchKernelGGL((k_cnn_conv_bwd_data<4, 4, 2>), cnn_grid((int64_t)n * 400, 32), dim3(256), 0, ctx->stream, a);
     // conv1 (no data gradient: the observation is a leaf)
     cnn_wgrad_layer(ctx, k_cnn_wgrad<8, 8, 4, 20>, dZ1, d_obs, d_idx, n, 400, c.C, 32, 64, 1, slabs, grad + c.w1, grad + c.b1, acc);
+    SG_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------- the recurrent CNN base
+// sg_policy.hip: value / action / log-prob / entropy of n rows from head stacks [2][n][hld] (k_gauss_head / k_discrete_head)
+int sg_policy_heads_device(sg_policy* p, const float* d_heads, int hld, int n, int mode, const float* d_noise, uint64_t seed,
+                           const float* d_action_in, float* d_value, float* d_action, float* d_logp, float* d_ent);
+int sg_policy_heads_ld(const SgPolicyDesc& d);
+
+// CNNBase.forward with recurrent=True (a2c/model.py:224-230): x = main(inputs / 255); x, rnn_hxs = _forward_gru(x, rnn_hxs, masks);
+// critic_linear(x), then the distribution on x.  The trunk runs in SG_CNN_FWD_ROWS-row passes into one feature matrix, the input
+// projection and the scan over all T*n rows, the heads on h_t.  A row's trunk, GI and state have the same bits in a one-step
+// call and inside a sequence (every output element is one fixed MFMA chain).
+int sg_cnn_gru_forward_device(sg_policy* p, const float* d_obs, const float* d_h0, const float* d_masks, int T, int n, int mode,
+                              const float* d_noise, uint64_t seed, const float* d_action_in, float* d_value, float* d_action,
+                              float* d_logp, float* d_ent, float* d_hlast) {
+    sg_ctx* ctx = p->ctx;
+    const SgCnnDesc& c = p->cnnd;
+    const SgGruDesc& g = p->gru;
+    const int rows = T * n;
+    const int hld = sg_policy_heads_ld(p->desc);
+    const int chunk = rows < SG_CNN_FWD_ROWS ? rows : SG_CNN_FWD_ROWS;
+    auto r4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    const size_t f_heads = r4(2 * (size_t)rows * hld), f_feat = r4((size_t)rows * c.Hs), f_gi = r4((size_t)rows * 3 * g.Hp);
+    float* scratch = nullptr;
+    SG_TRY(sg_ctx_scratch(ctx, sizeof(float) * (f_heads + 2 * f_feat + f_gi + sg_cnn_fwd_floats(c, chunk)), &scratch));
+    float* heads = scratch;
+    float* F = heads + f_heads;
+    float* hout = F + f_feat;
+    float* gi = hout + f_feat;
+    float* act = gi + f_gi;
+    for (int r0 = 0; r0 < rows; r0 += chunk)
+        SG_TRY(sg_cnn_trunk_forward_launch(ctx, p, d_obs + (size_t)r0 * p->desc.O, nullptr, rows - r0 < chunk ? rows - r0 : chunk, act,
+                                           F + (size_t)r0 * c.Hs));
+    SG_TRY(sg_gru_forward_launch(ctx, g, p->d_params + g.off, F, c.Hs, d_h0, d_masks, T, n, gi, hout, c.Hs, d_hlast, nullptr));
+    SG_TRY(sg_cnn_head_forward_launch(ctx, p, hout, rows, heads, hld, 0, rows));
+    return sg_policy_heads_device(p, heads, hld, rows, mode, d_noise, seed, d_action_in, d_value, d_action, d_logp, d_ent);
+}
+
+int sg_cnn_gru_heads_launch(sg_ctx* ctx, const sg_policy* p, const sg_rollout* r, const int64_t* d_idx, int n, const float* hstate,
+                            float* heads, int hld, float* bwd, float* grad, float* dxa, float* dxc, int dx_ld, float inv_B, float clip,
+                            float vcoef, float ecoef, int use_clipped) {
+    const SgCnnDesc& c = p->cnnd;
+    const float* W = p->d_params;
+    float* dZf = bwd + (size_t)n * (SG_CNN_A1 + SG_CNN_A2 + SG_CNN_A3);
+    float* dout = dZf + (size_t)n * c.Hs;
+    float* dls = dout + (size_t)n * (c.P + 1);
+    float* rowl = dls + (size_t)n * c.A;
+    SG_TRY(sg_cnn_head_forward_launch(ctx, p, hstate, n, heads, hld, 0, n));
+    CnnLossArgs l;
+    l.d = c; l.params = W; l.heads = heads; l.hld = hld; l.n = n; l.idx = d_idx; l.row0 = 0;
+    l.actions = r->d_field[SG_F_ACTIONS]; l.old_logp = r->d_field[SG_F_LOGP]; l.adv = r->d_field[SG_F_ADVANTAGES];
+    l.vpred = r->d_field[SG_F_VALUE_PREDS]; l.ret = r->d_field[SG_F_RETURNS];
+    l.inv_B = inv_B; l.clip = clip; l.vcoef = vcoef; l.ecoef = ecoef; l.use_clipped = use_clipped;
+    l.dout = dout; l.dls = dls; l.rowl = rowl;
+    hipLaunchKernelGGL(k_cnn_head_loss, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, l);
+    CnnHeadDhArgs dh;
+    dh.d = c; dh.params = W; dh.dout = dout; dh.n = n; dh.ld = dx_ld; dh.dxa = dxa; dh.dxc = dxc;
+    hipLaunchKernelGGL(k_cnn_head_dh, dim3((unsigned)(((int64_t)n * dx_ld + 255) / 256)), dim3(256), 0, ctx->stream, dh);
+    CnnHeadBwdArgs hb;
+    hb.d = c; hb.params = W; hb.feat = hstate; hb.dout = dout; hb.dls = dls; hb.rowl = rowl; hb.n = n; hb.acc = 0; hb.dzf = nullptr; hb.grad = grad;
+    hb.d.total = p->gru.off;   // the three loss sums go where k_gru_reduce picks them up: behind the flat block's padding
+    const int n_head = (c.P + 1) * (c.Hs + 1) + c.A;
+    hipLaunchKernelGGL(k_cnn_head_wgrad, dim3((unsigned)((n_head + 255) / 256)), dim3(256), 0, ctx->stream, hb);
     SG_CHECK(hipGetLastError());
     return 0;
 }

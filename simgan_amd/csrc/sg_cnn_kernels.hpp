@@ -394,6 +394,32 @@ __global__ __launch_bounds__(256) void k_cnn_head_dfeat(CnnHeadBwdArgs a) {
     a.dzf[i] = a.feat[i] > 0.f ? g : 0.f;
 }
 
+// The recurrent CNN base: the heads read the GRU state h_t, which is no ReLU output, so d loss / d h_t carries no mask.  Written as
+// the two [n][ld] tiles k_gru_scan_bwd adds (dxa: through the distribution's Linear, dxc: through critic_linear), the padding
+// columns Hs .. ld-1 as zero so that the padded hidden units' gate gradients stay zero.
+struct CnnHeadDhArgs {
+    SgCnnDesc d;
+    const float* params;
+    const float* dout;    // [n][1 + P]
+    int n, ld;
+    float *dxa, *dxc;     // [n][ld]
+};
+
+__global__ __launch_bounds__(256) void k_cnn_head_dh(CnnHeadDhArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const SgCnnDesc& d = a.d;
+    if (i >= a.n * a.ld) return;
+    const int row = i / a.ld, h = i - row * a.ld;
+    float ga = 0.f, gc = 0.f;
+    if (h < d.Hs) {
+        const float* dout = a.dout + (size_t)row * (d.P + 1);
+        gc = dout[0] * a.params[d.wc + h];
+        for (int j = 0; j < d.P; ++j) ga += dout[1 + j] * a.params[d.wd + (size_t)j * d.Hs + h];
+    }
+    a.dxa[i] = ga;
+    a.dxc[i] = gc;
+}
+
 // gradients of critic_linear, the distribution's Linear and the log-std: one thread per parameter, rows in ascending order;
 // block 0 also leaves the three loss sums behind the gradient (k_ppo_adam's convention).  acc: every element, the loss sums
 // too, starts from what grad already holds

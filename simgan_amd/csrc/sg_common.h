@@ -258,7 +258,11 @@ struct sg_policy {
     size_t io_bytes = 0;
     bool cnn = false;            // sg_policy_create_cnn: desc is then a stand-in (kind MLP, O = C*84*84) that carries the dims the
     SgCnnDesc cnnd;              // shared entry points check and the layout the head kernels read; the network is cnnd's
+    // cnn && recurrent (sg_policy_create_cnn_rnn, a2c/model.py:204-230 with recurrent=True): the CNN trunk, nn.GRU(Hs, Hs) on its
+    // features, critic_linear and the distribution's Linear on the GRU state.  d_params = the CNN's flat block | (up to 3 floats of
+    // zero padding) | the GRU's padded tile block at gru.off; the flat order has the four GRU tensors FIRST
 };
+static inline bool sg_policy_cnn_rnn(const sg_policy* p) { return p->cnn && p->recurrent; }
 
 #define SG_CNN_FWD_ROWS 128   // rows per pass of the CNN base's inference forward (78 KB of activations per row)
 // sg_cnn.hip: the CNN base's launches, enqueued on ctx->stream
@@ -273,6 +277,27 @@ int sg_cnn_forward_launch(sg_ctx* ctx, const sg_policy* p, const float* d_obs, c
 int sg_cnn_backward_launch(sg_ctx* ctx, const sg_policy* p, const struct sg_rollout* r, const float* d_obs, const int64_t* d_idx,
                            int n, const float* act, const float* heads, int hld, float* bwd, float* grad, float inv_B, float clip,
                            float vcoef, float ecoef, int use_clipped, int a2c, int acc, int64_t row0);
+
+// The trunk alone (conv1-3 and the FC layer) into the activation stacks; F_out != NULL: the features [n][Hs] go there instead of
+// the stacks' own F (the recurrent CNN base collects every pass's rows in one matrix).  Then the heads on any [n][Hs] matrix.
+int sg_cnn_trunk_forward_launch(sg_ctx* ctx, const sg_policy* p, const float* d_obs, const int64_t* d_idx, int n, float* act, float* F_out);
+int sg_cnn_head_forward_launch(sg_ctx* ctx, const sg_policy* p, const float* feat, int n, float* heads, int hld, int row0, int n_total);
+// The backward from dZf (the gradient at the FC layer's pre-activation, in the stacks of sg_cnn_backward_launch) down to conv1
+int sg_cnn_trunk_backward_launch(sg_ctx* ctx, const sg_policy* p, const float* d_obs, const int64_t* d_idx, int n, const float* act,
+                                 float* bwd, float* grad, int acc);
+// sg_cnn.hip: forward of the recurrent CNN base on device inputs (obs [T*n][C*7056] time-major, hxs [n][Hs], masks [T*n]): the
+// trunk in SG_CNN_FWD_ROWS-row passes, the GRU over all rows, the heads on its state, then k_gauss_head / k_discrete_head
+int sg_cnn_gru_forward_device(sg_policy* p, const float* d_obs, const float* d_h0, const float* d_masks, int T, int n, int mode,
+                              const float* d_noise, uint64_t seed, const float* d_action_in, float* d_value, float* d_action,
+                              float* d_logp, float* d_ent, float* d_hlast);
+// sg_cnn.hip: the heads of the recurrent CNN base on the GRU state hstate [n][Hs] (PPO through time, sg_ppo.hip): the head
+// forward into heads [2][n][hld], k_cnn_head_loss on the rollout rows d_idx, d loss / d h_t WITHOUT the FC layer's ReLU mask as
+// the two tiles the reverse scan adds (dxa: through the distribution's Linear, dxc: through critic_linear; [..][dx_ld], padding
+// columns written as zero), and the heads' weight gradients into grad with the three loss sums at grad[gru.off ..]
+int sg_cnn_gru_heads_launch(sg_ctx* ctx, const sg_policy* p, const struct sg_rollout* r, const int64_t* d_idx, int n, const float* hstate,
+                            float* heads, int hld, float* bwd, float* grad, float* dxa, float* dxc, int dx_ld, float inv_B, float clip,
+                            float vcoef, float ecoef, int use_clipped);
+bool sg_cnn_gru_fits(const sg_ctx* ctx, const SgGruDesc& g);   // sg_gru.hip: every GRU tile of the recurrent CNN base fits a CU's LDS
 
 size_t sg_policy_padded_count(const sg_policy* p);          // floats of d_params (heads + GRU block)
 // sg_policy.hip: the one way p->d_io grows.  Nothing while io_bytes >= bytes; otherwise the stream is drained (queued work may
@@ -335,7 +360,7 @@ struct SgGraphCache {
 // The scratch layout an sg_ppo's buffers were last cleared for: padding columns / rows that the kernels never write must
 // read as zero, which holds for as long as the layout is the same.  Compared whole.  SG_LAYOUT_INVALID: clear before the next
 // update whatever its layout (after a reallocation, after sg_ppo_set_adam).
-enum { SG_LAYOUT_INVALID = 0, SG_LAYOUT_PPO, SG_LAYOUT_A2C, SG_LAYOUT_GRU, SG_LAYOUT_A2C_GRU };
+enum { SG_LAYOUT_INVALID = 0, SG_LAYOUT_PPO, SG_LAYOUT_A2C, SG_LAYOUT_GRU, SG_LAYOUT_A2C_GRU, SG_LAYOUT_CNN_GRU };
 struct SgScratchLayout {
     int64_t mode = SG_LAYOUT_INVALID;
     int64_t dims[8] = {0};

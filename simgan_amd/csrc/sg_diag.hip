@@ -253,6 +253,8 @@ static int policy_diagnostics(const char* who, bool world_scope, sg_rollout* r, 
                               double* out10) {
     SG_REQUIRE(r && p, "%s: NULL argument", who);
     SG_REQUIRE(p->ctx == r->ctx, "%s: the policy and the rollout live on different contexts", who);
+    SG_REQUIRE(!sg_policy_cnn_rnn(p), "%s: the policy has the recurrent CNN base (sg_policy_create_cnn_rnn); the diagnostics launch "
+               "runs the MLP trunks only: evaluate the rollout through sg_policy_evaluate_rnn and reduce on the host", who);
     SG_REQUIRE(!p->cnn, "%s: the policy has the CNN base (image observations); the diagnostics launch runs "
                "the MLP trunks only: evaluate the rollout through sg_policy_evaluate and reduce on the host", who);
     const int O = p->recurrent ? p->gru.O : p->desc.O;

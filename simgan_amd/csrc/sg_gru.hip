@@ -73,6 +73,11 @@ bool sg_gru_fits(const sg_ctx* ctx, const SgGruDesc& g) {
            sg_gru_bwd_lds(g, true) <= (size_t)ctx->lds_bytes - 1024;
 }
 
+// the recurrent CNN base: the same three, and k_gru_dx's gate-gradient tile
+bool sg_cnn_gru_fits(const sg_ctx* ctx, const SgGruDesc& g) {
+    return sg_gru_fits(ctx, g) && sg_gru_dx_lds(g, true) <= (size_t)ctx->lds_bytes - 1024;
+}
+
 // GRU over a [T*n, O] time-major sequence (T == 1: one step) -> d_hout [T*n, H], d_hlast [n, H]; d_gi is [T*n][3*Hp] scratch.
 static int gru_forward_dev(sg_policy* p, const float* d_x, const float* d_h0, const float* d_masks, int T, int n, float* d_gi,
                            float* d_hout, float* d_hlast) {
@@ -89,13 +94,16 @@ static int gru_host_call(sg_policy* p, const char* who, const float* obs, const 
                who, p->desc.kind);
     SG_REQUIRE(T > 0 && n > 0 && (int64_t)T * n < (1ll << 30), "%s: T and n must be positive (got %d, %d)", who, T, n);
     const SgGruDesc& g = p->gru;
-    const int O = g.O, H = g.H, A = p->desc.A;
+    // the recurrent CNN base (sg_cnn.hip): an observation row is the C*84*84-float image; its features, GI and h_t live in the
+    // context's scratch, not in this staging block
+    const bool cnn = sg_policy_cnn_rnn(p);
+    const int O = cnn ? p->desc.O : g.O, H = g.H, A = p->desc.A;
     const size_t rows = (size_t)T * n;
     auto r4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
     SG_CHECK(hipSetDevice(ctx->device));
     // device staging: obs | noise/action_in | action | value | logp | ent | hxs | masks | GI | h_t | h_last
     const size_t f_obs = r4(rows * O), f_na = r4(rows * A), f_row = r4(rows), f_h = r4((size_t)n * H);
-    const size_t f_gi = r4(rows * 3 * g.Hp), f_hout = r4(rows * H);
+    const size_t f_gi = cnn ? 0 : r4(rows * 3 * g.Hp), f_hout = cnn ? 0 : r4(rows * H);
     const size_t need = sizeof(float) * (f_obs + 2 * f_na + 4 * f_row + 2 * f_h + f_gi + f_hout);
     SG_TRY(sg_policy_io_reserve(p, need));
     float* d_obs = p->d_io;
@@ -114,9 +122,14 @@ static int gru_host_call(sg_policy* p, const char* who, const float* obs, const 
     SG_CHECK(hipMemcpyAsync(d_masks, masks, sizeof(float) * rows, hipMemcpyHostToDevice, ctx->stream));
     const float* src_in = mode == 2 ? action_in : noise;
     if (src_in) SG_CHECK(hipMemcpyAsync(d_in, src_in, sizeof(float) * rows * A, hipMemcpyHostToDevice, ctx->stream));
-    SG_TRY(gru_forward_dev(p, d_obs, d_h0, d_masks, T, n, d_gi, d_hout, d_hlast));
-    SG_TRY(sg_policy_forward_device(p, d_hout, (int)rows, mode, (mode == 0 && noise) ? d_in : nullptr, seed,
-                                    mode == 2 ? d_in : nullptr, d_value, d_action, d_logp, d_ent));
+    if (cnn) {
+        SG_TRY(sg_cnn_gru_forward_device(p, d_obs, d_h0, d_masks, T, n, mode, (mode == 0 && noise) ? d_in : nullptr, seed,
+                                         mode == 2 ? d_in : nullptr, d_value, d_action, d_logp, d_ent, d_hlast));
+    } else {
+        SG_TRY(gru_forward_dev(p, d_obs, d_h0, d_masks, T, n, d_gi, d_hout, d_hlast));
+        SG_TRY(sg_policy_forward_device(p, d_hout, (int)rows, mode, (mode == 0 && noise) ? d_in : nullptr, seed,
+                                        mode == 2 ? d_in : nullptr, d_value, d_action, d_logp, d_ent));
+    }
     if (value) SG_CHECK(hipMemcpyAsync(value, d_value, sizeof(float) * rows, hipMemcpyDeviceToHost, ctx->stream));
     if (action) SG_CHECK(hipMemcpyAsync(action, d_action, sizeof(float) * rows * A, hipMemcpyDeviceToHost, ctx->stream));
     if (logp) SG_CHECK(hipMemcpyAsync(logp, d_logp, sizeof(float) * rows, hipMemcpyDeviceToHost, ctx->stream));

@@ -13,6 +13,8 @@
 //                      over row ranges into partial blocks;  k_gru_reduce adds the partials in a fixed order
 //   k_a2c_gru_gather   A2C through time: a group of environments in the rollout's own order, time-major;  k_gru_reduce_acc adds the
 //                      groups' GRU gradients in group order and finishes them after the last
+//   k_gru_dx           the recurrent CNN base (sg_cnn.hip, sg_ppo.hip: cnn_gru_ppo_update): dZf = (dGI W_ih) [F > 0], the gradient the
+//                      CNN trunk's backward continues from;  k_cnn_gru_index, k_gru_pad_rows: its step's index vector and padded x
 // No floating-point atomics anywhere: every sum has one order, two runs give the same bits.
 #pragma once
 #include "sg_common.h"
@@ -377,6 +379,87 @@ __global__ __launch_bounds__(256) void k_gru_epoch_gather(GruGatherArgs a) {
         for (int c = threadIdx.x; c < a.H; c += blockDim.x) a.H0[(size_t)(k * a.per + j) * a.H + c] = a.h0[(size_t)env * a.H + c];
 }
 
+// --------------------------------------------------------- the recurrent CNN base (a2c/model.py:204-230 with recurrent=True)
+// The GRU reads the FC layer's features F = relu(Zf), so the gradient that the CNN trunk's backward continues from is
+//   dZf[row][k] = (sum_{j < 3 Hp} dGI[row][j] W_ih[j][k]) * [F[row][k] > 0]      (ReLU's derivative at exactly 0 is 0, as in torch)
+// Row-parallel over the step's rows, a persistent grid: a workgroup stages W_ih once (GW: reads it through L2) and walks 16-row
+// tiles; per tile the dGI rows go to LDS and every wave forms whole 16x16 output tiles as one MFMA chain over K = 3 Hp in
+// ascending k -- one order whatever the grid is, no atomics.
+struct GruDxArgs {
+    SgGruDesc g;
+    const float* W;      // the GRU block
+    const float* dgi;    // [rows..][3*Hp]
+    const float* f;      // [rows][f_ld]: the features the GRU read (post-ReLU)
+    int f_ld;
+    int rows;
+    float* dzf;          // [rows][dz_ld], columns < g.O written
+    int dz_ld;
+    int wbuf_floats;     // LDS floats of the W_ih image (0: GW)
+};
+
+template <bool GW>
+__global__ __launch_bounds__(256) void k_gru_dx(GruDxArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const SgGruDesc& g = a.g;
+    const int G3 = 3 * g.Hp, ld3 = G3 + 4;
+    const float* W = GW ? a.W + g.wih : smem;
+    float* DG = smem + a.wbuf_floats;    // [16][ld3]
+    if (!GW) sg_stage(smem, a.W + g.wih, (3 * g.Hp * g.ldO) / 4);
+    for (int base = blockIdx.x * 16; base < a.rows; base += gridDim.x * 16) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < 16 * (G3 / 4); i += blockDim.x) {
+            const int r = i / (G3 / 4), c4 = i - r * (G3 / 4);
+            const int row = base + r;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (row < a.rows) v = *reinterpret_cast<const float4*>(a.dgi + (size_t)row * G3 + 4 * c4);
+            *reinterpret_cast<float4*>(DG + r * ld3 + 4 * c4) = v;
+        }
+        __syncthreads();
+        sg_layer_nn_u<1>(DG, ld3, W, g.ldO, G3, g.Op, [&](int r, int c, float v) {
+            const int row = base + r;
+            if (row < a.rows && c < g.O) a.dzf[(size_t)row * a.dz_ld + c] = a.f[(size_t)row * a.f_ld + c] > 0.f ? v : 0.f;
+        });
+    }
+}
+
+// One optimizer step's rows of PPO through time on the image rollout (a2c/storage.py:194-251): step row rr = t * per + j is
+// rollout row t * N + perm[j].  The index vector (the 28 K-float frames and the per-row scalars are read in place through
+// it), the masks time-major, and the hidden state of slot 0 per environment.
+struct CnnGruIndexArgs {
+    const int64_t* perm;   // [per] environments of this step
+    const float *masks, *h0;
+    int T, N, per, H;
+    int64_t* idx;          // [T*per]
+    float *MK, *H0;        // [T*per], [per][H]
+};
+
+template <int DUMMY = 0>
+__global__ __launch_bounds__(256) void k_cnn_gru_index(CnnGruIndexArgs a) {
+    const int rr = blockIdx.x * blockDim.x + threadIdx.x;
+    if (rr < a.T * a.per) {
+        const int t = rr / a.per, j = rr - t * a.per;
+        const int64_t src = (int64_t)t * a.N + a.perm[j];
+        a.idx[rr] = src;
+        a.MK[rr] = a.masks[src];
+    }
+    for (int i = rr; i < a.per * a.H; i += gridDim.x * blockDim.x) {
+        const int j = i / a.H, c = i - j * a.H;
+        a.H0[i] = a.h0[(size_t)a.perm[j] * a.H + c];
+    }
+}
+
+// compact rows [rows][w] -> padded rows [rows][ld] (zero in columns w .. ld-1): the features as k_gru_wgrad's x operand
+template <int DUMMY = 0>
+__global__ __launch_bounds__(256) void k_gru_pad_rows(const float* src, int rows, int w, float* dst, int ld) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)rows * ld) return;
+    const int r = (int)(i / ld), c = (int)(i - (int64_t)r * ld);
+    dst[i] = c < w ? src[(size_t)r * w + c] : 0.f;
+}
+
+static inline size_t sg_gru_dx_lds(const SgGruDesc& g, bool gw) {
+    return sizeof(float) * (size_t)((gw ? 0 : 3 * g.Hp * g.ldO) + 16 * (3 * g.Hp + 4));
+}
 static inline size_t sg_gru_proj_lds(const SgGruDesc& g, int MT, bool gw) {
     return sizeof(float) * (size_t)((gw ? 0 : 3 * g.Hp * g.ldO) + 16 * MT * g.ldO);
 }

@@ -197,6 +197,21 @@ int sg_policy_heads_ld(const SgPolicyDesc& d) {
     return m;
 }
 
+// value / action / log-prob / entropy of n rows from the head stacks [n_trunks][n][hld] (also the last launch of the recurrent
+// CNN base's forward, sg_cnn.hip)
+int sg_policy_heads_device(sg_policy* p, const float* d_heads, int hld, int n, int mode, const float* d_noise, uint64_t seed,
+                           const float* d_action_in, float* d_value, float* d_action, float* d_logp, float* d_ent) {
+    sg_ctx* ctx = p->ctx;
+    HeadArgs h;
+    h.d = p->desc; h.params = p->d_params; h.heads = d_heads; h.hld = hld; h.n = n; h.mode = mode;
+    h.noise = d_noise; h.seed = seed; h.stream = SG_ACT_STREAM + (uint64_t)ctx->rank; h.action_in = d_action_in;
+    h.value = d_value; h.action = d_action; h.logp = d_logp; h.ent = d_ent;
+    if (p->desc.dist == SG_DIST_GAUSSIAN) hipLaunchKernelGGL(k_gauss_head, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, h);
+    else hipLaunchKernelGGL(k_discrete_head, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, h);
+    SG_CHECK(hipGetLastError());
+    return 0;
+}
+
 // Device-side entry used by the rollout code (compute_returns_policy, synthetic fill).
 int sg_policy_forward_device(sg_policy* p, const float* d_obs, int n, int mode, const float* d_noise,
                              uint64_t seed, const float* d_action_in, float* d_value, float* d_action,
@@ -218,14 +233,7 @@ int sg_policy_forward_device(sg_policy* p, const float* d_obs, int n, int mode, 
         SG_TRY(sg_ctx_scratch(ctx, heads_bytes, &scratch));
         SG_TRY(policy_forward_dev(p, d_obs, nullptr, n, scratch, hld));
     }
-    HeadArgs h;
-    h.d = p->desc; h.params = p->d_params; h.heads = scratch; h.hld = hld; h.n = n; h.mode = mode;
-    h.noise = d_noise; h.seed = seed; h.stream = SG_ACT_STREAM + (uint64_t)ctx->rank; h.action_in = d_action_in;
-    h.value = d_value; h.action = d_action; h.logp = d_logp; h.ent = d_ent;
-    if (p->desc.dist == SG_DIST_GAUSSIAN) hipLaunchKernelGGL(k_gauss_head, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, h);
-    else hipLaunchKernelGGL(k_discrete_head, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, h);
-    SG_CHECK(hipGetLastError());
-    return 0;
+    return sg_policy_heads_device(p, scratch, hld, n, mode, d_noise, seed, d_action_in, d_value, d_action, d_logp, d_ent);
 }
 
 // ------------------------------------------------------------------------------ policy API
@@ -319,10 +327,11 @@ extern "C" int sg_policy_destroy(sg_policy* p) {
 // flat (state_dict) and padded (device) sizes of the whole policy: a recurrent one carries its GRU's four tensors FIRST in the
 // flat order (base.gru.* precede base.actor.*, a2c/model.py:124-131,240-251) and BEHIND the heads' block on the device
 static int64_t policy_flat_total(const sg_policy* p) {
-    if (p->cnn) return p->cnnd.total;   // the CNN base keeps the flat order on the device
+    if (p->cnn) return p->cnnd.total + (p->recurrent ? sg_gru_flat_count(p->gru) : 0);   // the CNN base keeps the flat order on the device
     return sg_policy_flat_count(p->desc) + (p->recurrent ? sg_gru_flat_count(p->gru) : 0);
 }
 size_t sg_policy_padded_count(const sg_policy* p) {
+    if (sg_policy_cnn_rnn(p)) return (size_t)p->gru.off + (size_t)p->gru.total;   // flat CNN block | padding to 16 bytes | GRU block
     return (size_t)p->desc.total + (p->recurrent ? (size_t)p->gru.total : 0);
 }
 
@@ -336,6 +345,15 @@ extern "C" int sg_policy_set_params(sg_policy* p, const float* flat, int64_t n) 
     SG_REQUIRE(p && flat, "sg_policy_set_params: NULL argument");
     SG_REQUIRE(n == policy_flat_total(p), "sg_policy_set_params: expected %lld floats, got %lld",
                (long long)policy_flat_total(p), (long long)n);
+    if (sg_policy_cnn_rnn(p)) {   // flat: the GRU's four tensors, then the CNN base's state_dict order; device: the other way round
+        std::vector<float> dev(sg_policy_padded_count(p), 0.f);
+        const int64_t n_gru = sg_gru_flat_count(p->gru);
+        sg_gru_pad(p->gru, flat, dev.data() + p->gru.off);
+        memcpy(dev.data(), flat + n_gru, sizeof(float) * (size_t)p->cnnd.total);
+        SG_CHECK(hipStreamSynchronize(p->ctx->stream));
+        SG_COPY_SYNC(p->ctx, p->d_params, dev.data(), sizeof(float) * dev.size(), hipMemcpyHostToDevice);
+        return 0;
+    }
     if (p->cnn) {
         SG_CHECK(hipStreamSynchronize(p->ctx->stream));
         SG_COPY_SYNC(p->ctx, p->d_params, flat, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
@@ -354,6 +372,15 @@ extern "C" int sg_policy_get_params(sg_policy* p, float* flat, int64_t n) {
     SG_REQUIRE(p && flat, "sg_policy_get_params: NULL argument");
     SG_REQUIRE(n == policy_flat_total(p), "sg_policy_get_params: expected %lld floats, got %lld",
                (long long)policy_flat_total(p), (long long)n);
+    if (sg_policy_cnn_rnn(p)) {
+        std::vector<float> dev(sg_policy_padded_count(p));
+        SG_CHECK(hipStreamSynchronize(p->ctx->stream));
+        SG_COPY_SYNC(p->ctx, dev.data(), p->d_params, sizeof(float) * dev.size(), hipMemcpyDeviceToHost);
+        const int64_t n_gru = sg_gru_flat_count(p->gru);
+        sg_gru_unpad(p->gru, dev.data() + p->gru.off, flat);
+        memcpy(flat + n_gru, dev.data(), sizeof(float) * (size_t)p->cnnd.total);
+        return 0;
+    }
     if (p->cnn) {
         SG_CHECK(hipStreamSynchronize(p->ctx->stream));
         SG_COPY_SYNC(p->ctx, flat, p->d_params, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);

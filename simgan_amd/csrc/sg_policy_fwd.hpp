@@ -156,6 +156,8 @@ static inline int ens_check_members(const char* who, const char* what, const sg_
                                     const int32_t* idx, int n_rows) {
     for (int k = 0; k < n; ++k) {
         SG_REQUIRE(members[k] && members[k]->ctx == ctx, "%s: member %d is NULL or lives on another context", who, k);
+        SG_REQUIRE(!sg_policy_cnn_rnn(members[k]), "%s: member %d has the recurrent CNN base (sg_policy_create_cnn_rnn); %s runs the MLP "
+                   "trunks only and carries no hidden state", who, k, what);
         SG_REQUIRE(!members[k]->cnn, "%s: member %d has the CNN base (image observations); %s runs the MLP trunks only", who, k, what);
         SG_REQUIRE(!members[k]->recurrent, "%s: member %d is a recurrent policy; %s carries no hidden state (feed-forward policies only)",
                    who, k, what);

@@ -220,6 +220,8 @@ static int ppo_launch(sg_ctx* ctx, const PpoInstance (&family)[NI], const char* 
 extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg, sg_ppo** out) {
     SG_DEVICE_WIDE();
     SG_REQUIRE(ctx && p && cfg && out, "sg_ppo_create: NULL argument");
+    SG_REQUIRE(!(sg_policy_cnn_rnn(p) && ctx->use_comm && ctx->world > 1), "sg_ppo_create: PPO on the recurrent CNN base runs on one rank: "
+               "this context has a communicator of world %d (data-parallel PPO through time on images is not implemented)", ctx->world);
     SG_REQUIRE(!(p->recurrent && ctx->use_comm && ctx->world > 1), "sg_ppo_create: PPO with a recurrent policy runs on one rank: this "
                "context has a communicator of world %d (data-parallel PPO through time is not implemented)", ctx->world);
     SG_REQUIRE(cfg->ppo_epoch > 0 && cfg->num_mini_batch > 0, "sg_ppo_create: ppo_epoch and num_mini_batch must be positive");
@@ -244,6 +246,8 @@ extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg
     SG_CHECK(hipMemsetAsync(a->d_m, 0, sizeof(float) * tot, ctx->stream));
     SG_CHECK(hipMemsetAsync(a->d_v, 0, sizeof(float) * tot, ctx->stream));
     SG_CHECK(hipMemsetAsync(a->d_loss_acc, 0, sizeof(double) * 8, ctx->stream));
+    // the recurrent CNN base: the floats between the flat block and the GRU block are written by no kernel and read by the norm and Adam
+    if (sg_policy_cnn_rnn(p)) SG_CHECK(hipMemsetAsync(a->d_grad, 0, sizeof(float) * tot, ctx->stream));
     SG_CHECK(sg_dev_malloc((void**)&a->d_pair, SG_PAIR_BYTES));            // k_ppo_pair: error word
     SG_CHECK(hipMemsetAsync(a->d_pair, 0, SG_PAIR_BYTES, ctx->stream));
     SgOptState st;
@@ -260,6 +264,7 @@ extern "C" int sg_ppo_create(sg_ctx* ctx, sg_policy* p, const sg_ppo_config* cfg
 // (a2c/algo/a2c_acktr.py:30-51: RMSprop, square_avg starting at zero).  Policy (MLP) on one rank only.
 extern "C" int sg_a2c_create(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg, sg_ppo** out) {
     SG_REQUIRE(ctx && p && cfg && out, "sg_a2c_create: NULL argument");
+    SG_REQUIRE(!sg_policy_cnn_rnn(p), "sg_a2c_create: A2C is not implemented for the recurrent CNN base (sg_policy_create_cnn_rnn): PPO is");
     SG_REQUIRE(!p->cnn, "sg_a2c_create: A2C is not implemented for the CNN base (image observations): PPO is (A2C on it has an "
                "entry point of its own, sg_a2c_create_cnn)");
     SG_REQUIRE(!p->recurrent, "sg_a2c_create: A2C is implemented for feed-forward policies only, not for a recurrent Policy");
@@ -287,6 +292,8 @@ extern "C" int sg_a2c_create(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg
 // tensors too.  An entry point of its own: sg_a2c_create keeps refusing a recurrent policy.
 extern "C" int sg_a2c_create_rnn(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg, sg_ppo** out) {
     SG_REQUIRE(ctx && p && cfg && out, "sg_a2c_create_rnn: NULL argument");
+    SG_REQUIRE(!sg_policy_cnn_rnn(p), "sg_a2c_create_rnn: A2C through time is not implemented for the recurrent CNN base "
+               "(sg_policy_create_cnn_rnn): PPO is");
     SG_REQUIRE(p->recurrent, "sg_a2c_create_rnn: A2C through time takes a recurrent Policy (kind SG_POLICY_GRU); this policy is "
                "feed-forward (sg_a2c_create)");
     SG_REQUIRE(!p->cnn && p->desc.kind == SG_POLICY_MLP,
@@ -315,6 +322,8 @@ extern "C" int sg_a2c_create_rnn(sg_ctx* ctx, sg_policy* p, const sg_a2c_config*
 // sg_a2c_create keeps refusing a CNN policy.
 extern "C" int sg_a2c_create_cnn(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg, sg_ppo** out) {
     SG_REQUIRE(ctx && p && cfg && out, "sg_a2c_create_cnn: NULL argument");
+    SG_REQUIRE(!sg_policy_cnn_rnn(p), "sg_a2c_create_cnn: A2C on image observations is not implemented for the recurrent CNN base "
+               "(sg_policy_create_cnn_rnn): its row chunks carry no hidden state; PPO is");
     SG_REQUIRE(p->cnn, "sg_a2c_create_cnn: A2C on image observations takes a policy with the CNN base (sg_policy_create_cnn); this "
                "policy has none (sg_a2c_create%s)", p->recurrent ? "_rnn" : "");
     SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_a2c_create_cnn: A2C on the CNN base (image observations) runs on one rank: this "
@@ -341,6 +350,8 @@ extern "C" int sg_a2c_create_cnn(sg_ctx* ctx, sg_policy* p, const sg_a2c_config*
 extern "C" int sg_acktr_create(sg_ctx* ctx, sg_policy* p, const sg_acktr_config* cfg, sg_ppo** out) {
     SG_DEVICE_WIDE();   // kfac_setup's clears and copies on ctx->stream, never beside a capture in flight (recursive with sg_ppo_create's)
     SG_REQUIRE(ctx && p && cfg && out, "sg_acktr_create: NULL argument");
+    SG_REQUIRE(!sg_policy_cnn_rnn(p), "sg_acktr_create: ACKTR is not implemented for the recurrent CNN base (sg_policy_create_cnn_rnn): "
+               "neither its convolutions nor its GRU have K-FAC blocks here; PPO is");
     SG_REQUIRE(!p->cnn, "sg_acktr_create: ACKTR is not implemented for the CNN base (image observations): its convolutions have no "
                "K-FAC blocks here; PPO is");
     SG_REQUIRE(!p->recurrent, "sg_acktr_create: ACKTR is not defined for a recurrent Policy (the reference refuses it too: "
@@ -417,6 +428,8 @@ extern "C" int sg_ppo_set_symmetry(sg_ppo* a, float coef, const float* m_obs, co
     SG_CHECK(hipStreamSynchronize(ctx->stream));   // a queued update may still read the mirrors
     if (coef == 0.f) { a->sym_coef = 0.f; return 0; }   // a2c/algo/ppo.py:111: plain PPO
     SG_REQUIRE(m_act, "sg_ppo_set_symmetry: symmetry_coef > 0 needs the action mirror m_act");
+    SG_REQUIRE(!sg_policy_cnn_rnn(a->policy), "sg_ppo_set_symmetry: the mirror-symmetry loss is not implemented for the recurrent CNN "
+               "base (image observations have no linear mirror map here, and the mirrored rows have no hidden state)");
     SG_REQUIRE(!a->policy->cnn, "sg_ppo_set_symmetry: the mirror-symmetry loss is not implemented for the CNN base (image "
                "observations have no linear mirror map here)");
     SG_REQUIRE(d.kind == SG_POLICY_MLP, "sg_ppo_set_symmetry: the mirror-symmetry loss is implemented for Policy (MLP) only, "
@@ -485,6 +498,20 @@ extern "C" int sg_ppo_get_adam(sg_ppo* a, float* m, float* v, int64_t n, int64_t
     const SgPolicyDesc& d = a->policy->desc;
     const sg_policy* pol = a->policy;
     const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;   // the GRU's tensors come first in the flat order
+    if (sg_policy_cnn_rnn(pol)) {   // flat: the GRU's tensors, then the CNN base's; device: the flat CNN block, then the GRU's tiles
+        SG_REQUIRE(n == pol->cnnd.total + n_gru, "sg_ppo_get_adam: bad length");
+        const size_t ptot = sg_policy_padded_count(pol);
+        std::vector<float> pm(ptot), pv(ptot);
+        SG_CHECK(hipStreamSynchronize(a->ctx->stream));
+        SG_COPY_SYNC(a->ctx, pm.data(), a->d_m, sizeof(float) * ptot, hipMemcpyDeviceToHost);
+        SG_COPY_SYNC(a->ctx, pv.data(), a->d_v, sizeof(float) * ptot, hipMemcpyDeviceToHost);
+        sg_gru_unpad(pol->gru, pm.data() + pol->gru.off, m);
+        sg_gru_unpad(pol->gru, pv.data() + pol->gru.off, v);
+        memcpy(m + n_gru, pm.data(), sizeof(float) * (size_t)pol->cnnd.total);
+        memcpy(v + n_gru, pv.data(), sizeof(float) * (size_t)pol->cnnd.total);
+        *step = a->opt_t;
+        return 0;
+    }
     if (pol->cnn) {   // the CNN base keeps the flat order on the device
         SG_REQUIRE(n == pol->cnnd.total, "sg_ppo_get_adam: bad length");
         SG_CHECK(hipStreamSynchronize(a->ctx->stream));
@@ -516,6 +543,23 @@ extern "C" int sg_ppo_set_adam(sg_ppo* a, const float* m, const float* v, int64_
     const SgPolicyDesc& d = a->policy->desc;
     const sg_policy* pol = a->policy;
     const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;
+    if (sg_policy_cnn_rnn(pol)) {
+        SG_REQUIRE(n == pol->cnnd.total + n_gru, "sg_ppo_set_adam: bad length");
+        SG_REQUIRE(step >= 0 && step < (1ll << 30), "sg_ppo_set_adam: step out of range");
+        const size_t ptot = sg_policy_padded_count(pol);
+        std::vector<float> pm(ptot, 0.f), pv(ptot, 0.f);
+        sg_gru_pad(pol->gru, m, pm.data() + pol->gru.off);
+        sg_gru_pad(pol->gru, v, pv.data() + pol->gru.off);
+        memcpy(pm.data(), m + n_gru, sizeof(float) * (size_t)pol->cnnd.total);
+        memcpy(pv.data(), v + n_gru, sizeof(float) * (size_t)pol->cnnd.total);
+        const int t0r = (int)step;
+        SG_CHECK(hipStreamSynchronize(a->ctx->stream));
+        SG_COPY_SYNC(a->ctx, a->d_m, pm.data(), sizeof(float) * ptot, hipMemcpyHostToDevice);
+        SG_COPY_SYNC(a->ctx, a->d_v, pv.data(), sizeof(float) * ptot, hipMemcpyHostToDevice);
+        SG_COPY_SYNC(a->ctx, &reinterpret_cast<SgOptState*>(a->d_state)->t0, &t0r, sizeof t0r, hipMemcpyHostToDevice);
+        a->opt_t = step;
+        return 0;
+    }
     if (pol->cnn) {
         SG_REQUIRE(n == pol->cnnd.total, "sg_ppo_set_adam: bad length");
         SG_REQUIRE(step >= 0 && step < (1ll << 30), "sg_ppo_set_adam: step out of range");
@@ -1191,6 +1235,190 @@ static int cnn_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_
     return 0;
 }
 
+// PPO.update on the recurrent CNN base (a2c/algo/ppo.py:74-90 over RolloutStorage.recurrent_generator, a2c/storage.py:194-251; the
+// network: a2c/model.py:117-230 with recurrent=True): per = N // num_mini_batch whole environments per optimizer step, time-major.
+//   k_adv_stats x3, the environment permutations [E][N]            (checks, per, S and the loss division as in gru_ppo_update)
+//   per step:  k_cnn_gru_index          row t * per + j -> rollout row t * N + perm[k * per + j]; masks and h0 gathered.  The frames
+//                                       and the per-row scalars are read in place through the index: no epoch copy of observations
+//              the CNN trunk's forward (sg_cnn.hip) -> k_gru_pad_rows (F as padded rows) -> k_gru_inproj -> k_gru_scan_fwd<TRAIN>
+//              -> k_cnn_head_fwd on h_t -> k_cnn_head_loss -> k_cnn_head_dh (d loss / d h_t, no ReLU mask) -> k_cnn_head_wgrad
+//              -> k_gru_scan_bwd -> k_gru_wgrad (x = F) -> k_gru_dx (dZf = (dGI W_ih) [F > 0]) -> the trunk's backward from dZf
+//              -> k_sumsq over the flat block, k_gru_reduce behind it -> k_ppo_adam over both blocks (one norm, one clip)
+//   then       k_opt_commit
+// All of it behind the permutations is one captured graph, replayed per update; no host wait inside.
+static int cnn_gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int64_t n_perms, uint64_t seed, float out3[3]) {
+    sg_ctx* ctx = a->ctx;
+    sg_policy* pol = a->policy;
+    const SgPolicyDesc& d = pol->desc;
+    const SgCnnDesc& c = pol->cnnd;
+    const SgGruDesc& g = pol->gru;
+    SG_REQUIRE(r->O == d.O && r->A == d.A, "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)", r->O, r->A,
+               d.O, d.A);
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_ppo_update: PPO on the recurrent CNN base runs on one rank (world %d)", ctx->world);
+    const int T = r->T, N = r->N, M = a->cfg.num_mini_batch, E = a->cfg.ppo_epoch;
+    // a2c/storage.py:196-199
+    SG_REQUIRE(N >= M, "PPO requires the number of processes (%d) to be greater than or equal to the number of PPO mini batches (%d).", N, M);
+    const int per = N / M;
+    SG_REQUIRE(N % per == 0, "sg_ppo_update: %d processes do not split into minibatches of %d = %d // %d environments (the reference "
+               "indexes past its permutation here)", N, per, N, M);
+    const int S = N / per;
+    const int64_t TN = (int64_t)T * N;
+    SG_REQUIRE(TN < (1ll << 30), "sg_ppo_update: rollout too large");
+    const int mb = T * per;
+    SG_REQUIRE(mb <= SG_CNN_MAX_MB, "sg_ppo_update: a minibatch of %d rows (%d steps x %d environments) on the recurrent CNN base exceeds "
+               "%d (its activation stacks are 158 KB per row): raise num_mini_batch", mb, T, per, SG_CNN_MAX_MB);
+    SG_REQUIRE((int64_t)a->h0_count == (int64_t)N * g.H, "sg_ppo_update: a recurrent policy takes the hidden states of rollout slot 0 "
+               "from the host: sg_ppo_set_hidden_states must hand over %lld floats before every update (pending: %lld)",
+               (long long)N * g.H, (long long)a->h0_count);
+    a->h0_count = 0;
+    if (perms) {
+        SG_REQUIRE(n_perms == (int64_t)E * N, "sg_ppo_update: perms holds %lld indices, %d epochs x %d environments need %lld",
+                   (long long)n_perms, E, N, (long long)E * N);
+        std::vector<uint8_t> seen((size_t)N);
+        for (int e = 0; e < E; ++e) {
+            std::fill(seen.begin(), seen.end(), (uint8_t)0);
+            for (int i = 0; i < N; ++i) {
+                const int64_t v = perms[(size_t)e * N + i];
+                SG_REQUIRE(v >= 0 && v < N && !seen[(size_t)v], "sg_ppo_update: perms of epoch %d are not a permutation of the %d environments", e, N);
+                seen[(size_t)v] = 1;
+            }
+        }
+    }
+    SG_CHECK(hipSetDevice(ctx->device));
+    SG_TRY(enqueue_adv_stats(ctx, r, a, false));
+    SG_TRY(ensure_cap(ctx->stream, &a->d_perms, &a->perms_cap, (int64_t)E * N));
+    a->last_perm_count = (int64_t)E * N;
+    if (perms) {
+        SG_CHECK(hipMemcpyAsync(a->d_perms, perms, sizeof(int64_t) * (size_t)E * N, hipMemcpyHostToDevice, ctx->stream));
+        if (!out3) SG_CHECK(hipStreamSynchronize(ctx->stream));
+    } else {
+        for (int e = 0; e < E; ++e) SG_TRY(sg_fill_perm(ctx, a->d_perms + (size_t)e * N, N, seed, (uint64_t)e * 2654435761ull));
+    }
+
+    // scratch.  d_stacks: head stacks | activation stacks | gradient stacks and slabs, as the feed-forward CNN step.  d_gru: the
+    // step's index vector, masks and h0, F as padded rows, GI, h_t, the scan's saves, the gate gradients, the two d loss / d h_t
+    // tiles and the weight-gradient partials; rows mb .. rows_p-1 of every [rows_p] block are never written and stay zero.
+    const int hld = d.trunk[0].Pp > 16 ? d.trunk[0].Pp : 16;
+    const size_t heads_f = 2 * (size_t)mb * hld, fwd_f = sg_cnn_fwd_floats(c, mb), bwd_f = sg_cnn_bwd_floats(c, mb);
+    const int rows_p = (mb + 15) & ~15;
+    const int Hp = g.Hp, G3 = 3 * Hp;
+    const int chunks = rows_p / 16;
+    const int KS = std::max(1, std::min(16, chunks / 8));
+    auto r4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    const size_t o_idx = 0, o_mk = o_idx + r4(2 * (size_t)rows_p), o_h0 = o_mk + r4((size_t)rows_p), o_fp = o_h0 + r4((size_t)per * g.H);
+    const size_t o_gi = o_fp + (size_t)rows_p * g.ldO, o_h = o_gi + (size_t)rows_p * G3, o_sr = o_h + r4((size_t)rows_p * g.H);
+    const size_t o_sz = o_sr + (size_t)rows_p * Hp, o_sn = o_sz + (size_t)rows_p * Hp, o_shn = o_sn + (size_t)rows_p * Hp;
+    const size_t o_hm = o_shn + (size_t)rows_p * Hp, o_dgi = o_hm + (size_t)rows_p * g.ldH, o_dgh = o_dgi + (size_t)rows_p * G3;
+    const size_t o_dxa = o_dgh + (size_t)rows_p * G3, o_dxc = o_dxa + (size_t)rows_p * g.ldH, o_part = o_dxc + (size_t)rows_p * g.ldH;
+    const size_t gru_f = o_part + (size_t)KS * g.total;
+    bool grew = false;
+    SG_TRY(ensure_cap(ctx->stream, &a->d_stacks, &a->stacks_cap, heads_f + fwd_f + bwd_f, &grew));
+    SG_TRY(ensure_cap(ctx->stream, &a->d_gru, &a->gru_cap, gru_f, &grew));
+    if (grew) a->cleared.mode = SG_LAYOUT_INVALID;
+    {
+        const SgScratchLayout layout = {SG_LAYOUT_CNN_GRU, {T, per, rows_p, KS, g.total, c.total, hld, N}};
+        if (memcmp(&a->cleared, &layout, sizeof layout) != 0) {
+            SG_CHECK(hipMemsetAsync(a->d_gru, 0, sizeof(float) * gru_f, ctx->stream));
+            a->cleared = layout;
+        }
+    }
+    float* heads = a->d_stacks;
+    float* act = heads + heads_f;
+    float* bwd = act + fwd_f;
+    float* F = act + (size_t)mb * (sg_cnn_fwd_floats(c, 1) - c.Hs);                       // [mb][Hs] in the activation stacks
+    float* dZf = bwd + (size_t)mb * (sg_cnn_fwd_floats(c, 1) - c.Hs);                     // [mb][Hs] in the gradient stacks
+    float* gb = a->d_gru;
+    int64_t* idx = reinterpret_cast<int64_t*>(gb + o_idx);
+    hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 4);
+    const float inv_B = 1.0f / (float)mb;
+    const float* obs = r->d_field[SG_F_OBS];
+    SgOptState* st = reinterpret_cast<SgOptState*>(a->d_state);
+
+    CnnGruIndexArgs ia;
+    ia.masks = r->d_field[SG_F_MASKS]; ia.h0 = a->d_h0; ia.T = T; ia.N = N; ia.per = per; ia.H = g.H;
+    ia.idx = idx; ia.MK = gb + o_mk; ia.H0 = gb + o_h0;
+    GruScanArgs tr;
+    tr.sr = gb + o_sr; tr.sz = gb + o_sz; tr.sn = gb + o_sn; tr.shn = gb + o_shn; tr.hm = gb + o_hm;
+    GruBwdArgs ba;
+    ba.g = g; ba.W = pol->d_params + g.off; ba.dxa = gb + o_dxa; ba.dxc = gb + o_dxc; ba.dx_ld = g.ldH;
+    ba.sr = tr.sr; ba.sz = tr.sz; ba.sn = tr.sn; ba.shn = tr.shn; ba.hm = tr.hm; ba.masks = gb + o_mk; ba.T = T; ba.n = per;
+    ba.dgi = gb + o_dgi; ba.dgh = gb + o_dgh;
+    GruWgradArgs wa;
+    wa.g = g; wa.dgi = ba.dgi; wa.dgh = ba.dgh; wa.x = gb + o_fp; wa.hm = tr.hm; wa.rows_p = rows_p; wa.KS = KS; wa.partial = gb + o_part;
+    const bool gw_scan = sg_gru_force_gw() || sg_gru_scan_lds(g, false) > (size_t)ctx->lds_bytes - 1024 ||
+                         sg_gru_bwd_lds(g, false) > (size_t)ctx->lds_bytes - 1024;
+    const bool gw_dx = sg_gru_force_gw() || sg_gru_dx_lds(g, false) > (size_t)ctx->lds_bytes - 1024;
+    GruDxArgs xa;
+    xa.g = g; xa.W = pol->d_params + g.off; xa.dgi = ba.dgi; xa.f = F; xa.f_ld = c.Hs; xa.rows = mb; xa.dzf = dZf; xa.dz_ld = c.Hs;
+    xa.wbuf_floats = gw_dx ? 0 : 3 * Hp * g.ldO;
+    // LDS-weight instance: persistent, a workgroup stages its W_ih image once and walks at least four 16-row tiles where the step
+    // has that many.  Global-weight instance: nothing is staged (W_ih comes through L2 for every tile whoever computes it), so one
+    // tile per workgroup -- measured at Hs = 512, 256 rows: 490 us against 1,069 us with four tiles per workgroup.
+    // The order of every output's sum is its tile's own, whatever the grid is.
+    const int dx_grid = gw_dx ? std::min(chunks, ctx->num_cu) : std::min((chunks + 3) / 4, ctx->num_cu);
+    const int n_tiles = (G3 / 16) * (g.Op / 16 + Hp / 16) + 2 * (G3 / 16);
+    const int gblocks = (g.total + 255) / 256;
+    const int nb_flat = (g.off + 255) / 256;
+    const int tot_all = g.off + g.total;
+    const int nblk = (tot_all + 8 + 255) / 256;
+
+    auto enqueue_steps = [&]() -> int {
+        hipLaunchKernelGGL(k_opt_prepare_first, dim3(1), dim3(1), 0, ctx->stream, st);
+        for (int e = 0; e < E; ++e)
+            for (int k = 0; k < S; ++k) {
+                ia.perm = a->d_perms + (size_t)e * N + (size_t)k * per;
+                hipLaunchKernelGGL(k_cnn_gru_index<0>, dim3((unsigned)((mb + 255) / 256)), dim3(256), 0, ctx->stream, ia);
+                SG_TRY(sg_cnn_trunk_forward_launch(ctx, pol, obs, idx, mb, act, nullptr));
+                hipLaunchKernelGGL(k_gru_pad_rows<0>, dim3((unsigned)(((int64_t)mb * g.ldO + 255) / 256)), dim3(256), 0, ctx->stream, F, mb,
+                                   c.Hs, gb + o_fp, g.ldO);
+                SG_TRY(sg_gru_forward_launch(ctx, g, pol->d_params + g.off, gb + o_fp, g.ldO, gb + o_h0, gb + o_mk, T, per, gb + o_gi,
+                                             gb + o_h, g.H, nullptr, &tr));
+                SG_TRY(sg_cnn_gru_heads_launch(ctx, pol, r, idx, mb, gb + o_h, heads, hld, bwd, a->d_grad, gb + o_dxa, gb + o_dxc, g.ldH,
+                                               inv_B, a->cfg.clip_param, a->cfg.value_loss_coef, a->cfg.entropy_coef,
+                                               a->cfg.use_clipped_value_loss));
+                if (gw_scan) hipLaunchKernelGGL(k_gru_scan_bwd<true>, dim3((per + 15) / 16), dim3(256), sg_gru_bwd_lds(g, true), ctx->stream, ba);
+                else hipLaunchKernelGGL(k_gru_scan_bwd<false>, dim3((per + 15) / 16), dim3(256), sg_gru_bwd_lds(g, false), ctx->stream, ba);
+                hipLaunchKernelGGL(k_gru_wgrad<0>, dim3(n_tiles, KS), dim3(64), 0, ctx->stream, wa);
+                if (gw_dx) hipLaunchKernelGGL(k_gru_dx<true>, dim3(dx_grid), dim3(256), sg_gru_dx_lds(g, true), ctx->stream, xa);
+                else hipLaunchKernelGGL(k_gru_dx<false>, dim3(dx_grid), dim3(256), sg_gru_dx_lds(g, false), ctx->stream, xa);
+                SG_TRY(sg_cnn_trunk_backward_launch(ctx, pol, obs, idx, mb, act, bwd, a->d_grad, 0));
+                hipLaunchKernelGGL(k_sumsq, dim3(nb_flat), dim3(256), 0, ctx->stream, a->d_grad, g.off, a->d_part);
+                hipLaunchKernelGGL(k_gru_reduce<0>, dim3(gblocks), dim3(256), 0, ctx->stream, wa.partial, KS, g.total, a->d_grad, g.off,
+                                   a->d_part, nb_flat);
+                SG_LAUNCH(ctx, SG_PROF_PPO_ADAM, k_ppo_adam, dim3(nblk), dim3(256), 0, pol->d_params, a->d_m, a->d_v, a->d_grad, a->d_part,
+                          nb_flat + gblocks, tot_all, st, e * S + k + 1, a->cfg.eps, a->cfg.max_grad_norm, inv_B, a->d_loss_acc);
+            }
+        hipLaunchKernelGGL(k_opt_commit, dim3(1), dim3(1), 0, ctx->stream, st, E * S);
+        SG_CHECK(hipGetLastError());
+        return 0;
+    };
+    const bool use_graph = !ctx->profile && !sg_env_is_off("SG_PPO_GRAPH");
+    uint32_t fbits[6];
+    const float fv[6] = {a->cfg.clip_param, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, inv_B};
+    memcpy(fbits, fv, sizeof fbits);
+    const uint64_t key[SG_GRAPH_KEY_WORDS] = {
+            (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_grad, (uint64_t)(uintptr_t)a->d_perms,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
+            (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)pol->d_params,
+            (uint64_t)TN, ((uint64_t)E << 32) | (uint64_t)M, (uint64_t)mb,
+            ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
+            ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)a->cfg.use_clipped_value_loss,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_LOGP] ^ ((uint64_t)(uintptr_t)r->d_field[SG_F_VALUE_PREDS] << 1) ^
+                    ((uint64_t)(uintptr_t)r->d_field[SG_F_ADVANTAGES] << 2),
+            // 'CNG': the recurrent CNN step sequence
+            0x434E47ull + (gw_scan ? 16 : 0) + (gw_dx ? 8 : 0) + ((uint64_t)N << 32),
+            (uint64_t)(uintptr_t)a->d_gru, (uint64_t)(uintptr_t)a->d_h0 ^ ((uint64_t)(uintptr_t)r->d_field[SG_F_MASKS] << 1)};
+    SG_TRY(sg_graph_run(ctx, &a->steps_graph, use_graph, key, enqueue_steps));
+    SG_CHECK(hipGetLastError());
+    a->opt_t += (int64_t)E * S;
+    if (!out3) return 0;
+    double acc[3];
+    SG_TRY(sg_ctx_fetch_f64(ctx, a->d_loss_acc, acc, 3));
+    const double nu = (double)E * M;   // a2c/algo/ppo.py:151-155 divides by ppo_epoch * num_mini_batch whatever N // per is
+    for (int i = 0; i < 3; ++i) out3[i] = (float)(acc[i] / nu);
+    return 0;
+}
+
 // ------------------------------------------------------------------- A2C on the CNN base
 // Rows of one chunk: its activation and gradient stacks are 167 KB per row, 684 MB at 4096 -- the fastest of 256 ... 4096 measured
 // at 8192 rows (66.6, 58.7, 58.2, 56.3, 56.0 ms) that stays under 1 GB, and PPO's minibatch cap.  A rollout of
@@ -1490,6 +1718,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
                    a->policy->desc.O, a->policy->desc.A);
         return a2c_update(a, r, seed, out3);
     }
+    if (sg_policy_cnn_rnn(a->policy)) return cnn_gru_ppo_update(a, r, perms, n_perms, seed, out3);
     if (a->policy->recurrent) return gru_ppo_update(a, r, perms, n_perms, seed, out3);
     if (a->policy->cnn) return cnn_ppo_update(a, r, perms, n_perms, seed, out3);
     sg_ctx* ctx = a->ctx;

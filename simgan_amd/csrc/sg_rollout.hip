@@ -122,6 +122,11 @@ extern "C" int sg_rollout_enable_hidden(sg_rollout* r, int hidden_dim) {
     SG_DEVICE_WIDE();
     SG_REQUIRE(r, "sg_rollout_enable_hidden: NULL argument");
     SG_REQUIRE(hidden_dim > 0, "sg_rollout_enable_hidden: hidden_dim must be positive (got %d)", hidden_dim);
+    // (rows of C * 84 * 84 floats are images: no GRU that reads them directly fits a CU's LDS, so only the recurrent CNN base could use
+    // the states, and its steps are not served on the device)
+    SG_REQUIRE(r->O % (84 * 84) != 0, "sg_rollout_enable_hidden: this is an image rollout (%d = %d x 84 x 84 floats per row): device "
+               "hidden states and on-device collection are not built for the recurrent CNN base; keep the states on the host and hand "
+               "slot 0 over with sg_ppo_set_hidden_states", r->O, r->O / (84 * 84));
     if (r->d_hidden) {
         SG_REQUIRE(r->hidden_dim == hidden_dim, "sg_rollout_enable_hidden: the rollout already holds hidden states of width %d, not %d",
                    r->hidden_dim, hidden_dim);
@@ -255,6 +260,8 @@ extern "C" int sg_rollout_compute_returns(sg_rollout* r, const float* next_value
 extern "C" int sg_rollout_compute_returns_policy(sg_rollout* r, sg_policy* p, int use_gae, float gamma,
                                                  float gae_lambda, int use_proper_time_limits) {
     SG_REQUIRE(r && p, "sg_rollout_compute_returns_policy: NULL argument");
+    SG_REQUIRE(!sg_policy_cnn_rnn(p), "sg_rollout_compute_returns_policy: the policy has the recurrent CNN base (sg_policy_create_cnn_rnn) "
+               "and an image rollout holds no hidden state on the device; pass sg_policy_get_value_rnn's result to sg_rollout_compute_returns");
     if (p->recurrent && r->d_hidden && r->hidden_dim == p->gru.H) {
         // next_value = get_value(obs[T], h[T], masks[T]) (a2c/main_gail_dyn_ppo.py:239-242) from the rollout's own slots: the
         // launches and the bits of sg_policy_get_value_rnn, the value left in the policy's staging; nothing waits

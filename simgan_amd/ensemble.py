@@ -20,6 +20,9 @@ class PolicyEnsemble(object):
     def __init__(self, policies, seed=0):
         assert 0 < len(policies) <= 8, "1..8 ensemble members (SG_ENSEMBLE_MAX)"
         self.policies = list(policies)
+        if any(getattr(p, "cnn", 0) and getattr(p, "is_recurrent", False) for p in self.policies):
+            raise NotImplementedError("PolicyEnsemble: a member with the recurrent CNN base is not served (the one-launch act runs the "
+                                      "MLP trunks only and carries no hidden state): it acts through Policy.act")
         if any(getattr(p, "cnn", 0) for p in self.policies):
             raise NotImplementedError("PolicyEnsemble: members with the MLP base only (the one-launch act does not run the CNN base of "
                                       "image observations)")

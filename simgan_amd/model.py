@@ -39,7 +39,10 @@ class _PolicyBase(object):
         self.critic_hidden = int(critic_hidden) if critic_hidden else self.hidden_size
         h = _lib.H()
         ch = 0 if self.critic_hidden == self.hidden_size else self.critic_hidden
-        if self.cnn:
+        if self.cnn and self._rec():   # the recurrent CNN base (a2c/model.py:204-230 with recurrent=True): an entry point of its own
+            _lib.check(self.lib.sg_policy_create_cnn_rnn(self.ctx.h, self.cnn, CNN_HW, CNN_HW, self.hidden_size, self.dist_kind, self.act_dim,
+                                                         self.n_out, C.byref(h)))
+        elif self.cnn:
             _lib.check(self.lib.sg_policy_create_cnn(self.ctx.h, self.cnn, CNN_HW, CNN_HW, self.hidden_size, self.dist_kind, self.act_dim,
                                                      self.n_out, C.byref(h)))
         elif self.dist_kind and self._rec():   # the GRU base with a Categorical / Bernoulli head: an entry point of its own
@@ -179,12 +182,12 @@ class _PolicyBase(object):
         workers do, my_pybullet_envs/utils.py:24-57).  Loading it here goes through `__setstate__`'s "_modules" branch like
         any reference checkpoint.  The package's own classes keep their compact native pickle."""
         if type(self).__module__.startswith("third_party."):
+            if self.__dict__.get("cnn"):   # (the recurrent CNN base too)
+                from .checkpoint import CNN_SAVE_MSG
+                raise NotImplementedError(CNN_SAVE_MSG)
             if self._rec():
                 from .checkpoint import RECURRENT_SAVE_MSG
                 raise NotImplementedError(RECURRENT_SAVE_MSG)
-            if self.__dict__.get("cnn"):
-                from .checkpoint import CNN_SAVE_MSG
-                raise NotImplementedError(CNN_SAVE_MSG)
             import copyreg
             from .checkpoint import reference_module_state
             kind = {_lib.DIST_CATEGORICAL: "mlp_categorical", _lib.DIST_BERNOULLI: "mlp_bernoulli"}.get(self.dist_kind, "mlp")
@@ -280,7 +283,13 @@ class _PolicyBase(object):
 class Policy(_PolicyBase):
     KIND = _lib.POLICY_MLP
 
-    def __init__(self, obs_shape, action_space, base=None, base_kwargs=None, ctx=None, seed=0, critic_hidden=None, recurrent_heads=None):
+    def __init__(self, obs_shape, action_space, base=None, base_kwargs=None, ctx=None, seed=0, critic_hidden=None, recurrent_heads=None,
+                 recurrent_cnn=None):
+        # recurrent_cnn: the CNN base with base_kwargs['recurrent'] (CNN + GRU, a2c/model.py:204-230 with recurrent=True) is opt-in the
+        # same way: True here, or SG_RECURRENT_CNN=1 in the environment when the policy is constructed; with neither it is refused as before
+        if recurrent_cnn is None:
+            import os
+            recurrent_cnn = os.environ.get("SG_RECURRENT_CNN", "") == "1"
         # recurrent_heads: the GRU base with a Categorical / Bernoulli head (Discrete / MultiBinary with base_kwargs['recurrent']) is
         # opt-in: True here, or SG_RECURRENT_HEADS=1 in the environment when the policy is constructed (for an unchanged reference
         # main); with neither the pair is refused as before
@@ -297,7 +306,7 @@ class Policy(_PolicyBase):
                              "reference hard-codes Linear(32 * 7 * 7, hidden) behind its three convolutions, a2c/model.py:216)")
         if cnn and int(obs_shape[0]) < 1:
             raise ValueError(f"Policy on image observations {tuple(obs_shape)}: need at least one channel")
-        if cnn and base_kwargs.get("recurrent", False):
+        if cnn and base_kwargs.get("recurrent", False) and not recurrent_cnn:
             raise NotImplementedError("Policy on image observations with base_kwargs={'recurrent': True}: the CNN base is built "
                                       "feed-forward only (a recurrent CNN base is not)")
         # a2c/model.py:52-62
@@ -316,7 +325,7 @@ class Policy(_PolicyBase):
         if cnn and dist == _lib.DIST_BERNOULLI:
             raise NotImplementedError("Policy on image observations with a MultiBinary action space: the CNN base is built with the "
                                       "Categorical (Discrete) and Gaussian (Box) heads only")
-        if dist != _lib.DIST_GAUSSIAN and base_kwargs.get("recurrent", False) and not recurrent_heads:
+        if not cnn and dist != _lib.DIST_GAUSSIAN and base_kwargs.get("recurrent", False) and not recurrent_heads:
             raise NotImplementedError(f"Policy on a {space} action space with base_kwargs={{'recurrent': True}}: the GRU base is built "
                                       "with the Gaussian head (Box actions) only")
         hidden = base_kwargs.get("hidden_size", 512 if cnn else 64)   # a2c/model.py:205,234
@@ -324,7 +333,8 @@ class Policy(_PolicyBase):
             if critic_hidden not in (None, hidden):
                 raise NotImplementedError("Policy on image observations: critic_linear reads the shared features (a2c/model.py:220-230); "
                                           "there is no critic trunk to give a width of its own")
-            self._create(int(obs_shape[0]) * CNN_HW * CNN_HW, act_dim, hidden, 1, ctx, dist=dist, n_out=n_out, cnn=int(obs_shape[0]))
+            self._create(int(obs_shape[0]) * CNN_HW * CNN_HW, act_dim, hidden, 1, ctx, recurrent=bool(base_kwargs.get("recurrent", False)),
+                         dist=dist, n_out=n_out, cnn=int(obs_shape[0]))
         else:
             self._create(obs_shape[0], act_dim, hidden, 1, ctx, critic_hidden=critic_hidden,
                          recurrent=base_kwargs.get("recurrent", False), dist=dist, n_out=n_out)
@@ -336,11 +346,14 @@ class Policy(_PolicyBase):
         if getattr(self, "cnn", 0):   # a2c/model.py:211-220: main = Conv, ReLU, Conv, ReLU, Conv, ReLU, Flatten, Linear, ReLU
             head = ([("dist.linear.weight", (self.n_out, Hh)), ("dist.linear.bias", (self.n_out,))] if self.dist_kind else
                     [("dist.fc_mean.weight", (A, Hh)), ("dist.fc_mean.bias", (A,)), ("dist.logstd._bias", (A, 1))])
-            return [("base.main.0.weight", (32, self.cnn, 8, 8)), ("base.main.0.bias", (32,)),
-                    ("base.main.2.weight", (64, 32, 4, 4)), ("base.main.2.bias", (64,)),
-                    ("base.main.4.weight", (32, 64, 3, 3)), ("base.main.4.bias", (32,)),
-                    ("base.main.7.weight", (Hh, 32 * 7 * 7)), ("base.main.7.bias", (Hh,)),
-                    ("base.critic_linear.weight", (1, Hh)), ("base.critic_linear.bias", (1,))] + head
+            # recurrent=True: NNBase.__init__ creates nn.GRU(Hs, Hs) before `main` (a2c/model.py:124-131,208-216), so its tensors come first
+            gru = ([("base.gru.weight_ih_l0", (3 * Hh, Hh)), ("base.gru.weight_hh_l0", (3 * Hh, Hh)),
+                    ("base.gru.bias_ih_l0", (3 * Hh,)), ("base.gru.bias_hh_l0", (3 * Hh,))] if self._rec() else [])
+            return gru + [("base.main.0.weight", (32, self.cnn, 8, 8)), ("base.main.0.bias", (32,)),
+                          ("base.main.2.weight", (64, 32, 4, 4)), ("base.main.2.bias", (64,)),
+                          ("base.main.4.weight", (32, 64, 3, 3)), ("base.main.4.bias", (32,)),
+                          ("base.main.7.weight", (Hh, 32 * 7 * 7)), ("base.main.7.bias", (Hh,)),
+                          ("base.critic_linear.weight", (1, Hh)), ("base.critic_linear.bias", (1,))] + head
         gru = []
         if self._rec():   # a2c/model.py:124-131: nn.GRU's four tensors come first and the trunks read its H-wide state
             gru = [("base.gru.weight_ih_l0", (3 * Hh, O)), ("base.gru.weight_hh_l0", (3 * Hh, Hh)),

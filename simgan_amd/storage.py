@@ -667,7 +667,8 @@ class RolloutStorage(object):
     def recurrent_generator(self, advantages, num_mini_batch, perm=None):
         """a2c/storage.py:194-251 -- host-side generator: whole environments per minibatch, rows time-major, the hidden
         state of slot 0.  `perm` injects the reference's torch.randperm(num_processes) draw; default: numpy's generator."""
-        if self.__dict__.get("image_shape"):
+        # (an image rollout built with recurrent_hidden_state_size > 1 serves the recurrent CNN base: frames come out 4-D, [T * per, C, H, W])
+        if self.__dict__.get("image_shape") and int(self.recurrent_hidden_states.shape[-1]) <= 1:
             raise NotImplementedError("recurrent_generator: image observations are read by the feed-forward CNN base only (a recurrent "
                                       "CNN base is not built): use feed_forward_generator")
         return recurrent_batches(self, advantages, num_mini_batch, perm)
@@ -703,6 +704,8 @@ def recurrent_batches(ro, advantages, num_mini_batch, perm=None):
 
         def g(t, sl):   # [T(+1), N, w] -> the minibatch's [T * per, w], time-major
             a = arr(t)[sl][:, envs]
+            if a.ndim == 5:   # image observations [T, per, C, H, W] -> [T * per, C, H, W] (a2c/storage.py:236-238: _flatten_helper)
+                return to_host_tensor(np.ascontiguousarray(a.reshape(-1, *a.shape[2:])))
             return to_host_tensor(np.ascontiguousarray(a.reshape(-1, a.shape[-1])))
 
         cur, al = slice(None, -1), slice(None)
