@@ -24,7 +24,13 @@ FAULTS, for the test of the test (`fault_grad`), each on the references alone:
   no_f_mask       no ReLU mask on d loss / d F (derivative 1 everywhere)
   no_h_mask       h not multiplied by masks[t]
   gate_order      the gates r, z, n of weight_ih permuted to z, n, r
-  gru_last        the GRU block placed after base.main.* in the flat order"""
+  gru_last        the GRU block placed after base.main.* in the flat order
+TILE_FAULTS, what a launch past one tile can lose (each does nothing at all -- distance exactly 0 -- where a step fits one tile of
+its kind, which is every GRAD_CASES key; tests/test_cnn_gru_tiles_host.py):
+  dx_rows_first_64     no gradient from the GRU's input into the trunk for step rows >= 64 (weight_ih's own gradient is whole)
+  scan_envs_first_16   environments j >= 16 of a step hand the heads a detached h_t (the heads' weights keep their gradient)
+  wgrad_first_range    the GRU block's weight and bias gradients lack the step rows of every KS range of k_gru_wgrad but the first
+  loss_rows_first_256  step rows >= 256 add nothing to the three loss sums or to any gradient; the divisor stays the row count"""
 import functools
 
 import numpy as np
@@ -54,21 +60,36 @@ def n_gru(Hs):
 
 
 # ------------------------------------------------------------------------------------------------------------ forward
-def gru_states(p, x, hxs0, masks, T, mask_h=True):
-    """float64: autograd_ref.gru_states itself.  Any other dtype (the float32 admission), or mask_h False (the injected defect):
-    the same stepping of the same torch.nn.GRU module at that dtype."""
-    if x.dtype == F64 and mask_h:
+def gru_states(p, x, hxs0, masks, T, mask_h=True, leaf_rows=None):
+    """float64: autograd_ref.gru_states itself.  Any other dtype (the float32 admission), mask_h False or leaf_rows (the injected
+    defects): the same stepping of the same torch.nn.GRU module at that dtype.  leaf_rows: time-major rows >= leaf_rows go through
+    the module with detached copies of its four tensors (the state and the input keep their gradient), the others with the leaves:
+    two calls per step on the two column subsets."""
+    if x.dtype == F64 and mask_h and leaf_rows is None:
         return ar.gru_states(p, x, hxs0, masks, T)
     H = p["base.gru.weight_hh_l0"].shape[1]
     gru = torch.nn.GRU(H, H).to(x.dtype)
     weights = {k: p["base.gru." + k] for k in GRU_NAMES}
+    detached = {k: w.detach() for k, w in weights.items()}
     n = x.shape[0] // T
     h, out = ar.t64(hxs0).to(x.dtype).unsqueeze(0), []
     masks = ar.t64(masks).to(x.dtype).reshape(T, n)
     for t in range(T):
         hin = h * masks[t].view(1, n, 1) if mask_h else h
-        y, h = torch.func.functional_call(gru, weights, (x[t * n:(t + 1) * n].unsqueeze(0), hin))
-        out.append(y[0])
+        xt = x[t * n:(t + 1) * n].unsqueeze(0)
+        if leaf_rows is None:
+            y, h = torch.func.functional_call(gru, weights, (xt, hin))
+            out.append(y[0])
+            continue
+        cut = min(n, max(0, leaf_rows - t * n))
+        ys, hs = [], []
+        for w, cols in ((weights, slice(0, cut)), (detached, slice(cut, n))):
+            if cols.stop > cols.start:
+                y, hn = torch.func.functional_call(gru, w, (xt[:, cols], hin[:, cols]))
+                ys.append(y[0])
+                hs.append(hn)
+        h = torch.cat(hs, 1)
+        out.append(torch.cat(ys, 0))
     return torch.cat(out, 0)
 
 
@@ -98,6 +119,9 @@ def states(p, x, hxs0, masks, T, fault=None, tap=None):
                 z = seen["zf"]
                 return t + (z - z.detach()) * (z <= 0).to(z.dtype)
             return t
+    if fault == "dx_rows_first_64" and x.shape[0] > 64:
+        def tap(name, t):  # noqa: F811
+            return torch.cat([t[:64], t[64:].detach()], 0) if name == "feat" else t
     feat, zs = cr.trunk(p, x, tap=tap)
     pg = p
     if fault == "gate_order":
@@ -105,23 +129,36 @@ def states(p, x, hxs0, masks, T, fault=None, tap=None):
         w = p["base.gru.weight_ih_l0"]
         pg = dict(p)
         pg["base.gru.weight_ih_l0"] = torch.cat([w[Hs:2 * Hs], w[2 * Hs:], w[:Hs]], 0)
-    h = gru_states(pg, feat, hxs0, masks, T, mask_h=fault != "no_h_mask")
+    leaf_rows = None
+    if fault == "wgrad_first_range":
+        n = x.shape[0] // T
+        geo = geometry(T, n, 1, feat.shape[1])
+        if geo["KS"] > 1:
+            leaf_rows = 16 * geo["ranges"][0][1]
+    h = gru_states(pg, feat, hxs0, masks, T, mask_h=fault != "no_h_mask", leaf_rows=leaf_rows)
     if fault == "head_relu_mask":
         h = _MaskedIdentity.apply(h, feat.detach())
+    if fault == "scan_envs_first_16" and x.shape[0] // T > 16:
+        late = (torch.arange(x.shape[0]) % (x.shape[0] // T) >= 16).view(-1, 1)
+        h = torch.where(late, h.detach(), h)
     return h, feat, zs
+
+
+def dist_terms(p, h, actions, dist):
+    """the heads on h [rows, Hs] and the distribution's terms at `actions` -> (values [rows], logp [rows], entropy.mean())"""
+    out = cr.heads(p, h, dist)
+    if dist == "categorical":
+        ls = torch.nn.functional.log_softmax(out[1], dim=-1)
+        a = torch.as_tensor(np.asarray(actions).reshape(-1).astype(np.int64))
+        return out[0], ls.gather(1, a.view(-1, 1))[:, 0], -(ls.exp() * ls).sum(-1).mean()
+    acts = torch.as_tensor(np.asarray(actions, np.float64).reshape(h.shape[0], -1), dtype=h.dtype)
+    return out[0], ar.normal_log_probs(out[1], out[2], acts), ar.normal_entropy(out[2])
 
 
 def evaluate(p, x, hxs0, masks, T, actions, dist, fault=None):
     """Policy.evaluate_actions (a2c/model.py:107-114) -> (values [rows], logp [rows], entropy.mean(), h_T [n, Hs])"""
     h, _, _ = states(p, x, hxs0, masks, T, fault)
-    out = cr.heads(p, h, dist)
-    n = x.shape[0] // T
-    if dist == "categorical":
-        ls = torch.nn.functional.log_softmax(out[1], dim=-1)
-        a = torch.as_tensor(np.asarray(actions).reshape(-1).astype(np.int64))
-        return out[0], ls.gather(1, a.view(-1, 1))[:, 0], -(ls.exp() * ls).sum(-1).mean(), h[-n:]
-    acts = torch.as_tensor(np.asarray(actions, np.float64).reshape(x.shape[0], -1), dtype=x.dtype)
-    return out[0], ar.normal_log_probs(out[1], out[2], acts), ar.normal_entropy(out[2]), h[-n:]
+    return dist_terms(p, h, actions, dist) + (h[-(x.shape[0] // T):],)
 
 
 def forward64(shapes, params, obs, hxs0, masks, T, dist):
@@ -159,9 +196,19 @@ def ppo_grad(shapes, params, obs, hxs0, masks, T, actions, old_logp, value_preds
     adv normalised over the WHOLE rollout) -> (flat gradient, losses[3])"""
     t = lambda a: ar.t64(a).to(dtype)  # noqa: E731
     p = cr.leaves(params, shapes, dtype, grad=True)
-    values, logp, entropy, _ = evaluate(p, t(obs), hxs0, masks, T, actions, dist, fault)
-    total, parts = ar.ppo_loss(values, logp, entropy, t(old_logp).reshape(-1), t(adv).reshape(-1), t(value_preds).reshape(-1),
-                               t(returns).reshape(-1), cr.CLIP, cr.VCOEF, ecoef, use_clipped)
+    B = np.asarray(obs).shape[0]
+    if fault == "loss_rows_first_256" and B > 256:
+        # ppo_loss on the first 256 rows alone, its means turned back into sums over them divided by B: the entropy term too
+        h, _, _ = states(p, t(obs), hxs0, masks, T)
+        values, logp, entropy = dist_terms(p, h[:256], np.asarray(actions)[:256], dist)
+        cut = lambda a: t(a).reshape(-1)[:256]  # noqa: E731
+        total, parts = ar.ppo_loss(values, logp, entropy, cut(old_logp), cut(adv), cut(value_preds), cut(returns), cr.CLIP, cr.VCOEF,
+                                   ecoef, use_clipped)
+        total, parts = total * (256.0 / B), tuple(x * (256.0 / B) for x in parts)
+    else:
+        values, logp, entropy, _ = evaluate(p, t(obs), hxs0, masks, T, actions, dist, fault)
+        total, parts = ar.ppo_loss(values, logp, entropy, t(old_logp).reshape(-1), t(adv).reshape(-1), t(value_preds).reshape(-1),
+                                   t(returns).reshape(-1), cr.CLIP, cr.VCOEF, ecoef, use_clipped)
     g = ar.flat_grad(total, p)
     if fault == "gru_last":
         k = n_gru(p["base.gru.weight_hh_l0"].shape[1])
@@ -194,8 +241,11 @@ def init_params(rng, C, Hs, dist, P, noise=0.02):
 
 # key (C, Hs, dist, P, T, N) -> seed
 SEEDS = {(1, 16, "categorical", 5, 4, 4): 0, (2, 20, "gaussian", 3, 3, 3): 0, (1, 18, "categorical", 4, 5, 7): 0,
-         (4, 512, "categorical", 6, 3, 2): 0, (1, 16, "gaussian", 3, 3, 3): 0}
-HEADS = {(4, 512, "categorical", 6, 3, 2): "peaked", (1, 16, "gaussian", 3, 3, 3): "fc_zero"}
+         (4, 512, "categorical", 6, 3, 2): 0, (1, 16, "gaussian", 3, 3, 3): 0,
+         # TILE_CASES (seeds 0 and 1 refuse the 4 x 17 Gaussian shape)
+         (1, 16, "categorical", 5, 8, 33): 0, (1, 16, "categorical", 5, 4, 34): 0, (2, 20, "gaussian", 3, 4, 17): 2,
+         (4, 512, "categorical", 6, 3, 6): 0}
+HEADS = {(4, 512, "categorical", 6, 3, 2): "peaked", (1, 16, "gaussian", 3, 3, 3): "fc_zero", (4, 512, "categorical", 6, 3, 6): "peaked"}
 ZERO_UNITS = 2     # "fc_zero": FC units 0, 1 have zero weight rows and zero bias -> F is exactly 0 there in every row
 
 
@@ -341,6 +391,45 @@ PERM_SEED = 3
 # at max_grad_norm = 0.5 the clip acts in every optimizer step of every case but this one, whose gradient norm stays below 0.5
 # (tests/test_cnn_gru_host.py holds both statements on the references)
 CLIP_INACTIVE = {(1, 18, "categorical", 4, 5, 7)}
+# the one-step gradient cases of tests/test_gpu_cnn_gru_tiles.py, past one row tile, one scan tile and one loss block: key ->
+# num_mini_batch (geometry() below and tests/test_cnn_gru_tiles_host.py's FACTS say which edge each one sits on)
+TILE_CASES = {(1, 16, "categorical", 5, 8, 33): 1, (1, 16, "categorical", 5, 4, 34): 2, (2, 20, "gaussian", 3, 4, 17): 1,
+              (4, 512, "categorical", 6, 3, 6): 1}
+# max_grad_norm at which the clip acts in every optimizer step of a TILE_CASES key under both value losses: half the smallest
+# float64 step-gradient norm of the case, two significant digits (tests/test_cnn_gru_tiles_host.py recomputes each)
+TILE_CLIP = {(1, 16, "categorical", 5, 8, 33): 0.037, (1, 16, "categorical", 5, 4, 34): 0.15, (2, 20, "gaussian", 3, 4, 17): 0.92,
+             (4, 512, "categorical", 6, 3, 6): 38.0}
+TILE_FAULTS = ("dx_rows_first_64", "scan_envs_first_16", "wgrad_first_range", "loss_rows_first_256")
+LDS_ROOM = 160 * 1024 - 1024     # a gfx950 workgroup's LDS less the 1 KiB the launchers leave
+
+
+def geometry(T, N, M, Hs, cus=256):
+    """The launch arithmetic of one optimizer step of cnn_gru_ppo_update (simgan_amd/csrc/sg_ppo.hip), restated: per, S, mb; rows_p,
+    the 16-row chunks, KS and the chunk range [c0, c1) of every blockIdx.y of k_gru_wgrad; the scans' workgroups and the live rows
+    of the last one; k_cnn_head_loss's blocks; k_gru_dx's grid by both formulas and the tiles each workgroup walks; which instances
+    run, by the LDS sizes of sg_gru_dx_lds / sg_gru_scan_lds / sg_gru_bwd_lds (the GRU reads the Hs features: O = H = Hs)."""
+    per = N // M
+    assert N % per == 0
+    mb = T * per
+    rows_p = (mb + 15) & ~15
+    chunks = rows_p // 16
+    KS = max(1, min(16, chunks // 8))
+    each = (chunks + KS - 1) // KS
+    ranges = [(ks * each, min(chunks, ks * each + each)) for ks in range(KS)]
+    Hp = (Hs + 15) & ~15
+    ld = Hp + 4
+    dx_lds = 4 * (3 * Hp * ld + 16 * (3 * Hp + 4))
+    scan_lds = 4 * (3 * Hp * ld + 2 * 16 * ld)
+    bwd_lds = 4 * (3 * Hp * ld + 16 * ld + 16 * (3 * Hp + 4))
+    gw_dx, gw_scan = dx_lds > LDS_ROOM, scan_lds > LDS_ROOM or bwd_lds > LDS_ROOM
+    dx_grid_lds, dx_grid_gw = min((chunks + 3) // 4, cus), min(chunks, cus)
+    tiles = (mb + 15) // 16     # k_gru_dx walks base = blockIdx.x * 16, + gridDim.x * 16, ... while base < mb
+    walk = lambda grid: [list(range(b, tiles, grid)) for b in range(grid)]  # noqa: E731
+    return dict(per=per, S=N // per, mb=mb, rows_p=rows_p, pad_rows=rows_p - mb, chunks=chunks, KS=KS, each=each, ranges=ranges,
+                sizes=[max(0, c1 - c0) for c0, c1 in ranges], scan_workgroups=(per + 15) // 16, last_live=per - 16 * ((per - 1) // 16),
+                loss_blocks=(mb + 255) // 256, Hp=Hp, gw_dx=gw_dx, gw_scan=gw_scan, dx_grid_lds=dx_grid_lds, dx_grid_gw=dx_grid_gw,
+                dx_grid=dx_grid_gw if gw_dx else dx_grid_lds, dx_walk_lds=walk(dx_grid_lds), dx_walk_gw=walk(dx_grid_gw),
+                last_tile_live=mb - 16 * ((mb - 1) // 16))
 
 
 def step_envs(key, M, perm):
