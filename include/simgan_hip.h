@@ -146,7 +146,8 @@ SG_API int sg_policy_create_cnn(sg_ctx *ctx, int channels, int height, int width
  * [T * n]; a one-step call and the same step inside a sequence give the same bits), sg_policy_get_params / _set_params,
  * sg_ppo_create (one rank) with sg_ppo_set_hidden_states (slot 0) before every sg_ppo_update -- PPO through time over minibatches
  * of N // num_mini_batch whole environments read time-major in place from the image rollout, injected perms [ppo_epoch][N],
- * minibatches above 4096 rows refused -- and sg_ppo_get_adam / _set_adam.  Everything else that can reach the handle refuses it
+ * minibatches above 4096 rows refused -- and sg_ppo_get_adam / _set_adam; and by sg_a2c_create_cnn_rnn (one rank; A2C through
+ * time, sg_a2c_get_rmsprop / _set_rmsprop).  Everything else that can reach the handle refuses it
  * with a message naming the recurrent CNN base: sg_a2c_create / _create_rnn / _create_cnn, sg_acktr_create, the diagnostics entry
  * points, sg_rollout_act_step / _act_step_rnn / _act_step_chain, sg_rollout_compute_returns_policy, sg_policy_act_ensemble,
  * sg_ppo_set_symmetry (coef > 0), sg_ppo_create on a communicator of world > 1; sg_rollout_enable_hidden refuses an image rollout. */
@@ -460,6 +461,22 @@ SG_API int sg_a2c_create_rnn(sg_ctx *ctx, sg_policy *p, const sg_a2c_config *cfg
  * with T*N, no rollout size is refused below 2^30 rows, and two runs are bit-identical.  sg_a2c_get_rmsprop / sg_a2c_set_rmsprop
  * take square_avg in the CNN's flat order (sg_policy_create_cnn). */
 SG_API int sg_a2c_create_cnn(sg_ctx *ctx, sg_policy *p, const sg_a2c_config *cfg, sg_ppo **out);
+/* The same learner on the recurrent CNN base (sg_policy_create_cnn_rnn; --algo a2c --recurrent-policy on image observations):
+ * a2c/algo/a2c_acktr.py:52-102 over a2c/model.py:117-230, A2C through time on images.  Opt-in by entry point: sg_a2c_create,
+ * sg_a2c_create_rnn and sg_a2c_create_cnn keep refusing that base.  Refused here, each with its own message: a policy that is not
+ * sg_policy_create_cnn_rnn's, and a context with a communicator of world > 1.
+ * One update: evaluate_actions on the rollout's T*N rows -- the trunk on every frame, the GRU stepped with h <- h * masks[t] from
+ * the hidden states of slot 0, which the caller hands over before EVERY update with sg_ppo_set_hidden_states ([N][hidden]; a
+ * missing hand-over is refused; sg_rollout_enable_hidden keeps refusing image rollouts) --, the losses and out3 as above, all
+ * means over T*N rows; back-propagation through the heads, through time and through the trunk; ONE clip_grad_norm_ over the CNN
+ * and GRU parameters together, one RMSprop step over both (the learning rate of sg_ppo_set_lr).  The rows go through the network
+ * in groups of max(1, min(N, 4096 / T)) whole environments with all T steps, time-major, read in place from the rollout
+ * (SG_A2C_CNN_GRU_GROUP_ENVS=<n >= 1> forces a smaller group: test and tuning knob); each group's gradient is added to that of
+ * the groups before it in a fixed order, so the scratch (167 KB per group row) does not grow with N and two runs are
+ * bit-identical.  T > 4096 is refused by sg_ppo_update.  perms must be NULL; out3 == NULL queues the update.  sg_ppo_set_lr,
+ * sg_ppo_destroy and sg_results_publish take the handle; sg_a2c_get_rmsprop / sg_a2c_set_rmsprop take square_avg in flat
+ * state_dict order: the GRU's four tensors first, then the CNN's flat order (sg_policy_create_cnn_rnn). */
+SG_API int sg_a2c_create_cnn_rnn(sg_ctx *ctx, sg_policy *p, const sg_a2c_config *cfg, sg_ppo **out);
 /* RMSprop state for checkpoint/parity: square_avg flat [n] in state_dict order; *step = optimizer steps taken. */
 SG_API int sg_a2c_get_rmsprop(sg_ppo *a, float *square_avg, int64_t n, int64_t *step);
 SG_API int sg_a2c_set_rmsprop(sg_ppo *a, const float *square_avg, int64_t n, int64_t step);

@@ -120,6 +120,7 @@ PROTOTYPES = {
     "sg_a2c_create": (C.c_int, [H, H, C.POINTER(A2CConfig), C.POINTER(H)]),
     "sg_a2c_create_rnn": (C.c_int, [H, H, C.POINTER(A2CConfig), C.POINTER(H)]),
     "sg_a2c_create_cnn": (C.c_int, [H, H, C.POINTER(A2CConfig), C.POINTER(H)]),
+    "sg_a2c_create_cnn_rnn": (C.c_int, [H, H, C.POINTER(A2CConfig), C.POINTER(H)]),
     "sg_a2c_get_rmsprop": (C.c_int, [H, c_float_p, C.c_int64, c_i64_p]),
     "sg_a2c_set_rmsprop": (C.c_int, [H, c_float_p, C.c_int64, C.c_int64]),
     "sg_acktr_create": (C.c_int, [H, H, C.POINTER(ACKTRConfig), C.POINTER(H)]),

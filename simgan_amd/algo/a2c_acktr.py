@@ -3,7 +3,8 @@ acktr=True (--algo acktr, a2c/main.py:159-161, with KFACOptimizer of a2c/algo/kf
 update() runs entirely on the GPU: evaluate_actions over the whole rollout, the A2C loss and its gradient, then either
 global-norm clipping and one RMSprop step, or the K-FAC statistics, preconditioning and KL-bounded momentum-SGD step.  The
 device object is an sg_ppo in A2C or ACKTR mode (include/simgan_hip.h: sg_a2c_create, sg_a2c_create_rnn, sg_a2c_create_cnn,
-sg_acktr_create).  A2C through time (recurrent=True) and A2C on the CNN base (cnn=True) are opt-in by keyword."""
+sg_a2c_create_cnn_rnn, sg_acktr_create).  A2C through time (recurrent=True), A2C on the CNN base (cnn=True) and A2C through time on
+the recurrent CNN base (recurrent_cnn=True) are opt-in by keyword."""
 import ctypes as C
 
 import numpy as np
@@ -67,7 +68,22 @@ class A2C_ACKTR():
                  acktr=False,
                  seed=0,
                  recurrent=False,
-                 cnn=False):
+                 cnn=False,
+                 recurrent_cnn=False):
+        is_rcnn = bool(getattr(actor_critic, "cnn", 0)) and bool(getattr(actor_critic, "is_recurrent", False))
+        if recurrent_cnn:
+            if not is_rcnn:
+                raise ValueError("A2C_ACKTR(recurrent_cnn=True) takes a Policy with the recurrent CNN base (a [C, 84, 84] obs_shape, "
+                                 "base_kwargs={'recurrent': True}, recurrent_cnn=True); this policy has another base: leave the keyword out")
+            if acktr:
+                raise NotImplementedError("A2C_ACKTR(acktr=True, recurrent_cnn=True): ACKTR is not implemented for the recurrent CNN "
+                                          "base: K-FAC has neither convolution nor GRU statistics here (the reference refuses "
+                                          "--recurrent-policy with acktr too); acktr=False (A2C through time) runs")
+            if getattr(getattr(actor_critic, "ctx", None), "world", 1) > 1:
+                raise NotImplementedError("A2C_ACKTR(recurrent_cnn=True): A2C on the recurrent CNN base runs on one rank "
+                                          f"(this context's world is {actor_critic.ctx.world}): data-parallel A2C through time on "
+                                          "images is not implemented")
+            cnn = recurrent = True   # the checks below then see both of its bases opted in
         if acktr:
             given = [k for k, v in (("lr", lr), ("eps", eps), ("alpha", alpha), ("max_grad_norm", max_grad_norm)) if v is not None]
             if given:
@@ -78,7 +94,7 @@ class A2C_ACKTR():
         if type(actor_critic).__name__ == "SplitPolicy":
             raise NotImplementedError("A2C_ACKTR: implemented for Policy (MLP) only, not for SplitPolicy")
         is_cnn = bool(getattr(actor_critic, "cnn", 0))
-        if is_cnn and getattr(actor_critic, "is_recurrent", False):
+        if is_rcnn and not recurrent_cnn:
             raise NotImplementedError("A2C_ACKTR: not implemented for the recurrent CNN base (image observations with "
                                       "base_kwargs={'recurrent': True}), in any mode -- acktr, cnn=True or recurrent=True; PPO is")
         if cnn and acktr:
@@ -128,7 +144,8 @@ class A2C_ACKTR():
         self.lib = self.ctx.lib
         cfg = _lib.A2CConfig(float(value_loss_coef), float(entropy_coef), float(lr), float(eps), float(alpha), float(max_grad_norm))
         h = _lib.H()
-        create = self.lib.sg_a2c_create_cnn if is_cnn else self.lib.sg_a2c_create_rnn if is_rec else self.lib.sg_a2c_create
+        create = (self.lib.sg_a2c_create_cnn_rnn if is_rcnn else self.lib.sg_a2c_create_cnn if is_cnn else
+                  self.lib.sg_a2c_create_rnn if is_rec else self.lib.sg_a2c_create)
         _lib.check(create(self.ctx.h, actor_critic.h, C.byref(cfg), C.byref(h)))
         self.h = h
         if hasattr(actor_critic, "_register_handle_user"):

@@ -291,9 +291,12 @@ int sg_cnn_gru_forward_device(sg_policy* p, const float* d_obs, const float* d_h
     return sg_policy_heads_device(p, heads, hld, rows, mode, d_noise, seed, d_action_in, d_value, d_action, d_logp, d_ent);
 }
 
+// The heads of the recurrent CNN base on the GRU states of n rows: forward, loss block, d loss / d h_t, head gradients.  a2c: the
+// A2C loss block on the indexed rows (k_cnn_head_loss_a2c_idx) instead of PPO's; acc: the head gradients and the three loss sums
+// add to what grad holds (a later environment group of one A2C update).  PPO passes 0, 0.
 int sg_cnn_gru_heads_launch(sg_ctx* ctx, const sg_policy* p, const sg_rollout* r, const int64_t* d_idx, int n, const float* hstate,
                             float* heads, int hld, float* bwd, float* grad, float* dxa, float* dxc, int dx_ld, float inv_B, float clip,
-                            float vcoef, float ecoef, int use_clipped) {
+                            float vcoef, float ecoef, int use_clipped, int a2c, int acc) {
     const SgCnnDesc& c = p->cnnd;
     const float* W = p->d_params;
     float* dZf = bwd + (size_t)n * (SG_CNN_A1 + SG_CNN_A2 + SG_CNN_A3);
@@ -307,12 +310,13 @@ int sg_cnn_gru_heads_launch(sg_ctx* ctx, const sg_policy* p, const sg_rollout* r
     l.vpred = r->d_field[SG_F_VALUE_PREDS]; l.ret = r->d_field[SG_F_RETURNS];
     l.inv_B = inv_B; l.clip = clip; l.vcoef = vcoef; l.ecoef = ecoef; l.use_clipped = use_clipped;
     l.dout = dout; l.dls = dls; l.rowl = rowl;
-    hipLaunchKernelGGL(k_cnn_head_loss, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, l);
+    if (a2c) hipLaunchKernelGGL(k_cnn_head_loss_a2c_idx, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, l);
+    else hipLaunchKernelGGL(k_cnn_head_loss, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, l);
     CnnHeadDhArgs dh;
     dh.d = c; dh.params = W; dh.dout = dout; dh.n = n; dh.ld = dx_ld; dh.dxa = dxa; dh.dxc = dxc;
     hipLaunchKernelGGL(k_cnn_head_dh, dim3((unsigned)(((int64_t)n * dx_ld + 255) / 256)), dim3(256), 0, ctx->stream, dh);
     CnnHeadBwdArgs hb;
-    hb.d = c; hb.params = W; hb.feat = hstate; hb.dout = dout; hb.dls = dls; hb.rowl = rowl; hb.n = n; hb.acc = 0; hb.dzf = nullptr; hb.grad = grad;
+    hb.d = c; hb.params = W; hb.feat = hstate; hb.dout = dout; hb.dls = dls; hb.rowl = rowl; hb.n = n; hb.acc = acc; hb.dzf = nullptr; hb.grad = grad;
     hb.d.total = p->gru.off;   // the three loss sums go where k_gru_reduce picks them up: behind the flat block's padding
     const int n_head = (c.P + 1) * (c.Hs + 1) + c.A;
     hipLaunchKernelGGL(k_cnn_head_wgrad, dim3((unsigned)((n_head + 255) / 256)), dim3(256), 0, ctx->stream, hb);

@@ -349,12 +349,10 @@ __global__ __launch_bounds__(256) void k_cnn_head_loss(CnnLossArgs a) {
     sg_cnn_dist_grad(d, a.params, z, a.actions, src, s, dlogp, dent, dout, a.dls + (size_t)row * d.A);
 }
 
-// A2C: loss = vcoef mean(adv^2) - mean(adv.detach() logp) - ecoef mean(ent) over ALL T N rows, of which this launch holds n
-__global__ __launch_bounds__(256) void k_cnn_head_loss_a2c(CnnLossArgs a) {
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= a.n) return;
+// A2C: loss = vcoef mean(adv^2) - mean(adv.detach() logp) - ecoef mean(ent) over ALL T N rows, of which this launch holds n;
+// src: the rollout row of the launch's row `row`
+__device__ __forceinline__ void sg_cnn_head_loss_a2c_row(const CnnLossArgs& a, int row, int64_t src) {
     const SgCnnDesc& d = a.d;
-    const int64_t src = a.row0 + row;
     const float* z = a.heads + (size_t)row * a.hld;
     const float v = a.heads[((size_t)a.n + row) * a.hld];
     float* dout = a.dout + (size_t)row * (d.P + 1);
@@ -367,6 +365,20 @@ __global__ __launch_bounds__(256) void k_cnn_head_loss_a2c(CnnLossArgs a) {
     a.rowl[2 * a.n + row] = s.ent;
     // d/dlogp of -adv logp inv_B with adv detached; the value head's gradient is dout[0] alone
     sg_cnn_dist_grad(d, a.params, z, a.actions, src, s, -adv * a.inv_B, a.ecoef * a.inv_B, dout, a.dls + (size_t)row * d.A);
+}
+
+// a row chunk of the rollout in its own order: row -> row0 + row
+__global__ __launch_bounds__(256) void k_cnn_head_loss_a2c(CnnLossArgs a) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= a.n) return;
+    sg_cnn_head_loss_a2c_row(a, row, a.row0 + row);
+}
+
+// the indexed form (A2C through time on the recurrent CNN base: a group of environments, time-major): row -> idx[row]
+__global__ __launch_bounds__(256) void k_cnn_head_loss_a2c_idx(CnnLossArgs a) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= a.n) return;
+    sg_cnn_head_loss_a2c_row(a, row, a.idx[row]);
 }
 
 struct CnnHeadBwdArgs {

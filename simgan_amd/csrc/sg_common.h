@@ -296,7 +296,7 @@ int sg_cnn_gru_forward_device(sg_policy* p, const float* d_obs, const float* d_h
 // columns written as zero), and the heads' weight gradients into grad with the three loss sums at grad[gru.off ..]
 int sg_cnn_gru_heads_launch(sg_ctx* ctx, const sg_policy* p, const struct sg_rollout* r, const int64_t* d_idx, int n, const float* hstate,
                             float* heads, int hld, float* bwd, float* grad, float* dxa, float* dxc, int dx_ld, float inv_B, float clip,
-                            float vcoef, float ecoef, int use_clipped);
+                            float vcoef, float ecoef, int use_clipped, int a2c, int acc);
 bool sg_cnn_gru_fits(const sg_ctx* ctx, const SgGruDesc& g);   // sg_gru.hip: every GRU tile of the recurrent CNN base fits a CU's LDS
 
 size_t sg_policy_padded_count(const sg_policy* p);          // floats of d_params (heads + GRU block)
@@ -360,7 +360,7 @@ struct SgGraphCache {
 // The scratch layout an sg_ppo's buffers were last cleared for: padding columns / rows that the kernels never write must
 // read as zero, which holds for as long as the layout is the same.  Compared whole.  SG_LAYOUT_INVALID: clear before the next
 // update whatever its layout (after a reallocation, after sg_ppo_set_adam).
-enum { SG_LAYOUT_INVALID = 0, SG_LAYOUT_PPO, SG_LAYOUT_A2C, SG_LAYOUT_GRU, SG_LAYOUT_A2C_GRU, SG_LAYOUT_CNN_GRU };
+enum { SG_LAYOUT_INVALID = 0, SG_LAYOUT_PPO, SG_LAYOUT_A2C, SG_LAYOUT_GRU, SG_LAYOUT_A2C_GRU, SG_LAYOUT_CNN_GRU, SG_LAYOUT_A2C_CNN_GRU };
 struct SgScratchLayout {
     int64_t mode = SG_LAYOUT_INVALID;
     int64_t dims[8] = {0};
@@ -408,6 +408,7 @@ struct sg_ppo {
     float alpha = 0.f;
     bool a2c_rnn = false;          // sg_a2c_create_rnn: A2C through time on a recurrent Policy (the update's recurrent branch)
     bool a2c_cnn = false;          // sg_a2c_create_cnn: A2C on the CNN base, the whole rollout in row chunks (a2c_cnn_update)
+    bool a2c_cnn_rnn = false;      // sg_a2c_create_cnn_rnn: A2C through time on the recurrent CNN base, in environment groups (a2c_cnn_gru_update)
     // ACKTR (sg_acktr_create): A2C's gradient (a2c is set too), then the K-FAC step (sg_ppo.hip); d_m holds SGD's momentum buffer
     struct SgKfac* kfac = nullptr;
 };

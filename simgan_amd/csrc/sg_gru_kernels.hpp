@@ -15,6 +15,7 @@
 //                      groups' GRU gradients in group order and finishes them after the last
 //   k_gru_dx           the recurrent CNN base (sg_cnn.hip, sg_ppo.hip: cnn_gru_ppo_update): dZf = (dGI W_ih) [F > 0], the gradient the
 //                      CNN trunk's backward continues from;  k_cnn_gru_index, k_gru_pad_rows: its step's index vector and padded x
+//                      (k_cnn_gru_index_group: the index of one environment group of a2c_cnn_gru_update, no permutation)
 // No floating-point atomics anywhere: every sum has one order, two runs give the same bits.
 #pragma once
 #include "sg_common.h"
@@ -446,6 +447,27 @@ __global__ __launch_bounds__(256) void k_cnn_gru_index(CnnGruIndexArgs a) {
         const int j = i / a.H, c = i - j * a.H;
         a.H0[i] = a.h0[(size_t)a.perm[j] * a.H + c];
     }
+}
+
+// The identity-offset form (A2C through time on the image rollout, a2c/algo/a2c_acktr.py:56-63): a group of n environments
+// e0 .. e0 + n - 1 in the rollout's own order, group row rr = t * n + j is rollout row t * N + e0 + j; H0 rows are h0's e0 ..
+struct CnnGruGroupIndexArgs {
+    const float *masks, *h0;
+    int T, N, e0, n, H;
+    int64_t* idx;          // [T*n]
+    float *MK, *H0;        // [T*n], [n][H]
+};
+
+template <int DUMMY = 0>
+__global__ __launch_bounds__(256) void k_cnn_gru_index_group(CnnGruGroupIndexArgs a) {
+    const int rr = blockIdx.x * blockDim.x + threadIdx.x;
+    if (rr < a.T * a.n) {
+        const int t = rr / a.n, j = rr - t * a.n;
+        const int64_t src = (int64_t)t * a.N + a.e0 + j;
+        a.idx[rr] = src;
+        a.MK[rr] = a.masks[src];
+    }
+    for (int i = rr; i < a.n * a.H; i += gridDim.x * blockDim.x) a.H0[i] = a.h0[(size_t)a.e0 * a.H + i];
 }
 
 // compact rows [rows][w] -> padded rows [rows][ld] (zero in columns w .. ld-1): the features as k_gru_wgrad's x operand

@@ -33,6 +33,11 @@
 //   the forward of sg_cnn.hip -> k_cnn_head_loss_a2c -> head, FC, conv3, conv2, conv1 gradients (adding from the second chunk on);
 //   then k_sumsq -> k_a2c_rmsprop
 //
+// A2C through time on the recurrent CNN base (sg_a2c_create_cnn_rnn; a2c_cnn_gru_update), per group of whole
+// environments:  k_cnn_gru_index_group -> the trunk's forward -> k_gru_pad_rows -> k_gru_inproj -> k_gru_scan_fwd<TRAIN> -> the heads
+//   on h_t -> k_cnn_head_loss_a2c_idx -> k_cnn_head_dh -> k_cnn_head_wgrad -> k_gru_scan_bwd -> k_gru_wgrad -> k_gru_reduce_acc ->
+//   k_gru_dx -> the trunk's backward (every gradient adding from the second group on);  then k_sumsq -> k_a2c_rmsprop over both blocks
+//
 // ACKTR (sg_acktr_create: A2C's gradient with the K-FAC step of a2c/algo/kfac.py, sg_kfac.hpp), one update:
 //   k_a2c_gather
 //   per chunk:  k_ppo_fwd -> k_a2c_bwd -> k_a2c_reduce -> k_acktr_fisher -> k_kfac_stats (adds to the factor sums)
@@ -345,6 +350,34 @@ extern "C" int sg_a2c_create_cnn(sg_ctx* ctx, sg_policy* p, const sg_a2c_config*
     return 0;
 }
 
+// The same learner on the recurrent CNN base (a2c/main.py --algo a2c --recurrent-policy on image observations:
+// a2c/algo/a2c_acktr.py:52-102 over a2c/model.py:117-230): the update takes the whole rollout through time in groups of whole
+// environments whose gradients accumulate (a2c_cnn_gru_update).  An entry point of its own: the three above keep refusing this base.
+extern "C" int sg_a2c_create_cnn_rnn(sg_ctx* ctx, sg_policy* p, const sg_a2c_config* cfg, sg_ppo** out) {
+    SG_REQUIRE(ctx && p && cfg && out, "sg_a2c_create_cnn_rnn: NULL argument");
+    SG_REQUIRE(sg_policy_cnn_rnn(p), "sg_a2c_create_cnn_rnn: A2C through time on image observations takes a policy with the recurrent "
+               "CNN base (sg_policy_create_cnn_rnn); this policy %s (sg_a2c_create%s)",
+               p->cnn ? "has the feed-forward CNN base" : p->recurrent ? "has the GRU base on vector observations" : "has neither a CNN nor a GRU",
+               p->cnn ? "_cnn" : p->recurrent ? "_rnn" : "");
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_a2c_create_cnn_rnn: A2C on the recurrent CNN base runs on one rank: this context "
+               "has a communicator of world %d (data-parallel A2C through time on images is not implemented)", ctx->world);
+    SG_REQUIRE(cfg->alpha >= 0.f && cfg->alpha <= 1.f && cfg->eps >= 0.f && cfg->max_grad_norm > 0.f,
+               "sg_a2c_create_cnn_rnn: alpha must lie in [0, 1], eps >= 0 and max_grad_norm > 0 (got %g, %g, %g)", (double)cfg->alpha,
+               (double)cfg->eps, (double)cfg->max_grad_norm);
+    sg_ppo_config pc;
+    memset(&pc, 0, sizeof pc);
+    pc.ppo_epoch = 1; pc.num_mini_batch = 1;
+    pc.value_loss_coef = cfg->value_loss_coef; pc.entropy_coef = cfg->entropy_coef;
+    pc.lr = cfg->lr; pc.eps = cfg->eps; pc.max_grad_norm = cfg->max_grad_norm;
+    sg_ppo* a = nullptr;
+    SG_TRY(sg_ppo_create(ctx, p, &pc, &a));
+    a->a2c = true;
+    a->a2c_cnn_rnn = true;
+    a->alpha = cfg->alpha;
+    *out = a;
+    return 0;
+}
+
 // a2c/main.py:159-161 -> A2C_ACKTR(actor_critic, value_loss_coef, entropy_coef, acktr=True): KFACOptimizer(actor_critic) with
 // the constructor values in cfg (a2c/algo/kfac.py:97-150).  Policy (MLP) on one rank only.
 extern "C" int sg_acktr_create(sg_ctx* ctx, sg_policy* p, const sg_acktr_config* cfg, sg_ppo** out) {
@@ -602,6 +635,18 @@ extern "C" int sg_a2c_get_rmsprop(sg_ppo* a, float* square_avg, int64_t n, int64
     const SgPolicyDesc& d = a->policy->desc;
     const sg_policy* pol = a->policy;
     const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;   // the GRU's tensors come first in the flat order
+    if (sg_policy_cnn_rnn(pol)) {   // flat: the GRU's tensors, then the CNN base's; device: the flat CNN block, then the GRU's tiles
+        SG_REQUIRE(n == pol->cnnd.total + n_gru, "sg_a2c_get_rmsprop: bad length");
+        const size_t ptot = sg_policy_padded_count(pol);
+        std::vector<float> pv(ptot);
+        SG_CHECK(hipSetDevice(a->ctx->device));
+        SG_CHECK(hipStreamSynchronize(a->ctx->stream));
+        SG_COPY_SYNC(a->ctx, pv.data(), a->d_v, sizeof(float) * ptot, hipMemcpyDeviceToHost);
+        sg_gru_unpad(pol->gru, pv.data() + pol->gru.off, square_avg);
+        memcpy(square_avg + n_gru, pv.data(), sizeof(float) * (size_t)pol->cnnd.total);
+        *step = a->opt_t;
+        return 0;
+    }
     if (pol->cnn) {   // the CNN base keeps the flat order on the device
         SG_REQUIRE(n == pol->cnnd.total, "sg_a2c_get_rmsprop: bad length");
         SG_CHECK(hipSetDevice(a->ctx->device));
@@ -629,6 +674,19 @@ extern "C" int sg_a2c_set_rmsprop(sg_ppo* a, const float* square_avg, int64_t n,
     const SgPolicyDesc& d = a->policy->desc;
     const sg_policy* pol = a->policy;
     const int64_t n_gru = pol->recurrent ? sg_gru_flat_count(pol->gru) : 0;
+    if (sg_policy_cnn_rnn(pol)) {
+        SG_REQUIRE(n == pol->cnnd.total + n_gru, "sg_a2c_set_rmsprop: bad length");
+        SG_REQUIRE(step >= 0, "sg_a2c_set_rmsprop: step out of range");
+        const size_t ptot = sg_policy_padded_count(pol);
+        std::vector<float> pv(ptot, 0.f);
+        sg_gru_pad(pol->gru, square_avg, pv.data() + pol->gru.off);
+        memcpy(pv.data(), square_avg + n_gru, sizeof(float) * (size_t)pol->cnnd.total);
+        SG_CHECK(hipSetDevice(a->ctx->device));
+        SG_CHECK(hipStreamSynchronize(a->ctx->stream));
+        SG_COPY_SYNC(a->ctx, a->d_v, pv.data(), sizeof(float) * ptot, hipMemcpyHostToDevice);
+        a->opt_t = step;
+        return 0;
+    }
     if (pol->cnn) {
         SG_REQUIRE(n == pol->cnnd.total, "sg_a2c_set_rmsprop: bad length");
         SG_REQUIRE(step >= 0, "sg_a2c_set_rmsprop: step out of range");
@@ -1375,7 +1433,7 @@ static int cnn_gru_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, in
                                              gb + o_h, g.H, nullptr, &tr));
                 SG_TRY(sg_cnn_gru_heads_launch(ctx, pol, r, idx, mb, gb + o_h, heads, hld, bwd, a->d_grad, gb + o_dxa, gb + o_dxc, g.ldH,
                                                inv_B, a->cfg.clip_param, a->cfg.value_loss_coef, a->cfg.entropy_coef,
-                                               a->cfg.use_clipped_value_loss));
+                                               a->cfg.use_clipped_value_loss, 0, 0));
                 if (gw_scan) hipLaunchKernelGGL(k_gru_scan_bwd<true>, dim3((per + 15) / 16), dim3(256), sg_gru_bwd_lds(g, true), ctx->stream, ba);
                 else hipLaunchKernelGGL(k_gru_scan_bwd<false>, dim3((per + 15) / 16), dim3(256), sg_gru_bwd_lds(g, false), ctx->stream, ba);
                 hipLaunchKernelGGL(k_gru_wgrad<0>, dim3(n_tiles, KS), dim3(64), 0, ctx->stream, wa);
@@ -1500,6 +1558,184 @@ static int a2c_cnn_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
             ((uint64_t)fbits[4] << 32) | fbits[5], 0, 0,
             0x413243434Eull,   // 'A2CCN': A2C on the CNN base, the chunked step sequence
             0, 0};
+    SG_TRY(sg_graph_run(ctx, &a->steps_graph, use_graph, key, enqueue_step));
+    SG_CHECK(hipGetLastError());
+    a->opt_t += 1;
+    if (!out3) return 0;   // queued: the losses come through the results ring (step count 1)
+    double acc[3];
+    SG_TRY(sg_ctx_fetch_f64(ctx, a->d_loss_acc, acc, 3));
+    for (int i = 0; i < 3; ++i) out3[i] = (float)acc[i];
+    return 0;
+}
+
+// ------------------------------------------------------------------- A2C through time on the recurrent CNN base
+// Rows of one environment group: the trunk's activation and gradient stacks are 167 KB per row, so a group holds the most whole
+// environments (all T steps each) that stay within a2c_cnn_update's chunk and PPO's minibatch cap.  SG_A2C_CNN_GRU_GROUP_ENVS (any
+// n >= 1: test and tuning knob, after SG_A2C_GROUP_ENVS and SG_A2C_CNN_CHUNK_ROWS) forces a smaller group.
+#define SG_A2C_CNN_GRU_GROUP_ROWS 4096
+static int a2c_cnn_gru_group_envs(int T, int N) {
+    int ne = std::max(1, std::min(N, SG_A2C_CNN_GRU_GROUP_ROWS / T));
+    if (const char* e = getenv("SG_A2C_CNN_GRU_GROUP_ENVS")) {
+        const long v = atol(e);
+        if (v >= 1) ne = (int)std::min<long>(v, ne);
+    }
+    return ne;
+}
+
+// A2C_ACKTR.update(rollouts), acktr=False, on CNNBase(recurrent=True) (a2c/algo/a2c_acktr.py:52-102 over a2c/model.py:117-230):
+// evaluate_actions runs the trunk on all T*N frames and steps the GRU through the T steps of the N environments from the state of
+// slot 0; ONE loss over the T*N rows (inv_B = 1 / (T N) in every group), one clip over the CNN and GRU parameters together, one
+// RMSprop step.  Per group k of n <= ne whole environments [e0, e0 + n), time-major (the last group may be smaller):
+//   k_cnn_gru_index_group     group row t * n + j -> rollout row t * N + e0 + j; masks and h0 rows e0 .. gathered.  Frames, actions
+//                             and returns are read in place through the index: no copy of observations
+//   the CNN trunk's forward -> k_gru_pad_rows -> k_gru_inproj -> k_gru_scan_fwd<TRAIN> -> k_cnn_head_fwd on h_t
+//   -> k_cnn_head_loss_a2c_idx -> k_cnn_head_dh -> k_cnn_head_wgrad (acc = k > 0: head gradients and the three loss sums add up)
+//   -> k_gru_scan_bwd -> k_gru_wgrad -> k_gru_reduce_acc (adds to the GRU's gradient; the last group finishes it) -> k_gru_dx
+//   -> the trunk's backward from dZf (acc = k > 0: every k_cnn_reduce adds to the flat gradient)
+// then k_sumsq over the flat block (the GRU block's sums are k_gru_reduce_acc's) -> k_a2c_rmsprop over both blocks.
+// Every sum has one order, fixed by T, N and the group size.  One captured graph, replayed per update; no host wait inside.  The
+// scratch is sized by the group, not by T*N.
+static int a2c_cnn_gru_update(sg_ppo* a, sg_rollout* r, float out3[3]) {
+    sg_ctx* ctx = a->ctx;
+    sg_policy* pol = a->policy;
+    const SgPolicyDesc& d = pol->desc;
+    const SgCnnDesc& c = pol->cnnd;
+    const SgGruDesc& g = pol->gru;
+    SG_REQUIRE(r->O == d.O && r->A == d.A, "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)", r->O, r->A,
+               d.O, d.A);
+    SG_REQUIRE(!(ctx->use_comm && ctx->world > 1), "sg_ppo_update: A2C on the recurrent CNN base runs on one rank (world %d)", ctx->world);
+    const int T = r->T, N = r->N;
+    SG_REQUIRE(T <= SG_A2C_CNN_GRU_GROUP_ROWS, "sg_ppo_update: A2C on the recurrent CNN base takes whole environments per group: the %d "
+               "steps of one exceed the %d rows a group may hold (its activation stacks are 167 KB per row)", T, SG_A2C_CNN_GRU_GROUP_ROWS);
+    SG_REQUIRE((int64_t)a->h0_count == (int64_t)N * g.H, "sg_ppo_update: a recurrent policy takes the hidden states of rollout slot 0 "
+               "from the host: sg_ppo_set_hidden_states must hand over %lld floats before every update (pending: %lld)",
+               (long long)N * g.H, (long long)a->h0_count);
+    a->h0_count = 0;
+    const int64_t TN = (int64_t)T * N;
+    SG_REQUIRE(TN > 0 && TN < (1ll << 30), "sg_ppo_update: %lld rollout rows", (long long)TN);
+    SG_CHECK(hipSetDevice(ctx->device));
+
+    // geometry of a full group; a smaller last group uses the head of every block
+    const int ne = a2c_cnn_gru_group_envs(T, N);
+    const int n_groups = (N + ne - 1) / ne;
+    const int mb = T * ne;
+    const int hld = d.trunk[0].Pp > 16 ? d.trunk[0].Pp : 16;
+    const size_t heads_f = 2 * (size_t)mb * hld, fwd_f = sg_cnn_fwd_floats(c, mb), bwd_f = sg_cnn_bwd_floats(c, mb);
+    const int rows_p = (mb + 15) & ~15;
+    const int Hp = g.Hp, G3 = 3 * Hp;
+    auto ks_of = [](int rp) { return std::max(1, std::min(16, (rp / 16) / 8)); };   // row ranges of k_gru_wgrad, as in the PPO step
+    const int KS = ks_of(rows_p);
+    // scratch.  d_stacks: head stacks | activation stacks | gradient stacks and slabs, as the feed-forward CNN step.  d_gru: the
+    // group's index vector, masks and h0, F as padded rows, GI, h_t, the scan's saves, the gate gradients, the two d loss / d h_t
+    // tiles, the weight-gradient partials and the running GRU gradient; rows mb .. rows_p-1 of every [rows_p] block are never
+    // written and stay zero.
+    auto r4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    const size_t o_idx = 0, o_mk = o_idx + r4(2 * (size_t)rows_p), o_h0 = o_mk + r4((size_t)rows_p), o_fp = o_h0 + r4((size_t)ne * g.H);
+    const size_t o_gi = o_fp + (size_t)rows_p * g.ldO, o_h = o_gi + (size_t)rows_p * G3, o_sr = o_h + r4((size_t)rows_p * g.H);
+    const size_t o_sz = o_sr + (size_t)rows_p * Hp, o_sn = o_sz + (size_t)rows_p * Hp, o_shn = o_sn + (size_t)rows_p * Hp;
+    const size_t o_hm = o_shn + (size_t)rows_p * Hp, o_dgi = o_hm + (size_t)rows_p * g.ldH, o_dgh = o_dgi + (size_t)rows_p * G3;
+    const size_t o_dxa = o_dgh + (size_t)rows_p * G3, o_dxc = o_dxa + (size_t)rows_p * g.ldH, o_part = o_dxc + (size_t)rows_p * g.ldH;
+    const size_t o_acc = o_part + (size_t)KS * g.total, gru_f = o_acc + r4((size_t)g.total);
+    bool grew = false;
+    SG_TRY(ensure_cap(ctx->stream, &a->d_stacks, &a->stacks_cap, heads_f + fwd_f + bwd_f, &grew));
+    SG_TRY(ensure_cap(ctx->stream, &a->d_gru, &a->gru_cap, gru_f, &grew));
+    if (grew) a->cleared.mode = SG_LAYOUT_INVALID;
+    {
+        const SgScratchLayout layout = {SG_LAYOUT_A2C_CNN_GRU, {T, ne, rows_p, KS, g.total, c.total, hld, N}};
+        if (memcmp(&a->cleared, &layout, sizeof layout) != 0) {
+            SG_CHECK(hipMemsetAsync(a->d_gru, 0, sizeof(float) * gru_f, ctx->stream));
+            a->cleared = layout;
+        }
+    }
+    float* heads = a->d_stacks;
+    float* act = heads + heads_f;
+    float* bwd = act + fwd_f;
+    float* gb = a->d_gru;
+    int64_t* idx = reinterpret_cast<int64_t*>(gb + o_idx);
+    hipLaunchKernelGGL(k_zero_f64, dim3(1), dim3(64), 0, ctx->stream, a->d_loss_acc, 4);
+    const float inv_B = 1.0f / (float)TN;   // 1 / (T N) of the whole rollout, whatever the group
+    const float* obs = r->d_field[SG_F_OBS];
+    SgOptState* st = reinterpret_cast<SgOptState*>(a->d_state);
+    const double oma = 1.0 - (double)a->alpha;   // torch: value = 1 - alpha in Python doubles
+
+    CnnGruGroupIndexArgs ia;
+    ia.masks = r->d_field[SG_F_MASKS]; ia.h0 = a->d_h0; ia.T = T; ia.N = N; ia.e0 = 0; ia.n = ne; ia.H = g.H;
+    ia.idx = idx; ia.MK = gb + o_mk; ia.H0 = gb + o_h0;
+    GruScanArgs tr;
+    tr.sr = gb + o_sr; tr.sz = gb + o_sz; tr.sn = gb + o_sn; tr.shn = gb + o_shn; tr.hm = gb + o_hm;
+    GruBwdArgs ba;
+    ba.g = g; ba.W = pol->d_params + g.off; ba.dxa = gb + o_dxa; ba.dxc = gb + o_dxc; ba.dx_ld = g.ldH;
+    ba.sr = tr.sr; ba.sz = tr.sz; ba.sn = tr.sn; ba.shn = tr.shn; ba.hm = tr.hm; ba.masks = gb + o_mk; ba.T = T; ba.n = ne;
+    ba.dgi = gb + o_dgi; ba.dgh = gb + o_dgh;
+    GruWgradArgs wa;
+    wa.g = g; wa.dgi = ba.dgi; wa.dgh = ba.dgh; wa.x = gb + o_fp; wa.hm = tr.hm; wa.rows_p = rows_p; wa.KS = KS; wa.partial = gb + o_part;
+    const bool gw_scan = sg_gru_force_gw() || sg_gru_scan_lds(g, false) > (size_t)ctx->lds_bytes - 1024 ||
+                         sg_gru_bwd_lds(g, false) > (size_t)ctx->lds_bytes - 1024;
+    const bool gw_dx = sg_gru_force_gw() || sg_gru_dx_lds(g, false) > (size_t)ctx->lds_bytes - 1024;
+    GruDxArgs xa;
+    xa.g = g; xa.W = pol->d_params + g.off; xa.dgi = ba.dgi; xa.f_ld = c.Hs; xa.dz_ld = c.Hs;
+    xa.wbuf_floats = gw_dx ? 0 : 3 * Hp * g.ldO;
+    const int n_tiles = (G3 / 16) * (g.Op / 16 + Hp / 16) + 2 * (G3 / 16);
+    const int gblocks = (g.total + 255) / 256;
+    const int nb_flat = (g.off + 255) / 256;
+    const int tot_all = g.off + g.total;
+    const int nblk = (tot_all + 8 + 255) / 256;
+    const size_t trunk_row_f = sg_cnn_fwd_floats(c, 1) - c.Hs;   // A1 | A2 | A3 of one row: F and dZf lie behind the group's
+
+    auto enqueue_step = [&]() -> int {
+        for (int k = 0; k < n_groups; ++k) {
+            const int e0 = k * ne, n = std::min(ne, N - e0), rows = T * n, rows_pk = (rows + 15) & ~15, chunks = rows_pk / 16;
+            const int acc = k > 0 ? 1 : 0;
+            float* F = act + (size_t)rows * trunk_row_f;      // [rows][Hs] in the activation stacks
+            float* dZf = bwd + (size_t)rows * trunk_row_f;    // [rows][Hs] in the gradient stacks
+            ia.e0 = e0; ia.n = n;
+            hipLaunchKernelGGL(k_cnn_gru_index_group<0>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream, ia);
+            SG_TRY(sg_cnn_trunk_forward_launch(ctx, pol, obs, idx, rows, act, nullptr));
+            hipLaunchKernelGGL(k_gru_pad_rows<0>, dim3((unsigned)(((int64_t)rows * g.ldO + 255) / 256)), dim3(256), 0, ctx->stream, F, rows,
+                               c.Hs, gb + o_fp, g.ldO);
+            SG_TRY(sg_gru_forward_launch(ctx, g, pol->d_params + g.off, gb + o_fp, g.ldO, gb + o_h0, gb + o_mk, T, n, gb + o_gi, gb + o_h,
+                                         g.H, nullptr, &tr));
+            SG_TRY(sg_cnn_gru_heads_launch(ctx, pol, r, idx, rows, gb + o_h, heads, hld, bwd, a->d_grad, gb + o_dxa, gb + o_dxc, g.ldH,
+                                           inv_B, 0.f, a->cfg.value_loss_coef, a->cfg.entropy_coef, 0, 1, acc));
+            if (rows_pk > rows && n < ne) {   // a smaller last group: its padding rows hold a full group's gate gradients
+                SG_CHECK(hipMemsetAsync(gb + o_dgi + (size_t)rows * G3, 0, sizeof(float) * (size_t)(rows_pk - rows) * G3, ctx->stream));
+                SG_CHECK(hipMemsetAsync(gb + o_dgh + (size_t)rows * G3, 0, sizeof(float) * (size_t)(rows_pk - rows) * G3, ctx->stream));
+            }
+            ba.n = n;
+            if (gw_scan) hipLaunchKernelGGL(k_gru_scan_bwd<true>, dim3((n + 15) / 16), dim3(256), sg_gru_bwd_lds(g, true), ctx->stream, ba);
+            else hipLaunchKernelGGL(k_gru_scan_bwd<false>, dim3((n + 15) / 16), dim3(256), sg_gru_bwd_lds(g, false), ctx->stream, ba);
+            wa.rows_p = rows_pk; wa.KS = ks_of(rows_pk);
+            hipLaunchKernelGGL(k_gru_wgrad<0>, dim3(n_tiles, wa.KS), dim3(64), 0, ctx->stream, wa);
+            hipLaunchKernelGGL(k_gru_reduce_acc<0>, dim3(gblocks), dim3(256), 0, ctx->stream, wa.partial, wa.KS, g.total, gb + o_acc, acc,
+                               k + 1 == n_groups ? 1 : 0, a->d_grad, g.off, a->d_part, nb_flat);
+            xa.f = F; xa.rows = rows; xa.dzf = dZf;
+            // grid: as cnn_gru_ppo_update (LDS-weight instance: at least four 16-row tiles per workgroup; global-weight: one)
+            const int dx_grid = gw_dx ? std::min(chunks, ctx->num_cu) : std::min((chunks + 3) / 4, ctx->num_cu);
+            if (gw_dx) hipLaunchKernelGGL(k_gru_dx<true>, dim3(dx_grid), dim3(256), sg_gru_dx_lds(g, true), ctx->stream, xa);
+            else hipLaunchKernelGGL(k_gru_dx<false>, dim3(dx_grid), dim3(256), sg_gru_dx_lds(g, false), ctx->stream, xa);
+            SG_TRY(sg_cnn_trunk_backward_launch(ctx, pol, obs, idx, rows, act, bwd, a->d_grad, acc));
+        }
+        hipLaunchKernelGGL(k_sumsq, dim3(nb_flat), dim3(256), 0, ctx->stream, a->d_grad, g.off, a->d_part);
+        SG_LAUNCH(ctx, SG_PROF_PPO_ADAM, k_a2c_rmsprop, dim3(nblk), dim3(256), 0, pol->d_params, a->d_v, a->d_grad, a->d_part,
+                  nb_flat + gblocks, tot_all, st, a->alpha, (float)oma, a->cfg.eps, a->cfg.max_grad_norm, inv_B, a->d_loss_acc);
+        SG_CHECK(hipGetLastError());
+        return 0;
+    };
+    const bool use_graph = !ctx->profile && !sg_env_is_off("SG_PPO_GRAPH");
+    uint32_t fbits[6];
+    const float fv[6] = {a->alpha, a->cfg.value_loss_coef, a->cfg.entropy_coef, a->cfg.eps, a->cfg.max_grad_norm, inv_B};
+    memcpy(fbits, fv, sizeof fbits);
+    const uint64_t key[SG_GRAPH_KEY_WORDS] = {
+            (uint64_t)(uintptr_t)a->d_stacks, (uint64_t)(uintptr_t)a->d_grad, (uint64_t)(uintptr_t)a->d_gru,
+            (uint64_t)(uintptr_t)r->d_field[SG_F_OBS], (uint64_t)(uintptr_t)r->d_field[SG_F_ACTIONS],
+            (uint64_t)(uintptr_t)r->d_field[SG_F_RETURNS], (uint64_t)(uintptr_t)pol->d_params,
+            (uint64_t)TN, ((uint64_t)T << 32) | (uint64_t)N, ((uint64_t)n_groups << 32) | (uint64_t)ne,
+            ((uint64_t)fbits[0] << 32) | fbits[1], ((uint64_t)fbits[2] << 32) | fbits[3],
+            ((uint64_t)fbits[4] << 32) | fbits[5], (uint64_t)(uintptr_t)r->d_field[SG_F_MASKS],
+            (uint64_t)(uintptr_t)a->d_h0,
+            // 'A2CNG': A2C through time on the recurrent CNN base, the grouped step sequence
+            0x4132434E47ull + (gw_scan ? 16 : 0) + (gw_dx ? 8 : 0),
+            ((uint64_t)rows_p << 32) | (uint64_t)KS, (uint64_t)(uintptr_t)a->d_part};
     SG_TRY(sg_graph_run(ctx, &a->steps_graph, use_graph, key, enqueue_step));
     SG_CHECK(hipGetLastError());
     a->opt_t += 1;
@@ -1713,6 +1949,7 @@ extern "C" int sg_ppo_update(sg_ppo* a, sg_rollout* r, const int64_t* perms, int
         SG_REQUIRE(!perms, "sg_ppo_update: an A2C update takes the rollout in its own order: perms must be NULL");
         if (a->a2c_rnn) return a2c_gru_update(a, r, out3);
         if (a->a2c_cnn) return a2c_cnn_update(a, r, out3);
+        if (a->a2c_cnn_rnn) return a2c_cnn_gru_update(a, r, out3);
         SG_REQUIRE(r->O == a->policy->desc.O && r->A == a->policy->desc.A,
                    "sg_ppo_update: rollout dims (obs %d, act %d) do not match the policy (%d, %d)", r->O, r->A,
                    a->policy->desc.O, a->policy->desc.A);
